@@ -2,7 +2,7 @@
 """bench.py — the hot path of ps-auxw/CLI-P on MI355X: ViT-B/32 encode_image throughput and exact
 flat inner-product top-50 search, on synthetic data, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
 
 N > 1 is accepted both ways: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or as plain `python bench.py --gpus N`,
@@ -13,7 +13,9 @@ A "step" is one pass of the hot path over one batch: encode a batch of B synthet
 images on every rank (weak: per-GPU work fixed), then — timed in its own bracket — one search
 batch of Q queries for the best K = 50 + 1 (query-index.py:111: k + offset + 1) over the 10M x 512
 f32 matrix split contiguously over the ranks (strong: total rows fixed), with ONE all-gather of the
-per-rank partial lists and the K-way merge. Rank 0 prints ONE JSON line.
+per-rank partial lists and the K-way merge. Rank 0 prints ONE JSON line; `ms_per_step` in it is one timed encode
+step, the search leg's own is `search.ms_per_step`. `--dump-outputs DIR` also writes what rank 0's last timed step of
+each returned (image_embeds, search_scores, search_ids .npy): the inputs are seeded, the same from run to run.
 
 `value` is images/s (BASELINE.json's first metric, configs[1]); the second metric (queries/s) and its own
 roofline and CPU baseline are in the "search" object of the same line. Further objects in the same line:
@@ -78,6 +80,10 @@ def parse():
     ap.add_argument("--quick", action="store_true",
                     help="headline encode + search only: no sustained / fp8 / ViT-L / shard legs, no CPU baseline "
                          "(profiling passes and tests)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step of the headline computed (the embeddings of the "
+                         "encode step, the scores and ids of the search batch) as DIR/<name>.npy in float32 / float64, "
+                         "at most 64 MB in all: same arguments, same inputs, so two builds can be compared output for output")
     a = ap.parse_args()
     if a.quick:
         a.sustained_images = a.shard_rows = a.l14_batch = 0
@@ -111,11 +117,12 @@ def bracket(dist, world):
     torch.cuda.synchronize()
 
 
-def timed(fn, steps, warmup, dist, world, spread=None):
+def timed(fn, steps, warmup, dist, world, spread=None, after=None):
     """The contract's bracket (barrier + synchronize on both sides of EXACTLY `steps` steps, max over ranks). `spread`:
     a dict that receives per-step min / median / max of a SECOND, per-step-synchronised run of the same steps (host
     clock around fn + synchronize): where a single step stalls (first touch of a fresh allocation, a clock ramp) it shows
-    up here instead of hiding inside the mean. The second run is not part of the reported time."""
+    up here instead of hiding inside the mean. The second run is not part of the reported time. `after`: called once
+    right behind the closing bracket, before that second run - it sees the results of the last timed step."""
     for _ in range(warmup):
         fn()
     bracket(dist, world)
@@ -124,6 +131,8 @@ def timed(fn, steps, warmup, dist, world, spread=None):
         fn()
     bracket(dist, world)
     dt = time.perf_counter() - t0
+    if after is not None:
+        after()
     if world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -160,6 +169,27 @@ def pmc_traffic(key):
     if key not in d:
         return None, f"{f}: no entry {key}"
     return d[key], f"profiles/{f}"
+
+
+DUMP_BYTES = 64 << 20                   # --dump-outputs: the whole dump stays under this
+
+
+def dump_outputs(d, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: every array as <d>/<name>.npy, floats as float32, integers (ids) as float64 (exact below 2**53).
+    An array larger than its share of `budget` keeps a fixed sample of its rows (seed 0, in row order): the same rows
+    from run to run. -> {name: shape written}"""
+    os.makedirs(d, exist_ok=True)
+    share = budget // max(1, len(arrays))
+    shapes = {}
+    for name, x in arrays.items():
+        x = np.asarray(x)
+        x = x.astype(np.float32 if x.dtype.kind == "f" and x.itemsize <= 4 else np.float64)
+        if x.nbytes > share and x.ndim > 0 and x.shape[0] > 1:
+            keep = max(1, min(x.shape[0], share // max(1, x[0].nbytes)))
+            x = x[np.sort(np.random.default_rng(0).choice(x.shape[0], keep, replace=False))]
+        np.save(os.path.join(d, name + ".npy"), x)
+        shapes[name] = list(x.shape)
+    return shapes
 
 
 def make_jpegs(n):
@@ -387,8 +417,9 @@ def scan_probe(L, idx, q, Qp, K, dev, kind):
 _SEARCH_STREAMS = {}
 
 
-def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, warmup, large_q=0):
-    """One search measurement: this rank's `n_local` rows of a `rows_total`-row index, Q queries, K = k + 1."""
+def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, warmup, large_q=0, keep=None):
+    """One search measurement: this rank's `n_local` rows of a `rows_total`-row index, Q queries, K = k + 1. `keep`: called
+    with the (scores, ids) of the last timed step of the headline form."""
     K, Q = a.k + 1, a.queries
     db = unit_rows_device(n_local, dev, seed + rank)          # every shard its own rows (no cross-shard duplicates)
     idx = clipmi.IndexFlatIP(512, device=dev, coarse=None if a.exact_only else a.coarse)
@@ -426,7 +457,8 @@ def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, w
         with torch.cuda.stream(streams[turn[0] % nfl]):
             res[0] = searcher.search_device(q, K)
         turn[0] += 1
-    dt_two = timed(search_step2, steps, nfl * ((warmup + nfl - 1) // nfl), dist, world, sp_two)
+    dt_two = timed(search_step2, steps, nfl * ((warmup + nfl - 1) // nfl), dist, world, sp_two,
+                   after=(lambda: keep(res[0])) if keep is not None else None)
     torch.cuda.synchronize()
     assert torch.equal(res[0][1], ref_i)
     # headline of the leg = ONE declared form, the same in every round and leg: two calls in flight (ADVICE r04 - a best-of-two
@@ -553,6 +585,14 @@ def main():
 
     def enc_step():
         enc_out[0] = model.encode_image(images, normalize=True)
+    # --dump-outputs: host copies of what the last timed step of the headline returned (encode here, search below)
+    dumps = {}
+
+    def keep_enc():
+        dumps["image_embeds"] = enc_out[0].float().cpu().numpy()
+
+    def keep_search(r):
+        dumps["search_scores"], dumps["search_ids"] = r[0].cpu().numpy(), r[1].cpu().numpy()
     # Two forms of the same step (round 5), as the search leg has: ONE kernel sequence of B images on one stream (rounds 1-4's
     # step; the form every per-kernel figure of `roofline` is measured in), and the product's default since round 5 - the step cut
     # into one-round chunks that alternate between the caller's stream and one internal stream (CLIP.image_lanes: 870 images =
@@ -561,7 +601,8 @@ def main():
     for fl in ((1, 2) if a.encode_in_flight == 2 else (1,)):      # (--encode-in-flight 1: the profiled runs hold ONE form only)
         model.chunks_in_flight = fl
         sp_ = {}
-        dt_ = timed(enc_step, a.steps, a.warmup, dist, world, sp_)
+        dt_ = timed(enc_step, a.steps, a.warmup, dist, world, sp_,
+                    after=keep_enc if a.dump_outputs and fl == a.encode_in_flight else None)
         forms[fl] = (dt_, sp_)
     model.chunks_in_flight = a.encode_in_flight
     dt_enc, sp_enc = forms[a.encode_in_flight]
@@ -722,7 +763,8 @@ def main():
 
     # ---------------- search: 10M x 512 f32 split over the ranks, Q queries, K = k + 1 -----------
     lo, hi = clipmi.shard_bounds(a.rows, world, rank)
-    search = search_leg(L, a, dev, dist, world, rank, a.rows, hi - lo, 1000, a.steps, a.warmup, large_q=a.large_q)
+    search = search_leg(L, a, dev, dist, world, rank, a.rows, hi - lo, 1000, a.steps, a.warmup, large_q=a.large_q,
+                        keep=keep_search if a.dump_outputs else None)
     search["metric"] = f"queries/sec top-{a.k} over {a.rows}x512 flat IP (exact results, f32 scores)"
     search["scaling"] = "strong"
     # configs[4] search half: 12.5 M rows on every rank (weak): at N = 8 a 100 M x 512 DB
@@ -797,6 +839,8 @@ def main():
         out["search"]["cpu_baseline"] = cpu_baseline_search(a.rows, Q, K)
     else:
         out["cpu_baseline"] = None
+    if a.dump_outputs:
+        out["dumped_outputs"] = dump_outputs(a.dump_outputs, dumps)
     print(json.dumps(out), flush=True)
     if world > 1:
         dist.barrier()

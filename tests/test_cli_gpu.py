@@ -183,6 +183,33 @@ def test_bench_spawns_its_own_ranks(tmp_path):
     assert r.returncode != 0 and '"error"' in r.stdout
 
 
+def test_bench_dump_outputs_same_inputs_same_outputs(tmp_path):
+    """bench.py --dump-outputs DIR: the embeddings of the last timed encode step and the scores / ids of the last timed search
+    batch as .npy; --steps sets the timed steps the line reports. Two runs with different step counts are given the same
+    inputs, so they write the same bits."""
+    import json
+    got = []
+    for steps in (2, 3):
+        d = tmp_path / f"out{steps}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", "1",
+               "--rows", "200000", "--batch", "64", "--quick", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert line["steps"] == steps and line["search"]["steps"] == steps and line["ms_per_step"] > 0
+        assert line["dumped_outputs"] == {"image_embeds": [64, 512], "search_scores": [64, 51], "search_ids": [64, 51]}
+        o = {k: np.load(d / f"{k}.npy") for k in line["dumped_outputs"]}
+        assert o["image_embeds"].dtype == np.float32 and o["search_scores"].dtype == np.float32
+        assert o["search_ids"].dtype == np.float64
+        assert np.allclose(np.linalg.norm(o["image_embeds"], axis=1), 1.0, atol=1e-3)
+        ids = o["search_ids"]
+        assert np.array_equal(ids, np.round(ids)) and ids.min() >= 0 and ids.max() < 200000
+        assert np.all(np.diff(o["search_scores"], axis=1) <= 0)
+        got.append(o)
+    for k in got[0]:
+        assert np.array_equal(got[0][k], got[1][k]), k
+
+
 def _resize_pipeline_worker(tmp):
     """Own process, the PRODUCT's start order (indexer.main, bench.py): the decode workers are started BEFORE this process
     touches the GPU; only then the model is built."""

@@ -385,3 +385,28 @@ def test_bench_refuses_missing_gpus_and_stale_traffic(tmp_path):
         assert val == rec["gemm_c_fc_bytes_per_launch"] and newest in src
     else:
         assert val is None and "stale" in src
+
+
+def test_bench_dump_outputs_types_and_budget(tmp_path):
+    """bench.py --dump-outputs: float outputs are written as float32, integer ids as float64 (exact), and an output above its
+    share of the size budget keeps a fixed sample of its rows, in row order - the same rows on every run."""
+    sys.path.insert(0, ROOT)
+    import bench
+    x = np.arange(4000 * 8, dtype=np.float32).reshape(4000, 8)
+    ids = np.arange(15, dtype=np.int64).reshape(3, 5) + (1 << 40)
+    budget = 2 * 100 * x[0].nbytes                                  # two arrays: 100 rows of x fit in x's share
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"d{k}"
+        shapes = bench.dump_outputs(str(d), {"image_embeds": x, "search_ids": ids}, budget=budget)
+        assert shapes == {"image_embeds": [100, 8], "search_ids": [3, 5]}
+        assert sum(os.path.getsize(d / f) - 128 for f in os.listdir(d)) <= budget      # (128 B: the .npy header)
+        got_x, got_i = np.load(d / "image_embeds.npy"), np.load(d / "search_ids.npy")
+        assert got_x.dtype == np.float32 and got_i.dtype == np.float64
+        assert np.array_equal(got_i.astype(np.int64), ids)
+        rows = got_x[:, 0].astype(np.int64) // 8
+        assert np.all(np.diff(rows) > 0) and np.array_equal(got_x, x[rows])
+        runs.append(got_x)
+    assert np.array_equal(runs[0], runs[1])
+    small = bench.dump_outputs(str(tmp_path / "s"), {"image_embeds": x[:10].astype(np.float16)})
+    assert small == {"image_embeds": [10, 8]} and np.array_equal(np.load(tmp_path / "s" / "image_embeds.npy"), x[:10])
