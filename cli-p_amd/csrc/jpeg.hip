@@ -22,7 +22,8 @@
 //                            Files with restart intervals need none of that: every interval starts on a byte the host found,
 //                            at a known block, with fresh DC predictions - one thread walks one interval.
 //   jpeg_dc_kernel           DC prediction: per-component running sums over the blocks in scan order
-//   jpeg_idct_kernel         jidctint.c's jpeg_idct_islow with the dequantisation folded in, one block per thread
+//   jpeg_idct_kernel         jidctint.c's jpeg_idct_islow with the dequantisation folded in, one block per thread; a block
+//                            outside the range where libjpeg-turbo's IDCT provably equals it is reported (status 4)
 //   jpeg_color_kernel        jdsample.c's fancy (triangle) upsampling with jdmainct.c's edge rows + jdcolor.c's
 //                            16-bit fixed-point YCbCr -> RGB; rows of width*3 bytes, as Pillow's array
 #include "common.hpp"
@@ -620,8 +621,24 @@ __device__ __forceinline__ void jp_idct8(const int* v, int stride, int* o, int o
 }
 
 // planes of an image (bytes from planes + coef_off * 64): Y [my vs 8][mx hs 8], then Cb, Cr [my 8][mx 8]
+//
+// Status 4: a block outside the range where Pillow's IDCT provably equals this one. libjpeg-turbo runs jpeg_idct_islow in one of
+// two forms, chosen by the CPU it runs on, and both equal int32 arithmetic + a clamp to [0, 255] only on a bounded range:
+//   * SIMD (jidctint-sse2 / -avx2): the dequantisation is a 16-bit multiply (pmullw: the low 16 bits), the pass-1 outputs are
+//     packed to 16 bits with saturation (packssdw; the all-zero-AC column shortcut shifts 16-bit words left instead), and the
+//     sums in0 +- in4, in3 + in7, in1 + in5 of each pass are 16-bit adds (paddw: wrap). Pass 2's outputs are saturated to 8
+//     bits (packssdw, packsswb) before the +128: a clamp.
+//   * C (jidctint.c): int dequantisation and workspace, but the output is range_limit[x & RANGE_MASK] - the clamp for
+//     x in [-512, 511] only (MAXJSAMPLE * 4 + 3 = 1023; outside it the table wraps).
+// So: every dequantised coefficient and every pass-1 output an int16, every pass-2 output in [-512, 511]. That covers the 16-bit
+// sums too: as a linear function of the eight outputs of a pass (the 1-D transform inverted), an input pair's sum is at most
+// 0.31 x the largest |output| in pass 1 (<= 10 031 for int16 outputs) and 39.2 x in pass 2 (<= 20 061 for outputs in
+// [-512, 511]), rounding included. And this kernel's own int32 arithmetic is exact there: with |inputs| <= 32 768 the largest row sum of the 1-D
+// transform's coefficients (61 214) keeps every pre-shift output under 2^31, so the wrap-around of any partial sum cancels.
+// A file outside the range goes back to Pillow (status 4) - whatever the SIMD level of the machine that decodes it there.
+// Files Pillow encodes itself stay far inside it (tests/test_jpeg.py).
 __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restrict__ images, const short* __restrict__ coef_all,
-                                                        unsigned char* __restrict__ planes) {
+                                                        unsigned char* __restrict__ planes, int* __restrict__ status) {
     const JpegImage& im = images[blockIdx.y];
     const int hs = im.ncomp == 1 ? 1 : im.hs, vs = im.ncomp == 1 ? 1 : im.vs;
     const int hv = hs * vs, bpm = im.ncomp == 1 ? 1 : hv + 2;
@@ -647,6 +664,7 @@ __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restr
     }
     const uint4* cp = reinterpret_cast<const uint4*>(coef_all + (im.coef_off + b) * 64);
     int x[64], ws[64];
+    unsigned out16 = 0, out10 = 0;           // nonzero: a value left int16 / [-512, 511] (status 4)
 #pragma unroll
     for (int i = 0; i < 8; ++i) {
         const uint4 q = cp[i];
@@ -655,10 +673,13 @@ __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restr
         for (int j = 0; j < 4; ++j) {
             x[i * 8 + 2 * j] = (int)(short)(u[j] & 0xffff) * im.quant[comp][i * 8 + 2 * j];
             x[i * 8 + 2 * j + 1] = ((int)u[j] >> 16) * im.quant[comp][i * 8 + 2 * j + 1];
+            out16 |= ((unsigned)x[i * 8 + 2 * j] + 32768u) | ((unsigned)x[i * 8 + 2 * j + 1] + 32768u);
         }
     }
 #pragma unroll
     for (int c = 0; c < 8; ++c) jp_idct8<11>(x + c, 8, ws + c, 8);       // pass 1: columns (CONST_BITS - PASS1_BITS)
+#pragma unroll
+    for (int i = 0; i < 64; ++i) out16 |= (unsigned)ws[i] + 32768u;
 #pragma unroll
     for (int r = 0; r < 8; ++r) {
         int o[8];
@@ -666,6 +687,7 @@ __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restr
         unsigned lo = 0, hi = 0;
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
+            out10 |= ((unsigned)o[j] + 512u) | ((unsigned)o[4 + j] + 512u);
             int a = o[j] + 128, c2 = o[4 + j] + 128;
             a = a < 0 ? 0 : (a > 255 ? 255 : a);
             c2 = c2 < 0 ? 0 : (c2 > 255 ? 255 : c2);
@@ -674,6 +696,7 @@ __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restr
         }
         *reinterpret_cast<uint2*>(plane + (size_t)(by * 8 + r) * pw + bx * 8) = make_uint2(lo, hi);
     }
+    if (((out16 >> 16) | (out10 >> 10)) && status[blockIdx.y] == 0) status[blockIdx.y] = 4;     // (the first error found stands)
 }
 
 __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __restrict__ images, const unsigned char* __restrict__ planes,
@@ -772,7 +795,8 @@ extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int 
     CLIPMI_CHECK_LAUNCH("jpeg_huffman_kernel");
     hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)n), dim3(256), 0, st, images, coef);
     CLIPMI_CHECK_LAUNCH("jpeg_dc_kernel");
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes);
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
+                       status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
                        static_cast<unsigned char*>(out_dev));

@@ -5,8 +5,9 @@ rest (Huffman decode in self-synchronising subsequences, DC prediction, jpeg_idc
 bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_crop_rgb8` takes (resize.py). Files this
 parser does not let through (progressive, CMYK / RGB-coded, 12-bit, odd sampling, anything that is not a
 JPEG) raise `Unsupported` and stay with Pillow in the decode workers - that is a choice of decoder per file format, made
-on the host from the file's own header; a file the device then reports as corrupt (status != 0) goes the same way, so
-that Pillow's error handling stays the reference's.
+on the host from the file's own header; a file the device then reports (status != 0: 1 an invalid Huffman code, 2 the data
+ended early or ran over, 3 a marker inside a segment handed over with its stuffing, 4 a block whose IDCT leaves the range where
+libjpeg-turbo's provably equals the device's) goes the same way, so that Pillow's error handling stays the reference's.
 """
 import numpy as np
 import torch

@@ -3,7 +3,9 @@ build-index.py:47). numpy only - the decode workers (decode_worker.py) import th
 
 `parse` lets through what the device decodes - 8-bit baseline / extended-sequential Huffman, one interleaved scan, grey or
 YCbCr with luma sampling 1x1 / 2x1 / 2x2 and 1x1 chroma, with or without restart intervals - and raises `Unsupported` for
-everything else (progressive, CMYK / RGB-coded, 12-bit, arithmetic coding, odd sampling, not a JPEG): those files stay with Pillow.
+everything else (progressive, CMYK / RGB-coded, 12-bit, arithmetic coding, odd sampling, not a JPEG) and every header libjpeg or
+Pillow refuses (a marker either does not know, a second SOI, sampling factors outside 1..4, Huffman codes that overflow their
+lengths, more than JPEG_MAX_DIMENSION or Pillow's decompression-bomb limit of pixels): those files stay with Pillow.
 That is a choice of decoder per file format, made on the host from the file's own header.
 """
 import re
@@ -20,6 +22,12 @@ _INV_NATURAL = np.argsort(_NATURAL)
 
 
 _MARKER = re.compile(rb"\xff[^\x00]")
+# Markers in front of the scan that the walk takes: SOF0/1, DHT, DQT, DRI, APP0-15, COM, SOS, and the other SOFn and DAC, which
+# it refuses by name. Every one of them is in Pillow's JpegImagePlugin.MARKER and read by libjpeg's jdmarker.c read_markers; any
+# other marker there - an unknown code, a second SOI, EOI, RSTn, DNL, JPG, JPGn - is an error for one of the two.
+_KNOWN = frozenset([0xC0, 0xC1, 0xC4, 0xDA, 0xDB, 0xDD, 0xFE, *range(0xC2, 0xD0), *range(0xE0, 0xF0)]) - {0xC8}
+MAX_DIMENSION = 65500          # jmorecfg.h JPEG_MAX_DIMENSION: libjpeg refuses a wider or taller frame (jdinput.c initial_setup)
+MAX_PIXELS = 2 * 89478485      # 2 x PIL.Image.MAX_IMAGE_PIXELS: above it Image.open raises DecompressionBombError
 
 
 class Unsupported(Exception):
@@ -62,16 +70,15 @@ def parse(data, keep_stuffing=False):
         if m == 0xFF:
             i += 1
             continue
-        if m == 0xD8 or m == 0x01 or 0xD0 <= m <= 0xD7:
-            i += 2
-            continue
+        if m not in _KNOWN:
+            raise Unsupported("marker")
         L = (data[i + 2] << 8) | data[i + 3]
         if L < 2 or i + 2 + L > n:
             raise Unsupported("truncated segment")
         if m == 0xDB:
             k = i + 4
             while k < i + 2 + L:
-                if data[k] >> 4 or k + 65 > i + 2 + L:
+                if data[k] >> 4 or (data[k] & 15) > 3 or k + 65 > i + 2 + L:
                     raise Unsupported("quantisation table")
                 qt[data[k] & 15] = data[k + 1:k + 65]
                 k += 65
@@ -83,6 +90,12 @@ def parse(data, keep_stuffing=False):
                 raise Unsupported("frame header")
             frame = ((data[i + 5] << 8) | data[i + 6], (data[i + 7] << 8) | data[i + 8],
                      [(data[i + 10 + 3 * c], data[i + 11 + 3 * c] >> 4, data[i + 11 + 3 * c] & 15, data[i + 12 + 3 * c]) for c in range(nf)])
+            # libjpeg: sampling factors 1..4 on every component, grey included (jdinput.c initial_setup), the size limit; Pillow:
+            # the decompression-bomb limit - checked before anything is sized for the file
+            if any(not (1 <= h <= 4 and 1 <= v <= 4) for _, h, v, _ in frame[2]) or len({c[0] for c in frame[2]}) != nf:
+                raise Unsupported("frame header")
+            if frame[0] > MAX_DIMENSION or frame[1] > MAX_DIMENSION or frame[0] * frame[1] > MAX_PIXELS:
+                raise Unsupported("too many pixels")
         elif 0xC2 <= m <= 0xCF and m != 0xC4 and m != 0xC8 and m != 0xCC:
             raise Unsupported("not a baseline frame")
         elif m == 0xCC:
@@ -97,13 +110,19 @@ def parse(data, keep_stuffing=False):
                     raise Unsupported("Huffman table")
                 if (data[k] >> 4) == 0 and cnt and max(data[k + 17:k + 17 + cnt]) > 15:
                     raise Unsupported("DC Huffman table")               # libjpeg refuses such a table (jdhuff.c)
+                code = 0                                                # canonical codes: every length's last code fits its
+                for l in range(1, 17):                                  # length and is not all ones (jdhuff.c
+                    code += data[k + l]                                 # jpeg_make_d_derived_tbl)
+                    if code >= 1 << l:
+                        raise Unsupported("Huffman table")
+                    code <<= 1
                 huff[data[k]] = bytes(data[k + 1:k + 17 + cnt]).ljust(272, b"\0") + bytes([data[k] >> 4]) + b"\0" * 15
                 k += 17 + cnt
         elif m == 0xDD:
             if L != 4:
                 raise Unsupported("restart interval")
             ri = (data[i + 4] << 8) | data[i + 5]
-        elif m == 0xE0 and data[i + 4:i + 9] == b"JFIF\0":
+        elif m == 0xE0 and L >= 16 and data[i + 4:i + 9] == b"JFIF\0":
             jfif = True
         elif m == 0xEE and L >= 14 and data[i + 4:i + 9] == b"Adobe":
             adobe, adobe_tf = True, data[i + 15]

@@ -261,7 +261,8 @@ int clipmi_resize_crop_rgb8(const void* raw_dev, const void* jobs_dev, int njobs
  * then the table class - 0 DC, 1 AC - and 15 zero bytes).
  * out_dev: per image height rows of width*3 RGB bytes at out_off (grey files replicated, as Image.convert("RGB") does) - the
  * layout clipmi_resize_crop_rgb8 takes. status_dev[i]: 0 decoded; 1 invalid Huffman code; 2 the data ended early or ran
- * over; 3 a marker inside a segment handed over with its stuffing - such a file goes back to Pillow, whose error handling is the reference's. total_blocks = sum of the images' 8x8 blocks
+ * over; 3 a marker inside a segment handed over with its stuffing; 4 a block outside the range where libjpeg-turbo's IDCT equals
+ * the device's (a dequantised coefficient or pass-1 value beyond int16, an output beyond [-512, 511]) - such a file goes back to Pillow, whose error handling is the reference's. total_blocks = sum of the images' 8x8 blocks
  * (coef_off counts in blocks), max_blocks / max_pixels = the largest image's. */
 typedef struct clipmi_jpeg_image {
     int64_t stream_off;           /* bytes from streams_dev */

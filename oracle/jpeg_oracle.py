@@ -18,6 +18,8 @@ every supported sampling, odd sizes included, with both and demands identical by
 
 Only tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg may import this module.
 """
+import functools
+
 import numpy as np
 
 NATURAL = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14,
@@ -27,6 +29,18 @@ NATURAL = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 
 
 class Unsupported(Exception):
     """A JPEG the device decoder does not take (progressive, CMYK, ...): Pillow's path decodes it."""
+
+
+class Reported(Exception):
+    """A file the device decoder hands back to Pillow after looking at its data (status != 0): here, a block whose IDCT leaves
+    the range where libjpeg-turbo's IDCT provably equals the plain arithmetic below (see idct_islow)."""
+
+
+# jdmarker.c read_markers / Pillow's JpegImagePlugin.MARKER: the markers a file may hold in front of its scan (SOFn other than
+# SOF0 / SOF1 are refused by name); JPEG_MAX_DIMENSION; 2 x PIL.Image.MAX_IMAGE_PIXELS (DecompressionBombError above it)
+HEADER_MARKERS = ({0xC0, 0xC1, 0xC4, 0xDA, 0xDB, 0xDD, 0xFE} | set(range(0xC2, 0xD0)) | set(range(0xE0, 0xF0))) - {0xC8}
+MAX_DIMENSION = 65500
+MAX_PIXELS = 2 * 89478485
 
 
 def parse(data):
@@ -46,6 +60,8 @@ def parse(data):
         if m == 0xFF:
             i += 1
             continue
+        if m not in HEADER_MARKERS:
+            raise Unsupported("marker")
         L = int.from_bytes(data[i + 2:i + 4], "big")
         seg = data[i + 4:i + 2 + L]
         if len(seg) != L - 2:
@@ -53,32 +69,52 @@ def parse(data):
         if m == 0xDB:
             k = 0
             while k < len(seg):
-                if seg[k] >> 4:
-                    raise Unsupported("16-bit quantisation table")
+                if seg[k] >> 4 or seg[k] & 15 > 3 or k + 65 > len(seg):
+                    raise Unsupported("quantisation table")
                 qt[seg[k] & 15] = list(seg[k + 1:k + 65])
                 k += 65
         elif m in (0xC0, 0xC1):
             if seg[0] != 8:
                 raise Unsupported("precision")
             height, width = int.from_bytes(seg[1:3], "big"), int.from_bytes(seg[3:5], "big")
+            if comps is not None or len(seg) < 6 or len(seg) != 6 + 3 * seg[5]:
+                raise Unsupported("frame")
             comps = [(seg[6 + 3 * c], seg[7 + 3 * c] >> 4, seg[7 + 3 * c] & 15, seg[8 + 3 * c]) for c in range(seg[5])]
-        elif 0xC2 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
-            raise Unsupported("not a baseline frame")
+            if any(not (1 <= c[1] <= 4 and 1 <= c[2] <= 4) for c in comps) or len({c[0] for c in comps}) != len(comps):
+                raise Unsupported("sampling factors / component ids")          # jdinput.c initial_setup
+            if max(width, height) > MAX_DIMENSION or width * height > MAX_PIXELS:
+                raise Unsupported("too many pixels")
+        elif 0xC2 <= m <= 0xCF and m != 0xC4:
+            raise Unsupported("not a baseline frame")            # (and DAC: arithmetic coding)
         elif m == 0xC4:
             k = 0
             while k < len(seg):
                 bits = list(seg[k + 1:k + 17])
                 cnt = sum(bits)
+                if len(bits) != 16 or cnt > 256 or k + 17 + cnt > len(seg) or seg[k] >> 4 > 1 or seg[k] & 15 > 3:
+                    raise Unsupported("Huffman table")
+                if seg[k] >> 4 == 0 and cnt and max(seg[k + 17:k + 17 + cnt]) > 15:
+                    raise Unsupported("DC Huffman table")
+                code = 0                               # jpeg_make_d_derived_tbl: no code of length l reaches 1 << l (all ones)
+                for length in range(1, 17):
+                    code += bits[length - 1]
+                    if code >= 1 << length:
+                        raise Unsupported("Huffman table")
+                    code <<= 1
                 huff[(seg[k] >> 4, seg[k] & 15)] = (bits, list(seg[k + 17:k + 17 + cnt]))
                 k += 17 + cnt
         elif m == 0xDD:
+            if L != 4:
+                raise Unsupported("restart interval")
             ri = int.from_bytes(seg[:2], "big")
-        elif m == 0xE0 and seg[:5] == b"JFIF\0":
+        elif m == 0xE0 and len(seg) >= 14 and seg[:5] == b"JFIF\0":
             jfif = True
         elif m == 0xEE and seg[:5] == b"Adobe" and len(seg) >= 12:
             adobe, adobe_tf = True, seg[11]
         elif m == 0xDA:
-            ns = seg[0]
+            ns = seg[0] if seg else 0
+            if L != 6 + 2 * ns or seg[1 + 2 * ns:4 + 2 * ns] != b"\x00\x3f\x00":
+                raise Unsupported("scan header")
             scan = [(seg[1 + 2 * c], seg[2 + 2 * c] >> 4, seg[2 + 2 * c] & 15) for c in range(ns)]
             i += 2 + L
             break
@@ -87,6 +123,8 @@ def parse(data):
         raise Unsupported("no frame")
     if len(comps) not in (1, 3) or len(scan) != len(comps) or [s[0] for s in scan] != [c[0] for c in comps]:
         raise Unsupported("components / scans")
+    if any((0, s[1]) not in huff or (1, s[2]) not in huff for s in scan) or any(c[3] not in qt for c in comps):
+        raise Unsupported("missing table")
     if len(comps) == 3:
         ids = tuple(c[0] for c in comps)
         # jdapimin.c default_decompress_parms: which 3-component files are YCbCr
@@ -123,6 +161,7 @@ def parse(data):
     return dict(width=width, height=height, comps=comps, qt=qt, huff=huff, scan=scan, stream=b"".join(parts), ri=ri, starts=starts)
 
 
+@functools.lru_cache(maxsize=64)                 # (a corpus of files that share their tables builds each once)
 def _huff_lut(bits, vals):
     """16-bit look-up: code length and symbol for every 16-bit window (jdhuff.c jpeg_make_d_derived_tbl's code
     assignment: canonical, shortest first)."""
@@ -150,7 +189,7 @@ def decode_coefficients(info):
     order = []
     for ci, c in enumerate(comps):
         order += [ci] * (c[1] * c[2] if len(comps) > 1 else 1)
-    luts = {k: _huff_lut(*v) for k, v in info["huff"].items()}
+    luts = {k: _huff_lut(tuple(v[0]), tuple(v[1])) for k, v in info["huff"].items()}
     s = info["stream"] + b"\0" * 8
     win = [int.from_bytes(s[k:k + 4], "big") for k in range(len(s) - 3)]
     nbits = 8 * len(info["stream"])
@@ -208,7 +247,10 @@ def decode_coefficients(info):
 
 def idct_islow(coef, q):
     """jidctint.c jpeg_idct_islow on [n][64] natural-order coefficients with the 64 quantisation steps q (natural order)
-    -> uint8 [n][8][8]."""
+    -> uint8 [n][8][8]. Raises Reported where a block leaves the range in which libjpeg-turbo's IDCT - the SIMD forms with
+    16-bit dequantisation and workspace, the C form with `range_limit[x & RANGE_MASK]` - equals this arithmetic and a clamp:
+    every dequantised coefficient and every pass-1 output an int16, every pass-2 output in [-512, 511] (csrc/jpeg.hip
+    jpeg_idct_kernel derives the bound; the device reports such a file with status 4)."""
     C = dict(f0298=2446, f0390=3196, f0541=4433, f0765=6270, f0899=7373, f1175=9633, f1501=12299, f1847=15137, f1961=16069,
              f2053=16819, f2562=20995, f3072=25172)
     x = (coef.astype(np.int64) * q.astype(np.int64)[None, :]).reshape(-1, 8, 8)
@@ -230,8 +272,14 @@ def idct_islow(coef, q):
         r = np.stack([t10 + o3, t11 + o2, t12 + o1, t13 + o0, t13 - o0, t12 - o1, t11 - o2, t10 - o3], axis=-1)
         return (r + (1 << (shift - 1))) >> shift
 
+    if x.size and (x.min() < -32768 or x.max() > 32767):
+        raise Reported("dequantised coefficient outside int16")
     ws = one_d(x.transpose(0, 2, 1), 11).transpose(0, 2, 1)      # pass 1: columns, CONST_BITS - PASS1_BITS
+    if ws.size and (ws.min() < -32768 or ws.max() > 32767):
+        raise Reported("pass-1 workspace outside int16")
     px = one_d(ws, 18)                                           # pass 2: rows, CONST_BITS + PASS1_BITS + 3
+    if px.size and (px.min() < -512 or px.max() > 511):
+        raise Reported("IDCT output outside [-512, 511]")
     return np.clip(px + 128, 0, 255).astype(np.uint8)
 
 

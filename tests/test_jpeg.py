@@ -2,12 +2,14 @@
 (oracle/jpeg_oracle.py) against Pillow itself and against the committed Pillow outputs, and the host parser."""
 import io
 import os
+import re
 
 import numpy as np
 import pytest
 from PIL import Image
 
 import clipmi
+import jpeg_corpus
 from clipmi import jpeg_parse
 from oracle import jpeg_oracle
 
@@ -174,3 +176,97 @@ def test_worker_regions_and_the_records_built_from_them(tmp_path):
         vc = np.frombuffer(big, np.int32, count=plan["vcoef"].size, offset=4 * int(j["vcoef_off"]))
         assert np.array_equal(hc, plan["hcoef"]) and np.array_equal(vc, plan["vcoef"])
     assert np.array_equal(jobs["tmp_off"], np.cumsum(jobs["nrows"].astype(np.int64) * n_px * 3) - jobs["nrows"].astype(np.int64) * n_px * 3)
+
+
+def _marker_in_stuffed_segment(p):
+    """What jpeg_unstuff_kernel looks for in a segment handed over with its stuffing (then the device reports the file, status 3)"""
+    return p.stuffed == 1 and (re.search(rb"\xff[^\x00]", p.stream) is not None or p.stream.endswith(b"\xff"))
+
+
+def test_parser_accepts_only_files_pillow_decodes():
+    """The device path's contract on the host side, over the seeded corpus of malformed files (tests/jpeg_corpus.py): a file
+    jpeg_parse.parse lets through, Pillow decodes - a file Pillow refuses the reference skips, so the parser must refuse it too
+    (a refusal only sends a file to Pillow). With keep_stuffing the device finishes the marker walk inside the scan; a segment
+    it would find a marker in is reported there (test_jpeg_gpu.py), so it is not counted here."""
+    files = jpeg_corpus.corpus()
+    accepted, wrong = 0, []
+    for fam, name, blob in files:
+        got = []
+        for ks in (False, True):
+            try:
+                p = jpeg_parse.parse(blob, keep_stuffing=ks)
+            except jpeg_parse.Unsupported:
+                continue
+            if not _marker_in_stuffed_segment(p):
+                got.append(ks)
+        if not got:
+            continue
+        accepted += 1
+        if jpeg_corpus.pillow(blob) is None:
+            wrong.append((fam, name, got))
+    assert not wrong, f"{len(wrong)} files parse accepts and Pillow refuses, e.g. {wrong[:8]}"
+    assert accepted > 10000 and len(files) > 20000
+    by = {}
+    for fam, name, blob in files:                     # every forged header Pillow refuses is refused by the parser
+        by.setdefault(fam, []).append(blob)
+    for fam in ("c:dht_dc_overflow", "c:dht_ac_overflow", "c:dht_dc_all_ones", "c:dht_ac_all_ones", "c:sampling_00", "c:sampling_51",
+                "c:second_soi", "c:size_20000x20000", "c:size_65535x65535"):
+        for blob in by[fam]:
+            assert jpeg_corpus.pillow(blob) is None, fam
+            for ks in (False, True):
+                with pytest.raises(jpeg_parse.Unsupported):
+                    jpeg_parse.parse(blob, keep_stuffing=ks)
+                with pytest.raises(jpeg_oracle.Unsupported):
+                    jpeg_oracle.parse(blob)
+    for fam in ("c:dht_dc_full", "c:dht_ac_full", "c:dqt_zero"):          # ... and the valid edge cases are taken
+        for blob in by[fam]:
+            assert np.array_equal(jpeg_oracle.decode(blob), jpeg_corpus.pillow(blob)), fam
+
+
+def test_parser_markers_are_pillows():
+    """The markers the parser walks over in front of the scan are all in Pillow's own table (JpegImagePlugin.MARKER), and the
+    pixel limit is Pillow's decompression-bomb limit."""
+    from PIL import JpegImagePlugin
+    assert all(0xFF00 | m in JpegImagePlugin.MARKER for m in jpeg_parse._KNOWN)
+    assert jpeg_parse._KNOWN == jpeg_oracle.HEADER_MARKERS
+    assert jpeg_parse.MAX_PIXELS == jpeg_oracle.MAX_PIXELS == 2 * Image.MAX_IMAGE_PIXELS
+
+
+def test_oracle_on_quantisation_table_mutations_equals_pillow_or_reports():
+    """Family (a) restricted to DQT: the entropy-coded data is intact, only the steps change (up to 255 on a coefficient that
+    was quantised for a step of 2). The oracle - the device's arithmetic - gives Pillow's pixels or raises Reported, where
+    libjpeg-turbo's 16-bit IDCT would leave the plain arithmetic (the device: status 4)."""
+    files = [f for f in jpeg_corpus.header_mutations(jpeg_corpus.base_files()) if f[0] == "a:DQT:body"]
+    n_eq = n_rep = 0
+    for fam, name, blob in files:
+        try:
+            jpeg_parse.parse(blob)
+        except jpeg_parse.Unsupported:
+            continue
+        ref = jpeg_corpus.pillow(blob)
+        assert ref is not None
+        try:
+            got = jpeg_oracle.decode(blob)
+        except jpeg_oracle.Reported:
+            n_rep += 1
+            continue
+        assert np.array_equal(got, ref), name
+        n_eq += 1
+    assert n_eq > 4000 and n_rep > 0
+
+
+@pytest.mark.parametrize("sub", [0, 1, 2, "grey"])
+def test_pillow_encoded_files_stay_inside_the_idct_range(sub):
+    """Status 4 costs real files nothing: Pillow's own encodes, quality 1 to 100, noise and checkerboards, never leave the
+    range where the device's IDCT equals libjpeg-turbo's."""
+    rng = np.random.default_rng(27)
+    yy, xx = np.mgrid[0:48, 0:64]
+    contents = [rng.integers(0, 256, (48, 64, 3), dtype=np.uint8),
+                np.repeat((((xx // 8 + yy // 8) % 2) * 255).astype(np.uint8)[..., None], 3, -1),
+                np.repeat((((xx + yy) % 2) * 255).astype(np.uint8)[..., None], 3, -1),
+                np.stack([((xx % 2) * 255), ((yy % 2) * 255), (((xx + yy) % 2) * 255)], -1).astype(np.uint8),
+                smooth(rng, 48, 64)]
+    for q in (1, 5, 50, 100):
+        for a in contents:
+            blob = encode(a[..., 0], quality=q) if sub == "grey" else encode(a, quality=q, subsampling=sub)
+            assert np.array_equal(jpeg_oracle.decode(blob), np.asarray(Image.open(io.BytesIO(blob)).convert("RGB")))

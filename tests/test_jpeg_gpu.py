@@ -1,5 +1,8 @@
-"""csrc/jpeg.hip against Pillow itself (the reference's decoder, build-index.py:47) and the committed Pillow pixels:
-bit-exact RGB for every file the host parser lets through; corrupt files are reported, not mis-decoded."""
+"""csrc/jpeg.hip against Pillow itself (the reference's decoder, build-index.py:47) and the committed Pillow pixels. The rule:
+every file the device returns pixels for (status 0) gives exactly Pillow's `convert("RGB")` bytes; a file Pillow refuses is
+never returned; anything else is handed back (Unsupported on the host, status != 0 from the device) and Pillow decides.
+Well-formed files are returned, not handed back."""
+import collections
 import io
 
 import numpy as np
@@ -9,6 +12,8 @@ from PIL import Image
 
 import clipmi
 from clipmi import jpeg, jpeg_parse
+from oracle import jpeg_oracle
+import jpeg_corpus
 from test_jpeg import encode, golden_cases, smooth
 
 pytestmark = pytest.mark.gpu
@@ -87,16 +92,78 @@ def test_corrupt_entropy_data_is_reported_or_decoded_as_pillow_does():
         (g,) = jpeg.decode_files([bad], DEV)
         if g is None:
             continue                                             # reported: the file goes to Pillow
-        import warnings
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            try:
-                ref = pillow(bad)
-            except Exception:
-                continue                                         # Pillow refuses the file; the device decoded what was there
-        if np.array_equal(g, ref):
-            n_checked += 1
+        ref = jpeg_corpus.pillow(bad)
+        assert ref is not None, "the device returned pixels for a file Pillow refuses"
+        assert np.array_equal(g, ref)
+        n_checked += 1
     assert n_checked >= 4
+
+
+def _decode_with_status(blobs, keep_stuffing):
+    """-> [(status, pixels)] per file: status None where the host parser refuses the file, pixels only for status 0"""
+    items, where = [], []
+    for k, b in enumerate(blobs):
+        try:
+            items.append(jpeg_parse.parse(b, keep_stuffing=keep_stuffing))
+            where.append(k)
+        except jpeg_parse.Unsupported:
+            pass
+    res = [(None, None)] * len(blobs)
+    if not items:
+        return res
+    out, recs, status = jpeg.decode_device(items, DEV)
+    st = status.cpu().numpy()
+    host = out.cpu().numpy()
+    for t, k in enumerate(where):
+        px = None
+        if st[t] == 0:
+            r = recs[t]
+            h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
+            px = host[o:o + h * w * 3].reshape(h, w, 3)
+        res[k] = (int(st[t]), px)
+    return res
+
+
+def test_malformed_corpus_is_reported_or_decoded_as_pillow_does():
+    """The seeded corpus of malformed files (tests/jpeg_corpus.py: header bytes replaced, entropy-coded data damaged, forged
+    headers) through the device, plain and with the stuffing left to the device: status 0 only with Pillow's exact pixels,
+    never for a file Pillow refuses. The counts by family and status are printed (pytest -s)."""
+    files = jpeg_corpus.corpus()
+    refs = {}
+    counts = collections.Counter()
+    wrong = []
+    for ks in (False, True):
+        for lo in range(0, len(files), 4096):
+            chunk = files[lo:lo + 4096]
+            for k, (st, px) in enumerate(_decode_with_status([b for _, _, b in chunk], ks)):
+                fam, name, blob = chunk[k]
+                kind = ":".join(fam.split(":")[:2])
+                counts[(kind, ks, "refused" if st is None else st)] += 1
+                if fam == "a:DQT:body" and st is not None:   # intact data, new steps: the device reports where the oracle does
+                    try:
+                        jpeg_oracle.decode(blob)
+                        reported = False
+                    except jpeg_oracle.Reported:
+                        reported = True
+                    if reported != (st == 4):
+                        wrong.append((fam, name, ks, f"status {st}, oracle reported: {reported}"))
+                if st != 0:
+                    continue
+                if lo + k not in refs:
+                    refs[lo + k] = jpeg_corpus.pillow(blob)
+                ref = refs[lo + k]
+                if ref is None or not np.array_equal(px, ref):
+                    diff = "Pillow refuses" if ref is None else int(np.abs(px.astype(int) - ref.astype(int)).max())
+                    wrong.append((fam, name, ks, diff))
+    print("\nfamily, keep_stuffing: files by status (refused = the host parser hands the file to Pillow)")
+    for kind in sorted({c[0] for c in counts}):
+        for ks in (False, True):
+            row = {st: n for (k_, ks_, st), n in counts.items() if k_ == kind and ks_ == ks}
+            print(f"  {kind:22s} {str(ks):5s} " + " ".join(f"{st}={row[st]}" for st in sorted(row, key=str)))
+    print(f"status 0 with pixels other than Pillow's: {len(wrong)}", wrong[:20])
+    assert not wrong
+    assert sum(n for (k_, ks_, st), n in counts.items() if k_ == "a:DQT" and st == 4) > 0
+    assert sum(n for (k_, ks_, st), n in counts.items() if st == 0) > 20000
 
 
 def test_marker_inside_a_stuffed_segment_is_reported():
