@@ -2,7 +2,7 @@
 """bench.py — the hot path of ps-auxw/CLI-P on MI355X: ViT-B/32 encode_image throughput and exact
 flat inner-product top-50 search, on synthetic data, one process per GPU.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 N > 1 is accepted both ways: launched by `python -m torch.distributed.run --nproc-per-node N ... bench.py
 --gpus N ...` (RANK / LOCAL_RANK / WORLD_SIZE in the environment), or as plain `python bench.py --gpus N`,
@@ -17,8 +17,11 @@ per-rank partial lists and the K-way merge. Rank 0 prints ONE JSON line; `ms_per
 step, the search leg's own is `search.ms_per_step`. `--dump-outputs DIR` also writes what rank 0's last timed step of
 each returned (image_embeds, search_scores, search_ids .npy): the inputs are seeded, the same from run to run.
 
-`value` is images/s (BASELINE.json's first metric, configs[1]); the second metric (queries/s) and its own
-roofline and CPU baseline are in the "search" object of the same line. Further objects in the same line:
+`value` is images/s (BASELINE.json's first metric, configs[1]); the second metric (queries/s) is in the "search"
+object of the same line. A plain run times the headline form of the two and nothing else, so both `roofline` objects
+hold only the figures of the whole step and call. `--full` adds everything else: the other form of each, a per-step
+spread of every timed form, per-kernel rooflines (runs of their own), sweeps over batch and query counts, one prompt
+through the text tower, the CPU baselines, and these objects of the same line:
   encode_sustained      the same encode step for >= 1 M images (configs[1] says "encode 1M images": ~11 s)
   encode_fp8            configs[4] encode half (FP8 linear layers)
   encode_vitl14_336     configs[3]: ViT-L/14@336px, own MFMA roofline
@@ -26,6 +29,7 @@ roofline and CPU baseline are in the "search" object of the same line. Further o
                         all-gather merge when N > 1: at N = 8 this IS the 100 M-row sharded search)
   cpu_baseline          configs[0] as SURVEY.md §8(d) specifies it (256 JPEGs, B = 1; B = 32 beside it;
                         flat-IP top-11 over the 256 x 512 result for 16 image-id + 16 text queries)
+  files_to_vectors      build-index.py's loop from JPEG files on disk (one GPU)
 """
 import argparse
 import ctypes as C
@@ -50,7 +54,10 @@ PEAK_BF16_TFLOPS = 2500.0               # MI355X dense bf16 MFMA (MI355X_MICROAR
 PEAK_HBM_GBS = 8000.0                   # MI355X HBM3E spec
 
 
-def parse():
+FULL_LEGS = {"sustained_images": 1_000_000, "shard_rows": 12_500_000, "l14_batch": 266, "large_q": 1024}   # defaults under --full
+
+
+def parse(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
@@ -66,30 +73,38 @@ def parse():
     ap.add_argument("--coarse", choices=["int8", "bf16"], default="int8",
                     help="coarse copy scanned before the exact f32 re-scoring (results are identical either way)")
     ap.add_argument("--k", type=int, default=50, help="results per query (K = k + 1 is searched)")
-    ap.add_argument("--sustained-images", type=int, default=1_000_000, help="images of the encode_sustained leg (0 = skip)")
-    ap.add_argument("--shard-rows", type=int, default=12_500_000, help="rows per rank of the search_shard leg (0 = skip)")
-    ap.add_argument("--l14-batch", type=int, default=266, help="images per step of the ViT-L/14@336px leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline too (other forms, spreads, per-kernel rooflines, sweeps, the "
+                         "sustained / FP8 / ViT-L / shard / many-query / files-to-vectors legs, CPU baselines), shaped by "
+                         "--sustained-images, --shard-rows, --l14-batch, --no-cpu-baseline, --no-fp8, --large-q and --quick")
+    ap.add_argument("--sustained-images", type=int, default=None, help="images of the encode_sustained leg (default 1M; 0 = skip)")
+    ap.add_argument("--shard-rows", type=int, default=None, help="rows per rank of the search_shard leg (default 12.5M; 0 = skip)")
+    ap.add_argument("--l14-batch", type=int, default=None, help="images per step of the ViT-L/14@336px leg (default 266; 0 = skip)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-fp8", action="store_true", help="skip the FP8 (configs[4]) encode measurement")
-    ap.add_argument("--large-q", type=int, default=-1,
+    ap.add_argument("--large-q", type=int, default=None,
                     help="queries of the one-call-many-queries leg (default 1024; 0 = skip; --quick skips it unless given)")
     ap.add_argument("--encode-in-flight", type=int, default=2, choices=[1, 2],
                     help="kernel sequences of ONE encode step kept in flight (CLIP.chunks_in_flight): 2 = the product's default "
                          "(two half-batches on two streams), 1 = one sequence on one stream - the form the rocprofv3 summaries under "
                          "profiles/ are taken in, so that per-kernel averages are averages over one shape and no overlap")
     ap.add_argument("--quick", action="store_true",
-                    help="headline encode + search only: no sustained / fp8 / ViT-L / shard legs, no CPU baseline "
-                         "(profiling passes and tests)")
+                    help="with --full: no sustained / fp8 / ViT-L / shard legs, no sweeps, no CPU baseline (profiling passes "
+                         "and tests); a plain run is leaner still and ignores it")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step of the headline computed (the embeddings of the "
                          "encode step, the scores and ids of the search batch) as DIR/<name>.npy in float32 / float64, "
                          "at most 64 MB in all: same arguments, same inputs, so two builds can be compared output for output")
-    a = ap.parse_args()
-    if a.quick:
+    a = ap.parse_args(argv)
+    for k, default in FULL_LEGS.items():
+        if not a.full and getattr(a, k):
+            ap.error(f"--{k.replace('_', '-')} sizes a leg that only --full measures")
+        if getattr(a, k) is None:
+            setattr(a, k, default if a.full and not a.quick else 0)
+    if a.quick:                                     # (a --large-q given beside it stays)
         a.sustained_images = a.shard_rows = a.l14_batch = 0
+    if a.quick or not a.full:
         a.no_cpu_baseline = a.no_fp8 = True
-    if a.large_q < 0:
-        a.large_q = 0 if a.quick else 1024
     return a
 
 
@@ -378,9 +393,14 @@ def unit_rows_device(n, dev, seed):
     return db
 
 
+# bytes one pass of the dominant search kernel streams per row of the index, by the copy it scans
+SCAN_ROW_BYTES = {"int8": 512 + 8,          # int8 row + its (scale, error norm) pair
+                  "bf16": 512 * 2, "f32": 512 * 4}
+
+
 def scan_probe(L, idx, q, Qp, K, dev, kind):
     """The dominant search kernel alone: HIP events recorded by the library around it on the launch stream.
-    -> (ms, survivors per query or None, algorithmic bytes, kernel name, traffic key)"""
+    -> (ms, survivors per query or None, kernel name, traffic key)"""
     db = idx.matrix()
     n_local = db.shape[0]
     os_ = torch.empty((64, K), dtype=torch.float32, device=dev)
@@ -395,7 +415,7 @@ def scan_probe(L, idx, q, Qp, K, dev, kind):
                                                               rmax, q.data_ptr(), Qp, K, os_.data_ptr(), oi_.data_ptr(),
                                                               ws.data_ptr(), ws.numel(), clipmi._lib.stream_ptr(dev), 10,
                                                               C.byref(scan_ms), C.byref(survivors)), "coarse_i8_scan_ms")
-        return (scan_ms.value, survivors.value / Qp, n_local * (512 + 8),     # int8 row + its (scale, error norm) pair
+        return (scan_ms.value, survivors.value / Qp,
                 f"scan_coarse_kernel<512,{qg},*,true> (three launches stream the copy once)", "scan_coarse_i8_bytes_per_pass")
     if kind == "bf16":
         dbh, rmax = idx.matrix_bf16()
@@ -404,22 +424,97 @@ def scan_probe(L, idx, q, Qp, K, dev, kind):
                                                            K, os_.data_ptr(), oi_.data_ptr(), ws.data_ptr(), ws.numel(),
                                                            clipmi._lib.stream_ptr(dev), 10, C.byref(scan_ms),
                                                            C.byref(survivors)), "coarse_scan_ms")
-        return (scan_ms.value, survivors.value / Qp, n_local * 512 * 2,
+        return (scan_ms.value, survivors.value / Qp,
                 f"scan_coarse_kernel<512,{qg},false,false>", "scan_coarse_bytes_per_launch")
     ws = torch.empty(L.clipmi_topk_ip_workspace_bytes(n_local, 512, Qp, K), dtype=torch.uint8, device=dev)
     clipmi._lib.check(L.clipmi_dbg_topk_scan_ms(db.data_ptr(), n_local, 512, q.data_ptr(), Qp, K, os_.data_ptr(),
                                                 oi_.data_ptr(), ws.data_ptr(), ws.numel(), clipmi._lib.stream_ptr(dev),
                                                 10, C.byref(scan_ms)), "scan_ms")
-    return (scan_ms.value, None, n_local * 512 * 4, f"scan_topk_f32_kernel<512,false,{2 if Qp > 16 else 1}>",
+    return (scan_ms.value, None, f"scan_topk_f32_kernel<512,false,{2 if Qp > 16 else 1}>",
             "scan_bytes_per_launch")
+
+
+def encode_kernel_roofline(L, model, images, B, dev):
+    """--full: the per-kernel part of the encode step's `roofline`, from runs of the library's probe of their own."""
+    # The encode step's GEMMs timed IN SITU: HIP events recorded by the library around its launches on the launch stream.
+    # The DOMINANT family by time is the residual producer gemm256p<7, false> (out_proj K = 768 + c_proj K = 3072: 24 launches,
+    # ~41 % of the step): `roofline` reports it; the c_fc GEMM (28 % of the step, the kernel `roofline` named up to round 3)
+    # is beside it as `roofline.c_fc`.
+    M, N, Kd = B * 50, 3072, 768
+    need = L.clipmi_encode_image_workspace_bytes(model.vision, B)
+    ews = torch.empty(need, dtype=torch.uint8, device=dev)
+    eout = torch.empty((B, 512), dtype=torch.float32, device=dev)
+
+    def probe(epi):
+        ms3, nl, kkind, kepi = (C.c_float * 3)(), C.c_int(0), C.c_int(-1), C.c_int(-1)
+        clipmi._lib.check(L.clipmi_dbg_encode_image_probe3_ms(model.vision, model._vblob.data_ptr(), images.data_ptr(),
+                                                              clipmi._lib.U8, B, eout.data_ptr(), ews.data_ptr(), ews.numel(),
+                                                              clipmi._lib.stream_ptr(dev), epi, 3, ms3, C.byref(nl), C.byref(kkind),
+                                                              C.byref(kepi)), "encode_image_probe3")
+        sym = (["gemm_bf16_nt_kernel<%d>", "gemm256_bf16_nt_kernel<%d>", "gemm256p_bf16_nt_kernel<%d, false>"][kkind.value]
+               % kepi.value) if 0 <= kkind.value <= 2 else "?"
+        return [float(v) for v in ms3], nl.value, sym
+    # The kernel's in-situ duration: completion of the kernel directly in front -> completion of this one. For c_fc that is
+    # ms3[2] (the GEMM in front is the residual producer of the same block, no kernel between them); for the residual
+    # producers ms3[1] (an event recorded in front of the launch: out_proj follows attention, c_proj follows c_fc) - the
+    # kernel + one kernel boundary, the estimator that agrees with rocprofv3's dispatch duration (profiles/). The launch's
+    # own begin -> end events (ms3[0]) read ~14 % long in a back-to-back stream: the begin stamp is taken when the packet is
+    # processed, before the previous kernel has drained. All estimators are in the line.
+    ms_fc, nl_fc, sym_fc = probe(1)
+    fc_ms = ms_fc[2] if ms_fc[2] > 0 else ms_fc[1] if ms_fc[1] > 0 else ms_fc[0]
+    fc_tflops = 2.0 * M * N * Kd / (fc_ms * 1e-3) / 1e12
+    rs_flop = (2.0 * M * 768 * 768 + 2.0 * M * 768 * 3072) / 2.0           # per launch, averaged over the pair
+    rs_parts = None
+    try:
+        # completion of the kernel directly in front -> completion of this one (ms3[2], the estimator that agrees with
+        # rocprofv3): c_proj (K = 3072) follows c_fc, out_proj (K = 768) follows attention, whose launch carries its own end
+        # stamp in this mode. Average of the pair = the family.
+        ms_cp, nl_cp, sym_rs = probe(2 | (3072 << 8))
+        ms_op, nl_op, _ = probe(2 | (768 << 8))
+        cp_ms = ms_cp[2] if ms_cp[2] > 0 else ms_cp[1]
+        op_ms = ms_op[2] if ms_op[2] > 0 else ms_op[1]
+        rs_ms, nl_rs = (cp_ms + op_ms) / 2.0, nl_cp + nl_op
+        ms_rs = [(ms_cp[0] + ms_op[0]) / 2.0, (ms_cp[1] + ms_op[1]) / 2.0, 0.0]
+        rs_parts = {"c_proj_K3072": {"kernel_ms": cp_ms, "tflops": 2.0 * M * 768 * 3072 / (cp_ms * 1e-3) / 1e12,
+                                     "estimator": "completion_to_completion", "completion_to_completion": ms_cp[2],
+                                     "event_in_front_to_end": ms_cp[1], "launch_begin_to_end_events": ms_cp[0]},
+                    "out_proj_K768": {"kernel_ms": op_ms, "tflops": 2.0 * M * 768 * 768 / (op_ms * 1e-3) / 1e12,
+                                      "estimator": "completion_to_completion" if ms_op[2] > 0 else "event_in_front_to_end",
+                                      "completion_to_completion": ms_op[2], "event_in_front_to_end": ms_op[1],
+                                      "launch_begin_to_end_events": ms_op[0]}}
+    except clipmi.ClipmiError:
+        # small batches (fewer tiles than CUs): the residual producer runs as GEMM-into-scratch + split_stats, which this
+        # probe does not bracket - report the c_fc GEMM in its place (not the headline configuration)
+        ms_rs, nl_rs, sym_rs, rs_ms, rs_flop = ms_fc, nl_fc, sym_fc + " [residual producer not on the persistent kernel at this batch: c_fc reported]", fc_ms, 2.0 * M * N * Kd
+    rs_tflops = rs_flop / (rs_ms * 1e-3) / 1e12
+    traffic, tsrc = pmc_traffic("gemm_resid_bytes_per_launch")
+    traffic_fc, tsrc_fc = pmc_traffic("gemm_c_fc_bytes_per_launch")
+    return {"kernel": sym_rs + f" (residual producers: attn.out_proj K=768 and mlp.c_proj K=3072, M={M} N=768, + bias + "
+                              f"split-residual update + LayerNorm statistics; the dominant kernel by time: 24 launches per step)",
+            "achieved": rs_tflops, "frac": rs_tflops / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": tsrc,
+            "kernel_ms": rs_ms, "launches_timed": nl_rs,
+            "algorithmic_flop_per_launch": rs_flop,
+            "kernel_ms_estimators": {"event_in_front_to_end": ms_rs[1], "launch_begin_to_end_events": ms_rs[0],
+                                     "used": "mean of c_proj and out_proj, each completion of the kernel in front -> own completion"},
+            "per_shape": rs_parts,
+            "c_fc": {"kernel": sym_fc + f" (MLP c_fc + LayerNorm fold + bias + QuickGELU, M={M} N={N} K={Kd}; 12 launches per step)",
+                     "achieved": fc_tflops, "frac": fc_tflops / PEAK_BF16_TFLOPS, "kernel_ms": fc_ms,
+                     "launches_timed": nl_fc, "traffic": traffic_fc, "traffic_source": tsrc_fc,
+                     "kernel_ms_estimators": {"completion_to_completion": ms_fc[2], "event_in_front_to_end": ms_fc[1],
+                                              "launch_begin_to_end_events": ms_fc[0]}},
+            "kernel_figures_form": "one_sequence: every per-kernel figure above is measured inside ONE kernel sequence of "
+                                   f"{B} images on one stream (M = {M}: the library's own probe), the form the rocprofv3 summaries "
+                                   "under profiles/ are taken in (bench.py --full --encode-in-flight 1); with two sequences in flight "
+                                   "two launches of half the rows share the chip and a launch's own duration says nothing"}
 
 
 _SEARCH_STREAMS = {}
 
 
-def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, warmup, large_q=0, keep=None):
+def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, warmup, large_q=0, keep=None, full=True):
     """One search measurement: this rank's `n_local` rows of a `rows_total`-row index, Q queries, K = k + 1. `keep`: called
-    with the (scores, ids) of the last timed step of the headline form."""
+    with the (scores, ids) of the last timed step of the headline form. `full=False`: the headline form alone (no per-step
+    spread, no kernel probe; large_q must be 0)."""
     K, Q = a.k + 1, a.queries
     db = unit_rows_device(n_local, dev, seed + rank)          # every shard its own rows (no cross-shard duplicates)
     idx = clipmi.IndexFlatIP(512, device=dev, coarse=None if a.exact_only else a.coarse)
@@ -437,10 +532,10 @@ def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, w
 
     def search_step():
         res[0] = searcher.search_device(q, K)
-    sp_one, sp_two = {}, {}
-    dt_one = timed(search_step, steps, warmup, dist, world, sp_one)
-    assert (res[0][1][:, 0] >= 0).all()
-    ref_i = res[0][1].clone()
+    sp_one, sp_two = ({}, {}) if full else (None, None)
+    if full:
+        dt_one = timed(search_step, steps, warmup, dist, world, sp_one)
+        ref_i = res[0][1].clone()
     # the same K steps with TWO batches in flight on two HIP streams (every call owns its stream's workspace and
     # result buffers): one batch's short latency-bound kernels (pre-pass, re-scoring, selects, merge) run beside the
     # other batch's HBM-bound scan. Results are identical; throughput is what BASELINE.json's queries/s asks for.
@@ -460,33 +555,36 @@ def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, w
     dt_two = timed(search_step2, steps, nfl * ((warmup + nfl - 1) // nfl), dist, world, sp_two,
                    after=(lambda: keep(res[0])) if keep is not None else None)
     torch.cuda.synchronize()
-    assert torch.equal(res[0][1], ref_i)
+    assert (res[0][1][:, 0] >= 0).all()
+    if full:
+        assert torch.equal(res[0][1], ref_i)
     # headline of the leg = ONE declared form, the same in every round and leg: two calls in flight (ADVICE r04 - a best-of-two
     # chosen after measuring biases the figure upward and makes rounds incomparable); the other form is published beside it.
     # CLIPMI_BENCH_IN_FLIGHT=1 makes the two forms the same.
     dt_s = dt_two
     headline_form = "two_batches_in_flight"
     Qp = min(Q, 64 if coarse else 32)            # queries of ONE pass
-    scan_ms, surv, scan_bytes, scan_name, traffic_key = scan_probe(L, idx, q, Qp, K, dev, kind)
-    scan_gbs = scan_bytes / (scan_ms * 1e-3) / 1e9
+    scan_bytes = n_local * SCAN_ROW_BYTES[kind]
     passes = (Q + Qp - 1) // Qp
-    traffic, tsrc = pmc_traffic(traffic_key)
     out = {"value": Q * steps / dt_s, "unit": "queries/s", "ms_per_step": dt_s / steps * 1e3, "steps": steps,
            "batches_in_flight": nfl, "headline_form": headline_form,
-           "one_batch_in_flight": dict({"value": Q * steps / dt_one, "ms_per_step": dt_one / steps * 1e3}, **sp_one),
-           "two_batches_in_flight": dict({"value": Q * steps / dt_two, "ms_per_step": dt_two / steps * 1e3}, **sp_two),
+           "two_batches_in_flight": dict({"value": Q * steps / dt_two, "ms_per_step": dt_two / steps * 1e3}, **(sp_two or {})),
            "dtype": ("int8 coarse scan (i32 MFMA) + f32 exact re-scoring" if kind == "int8" else
                      "bf16 coarse scan + f32 exact re-scoring" if kind == "bf16" else "f32"),
            "path": ("coarse-then-exact (clipmi_topk_ip_coarse_i8)" if kind == "int8" else
                     "coarse-then-exact (clipmi_topk_ip_coarse)" if kind == "bf16" else "exact scan (clipmi_topk_ip)"),
            "queries_per_batch": Q, "K": K, "rows_per_gpu": n_local, "rows_total": rows_total,
-           "roofline": {"bound": "hbm", "kernel": scan_name, "achieved": scan_gbs, "peak": PEAK_HBM_GBS, "unit": "GB/s",
-                        "frac": scan_gbs / PEAK_HBM_GBS, "traffic": traffic, "traffic_source": tsrc,
-                        "kernel_ms": scan_ms, "algorithmic_bytes_per_launch": scan_bytes,
-                        "coarse_survivors_per_query": surv,
+           "roofline": {"bound": "hbm", "peak": PEAK_HBM_GBS, "unit": "GB/s", "algorithmic_bytes_per_launch": scan_bytes,
                         "whole_call_gbs_per_gpu": scan_bytes * passes * steps / dt_s / 1e9,
-                        "whole_call_frac": scan_bytes * passes * steps / dt_s / 1e9 / PEAK_HBM_GBS,
-                        "whole_call_frac_one_in_flight": scan_bytes * passes * steps / dt_one / 1e9 / PEAK_HBM_GBS}}
+                        "whole_call_frac": scan_bytes * passes * steps / dt_s / 1e9 / PEAK_HBM_GBS}}
+    if full:
+        scan_ms, surv, scan_name, traffic_key = scan_probe(L, idx, q, Qp, K, dev, kind)
+        scan_gbs = scan_bytes / (scan_ms * 1e-3) / 1e9
+        traffic, tsrc = pmc_traffic(traffic_key)
+        out["one_batch_in_flight"] = dict({"value": Q * steps / dt_one, "ms_per_step": dt_one / steps * 1e3}, **sp_one)
+        out["roofline"].update({"kernel": scan_name, "achieved": scan_gbs, "frac": scan_gbs / PEAK_HBM_GBS, "traffic": traffic,
+                                "traffic_source": tsrc, "kernel_ms": scan_ms, "coarse_survivors_per_query": surv,
+                                "whole_call_frac_one_in_flight": scan_bytes * passes * steps / dt_one / 1e9 / PEAK_HBM_GBS})
     # ONE search call of 1024 queries (query-index.py:111 is one index.search call whatever Q): the int8 path takes it as ONE
     # wide pass of the copy (csrc/topk.hip scan_coarse_wide_kernel: query tiles resident in LDS, integer MFMA). Two rooflines:
     # SURVEY.md 8(d)'s bytes (the copy streamed once per call) against HBM, and 2 N Q E int8 operations against the dense
@@ -501,7 +599,7 @@ def search_leg(L, a, dev, dist, world, rank, rows_total, n_local, seed, steps, w
         sp_big = {}
         dt_big = timed(big_step, 5, 2, dist, world, sp_big)
         ms_call = dt_big / 5 * 1e3
-        copy_bytes = n_local * (512 + 8) if kind == "int8" else n_local * 1024
+        copy_bytes = n_local * SCAN_ROW_BYTES[kind]
         ops = 2.0 * n_local * large_q * 512
         out["one_call_many_queries"] = dict({
             "queries": large_q, "value": large_q * 5 / dt_big, "unit": "queries/s", "ms_per_call": ms_call, "steps": 5,
@@ -596,14 +694,21 @@ def main():
     # Two forms of the same step (round 5), as the search leg has: ONE kernel sequence of B images on one stream (rounds 1-4's
     # step; the form every per-kernel figure of `roofline` is measured in), and the product's default since round 5 - the step cut
     # into one-round chunks that alternate between the caller's stream and one internal stream (CLIP.image_lanes: 870 images =
-    # two sequences of 435 in flight). The headline is ONE declared form: --encode-in-flight (default 2); both are published.
+    # two sequences of 435 in flight). The headline is ONE declared form: --encode-in-flight (default 2); --full publishes both.
+    full = a.full
+    if not full and a.encode_in_flight == 2:
+        # --full times the one-sequence form before the headline. One untimed call of that form keeps what the run did for
+        # the headline here: the model's first call (code object load, the workspace of the caller's stream) stays out of
+        # the headline's steps, whatever --warmup is
+        model.chunks_in_flight = 1
+        enc_step()
     forms = {}
-    for fl in ((1, 2) if a.encode_in_flight == 2 else (1,)):      # (--encode-in-flight 1: the profiled runs hold ONE form only)
+    for fl in ((1, 2) if full and a.encode_in_flight == 2 else (a.encode_in_flight,)):   # (--encode-in-flight 1: ONE form only)
         model.chunks_in_flight = fl
-        sp_ = {}
+        sp_ = {} if full else None
         dt_ = timed(enc_step, a.steps, a.warmup, dist, world, sp_,
                     after=keep_enc if a.dump_outputs and fl == a.encode_in_flight else None)
-        forms[fl] = (dt_, sp_)
+        forms[fl] = (dt_, sp_ or {})
     model.chunks_in_flight = a.encode_in_flight
     dt_enc, sp_enc = forms[a.encode_in_flight]
     img_per_s = world * B * a.steps / dt_enc
@@ -649,7 +754,7 @@ def main():
     # SURVEY.md 8(d) cfg-2 sweep: images/s at B in {64, 128, 256, 512} (compact: 10 synchronised steps each), beside the
     # headline's B - the number a caller gets without knowing which batch sizes fill whole rounds of GEMM tiles
     enc_sweep = None
-    if not a.quick:
+    if full and not a.quick:
         enc_sweep = {}
         for Bs in (64, 128, 256, 512):
             imgs_s = images[:Bs] if Bs <= B else torch.randint(0, 256, (Bs, 3, 224, 224), generator=g, device=dev, dtype=torch.uint8)
@@ -663,7 +768,7 @@ def main():
     # tokenizer hands them over (EOT at position 9: the tower runs on 10 positions, skinny GEMM kernels), beside the CPU
     # baseline's text_encode_ms_per_query
     text_one = None
-    if not a.quick:
+    if full and not a.quick:
         ids1 = torch.zeros(1, 77, dtype=torch.int64)
         ids1[0, 0] = 49406; ids1[0, 1:9] = torch.randint(1, 40000, (8,)); ids1[0, 9] = 49407
         ids77 = ids1.clone(); ids77[0, 9] = 5; ids77[0, 76] = 49407
@@ -679,58 +784,13 @@ def main():
                     "what": "encode_text + normalise of ONE prompt, back-to-back calls on one stream (10 tokens incl. SOT / EOT; "
                             "and a prompt that fills all 77 positions)"}
 
-    # The encode step's GEMMs timed IN SITU: HIP events recorded by the library around its launches on the launch stream.
-    # The DOMINANT family by time is the residual producer gemm256p<7, false> (out_proj K = 768 + c_proj K = 3072: 24 launches,
-    # ~41 % of the step): `roofline` reports it; the c_fc GEMM (28 % of the step, the kernel `roofline` named up to round 3)
-    # is beside it as `roofline.c_fc`.
-    M, N, Kd = B * 50, 3072, 768
-    need = L.clipmi_encode_image_workspace_bytes(model.vision, B)
-    ews = torch.empty(need, dtype=torch.uint8, device=dev)
-    eout = torch.empty((B, 512), dtype=torch.float32, device=dev)
-
-    def probe(epi):
-        ms3, nl, kkind, kepi = (C.c_float * 3)(), C.c_int(0), C.c_int(-1), C.c_int(-1)
-        clipmi._lib.check(L.clipmi_dbg_encode_image_probe3_ms(model.vision, model._vblob.data_ptr(), images.data_ptr(),
-                                                              clipmi._lib.U8, B, eout.data_ptr(), ews.data_ptr(), ews.numel(),
-                                                              clipmi._lib.stream_ptr(dev), epi, 3, ms3, C.byref(nl), C.byref(kkind),
-                                                              C.byref(kepi)), "encode_image_probe3")
-        sym = (["gemm_bf16_nt_kernel<%d>", "gemm256_bf16_nt_kernel<%d>", "gemm256p_bf16_nt_kernel<%d, false>"][kkind.value]
-               % kepi.value) if 0 <= kkind.value <= 2 else "?"
-        return [float(v) for v in ms3], nl.value, sym
-    # The kernel's in-situ duration: completion of the kernel directly in front -> completion of this one. For c_fc that is
-    # ms3[2] (the GEMM in front is the residual producer of the same block, no kernel between them); for the residual
-    # producers ms3[1] (an event recorded in front of the launch: out_proj follows attention, c_proj follows c_fc) - the
-    # kernel + one kernel boundary, the estimator that agrees with rocprofv3's dispatch duration (profiles/). The launch's
-    # own begin -> end events (ms3[0]) read ~14 % long in a back-to-back stream: the begin stamp is taken when the packet is
-    # processed, before the previous kernel has drained. All estimators are in the line.
-    ms_fc, nl_fc, sym_fc = probe(1)
-    fc_ms = ms_fc[2] if ms_fc[2] > 0 else ms_fc[1] if ms_fc[1] > 0 else ms_fc[0]
-    fc_tflops = 2.0 * M * N * Kd / (fc_ms * 1e-3) / 1e12
-    rs_flop = (2.0 * M * 768 * 768 + 2.0 * M * 768 * 3072) / 2.0           # per launch, averaged over the pair
-    rs_parts = None
-    try:
-        # completion of the kernel directly in front -> completion of this one (ms3[2], the estimator that agrees with
-        # rocprofv3): c_proj (K = 3072) follows c_fc, out_proj (K = 768) follows attention, whose launch carries its own end
-        # stamp in this mode. Average of the pair = the family.
-        ms_cp, nl_cp, sym_rs = probe(2 | (3072 << 8))
-        ms_op, nl_op, _ = probe(2 | (768 << 8))
-        cp_ms = ms_cp[2] if ms_cp[2] > 0 else ms_cp[1]
-        op_ms = ms_op[2] if ms_op[2] > 0 else ms_op[1]
-        rs_ms, nl_rs = (cp_ms + op_ms) / 2.0, nl_cp + nl_op
-        ms_rs = [(ms_cp[0] + ms_op[0]) / 2.0, (ms_cp[1] + ms_op[1]) / 2.0, 0.0]
-        rs_parts = {"c_proj_K3072": {"kernel_ms": cp_ms, "tflops": 2.0 * M * 768 * 3072 / (cp_ms * 1e-3) / 1e12,
-                                     "estimator": "completion_to_completion", "completion_to_completion": ms_cp[2],
-                                     "event_in_front_to_end": ms_cp[1], "launch_begin_to_end_events": ms_cp[0]},
-                    "out_proj_K768": {"kernel_ms": op_ms, "tflops": 2.0 * M * 768 * 768 / (op_ms * 1e-3) / 1e12,
-                                      "estimator": "completion_to_completion" if ms_op[2] > 0 else "event_in_front_to_end",
-                                      "completion_to_completion": ms_op[2], "event_in_front_to_end": ms_op[1],
-                                      "launch_begin_to_end_events": ms_op[0]}}
-    except clipmi.ClipmiError:
-        # small batches (fewer tiles than CUs): the residual producer runs as GEMM-into-scratch + split_stats, which this
-        # probe does not bracket - report the c_fc GEMM in its place (not the headline configuration)
-        ms_rs, nl_rs, sym_rs, rs_ms, rs_flop = ms_fc, nl_fc, sym_fc + " [residual producer not on the persistent kernel at this batch: c_fc reported]", fc_ms, 2.0 * M * N * Kd
-    rs_tflops = rs_flop / (rs_ms * 1e-3) / 1e12
-    del ews, eout, model, images
+    roofline = {"bound": "mfma", "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                "whole_step_tflops_per_gpu": FLOP_PER_IMAGE * B * a.steps / dt_enc / 1e12,
+                "whole_step_frac": FLOP_PER_IMAGE * B * a.steps / dt_enc / 1e12 / PEAK_BF16_TFLOPS}
+    if full:
+        roofline.update(encode_kernel_roofline(L, model, images, B, dev),
+                        whole_step_frac_one_sequence=enc_forms["one_sequence"]["whole_step_frac"])
+    del model, images
     torch.cuda.empty_cache()
 
     # ---------------- configs[3]: ViT-L/14@336px (24 layers, width 1024, 577 tokens, 768-D) -----------------------
@@ -764,7 +824,7 @@ def main():
     # ---------------- search: 10M x 512 f32 split over the ranks, Q queries, K = k + 1 -----------
     lo, hi = clipmi.shard_bounds(a.rows, world, rank)
     search = search_leg(L, a, dev, dist, world, rank, a.rows, hi - lo, 1000, a.steps, a.warmup, large_q=a.large_q,
-                        keep=keep_search if a.dump_outputs else None)
+                        keep=keep_search if a.dump_outputs else None, full=full)
     search["metric"] = f"queries/sec top-{a.k} over {a.rows}x512 flat IP (exact results, f32 scores)"
     search["scaling"] = "strong"
     # configs[4] search half: 12.5 M rows on every rank (weak): at N = 8 a 100 M x 512 DB
@@ -781,8 +841,6 @@ def main():
             dist.destroy_process_group()
         return
 
-    traffic, tsrc = pmc_traffic("gemm_resid_bytes_per_launch")
-    traffic_fc, tsrc_fc = pmc_traffic("gemm_c_fc_bytes_per_launch")
     K, Q = a.k + 1, a.queries
     out = {
         "metric": "images/sec ViT-B/32 encode", "value": img_per_s, "unit": "images/s",
@@ -794,28 +852,7 @@ def main():
                                f"inputs resident in HBM; then exact-result flat-IP top-{K} (k={a.k}+1, "
                                f"query-index.py:111) over {a.rows} x 512 f32 split over {world} GPU(s), Q={Q} per batch",
                    "images_per_gpu_per_step": B, "index_rows_total": a.rows, "queries_per_batch": Q, "K": K},
-        "roofline": {"bound": "mfma",
-                     "kernel": sym_rs + f" (residual producers: attn.out_proj K=768 and mlp.c_proj K=3072, M={M} N=768, + bias + "
-                                        f"split-residual update + LayerNorm statistics; the dominant kernel by time: 24 launches per step)",
-                     "achieved": rs_tflops, "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-                     "frac": rs_tflops / PEAK_BF16_TFLOPS, "traffic": traffic, "traffic_source": tsrc,
-                     "kernel_ms": rs_ms, "launches_timed": nl_rs,
-                     "algorithmic_flop_per_launch": rs_flop,
-                     "kernel_ms_estimators": {"event_in_front_to_end": ms_rs[1], "launch_begin_to_end_events": ms_rs[0],
-                                              "used": "mean of c_proj and out_proj, each completion of the kernel in front -> own completion"},
-                     "per_shape": rs_parts,
-                     "c_fc": {"kernel": sym_fc + f" (MLP c_fc + LayerNorm fold + bias + QuickGELU, M={M} N={N} K={Kd}; 12 launches per step)",
-                              "achieved": fc_tflops, "frac": fc_tflops / PEAK_BF16_TFLOPS, "kernel_ms": fc_ms,
-                              "launches_timed": nl_fc, "traffic": traffic_fc, "traffic_source": tsrc_fc,
-                              "kernel_ms_estimators": {"completion_to_completion": ms_fc[2], "event_in_front_to_end": ms_fc[1],
-                                                       "launch_begin_to_end_events": ms_fc[0]}},
-                     "kernel_figures_form": "one_sequence: every per-kernel figure above is measured inside ONE kernel sequence of "
-                                            f"{B} images on one stream (M = {M}: the library's own probe), the form the rocprofv3 summaries "
-                                            "under profiles/ are taken in (bench.py --encode-in-flight 1); with two sequences in flight two "
-                                            "launches of half the rows share the chip and a launch's own duration says nothing",
-                     "whole_step_tflops_per_gpu": FLOP_PER_IMAGE * B * a.steps / dt_enc / 1e12,
-                     "whole_step_frac": FLOP_PER_IMAGE * B * a.steps / dt_enc / 1e12 / PEAK_BF16_TFLOPS,
-                     "whole_step_frac_one_sequence": enc_forms["one_sequence"]["whole_step_frac"]},
+        "roofline": roofline,
         "search": search,
     }
     if text_one is not None:

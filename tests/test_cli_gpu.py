@@ -153,10 +153,10 @@ def _check_bench_line(stdout):
 
 
 def test_bench_contract_under_torchrun_one_rank(tmp_path):
-    """bench.py launched the way the driver launches N>1 (torch.distributed.run), with one rank and a
+    """bench.py --full launched the way the driver launches N>1 (torch.distributed.run), with one rank and a
     small index: one JSON line with the contract's keys; the small configs[3]/configs[4] legs are in the line."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr",
-           "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+           "127.0.0.1", "--master-port", "29731", os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--full",
            "--warmup", "1", "--rows", "200000", "--batch", "64", "--no-cpu-baseline", "--no-fp8", "--sustained-images", "256",
            "--shard-rows", "150000", "--l14-batch", "0"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)

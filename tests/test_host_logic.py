@@ -410,3 +410,25 @@ def test_bench_dump_outputs_types_and_budget(tmp_path):
     assert np.array_equal(runs[0], runs[1])
     small = bench.dump_outputs(str(tmp_path / "s"), {"image_embeds": x[:10].astype(np.float16)})
     assert small == {"image_embeds": [10, 8]} and np.array_equal(np.load(tmp_path / "s" / "image_embeds.npy"), x[:10])
+
+
+def test_bench_plain_run_leaves_the_other_legs_to_full():
+    """A plain bench.py run measures the headline alone: every leg beside it is off, and asking for one without --full is a
+    usage error rather than a leg silently skipped. --full keeps the defaults every leg had, and --quick its meaning there."""
+    sys.path.insert(0, ROOT)
+    import bench
+    legs = ("sustained_images", "shard_rows", "l14_batch", "large_q")
+    for argv in ([], ["--quick"], ["--sustained-images", "0", "--no-fp8"]):
+        a = bench.parse(argv)
+        assert not a.full and all(getattr(a, k) == 0 for k in legs) and a.no_cpu_baseline and a.no_fp8
+    for flag in ("--sustained-images", "--shard-rows", "--l14-batch", "--large-q"):
+        with pytest.raises(SystemExit) as e:
+            bench.parse([flag, "256"])
+        assert e.value.code == 2
+    a = bench.parse(["--full"])
+    assert (a.sustained_images, a.shard_rows, a.l14_batch, a.large_q) == (1_000_000, 12_500_000, 266, 1024)
+    assert not a.no_cpu_baseline and not a.no_fp8
+    a = bench.parse(["--full", "--quick", "--large-q", "512", "--sustained-images", "256"])
+    assert (a.sustained_images, a.shard_rows, a.l14_batch, a.large_q) == (0, 0, 0, 512) and a.no_cpu_baseline and a.no_fp8
+    a = bench.parse(["--full", "--sustained-images", "256", "--shard-rows", "150000", "--l14-batch", "0", "--no-fp8"])
+    assert (a.sustained_images, a.shard_rows, a.l14_batch, a.large_q) == (256, 150000, 0, 1024) and a.no_fp8
