@@ -196,7 +196,9 @@ size_t clipmi_i8_meta_bytes(int64_t N);
  *  returns a permutation by construction.) */
 int clipmi_quantize_rows_i8(const float* db_dev, int64_t N, int E, const uint32_t* perm_dev, void* out_i8_dev, size_t out_i8_bytes,
                             float* meta_dev, size_t meta_bytes, void* stream);
-/* out_dev[r] = largest |x_rk| of row r (f32 [N]); E a multiple of 4. Asynchronous on `stream`. */
+/* out_dev[r] = largest |x_rk| of row r (f32 [N]); E a multiple of 4. Asynchronous on `stream`.
+ * NaN components are skipped (the maximum is taken with fmaxf): a row of NaN and finite values gives its largest finite
+ * |x|, NaN beside +-inf gives +inf, a row of NaN only gives 0. */
 int clipmi_rows_absmax(const float* db_dev, int64_t N, int E, float* out_dev, void* stream);
 /* perm_dev[t] (u32 [N]) = the row that belongs in slot t of the int8 copy: the rows ordered by their largest |component|,
  * ascending, equal maxima in row order (a stable radix sort of clipmi_rows_absmax's values on the device; no framework sort is
