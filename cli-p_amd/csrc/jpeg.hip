@@ -755,6 +755,351 @@ __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __rest
     o[2] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
 }
 
+
+// ---- Progressive files (SOF2, Huffman; ITU T.81 Annex G as libjpeg's jdphuff.c decodes it). The host (jpeg_parse.parse_progressive)
+// hands over only files whose scan script is complete - every coefficient of every component at Al = 0 by EOI - so that
+// libjpeg applies no block smoothing and the output is jpeg_idct_islow of the final coefficients. jpeg_progressive_kernel
+// writes those final coefficients (absolute DC, every refinement applied) into the buffer jpeg_idct_kernel reads, in its MCU
+// order; jpeg_idct_kernel and jpeg_color_kernel then run as for a baseline file (jpeg_dc_kernel does not: the walk predicts DC).
+//
+// Progressive symbols need the symbol itself (EOBn's run bits, a refinement's (r, s)), which the baseline entry does not keep:
+// a second table form, entry = code length << 8 | symbol.
+struct JppLut {
+    unsigned short fast[1 << JP_FAST];   // length << 8 | symbol of codes of up to JP_FAST bits, 0 = longer (or invalid)
+    int maxcode[18];
+    int valoff[18];
+    unsigned char vals[256];
+};
+static_assert(sizeof(JppLut) % 16 == 0, "tables are copied as 16-byte pieces");
+
+struct JpegScan {              // mirrors clipmi_jpeg_scan (include/clipmi.h)
+    long long stream_off;
+    int stream_bytes;
+    int ncomp;
+    int comp[3];
+    int tbl[3];
+    int ss, se, ah, al;
+    int reserved[2];
+};
+
+struct JpegProgImage {         // mirrors clipmi_jpeg_progressive_image
+    long long coef_off, out_off;
+    int width, height;
+    int ncomp;
+    int hs, vs;
+    int first_scan, n_scans;
+    int reserved[5];
+    unsigned char quant[3][64];
+};
+
+__global__ void __launch_bounds__(256) jpeg_build_pluts_kernel(const unsigned char* __restrict__ raw, JppLut* __restrict__ luts) {
+    __shared__ int first_code[18], first_idx[18];
+    const unsigned char* t = raw + (size_t)blockIdx.x * JP_RAW;
+    JppLut& L = luts[blockIdx.x];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < (1 << JP_FAST); i += 256) L.fast[i] = 0;
+    if (tid == 0) {
+        int code = 0, k = 0;
+        for (int l = 1; l <= 16; ++l) {
+            const int n = t[l - 1];
+            first_code[l] = code;
+            first_idx[l] = k;
+            L.maxcode[l] = n ? code + n - 1 : -1;
+            L.valoff[l] = k - code;
+            code = (code + n) << 1;
+            k += n;
+        }
+        first_idx[17] = k > 256 ? 256 : k;
+        L.maxcode[0] = L.maxcode[17] = -1;
+        L.valoff[0] = L.valoff[17] = 0;
+    }
+    L.vals[tid] = t[16 + tid];
+    __syncthreads();
+    if (tid < first_idx[17]) {
+        int l = 1;
+        while (l < 16 && tid >= first_idx[l + 1]) ++l;
+        const int code = first_code[l] + (tid - first_idx[l]);
+        if (l <= JP_FAST && code < (1 << l)) {
+            const int base = code << (JP_FAST - l);
+            for (int j = 0; j < (1 << (JP_FAST - l)); ++j) L.fast[base + j] = (unsigned short)((l << 8) | t[16 + tid]);
+        }
+    }
+}
+
+// A lane's bit reader over one scan's segment: 64 bits buffered, MSB first (bits behind the segment read as zeros).
+struct JppBits {
+    const unsigned* src;
+    unsigned nwords, wpos, p;
+    unsigned long long buf;
+    int nb;
+    __device__ __forceinline__ void fill() {
+        while (nb <= 32) {
+            const unsigned w = wpos < nwords ? __builtin_bswap32(src[wpos]) : 0u;
+            buf |= (unsigned long long)w << (32 - nb);
+            ++wpos;
+            nb += 32;
+        }
+    }
+    __device__ __forceinline__ unsigned peek() {
+        fill();
+        return (unsigned)(buf >> 32);
+    }
+    __device__ __forceinline__ void skip(int n) {
+        buf <<= n;
+        nb -= n;
+        p += (unsigned)n;
+    }
+    __device__ __forceinline__ int get(int n) {          // n <= 16
+        if (!n) return 0;
+        const int v = (int)(peek() >> (32 - n));
+        skip(n);
+        return v;
+    }
+    // the next Huffman symbol, -1 for no such code
+    __device__ __forceinline__ int sym(const JppLut& L) {
+        const unsigned x = peek();
+        unsigned e = L.fast[x >> (32 - JP_FAST)];
+        if (!e) {
+            for (int l = JP_FAST + 1; l <= 16; ++l) {
+                const int code = (int)(x >> (32 - l));
+                if (code <= L.maxcode[l]) {
+                    e = (unsigned)(l << 8) | L.vals[(code + L.valoff[l]) & 255];
+                    break;
+                }
+            }
+            if (!e) return -1;
+        }
+        skip((int)(e >> 8));
+        return (int)(e & 255);
+    }
+};
+
+__device__ __forceinline__ int jpp_extend(int v, int s) { return s && v < (1 << (s - 1)) ? v - (1 << s) + 1 : v; }
+
+constexpr int JPP_T = 64;            // one wave per image: its lanes walk the image's independent scan chains
+constexpr int JPP_MAX_SCANS = 128;
+
+// One workgroup (one wave) per image. Scans that share no (component, coefficient) pair do not depend on each other: lane 0
+// groups the scans into chains (a scan joins every earlier scan it shares a pair with), and every lane walks whole chains,
+// scan after scan, block after block - a serial walk per chain. In libjpeg's standard YCbCr script the chains are the DC
+// scans, Cb's two, Cr's two and luma's four. Each chain writes only its own coefficients, so lanes never write the same int16.
+// Status: 1 an invalid Huffman code, a coefficient behind its band or a record the kernel cannot take; 2 a scan's data ran out.
+__global__ void __launch_bounds__(JPP_T) jpeg_progressive_kernel(const unsigned char* __restrict__ streams,
+                                                                const JpegProgImage* __restrict__ pimages,
+                                                                const JpegScan* __restrict__ scans_all, int nscans_all,
+                                                                const JppLut* __restrict__ luts, int ntables,
+                                                                JpegImage* __restrict__ images, short* __restrict__ coef_all,
+                                                                int* __restrict__ status) {
+    __shared__ unsigned long long mask[JPP_MAX_SCANS][3];
+    __shared__ int root[JPP_MAX_SCANS];
+    __shared__ int roots[JPP_MAX_SCANS];
+    __shared__ int nroots, bad, ran_out;
+    __shared__ unsigned char nat[80];
+    const JpegProgImage& pim = pimages[blockIdx.x];
+    const int tid = threadIdx.x;
+    const int ncomp = pim.ncomp;
+    const int hs = ncomp == 1 ? 1 : pim.hs, vs = ncomp == 1 ? 1 : pim.vs;
+    const int hv = hs * vs, bpm = ncomp == 1 ? 1 : hv + 2;
+    const int mx = hs > 0 ? (pim.width + 8 * hs - 1) / (8 * hs) : 0, my = vs > 0 ? (pim.height + 8 * vs - 1) / (8 * vs) : 0;
+    const int nsc = pim.n_scans, s0 = pim.first_scan;
+    short* coef = coef_all + pim.coef_off * 64;
+    const bool valid = nsc >= 1 && nsc <= JPP_MAX_SCANS && s0 >= 0 && s0 <= nscans_all - nsc && (ncomp == 1 || ncomp == 3) &&
+                       pim.width >= 1 && pim.height >= 1 && hs >= 1 && hs <= 2 && vs >= 1 && vs <= hs;
+    if (tid == 0) {                                     // the record jpeg_idct_kernel / jpeg_color_kernel read
+        JpegImage r{};
+        r.coef_off = pim.coef_off;
+        r.out_off = pim.out_off;
+        r.ncomp = 1;                                    // a record outside the limits: an empty grey image, nothing to do
+        r.hs = r.vs = 1;
+        if (valid) {
+            r.width = pim.width;
+            r.height = pim.height;
+            r.ncomp = ncomp;
+            r.hs = pim.hs;
+            r.vs = pim.vs;
+            for (int c = 0; c < 3; ++c)
+                for (int k = 0; k < 64; ++k) r.quant[c][k] = pim.quant[c][k];
+        }
+        images[blockIdx.x] = r;
+        bad = ran_out = 0;
+        nroots = 0;
+    }
+    for (int k = tid; k < 80; k += JPP_T) nat[k] = k < 64 ? jp_natural[k] : 63;
+    __syncthreads();
+    if (!valid) {
+        if (tid == 0) status[blockIdx.x] = 1;
+        return;
+    }
+    for (int s = tid; s < nsc; s += JPP_T) {            // the (component, coefficient) pairs of every scan; records checked
+        const JpegScan& sc = scans_all[s0 + s];
+        bool ok = sc.ncomp >= 1 && sc.ncomp <= ncomp && sc.ss >= 0 && sc.ss <= sc.se && sc.se <= 63 && (sc.ss == 0) == (sc.se == 0) &&
+                  (sc.ss == 0 || sc.ncomp == 1) && sc.al >= 0 && sc.al <= 13 && sc.stream_bytes >= 0;
+        const unsigned long long band = (sc.se == 63 ? ~0ull : ((1ull << (sc.se + 1)) - 1)) & ~((1ull << sc.ss) - 1);
+        unsigned long long m[3] = {0, 0, 0};
+        for (int i = 0; ok && i < sc.ncomp; ++i) {
+            const int c = sc.comp[i];
+            ok = c >= 0 && c < ncomp && (i == 0 || c > sc.comp[i - 1]);
+            if (ok && !(sc.ss == 0 && sc.ah)) ok = sc.tbl[i] >= 0 && sc.tbl[i] < ntables;
+            if (ok) m[c] = band;
+        }
+        for (int c = 0; c < 3; ++c) mask[s][c] = m[c];
+        if (!ok) bad = 1;
+    }
+    __syncthreads();
+    if (bad) {
+        if (tid == 0) status[blockIdx.x] = 1;
+        return;
+    }
+    if (tid == 0) {                                     // chains: union of scans that share a pair (roots: the first scan of a chain)
+        for (int s = 0; s < nsc; ++s) {
+            int r = s;
+            root[s] = s;
+            for (int t = 0; t < s; ++t) {
+                if (!((mask[s][0] & mask[t][0]) | (mask[s][1] & mask[t][1]) | (mask[s][2] & mask[t][2]))) continue;
+                int u = t;
+                while (root[u] != u) u = root[u];
+                if (u < r) {
+                    root[r] = u;
+                    r = u;
+                } else if (u > r) {
+                    root[u] = r;
+                }
+            }
+        }
+        for (int s = 0; s < nsc; ++s) {
+            int u = s;
+            while (root[u] != u) u = root[u];
+            root[s] = u;
+            if (u == s) roots[nroots++] = s;
+        }
+    }
+    __syncthreads();
+    for (int ch = tid; ch < nroots; ch += JPP_T) {
+        const int r = roots[ch];
+        bool failed = false;
+        for (int s = r; s < nsc && !failed; ++s) {
+            if (root[s] != r) continue;
+            const JpegScan& sc = scans_all[s0 + s];
+            JppBits br{reinterpret_cast<const unsigned*>(streams + sc.stream_off), ((unsigned)sc.stream_bytes + 3u) >> 2, 0u, 0u, 0ull, 0};
+            const int al = sc.al, p1 = 1 << al, m1 = -(1 << al);
+            const bool inter = sc.ncomp > 1;
+            // the scan's walk: interleaved - MCU after MCU, each scan component's blocks in turn; non-interleaved - the
+            // component's own block grid ceil(ceil(W h / hmax) / 8) x ceil(ceil(H v / vmax) / 8) in raster order, no padding blocks
+            const int c1 = sc.comp[0];
+            const int cw = inter ? mx : (c1 == 0 ? (pim.width + 7) / 8 : ((pim.width + hs - 1) / hs + 7) / 8);
+            const int chh = inter ? my : (c1 == 0 ? (pim.height + 7) / 8 : ((pim.height + vs - 1) / vs + 7) / 8);
+            const int per = inter ? (sc.comp[0] == 0 ? hv : 1) + sc.ncomp - 1 : 1;      // blocks per unit
+            const long long units = (long long)cw * chh;
+            int pred[3] = {0, 0, 0};
+            int eobrun = 0;
+            const JppLut* lut0 = &luts[sc.tbl[0] < 0 ? 0 : sc.tbl[0]];
+            for (long long u = 0; u < units && !failed; ++u) {
+                const int ux = (int)(u % cw), uy = (int)(u / cw);
+                for (int j = 0; j < per && !failed; ++j) {
+                    long long slot;
+                    int c;
+                    const JppLut* L = lut0;
+                    if (inter) {
+                        int i = 0, k = j;                  // block j of the MCU: which scan component, which of its blocks
+                        if (sc.comp[0] == 0) {
+                            if (k < hv) i = 0;
+                            else i = k - hv + 1, k = 0;
+                        } else {
+                            i = k, k = 0;
+                        }
+                        c = sc.comp[i];
+                        slot = u * bpm + (c == 0 ? k : hv + c - 1);
+                        if (sc.ah == 0) L = &luts[sc.tbl[i]];
+                    } else {
+                        c = c1;
+                        slot = c == 0 ? ((long long)(uy / vs) * mx + ux / hs) * bpm + (uy % vs) * hs + ux % hs
+                                      : ((long long)uy * mx + ux) * bpm + hv + c - 1;
+                    }
+                    short* blk = coef + slot * 64;
+                    if (sc.ss == 0) {
+                        if (sc.ah == 0) {
+                            const int t = br.sym(*L);
+                            if (t < 0 || t > 15) { failed = true; break; }
+                            pred[c] += jpp_extend(br.get(t), t);
+                            if (pred[c] > (1 << 30) || pred[c] < -(1 << 30)) { failed = true; break; }
+                            blk[0] = (short)((unsigned)pred[c] << al);
+                        } else if (br.get(1)) {
+                            blk[0] = (short)(blk[0] | p1);
+                        }
+                        continue;
+                    }
+                    if (sc.ah == 0) {                       // AC first scan
+                        if (eobrun) {
+                            --eobrun;
+                            continue;
+                        }
+                        for (int k = sc.ss; k <= sc.se; ++k) {
+                            const int t = br.sym(*L);
+                            if (t < 0) { failed = true; break; }
+                            const int rr = t >> 4, ss = t & 15;
+                            if (ss) {
+                                k += rr;
+                                if (k > sc.se) { failed = true; break; }
+                                blk[nat[k]] = (short)((unsigned)jpp_extend(br.get(ss), ss) << al);
+                            } else if (rr == 15) {
+                                k += 15;
+                            } else {
+                                eobrun = (1 << rr) + br.get(rr) - 1;
+                                break;
+                            }
+                        }
+                        continue;
+                    }
+                    int k = sc.ss;                          // AC refinement
+                    if (!eobrun) {
+                        for (; k <= sc.se; ++k) {
+                            const int t = br.sym(*L);
+                            if (t < 0) { failed = true; break; }
+                            int rr = t >> 4, ss = t & 15, v = 0;
+                            if (ss) {
+                                if (ss != 1) { failed = true; break; }
+                                v = br.get(1) ? p1 : m1;
+                            } else if (rr != 15) {
+                                eobrun = (1 << rr) + br.get(rr);
+                                break;
+                            }
+                            for (; k <= sc.se; ++k) {       // skip rr zeros; a correction bit for every nonzero passed
+                                const int z = nat[k];
+                                const int cv = blk[z];
+                                if (cv) {
+                                    if (br.get(1) && !(cv & p1)) blk[z] = (short)(cv + (cv >= 0 ? p1 : m1));
+                                } else if (--rr < 0) {
+                                    break;
+                                }
+                            }
+                            if (v) {
+                                if (k > sc.se) { failed = true; break; }
+                                blk[nat[k]] = (short)v;
+                            }
+                        }
+                        if (failed) break;
+                    }
+                    if (eobrun) {                           // the rest of the band in an EOB run: correction bits only
+                        for (; k <= sc.se; ++k) {
+                            const int z = nat[k];
+                            const int cv = blk[z];
+                            if (cv && br.get(1) && !(cv & p1)) blk[z] = (short)(cv + (cv >= 0 ? p1 : m1));
+                        }
+                        --eobrun;
+                    }
+                }
+            }
+            if (failed) bad = 1;
+            else if (br.p > (unsigned)sc.stream_bytes * 8u) {
+                ran_out = 1;
+                failed = true;
+            }
+        }
+    }
+    __syncthreads();
+    if (tid == 0) status[blockIdx.x] = bad ? 1 : (ran_out ? 2 : 0);
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -795,6 +1140,51 @@ extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int 
     CLIPMI_CHECK_LAUNCH("jpeg_huffman_kernel");
     hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)n), dim3(256), 0, st, images, coef);
     CLIPMI_CHECK_LAUNCH("jpeg_dc_kernel");
+    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
+                       status_dev);
+    CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
+                       static_cast<unsigned char*>(out_dev));
+    CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
+    return 0;
+}
+
+extern "C" int64_t clipmi_jpeg_progressive_workspace_bytes(int n, int64_t total_blocks, int ntables) {
+    if (n < 0 || total_blocks < 0 || ntables < 0) return -1;
+    return (int64_t)align_up((size_t)ntables * sizeof(JppLut), 256) + (int64_t)align_up((size_t)n * sizeof(JpegImage), 256) +
+           (int64_t)align_up((size_t)total_blocks * 128, 256) + (int64_t)align_up((size_t)total_blocks * 64, 256);
+}
+
+extern "C" int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev, int nscans,
+                                                   const void* tables_dev, int ntables, int64_t total_blocks, int64_t max_blocks,
+                                                   int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                                   void* stream) {
+    static_assert(sizeof(JpegScan) == sizeof(clipmi_jpeg_scan) && sizeof(JpegScan) == 64, "clipmi_jpeg_scan layout");
+    static_assert(sizeof(JpegProgImage) == sizeof(clipmi_jpeg_progressive_image) && sizeof(JpegProgImage) == 256,
+                  "clipmi_jpeg_progressive_image layout");
+    if (n == 0) return 0;
+    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 ||
+        ntables < 1 || total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: bad arguments");
+    if (ws_bytes < clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, ntables))
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+                       (long long)clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, ntables));
+    if ((max_blocks + 127) / 128 > 0x7fffffffLL || (max_pixels + 255) / 256 > 0x7fffffffLL || n > 65535)
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: batch too large for one launch");
+    hipStream_t st = as_stream(stream);
+    Arena ar(ws_dev, (size_t)ws_bytes);
+    JppLut* luts = ar.take<JppLut>((size_t)ntables);
+    JpegImage* images = ar.take<JpegImage>((size_t)n);
+    short* coef = ar.take<short>((size_t)total_blocks * 64);
+    unsigned char* planes = ar.take<unsigned char>((size_t)total_blocks * 64);
+    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess)
+        return set_err(CLIPMI_EHIP, "jpeg_decode_progressive_rgb8: memset");
+    hipLaunchKernelGGL(jpeg_build_pluts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
+    CLIPMI_CHECK_LAUNCH("jpeg_build_pluts_kernel");
+    hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)n), dim3(JPP_T), 0, st, static_cast<const unsigned char*>(streams_dev),
+                       static_cast<const JpegProgImage*>(images_dev), static_cast<const JpegScan*>(scans_dev), nscans, luts, ntables,
+                       images, coef, status_dev);
+    CLIPMI_CHECK_LAUNCH("jpeg_progressive_kernel");
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
                        status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");

@@ -182,16 +182,85 @@ def stage_jpeg(path, n_px, region):
     return p.width, p.height, total
 
 
+PROG_SCAN_BYTES = 64      # one scan record in a progressive region: jpeg.SCAN's layout (clipmi_jpeg_scan), offsets region-relative
+
+
+def stage_jpeg_progressive(path, n_px, region):
+    """For the progressive decode on the device (csrc/jpeg.hip jpeg_progressive_kernel): read the file, walk its markers
+    (jpeg_parse.parse_progressive) and lay out in `region` [header | quantisation steps | resize plan coefficients | scan records |
+    the scans' Huffman tables | the scans' entropy-coded segments without byte stuffing, each 16-byte aligned and followed by
+    >= 16 zero bytes]. The header is stage_jpeg's, with kind 4, the number of scans at [6], and at [18] / [20] / [21] the offsets
+    of the scan records and of the tables and the number of tables. A scan record's stream_off counts from the region's start
+    and its table indices from the region's first table. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not
+    fit; raises jpeg_parse.Unsupported for files Pillow has to decode."""
+    try:
+        from . import jpeg_parse
+    except ImportError:
+        import jpeg_parse
+    with open(path, "rb") as f:
+        data = f.read()
+    p = jpeg_parse.parse_progressive(data)
+    key = (p.width, p.height, n_px)
+    plan = _plans.get(key)
+    if plan is None:
+        if len(_plans) > 256:
+            _plans.clear()
+        plan = _plans[key] = resize_plan(p.width, p.height, n_px)
+    nh, nv = plan["hcoef"].size, plan["vcoef"].size
+    tables = {}
+    for sc in p.scans:
+        for t in (sc.dc if sc.ss == 0 else sc.ac):
+            if t is not None:
+                tables.setdefault(t, len(tables))
+    o_scans = (JPEG_COEF_OFF + 4 * (nh + nv) + 15) // 16 * 16
+    o_tab = o_scans + PROG_SCAN_BYTES * len(p.scans)
+    o = o_tab + jpeg_parse.TABLE_BYTES * len(tables)
+    offs = []
+    for sc in p.scans:
+        o = (o + 15) // 16 * 16
+        offs.append(o)
+        o += len(sc.stream) + 16
+    total = (o + 15) // 16 * 16
+    if total > region.size:
+        return p.width, p.height, -total
+    ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
+    ints[:] = [4, p.width, p.height, p.ncomp, p.hs, p.vs, len(p.scans), p.blocks(), plan["r0"], plan["nrows"], plan["need_h"],
+               plan["need_v"], plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, o_scans, JPEG_COEF_OFF, o_tab, len(tables),
+               0, 0] + [0] * 8
+    region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
+    if nh + nv:
+        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
+        co[:nh] = plan["hcoef"]
+        co[nh:] = plan["vcoef"]
+    rec = np.frombuffer(region, dtype=np.int32, count=PROG_SCAN_BYTES // 4 * len(p.scans), offset=o_scans).reshape(len(p.scans), -1)
+    rec[:] = 0
+    for k, sc in enumerate(p.scans):
+        tabs = sc.dc if sc.ss == 0 else sc.ac
+        idx = [tables[t] if t is not None else -1 for t in tabs] + [-1] * (3 - len(tabs))
+        comps = list(sc.comps) + [0] * (3 - len(sc.comps))
+        # <i8 stream_off | i4 stream_bytes, ncomp | comp[3] | tbl[3] | ss se ah al | reserved[2]
+        rec[k, 0], rec[k, 1] = offs[k], 0
+        rec[k, 2:14] = [len(sc.stream), len(sc.comps)] + comps + idx + [sc.ss, sc.se, sc.ah, sc.al]
+    for t, j in tables.items():
+        region[o_tab + j * jpeg_parse.TABLE_BYTES:o_tab + (j + 1) * jpeg_parse.TABLE_BYTES] = np.frombuffer(t, np.uint8)
+    for sc, off in zip(p.scans, offs):
+        region[off:off + len(sc.stream)] = np.frombuffer(sc.stream, np.uint8)
+        region[off + len(sc.stream):(off + len(sc.stream) + 16 + 15) // 16 * 16] = 0
+    return p.width, p.height, total
+
+
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (1 full-size pixels, 2 a parsed JPEG file, 3 both) | path as hex (file names may contain
-         newlines and tabs)
+         what the region may take (bits: 1 full-size pixels, 2 a parsed baseline JPEG file, 4 a parsed progressive JPEG file) |
+         path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
               b"2" + <iiq (w, h, bytes)>: the image sits at full size, with its resize plan, in the region (decode_full) |
               b"3" + <iiq (w, h, bytes)>: a baseline JPEG file, parsed, with its resize plan, in the region (stage_jpeg) |
-              b"5" + <iiq (w, h, bytes)>: as b"1", and the file would have been a b"3" with a region of that many bytes."""
+              b"4" + <iiq (w, h, bytes)>: a progressive JPEG file, parsed, with its resize plan, in the region
+              (stage_jpeg_progressive) |
+              b"5" + <iiq (w, h, bytes)>: as b"1", and the file would have been a b"3" or b"4" with a region of that many bytes."""
     import mmap
     import os
     import struct
@@ -232,6 +301,15 @@ def serve(fin, fout):
                         full, wanted = None, (full[0], full[1], -full[2])
                     if full is not None:
                         reply = b"3" + struct.pack("<iiq", *full)
+                if full is None and wanted is None and mode & 4:
+                    try:
+                        full = stage_jpeg_progressive(fname, n_px, region)
+                    except Exception:                          # not a progressive file for the device (or unreadable)
+                        full = None
+                    if full is not None and full[2] < 0:
+                        full, wanted = None, (full[0], full[1], -full[2])
+                    if full is not None:
+                        reply = b"4" + struct.pack("<iiq", *full)
                 if full is None and mode & 1:
                     full = decode_full(fname, n_px, region)
                     if full is not None:

@@ -13,7 +13,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .jpeg_parse import TABLE_BYTES, Parsed, Unsupported, parse  # noqa: F401
+from .jpeg_parse import TABLE_BYTES, Parsed, Progressive, Unsupported, parse, parse_progressive  # noqa: F401
 
 IMAGE = np.dtype([("stream_off", "<i8"), ("coef_off", "<i8"), ("out_off", "<i8"), ("intervals_off", "<i8"), ("stream_bytes", "<i4"),
                   ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("dc_tbl", "<i4", 3),
@@ -103,6 +103,110 @@ def decode_files(blobs, device, keep_stuffing=False):
     if not items:
         return res
     out, recs, status = decode_device(items, device)
+    st = status.cpu().numpy()
+    host = out.cpu().numpy()
+    for t, k in enumerate(where):
+        if st[t] == 0:
+            r = recs[t]
+            h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
+            res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
+    return res
+
+
+# ---- progressive files (jpeg_parse.parse_progressive; csrc/jpeg.hip jpeg_progressive_kernel). Opt-in in the pipeline.
+PIMAGE = np.dtype([("coef_off", "<i8"), ("out_off", "<i8"), ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"),
+                   ("vs", "<i4"), ("first_scan", "<i4"), ("n_scans", "<i4"), ("reserved", "<i4", 5), ("quant", "u1", (3, 64))], align=True)
+SCAN = np.dtype([("stream_off", "<i8"), ("stream_bytes", "<i4"), ("ncomp", "<i4"), ("comp", "<i4", 3), ("tbl", "<i4", 3), ("ss", "<i4"),
+                 ("se", "<i4"), ("ah", "<i4"), ("al", "<i4"), ("reserved", "<i4", 2)], align=True)
+assert PIMAGE.itemsize == 256 and SCAN.itemsize == 64
+
+
+def pack_progressive(items):
+    """Progressive records -> (PIMAGE array, SCAN array, tables uint8 [nt][288], streams uint8, out_bytes, total_blocks,
+    max_blocks, max_pixels)"""
+    recs = np.zeros(len(items), dtype=PIMAGE)
+    scans = np.zeros(sum(len(it.scans) for it in items), dtype=SCAN)
+    pool = {}
+    soff = coff = ooff = 0
+    ns = 0
+    max_blocks = max_pixels = 1
+    pieces = []
+    for k, it in enumerate(items):
+        r = recs[k]
+        r["coef_off"], r["out_off"] = coff, ooff
+        r["width"], r["height"], r["ncomp"], r["hs"], r["vs"] = it.width, it.height, it.ncomp, it.hs, it.vs
+        r["first_scan"], r["n_scans"] = ns, len(it.scans)
+        r["quant"] = it.quant
+        for sc in it.scans:
+            s = scans[ns]
+            s["stream_off"], s["stream_bytes"], s["ncomp"] = soff, len(sc.stream), len(sc.comps)
+            s["comp"] = list(sc.comps) + [0] * (3 - len(sc.comps))
+            tabs = sc.dc if sc.ss == 0 else sc.ac
+            s["tbl"] = [pool.setdefault(t, len(pool)) if t is not None else -1 for t in tabs] + [-1] * (3 - len(tabs))
+            s["ss"], s["se"], s["ah"], s["al"] = sc.ss, sc.se, sc.ah, sc.al
+            pad = (-len(sc.stream)) % 16 + 16
+            pieces.append(sc.stream)
+            pieces.append(b"\0" * pad)
+            soff += len(sc.stream) + pad
+            ns += 1
+        nb = it.blocks()
+        coff += nb
+        ooff += (it.width * it.height * 3 + 15) // 16 * 16
+        max_blocks, max_pixels = max(max_blocks, nb), max(max_pixels, it.width * it.height)
+    tables = np.frombuffer(b"".join(pool), np.uint8).reshape(-1, TABLE_BYTES) if pool else np.zeros((0, TABLE_BYTES), np.uint8)
+    return recs, scans, tables, np.frombuffer(b"".join(pieces), np.uint8), ooff, coff, max_blocks, max_pixels
+
+
+def decode_progressive_device(items, device, stream=None):
+    """Progressive records -> (out uint8 device tensor, records, status int32 device tensor), as decode_device: the RGB rows of
+    image k start at records[k]["out_off"]. Asynchronous on torch's current stream of `device`."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ClipmiError("jpeg.decode_progressive_device needs the HIP path (no CPU fallback)")
+    L = _lib.lib()
+    recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items)
+    n = len(items)
+    out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=device)
+    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
+    if n == 0:
+        return out, recs, status
+    o_scan = (recs.nbytes + 15) // 16 * 16
+    o_tab = (o_scan + scans.nbytes + 15) // 16 * 16
+    o_str = (o_tab + tables.nbytes + 15) // 16 * 16
+    host = torch.empty(o_str + streams.nbytes, dtype=torch.uint8).pin_memory()
+    hv = host.numpy()
+    hv[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
+    hv[o_scan:o_scan + scans.nbytes] = scans.view(np.uint8).reshape(-1)
+    hv[o_tab:o_tab + tables.nbytes] = tables.reshape(-1)
+    hv[o_str:] = streams
+    dev = host.to(device, non_blocking=True)
+    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, len(tables)))
+    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
+    base = dev.data_ptr()
+    rc = L.clipmi_jpeg_decode_progressive_rgb8(base + o_str, base, n, base + o_scan, len(scans), base + o_tab, len(tables), total_blocks,
+                                               max_blocks, max_pixels, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
+                                               _lib.stream_ptr(device))
+    _lib.check(rc, "clipmi_jpeg_decode_progressive_rgb8")
+    cur = torch.cuda.current_stream(device)
+    dev.record_stream(cur)
+    ws.record_stream(cur)
+    return out, recs, status
+
+
+def decode_progressive_files(blobs, device):
+    """Progressive JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder
+    or the device reported it). Synchronises; a convenience for tests and tools."""
+    items, where = [], []
+    for k, b in enumerate(blobs):
+        try:
+            items.append(parse_progressive(b))
+            where.append(k)
+        except Unsupported:
+            pass
+    res = [None] * len(blobs)
+    if not items:
+        return res
+    out, recs, status = decode_progressive_device(items, device)
     st = status.cpu().numpy()
     host = out.cpu().numpy()
     for t, k in enumerate(where):

@@ -219,3 +219,232 @@ def parse(data, keep_stuffing=False):
     if len(out.stream) >= MAX_STREAM:
         raise Unsupported("too large")
     return out
+
+
+MAX_SCANS = 100            # more scans than any encoder writes (libjpeg's richest script has 10; a file of 100+ is an attack)
+MAX_WORK = 1 << 26         # coefficient steps of the device's serial walk: blocks x band width, summed over the scans. A 12-megapixel
+                           # 4:2:0 photo in libjpeg's script takes ~48 M; above the bound the walk would keep a GPU busy for seconds
+_BETWEEN = frozenset([0xC4, 0xDA, 0xFE, *range(0xE0, 0xF0)])          # markers a progressive file may hold between its scans
+
+
+class Scan:
+    __slots__ = ("comps", "ss", "se", "ah", "al", "dc", "ac", "stream")
+    # comps: frame component indices, increasing; dc / ac: per scan component the 288-byte record of the table the scan decodes with
+    # (DC first scans: dc; AC scans: ac; DC refinements read raw bits and name none - None); stream: the segment, stuffing removed
+
+
+class Progressive:
+    __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "scans")
+
+    def mcus(self):
+        hs, vs = (self.hs, self.vs) if self.ncomp == 3 else (1, 1)
+        return -(-self.width // (8 * hs)) * -(-self.height // (8 * vs))
+
+    def blocks(self):
+        return self.mcus() * (self.hs * self.vs + 2 if self.ncomp == 3 else 1)
+
+
+def _dht(data, k, end, huff):
+    """DHT payload data[k:end] -> huff[class << 4 | id] = 288-byte record (the checks of parse)"""
+    while k < end:
+        if k + 17 > end:
+            raise Unsupported("Huffman table")
+        cnt = sum(data[k + 1:k + 17])
+        if cnt > 256 or k + 17 + cnt > end or (data[k] >> 4) > 1 or (data[k] & 15) > 3:
+            raise Unsupported("Huffman table")
+        if (data[k] >> 4) == 0 and cnt and max(data[k + 17:k + 17 + cnt]) > 15:
+            raise Unsupported("DC Huffman table")
+        code = 0
+        for l in range(1, 17):
+            code += data[k + l]
+            if code >= 1 << l:
+                raise Unsupported("Huffman table")
+            code <<= 1
+        huff[data[k]] = bytes(data[k + 1:k + 17 + cnt]).ljust(272, b"\0") + bytes([data[k] >> 4]) + b"\0" * 15
+        k += 17 + cnt
+
+
+def parse_progressive(data):
+    """Progressive JPEG file bytes -> Progressive (header fields, quantisation steps in natural order, the scans in file order
+    with their own Huffman tables and segments). Raises Unsupported for every file the device decoder does not vouch for:
+      * anything `parse` refuses in a frame header (marker whitelist, size and decompression-bomb limits, Huffman codes that
+        overflow, the YCbCr / Adobe rule, grey or luma 1x1 / 2x1 / 2x2 with 1x1 chroma, too narrow for fancy upsampling);
+      * a frame other than SOF2 (baseline files go to `parse`; SOF10 and the other arithmetic-coded frames stay with Pillow);
+      * scan parameters libjpeg refuses (jdphuff.c start_pass_phuff_decoder: a DC scan with Se != 0, an AC scan of more than one
+        component, Ss > Se, Se > 63, Al > 13, Ah neither 0 nor Al + 1) or only warns about (jdphuff.c: a "bogus progression" -
+        an AC scan before the component's DC scan, a refinement whose Ah is not the bit its coefficient has reached, a first
+        scan of a coefficient already coded);
+      * an incomplete script - some coefficient of some component not at Al = 0 by EOI. libjpeg(-turbo) then applies block
+        smoothing (jdcoefct.c smoothing_ok / decompress_smooth_data); a complete script decodes with plain jpeg_idct_islow;
+      * restart intervals (DRI) anywhere in the file: not handled on the device for now;
+      * DQT or DNL after the first SOS, a marker other than SOS, DHT, COM or APPn between scans, a missing EOI,
+        more than MAX_SCANS scans, scan components out of frame order, a missing table;
+      * more than MAX_WORK coefficient steps (blocks x band width, summed over the scans): the device walks each chain of
+        scans serially, so the cost grows with pixels x bands x scans whatever the size of the data."""
+    if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise Unsupported("not a JPEG file")
+    n = len(data)
+    i = 2
+    qt, huff = {}, {}
+    frame = None
+    jfif = adobe = False
+    adobe_tf = 0
+    while True:                                              # the header, up to the first SOS
+        if i + 4 > n or data[i] != 0xFF:
+            raise Unsupported("marker expected")
+        m = data[i + 1]
+        if m == 0xFF:
+            i += 1
+            continue
+        if m not in _KNOWN:
+            raise Unsupported("marker")
+        L = (data[i + 2] << 8) | data[i + 3]
+        if L < 2 or i + 2 + L > n:
+            raise Unsupported("truncated segment")
+        if m == 0xDB:
+            k = i + 4
+            while k < i + 2 + L:
+                if data[k] >> 4 or (data[k] & 15) > 3 or k + 65 > i + 2 + L:
+                    raise Unsupported("quantisation table")
+                qt[data[k] & 15] = data[k + 1:k + 65]
+                k += 65
+        elif m == 0xC2:
+            if frame is not None or L < 11 or data[i + 4] != 8:
+                raise Unsupported("frame header")
+            nf = data[i + 9]
+            if L != 8 + 3 * nf:
+                raise Unsupported("frame header")
+            frame = ((data[i + 5] << 8) | data[i + 6], (data[i + 7] << 8) | data[i + 8],
+                     [(data[i + 10 + 3 * c], data[i + 11 + 3 * c] >> 4, data[i + 11 + 3 * c] & 15, data[i + 12 + 3 * c]) for c in range(nf)])
+            if any(not (1 <= h <= 4 and 1 <= v <= 4) for _, h, v, _ in frame[2]) or len({c[0] for c in frame[2]}) != nf:
+                raise Unsupported("frame header")
+            if frame[0] > MAX_DIMENSION or frame[1] > MAX_DIMENSION or frame[0] * frame[1] > MAX_PIXELS:
+                raise Unsupported("too many pixels")
+        elif 0xC0 <= m <= 0xCF and m not in (0xC4, 0xC8, 0xCC):
+            raise Unsupported("not a progressive Huffman frame")
+        elif m == 0xCC:
+            raise Unsupported("arithmetic coding")
+        elif m == 0xC4:
+            _dht(data, i + 4, i + 2 + L, huff)
+        elif m == 0xDD:
+            raise Unsupported("restart intervals in a progressive file")
+        elif m == 0xE0 and L >= 16 and data[i + 4:i + 9] == b"JFIF\0":
+            jfif = True
+        elif m == 0xEE and L >= 14 and data[i + 4:i + 9] == b"Adobe":
+            adobe, adobe_tf = True, data[i + 15]
+        elif m == 0xDA:
+            break
+        i += 2 + L
+    if frame is None:
+        raise Unsupported("no frame header")
+    height, width, comps = frame
+    nc = len(comps)
+    if width == 0 or height == 0 or nc not in (1, 3):
+        raise Unsupported("frame")
+    out = Progressive()
+    out.width, out.height, out.ncomp = width, height, nc
+    if nc == 3:
+        ids = (comps[0][0], comps[1][0], comps[2][0])
+        ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
+        if not ycc:
+            raise Unsupported("RGB-coded JPEG")
+        if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1) or (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)):
+            raise Unsupported("sampling factors")
+        out.hs, out.vs = comps[0][1], comps[0][2]
+        if out.hs == 2 and (width + 1) // 2 <= 2:
+            raise Unsupported("too narrow for fancy upsampling")
+    else:
+        out.hs = out.vs = 1
+    quant = np.zeros((3, 64), np.uint8)
+    for c in range(nc):
+        q = qt.get(comps[c][3])
+        if q is None:
+            raise Unsupported("missing table")
+        quant[c] = np.frombuffer(q, np.uint8)[_INV_NATURAL]
+    out.quant = quant
+    cid = {c[0]: k for k, c in enumerate(comps)}
+    bits = [[-1] * 64 for _ in range(nc)]                  # jdphuff.c coef_bits: the bit each coefficient has reached (-1: none)
+    scans = []
+    while True:                                              # data[i] is an SOS marker here
+        ns = data[i + 4] if i + 4 < n else 0
+        if not 1 <= ns <= nc or L != 6 + 2 * ns:
+            raise Unsupported("scan header")
+        if len(scans) == MAX_SCANS:
+            raise Unsupported("too many scans")
+        s = Scan()
+        idx = [cid.get(data[i + 5 + 2 * k], -1) for k in range(ns)]
+        if min(idx) < 0 or any(a >= b for a, b in zip(idx, idx[1:])):
+            raise Unsupported("scan components")
+        s.comps = tuple(idx)
+        s.ss, s.se = data[i + 5 + 2 * ns], data[i + 6 + 2 * ns]
+        s.ah, s.al = data[i + 7 + 2 * ns] >> 4, data[i + 7 + 2 * ns] & 15
+        if s.ss == 0:
+            if s.se != 0:
+                raise Unsupported("DC scan with Se != 0")
+        elif s.se > 63 or s.ss > s.se or ns != 1:
+            raise Unsupported("AC scan parameters")
+        if s.al > 13 or (s.ah and s.al != s.ah - 1):
+            raise Unsupported("successive approximation")
+        for c in idx:
+            b = bits[c]
+            if s.ss and b[0] < 0:
+                raise Unsupported("AC scan before the DC scan")
+            for k in range(s.ss, s.se + 1):
+                if (s.ah == 0 and b[k] >= 0) or (s.ah and b[k] != s.ah):
+                    raise Unsupported("bogus progression")
+                b[k] = s.al
+        tabs = []
+        for k in range(ns):
+            td_ta = data[i + 6 + 2 * k]
+            t = None if (s.ss == 0 and s.ah) else huff.get(td_ta >> 4) if s.ss == 0 else huff.get(0x10 | (td_ta & 15))
+            if t is None and not (s.ss == 0 and s.ah):
+                raise Unsupported("missing table")
+            tabs.append(t)
+        s.dc, s.ac = (tabs, None) if s.ss == 0 else (None, tabs)
+        i += 2 + L
+        m_ = _MARKER.search(data, i)
+        if m_ is None:
+            raise Unsupported("no end of image")
+        j = m_.start()
+        while data[j + 1] == 0xFF:                           # fill bytes in front of a marker
+            j += 1
+            if j + 1 >= n:
+                raise Unsupported("no end of image")
+        if data[j + 1] == 0:
+            raise Unsupported("fill bytes inside the scan")
+        s.stream = data[i:m_.start()].replace(b"\xff\x00", b"\xff")
+        if len(s.stream) >= MAX_STREAM:
+            raise Unsupported("too large")
+        scans.append(s)
+        i = j
+        while True:                                          # the markers up to the next SOS or EOI
+            if i + 2 > n or data[i] != 0xFF:
+                raise Unsupported("marker expected")
+            m = data[i + 1]
+            if m == 0xFF:
+                i += 1
+                continue
+            if m == 0xD9:
+                break
+            if m not in _BETWEEN:
+                raise Unsupported("marker between scans")
+            if i + 4 > n:
+                raise Unsupported("truncated segment")
+            L = (data[i + 2] << 8) | data[i + 3]
+            if L < 2 or i + 2 + L > n:
+                raise Unsupported("truncated segment")
+            if m == 0xDA:
+                break
+            if m == 0xC4:
+                _dht(data, i + 4, i + 2 + L, huff)
+            i += 2 + L
+        if m == 0xD9:
+            break
+    if any(b != 0 for row in bits for b in row):
+        raise Unsupported("incomplete scan script (block smoothing)")
+    blocks_of = [-(-width // 8) * -(-height // 8)] if nc == 1 else [
+        -(-width // 8) * -(-height // 8), *[-(-(-(-width // out.hs)) // 8) * -(-(-(-height // out.vs)) // 8)] * 2]
+    if sum(sum(blocks_of[c] for c in s.comps) * (s.se - s.ss + 1) for s in scans) > MAX_WORK:
+        raise Unsupported("too much work for the serial walk")
+    out.scans = scans
+    return out

@@ -123,7 +123,8 @@ class DecodePool:
     def _run(self, w, jobs, n_px, name, seg, big=None):
         """Worker w decodes its share of the batch: (slot, path) pairs -> (slot, status) with status False (failed), True
         (the transform's pixels are in the slot) or (kind, w, h, bytes): the image is in its region of the big segment -
-        kind 2 at full size, for the resize on the device; kind 3 as a parsed JPEG file, for the decode on the device. If the worker process dies (a file that crashes the decoder, an OOM kill), that
+        kind 2 at full size, for the resize on the device; kind 3 as a parsed JPEG file, for the decode on the device; kind 4 as
+        a parsed progressive JPEG file. If the worker process dies (a file that crashes the decoder, an OOM kill), that
         file is reported as failed and the rest of the share - and of every later batch - is decoded in this process: no
         program is spawned once the GPU may have been initialised."""
         import struct
@@ -147,7 +148,7 @@ class DecodePool:
                 raw = p.stdout.read(17 * len(jobs))
                 for k in range(len(raw) // 17):
                     st = raw[17 * k:17 * k + 1]
-                    if st == b"2" or st == b"3":
+                    if st == b"2" or st == b"3" or st == b"4":
                         ok.append((jobs[k][0], (int(st),) + struct.unpack_from("<iiq", raw, 17 * k + 1)))
                     elif st == b"5":                       # Pillow decoded it; a larger region would have taken the file itself
                         self.jpeg_wanted = max(self.jpeg_wanted, struct.unpack_from("<iiq", raw, 17 * k + 1)[2])
@@ -179,7 +180,8 @@ class DecodePool:
         size in a second segment, one region of full_cap bytes per slot (tmpfs pages exist only where written), for the
         resize on the device; the result is then ((slots view, good mask, big view, {slot: (kind, w, h, bytes)}), ok, bad).
         full_mode: what a region may take - bit 0 full-size pixels (kind 2), bit 1 baseline JPEG files parsed for the decode on
-        the device (kind 3: decode_worker.stage_jpeg)."""
+        the device (kind 3: decode_worker.stage_jpeg), bit 2 progressive JPEG files parsed for it (kind 4:
+        decode_worker.stage_jpeg_progressive)."""
         n = len(paths)
         per = 3 * n_px * n_px
         seg = self._segment(max(1, n * per), segment)
@@ -287,8 +289,51 @@ def jpeg_records(bigview, n, cap, slots, comp, n_px):
     return recs, tables, jobs, out_sz, blocks, len(pool_t)
 
 
+def progressive_records(bigview, n, cap, slots, comp, n_px):
+    """jpeg_records for progressive files (decode_worker.stage_jpeg_progressive wrote the regions). -> (clipmi_jpeg_progressive_image
+    records, clipmi_jpeg_scan records with offsets into the segment, distinct raw Huffman tables uint8, clipmi_resize_job records
+    whose sources are the decoder's outputs laid out back to back, output bytes per image, blocks per image, number of tables)"""
+    from . import jpeg as J
+    from .decode_worker import JPEG_HDR_INTS, JPEG_QUANT_OFF, PROG_SCAN_BYTES
+    from .resize import JOB
+    slots = np.asarray(slots, dtype=np.int64)
+    n4 = len(slots)
+    st = np.lib.stride_tricks.as_strided
+    H = st(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[slots].astype(np.int64)
+    w, h, nscans, blocks, nrows = H[:, 1], H[:, 2], H[:, 6], H[:, 7], H[:, 9]
+    recs = np.zeros(n4, dtype=J.PIMAGE)
+    out_sz = (w * h * 3 + 15) // 16 * 16
+    out_off = np.cumsum(out_sz) - out_sz
+    recs["coef_off"], recs["out_off"], recs["width"], recs["height"] = np.cumsum(blocks) - blocks, out_off, w, h
+    recs["ncomp"], recs["hs"], recs["vs"] = H[:, 3], H[:, 4], H[:, 5]
+    recs["first_scan"], recs["n_scans"] = np.cumsum(nscans) - nscans, nscans
+    recs["quant"] = st(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n4, 3, 64)
+    scans = np.zeros(int(nscans.sum()), dtype=J.SCAN)
+    pool_t = {}
+    for k in range(n4):
+        base = int(slots[k]) * cap
+        o_scans, o_tab, nt = int(H[k, 18]), int(H[k, 20]), int(H[k, 21])
+        local = bigview[base + o_scans:base + o_scans + PROG_SCAN_BYTES * int(nscans[k])].copy().view(J.SCAN)
+        remap = np.array([pool_t.setdefault(bigview[base + o_tab + t * J.TABLE_BYTES:base + o_tab + (t + 1) * J.TABLE_BYTES].tobytes(),
+                                            len(pool_t)) for t in range(nt)] + [-1], dtype=np.int32)
+        local["stream_off"] += base
+        local["tbl"] = remap[np.where(local["tbl"] >= 0, local["tbl"], nt)]
+        f = int(recs["first_scan"][k])
+        scans[f:f + len(local)] = local
+    tables = np.frombuffer(b"".join(pool_t), np.uint8)
+    jobs = np.zeros(n4, dtype=JOB)
+    jobs["src_off"], jobs["w"], jobs["h"], jobs["r0"], jobs["nrows"], jobs["out_index"] = out_off, w, h, H[:, 8], nrows, np.asarray(comp)[slots]
+    jobs["need_h"], jobs["need_v"], jobs["left"], jobs["top"], jobs["hk"], jobs["vk"] = (H[:, 10], H[:, 11], H[:, 12], H[:, 13],
+                                                                                      H[:, 14], H[:, 15])
+    jobs["hcoef_off"] = (slots * cap + H[:, 19]) // 4
+    jobs["vcoef_off"] = jobs["hcoef_off"] + H[:, 16]
+    tmp = nrows * n_px * 3
+    jobs["tmp_off"] = np.cumsum(tmp) - tmp
+    return recs, scans, tables, jobs, out_sz, blocks, len(pool_t)
+
+
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
-                 jpeg_group_mb=32768):
+                 jpeg_group_mb=32768, device_progressive=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -300,10 +345,14 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     (jpeg_parse.py), and clipmi_jpeg_decode_rgb8 + clipmi_resize_crop_rgb8 produce the transform's pixels in HBM, the same
     bytes as Pillow's. Every other file (progressive, PNG, CMYK ...) and every file the device reports corrupt takes the
     Pillow path as before.
+    device_progressive (default $CLIPMI_DEVICE_PROGRESSIVE, else off; "1" = on; needs the JPEG decode on the device above):
+    progressive JPEG files take the device too (jpeg_parse.parse_progressive in the workers, clipmi_jpeg_decode_progressive_rgb8
+    + clipmi_resize_crop_rgb8 beside the baseline decode), the same bytes as Pillow's; files it reports go back to Pillow.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
-    shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoder (jpeg_files)."""
+    shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoder (jpeg_files;
+    progressive ones: jpeg_progressive_files)."""
     import os
     import time
     n_px = model.visual.input_resolution
@@ -344,7 +393,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     # files: a file that does not fit is decoded by Pillow this once and says what it would have needed (DecodePool.jpeg_wanted)
     jpeg_now = min(jpeg_cap, pool.jpeg_cap_hint or (128 << 10)) if jpeg_cap else 0
     full_cap = [max(resize_cap, jpeg_now)]               # bytes per region of the big segment; [0]: mutable (may be switched off)
-    full_mode = (1 if resize_cap else 0) | (2 if jpeg_cap else 0)
+    if device_progressive is None:
+        device_progressive = os.environ.get("CLIPMI_DEVICE_PROGRESSIVE", "0") not in ("", "0")
+    full_mode = (1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0)
 
     # three pinned staging buffers used in turn (GPU): batch i may still be in its H2D copy while batch i+1 is filled;
     # a buffer is reused only after the copy that read it has finished. Pixels go shared memory -> pinned -> device:
@@ -378,7 +429,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         """The batch's regions of the big segment -> their rows of devt, on the copy stream behind devt's own copy: ONE H2D copy
         of the segment where it lies (it is page-locked: no packing copy on the host - packing 1 GB per batch of photo-sized
         images with one thread was slower than Pillow's resize), then clipmi_resize_crop_rgb8 for the full-size images (kind 2)
-        and clipmi_jpeg_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed JPEG files (kind 3).
+        and clipmi_jpeg_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed JPEG files (kind 3), and
+        clipmi_jpeg_decode_progressive_rgb8 + clipmi_resize_crop_rgb8 for the parsed progressive ones (kind 4).
         The copy stream carries the copies only; the kernels go to the process's ONE side stream (_lib.side_stream: this ROCm gives a
         process three hardware queues) behind an event, so that the next batch's copy runs beside this batch's kernels instead of
         behind them, and the consumer finds them queued in front of its encode step.
@@ -395,6 +447,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         used = (max(full) + 1) * cap
         e2 = sorted((s_, v) for s_, v in full.items() if v[0] == 2)
         e3 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 3), dtype=np.int64)
+        e4 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 4), dtype=np.int64)
         if not pool.pin_segment(2 + seg_index[0]):
             # the segment could not be page-locked (locked-memory limit?): this batch goes through a pinned copy of it, the
             # following ones take the host path
@@ -448,7 +501,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                         lo, acc = k, 0
                     acc += int(need[k])
                 groups.append((lo, len(e3)))
-                status = torch.empty(len(e3), dtype=torch.int32, device=dev)
+                status = torch.empty(len(e3) + len(e4), dtype=torch.int32, device=dev)
                 calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
                 for lo, hi in groups:
                     recs, tables, jobs, out_sz, blocks, nt = jpeg_records(bigview, n, cap, e3[lo:hi], comp, n_px)
@@ -484,6 +537,58 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                 pending["launch"].append(decode_jpeg)
                 pending["keep"] += [ws, rgb, scratch3]
                 pending["status"], pending["slots"] = status, e3
+            if len(e4):
+                # progressive files: the same grouping, their own records and workspace, behind the baseline decode on the side stream;
+                # their statuses follow the baseline files' in one tensor
+                st_ = np.lib.stride_tricks.as_strided
+                H4 = st_(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[e4].astype(np.int64)
+                need = H4[:, 7] * 192 + (H4[:, 1] * H4[:, 2] * 3 + 15) // 16 * 16 + H4[:, 9] * n_px * 3
+                groups, lo, acc = [], 0, 0
+                for k in range(len(e4)):
+                    if k > lo and acc + need[k] > jpeg_group_bytes:
+                        groups.append((lo, k))
+                        lo, acc = k, 0
+                    acc += int(need[k])
+                groups.append((lo, len(e4)))
+                status = pending["status"] if pending["status"] is not None else torch.empty(len(e4), dtype=torch.int32, device=dev)
+                calls4, ws_max, rgb_max, tmp_max = [], 0, 0, 0
+                for lo, hi in groups:
+                    recs, scans, tables, jobs, out_sz, blocks, nt = progressive_records(bigview, n, cap, e4[lo:hi], comp, n_px)
+                    w, h, nrows = recs["width"].astype(np.int64), recs["height"].astype(np.int64), jobs["nrows"].astype(np.int64)
+                    o_scan = (recs.nbytes + 15) // 16 * 16
+                    o_tab = (o_scan + scans.nbytes + 15) // 16 * 16
+                    o_job = (o_tab + tables.nbytes + 15) // 16 * 16
+                    small = np.zeros(o_job + jobs.nbytes, np.uint8)
+                    small[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
+                    small[o_scan:o_scan + scans.nbytes] = scans.view(np.uint8).reshape(-1)
+                    small[o_tab:o_tab + tables.nbytes] = tables
+                    small[o_job:] = jobs.view(np.uint8).reshape(-1)
+                    dsmall = torch.from_numpy(small).to(dev)
+                    total_blocks = int(blocks.sum())
+                    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(hi - lo, total_blocks, nt))
+                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
+                    tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
+                    calls4.append((dsmall, o_scan, len(scans), o_tab, o_job, hi - lo, nt, total_blocks, int(blocks.max()), int((w * h).max()),
+                                   int(nrows.max()), ws_bytes, len(e3) + lo))
+                    pending["keep"].append(dsmall)
+                ws4 = torch.empty(ws_max, dtype=torch.uint8, device=dev)
+                rgb4 = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
+                scratch4 = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
+
+                def decode_progressive(status=status):
+                    for dsmall, o_scan, ns, o_tab, o_job, n4, nt, total_blocks, mb, mp, mr, ws_bytes, lo in calls4:
+                        sb = dsmall.data_ptr()
+                        rc = L.clipmi_jpeg_decode_progressive_rgb8(base, sb, n4, sb + o_scan, ns, sb + o_tab, nt, total_blocks, mb, mp,
+                                                                   rgb4.data_ptr(), status.data_ptr() + 4 * lo, ws4.data_ptr(), ws_bytes,
+                                                                   _lib.stream_ptr(dev))
+                        _lib.check(rc, "clipmi_jpeg_decode_progressive_rgb8")
+                        rc = L.clipmi_resize_crop_rgb8(rgb4.data_ptr(), sb + o_job, n4, mr, base, n_px, devt.data_ptr(), scratch4.data_ptr(),
+                                                       _lib.stream_ptr(dev))
+                        _lib.check(rc, "clipmi_resize_crop_rgb8")
+
+                pending["launch"].append(decode_progressive)
+                pending["keep"] += [ws4, rgb4, scratch4]
+                pending["status"], pending["slots"] = status, np.concatenate([e3, e4])
             ev_copy = torch.cuda.Event()
             ev_copy.record(copy_stream)
         side = _lib.side_stream(dev)[1]
@@ -550,7 +655,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
             pending["chunk"], pending["good"] = chunk, good.copy()
         if jpeg_cap and full_cap[0]:
             # the next batches' JPEG regions: 1.25 x the largest file this batch held or turned away
-            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] == 3] + [pool.jpeg_wanted])
+            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] in (3, 4)] + [pool.jpeg_wanted])
             pool.jpeg_wanted = 0
             if used3:
                 pool.jpeg_cap_hint = min(jpeg_cap, max(1 << 16, (used3 + used3 // 4 + 65535) // 65536 * 65536))
@@ -640,6 +745,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                     stats["copy_s"] = stats.get("copy_s", 0.0) + time.perf_counter() - t0
                     if len(dec_[0]) == 4:
                         stats["jpeg_files"] = stats.get("jpeg_files", 0) + sum(1 for v in dec_[0][3].values() if v[0] == 3)
+                        stats["jpeg_progressive_files"] = stats.get("jpeg_progressive_files", 0) + sum(1 for v in dec_[0][3].values()
+                                                                                                       if v[0] == 4)
                 return r
 
             def submit(j):

@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CLIPMI_ABI_VERSION 6
+#define CLIPMI_ABI_VERSION 7
 
 enum {
     CLIPMI_OK = 0,
@@ -287,6 +287,44 @@ int64_t clipmi_jpeg_workspace_bytes(int64_t total_blocks, int ntables);
 int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
                             int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
                             void* ws_dev, int64_t ws_bytes, void* stream);
+
+/* ---- ABI 7. Progressive JPEG files on the device (SOF2, 8-bit, Huffman): the same bytes as Pillow's `convert("RGB")`, for the
+ * files the host parser lets through (cli-p_amd/jpeg_parse.py parse_progressive: grey or YCbCr with luma sampling 1x1, 2x1 or
+ * 2x2 and 1x1 chroma, no restart intervals, a scan script libjpeg accepts without a warning and that brings every coefficient of
+ * every component to Al = 0 - libjpeg then applies no block smoothing). Per image one record, per scan one record: an image's
+ * scans are scans_dev[first_scan .. first_scan + n_scans - 1], in file order (n_scans 1..128). Every scan's entropy-coded
+ * segment travels with the 0xFF00 stuffing removed, 4-byte aligned and followed by at least 16 zero bytes. tables_dev: the
+ * batch's distinct Huffman tables in the 288-byte form of clipmi_jpeg_decode_rgb8. out_dev, total_blocks, max_blocks,
+ * max_pixels: as clipmi_jpeg_decode_rgb8. status_dev[i]: 0 decoded; 1 invalid Huffman code (also: a coefficient behind its
+ * band, a refinement value of more than one bit, a record outside the limits above); 2 a scan's data ended early; 3 (not
+ * produced: segments arrive unstuffed); 4 a block outside the range where libjpeg-turbo's IDCT equals the device's - as
+ * clipmi_jpeg_decode_rgb8, and such a file goes back to Pillow. */
+typedef struct clipmi_jpeg_scan {
+    int64_t stream_off;           /* bytes from streams_dev */
+    int32_t stream_bytes;
+    int32_t ncomp;                /* components in the scan, 1..3 (AC scans: 1) */
+    int32_t comp[3];              /* frame component indices, increasing */
+    int32_t tbl[3];               /* per scan component: index into tables_dev - the DC table of a DC first scan, the AC table of
+                                     an AC scan; -1 for a DC refinement (raw bits) */
+    int32_t ss, se, ah, al;       /* spectral selection and successive approximation, as in the SOS header */
+    int32_t reserved[2];
+} clipmi_jpeg_scan;
+typedef struct clipmi_jpeg_progressive_image {
+    int64_t coef_off;             /* as clipmi_jpeg_image */
+    int64_t out_off;
+    int32_t width, height;
+    int32_t ncomp;                /* 1 or 3 */
+    int32_t hs, vs;               /* luma sampling factors (1,1) (2,1) (2,2) */
+    int32_t first_scan;           /* index into scans_dev */
+    int32_t n_scans;
+    int32_t reserved[5];
+    uint8_t quant[3][64];         /* per component: quantisation steps, natural (row-major) order */
+} clipmi_jpeg_progressive_image;
+int64_t clipmi_jpeg_progressive_workspace_bytes(int n, int64_t total_blocks, int ntables);
+int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev, int nscans,
+                                        const void* tables_dev, int ntables, int64_t total_blocks, int64_t max_blocks,
+                                        int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                        void* stream);
 
 /* thread-local message of the last failing call on this thread ("" if none) */
 const char* clipmi_last_error(void);
