@@ -302,8 +302,11 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(const float* __restr
     const int col = lane & 15, g = lane >> 4;
     const int qbase = blockIdx.y * 16 * QG;
     f32x4* qimg = reinterpret_cast<f32x4*>(smem);
-    // QG*NT*64 = 2048 entries over 256 threads, 8 loads in flight per thread (one at a time cost ~10 us per block)
-    for (int base = tid; base < QG * NT * 64; base += 8 * 256) {
+    // QG*NT*64 = 2048 entries (E = 512; 3072 at E = 768) over 256 threads, 8 loads in flight per thread (one at a time cost
+    // ~10 us per block). RAGGED: the image is not a whole number of 2048-entry rounds (E = 768), so the last round is bounded.
+    constexpr int NIMG = QG * NT * 64;
+    constexpr bool RAGGED = NIMG % (8 * 256) != 0;
+    for (int base = tid; base < NIMG; base += 8 * 256) {
         f32x4 v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
@@ -311,10 +314,11 @@ __global__ void __launch_bounds__(256) sample_scores_kernel(const float* __restr
             const int l = idx & 63, t = (idx >> 6) % NT, qg = (idx >> 6) / NT;
             const int c_ = qbase + qg * 16 + (l & 15), g_ = l >> 4;
             v[j] = f32x4{0.f, 0.f, 0.f, 0.f};
-            if (c_ < QA) v[j] = *reinterpret_cast<const f32x4*>(q + (size_t)c_ * E + 16 * t + 4 * g_);
+            if (c_ < QA && (!RAGGED || idx < NIMG)) v[j] = *reinterpret_cast<const f32x4*>(q + (size_t)c_ * E + 16 * t + 4 * g_);
         }
 #pragma unroll
-        for (int j = 0; j < 8; ++j) qimg[base + j * 256] = v[j];
+        for (int j = 0; j < 8; ++j)
+            if (!RAGGED || base + j * 256 < NIMG) qimg[base + j * 256] = v[j];
     }
     if (blockIdx.x == 0 && tid < 16 * QG && qbase + tid < QA) gcnt[qbase + tid] = (unsigned)nrows;
     __syncthreads();
@@ -670,10 +674,10 @@ __global__ void __launch_bounds__(256) merge_lists_i64_kernel(const float* __res
 //
 // Superset argument. Let s(r) be the exact (fmaf-chain) score of row r and c(r) the bf16-MFMA score of
 // the bf16-rounded operands. bf16 RNE has relative error u = 2^-9 per operand, so the exact products
-// differ by at most (2u + u^2)|a_k b_k|; both accumulations (f32, 512 terms, any order) add at most
-// ~2 * 512 * 2^-24 * sum|a_k b_k|. With sum|a_k b_k| <= ||row|| ||q||:
+// differ by at most (2u + u^2)|a_k b_k|; both accumulations (f32, E terms, any order) add at most
+// ~2 * E * 2^-24 * sum|a_k b_k|. With sum|a_k b_k| <= ||row|| ||q||, at E = 512:
 //        |c(r) - s(r)| <= 0.004 * ||row|| * ||q||  <=  margin_q := 0.0041 * R_max * ||q||
-// (R_max = largest row norm, kept with the bf16 copy). tau0_q = exact K-th best of the first S rows is
+// (R_max = largest row norm, kept with the bf16 copy). E = 768: 0.0040017 and 0.0041305, bf16_margin_coef<E> below. tau0_q = exact K-th best of the first S rows is
 // a lower bound of the final K-th best score; every row of the true top-K has s >= tau0_q, hence
 // c >= tau0_q - margin_q =: the coarse threshold. If a candidate list overflows its capacity a device
 // flag makes the (otherwise early-exiting) exact-scan fallback launches run and overwrite the result.
@@ -691,12 +695,13 @@ __device__ __forceinline__ unsigned pack2_bf16(float a, float b) {
 // ---- int8 coarse copy (clipmi_quantize_rows_i8 / clipmi_topk_ip_coarse_i8) -------------------------------
 // Row r: s_r = (max |x| over r's 32-row block) / 127, q_rk = rint(x_rk / s_r) in [-127, 127], a_r = 1.001 * ||x_r - s_r q_r||_2.
 // Query: t_q, p_qk the same way, f_q = y - t_q p_q. The int8 MFMA gives the EXACT integer D = q_r . p_q
-// (|D| <= 512 * 127^2 < 2^24), and
+// (|D| <= E * 127^2 < 2^24 for E <= 768), and
 //      x.y = s_r t_q D + e_r.y + (s_r q_r).f_q      =>      |x.y - s_r t_q D| <= a_r ||y|| + (R_max + A_max) ||f_q||
 // (Cauchy-Schwarz twice; ||s_r q_r|| <= ||x_r|| + a_r). A row can be in the exact top-K only if its exact score is
 // >= tau_q (the exact K-th best of a sample), so the scan keeps row r for query q when
-//      s_r t_q D + a_r * 1.001 ||y|| >= tau_q - 1.001 (R_max + A_max) ||f_q|| - 1e-4 R_max ||y||
-// (the last term covers f32 rounding of both sides and of the exact kernel's fmaf chain: < 512 * 2^-23 relative).
+//      s_r t_q D + a_r * 1.001 ||y|| >= tau_q - 1.001 (R_max + A_max) ||f_q|| - c(E) R_max ||y||,   c(512) = 1e-4
+// (the last term covers f32 rounding of both sides and of the exact kernel's fmaf chain: < E * 2^-23 relative;
+//  c(E) = 1e-4 E / 512, derived at i8_round_slack<E> below).
 // Divided by t_q > 0 so that the kernel's test is one convert + one multiply + one fma + one compare per pair.
 // (A second int8 digit of the query - y = t p + u p' + f', a second MFMA chain per row tile - removes the query half of
 //  the margin and was measured: 45 % fewer rows reach the exact re-scoring pass (-30 us per 64 queries at 10 M rows), but
@@ -790,12 +795,37 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
 // q2 (int8, 64-query passes; round 4): the query as TWO int8 digits, y = t p1 + (t / 254) p2 + f' - the second image sits
 // COARSE_IMG2 entries behind the first and the margin is built from ||f'|| (1 / 254 of ||f||): the query's half of the
 // bound's margin is gone, the scan pays a second MFMA per fragment (it is HBM-latency bound with the matrix pipe 16 % busy).
-constexpr int COARSE_IMG2 = 4 * 8 * 64;          // entries of a full 64-query int8 image (32 KiB)
-template <bool I8>
+constexpr int COARSE_IMG2 = 4 * 8 * 64;          // entries of a full 64-query int8 image at E = 512 (32 KiB); q2 is 512-only
+// Rounding slack of the two superset bounds as a function of the row width (derivations: DESIGN.md 4.1l, summary here).
+// int8: the test compares f32 evaluations of both sides of
+//      s_r t_q D + a_r 1.001 ||y||  >=  tau_q - 1.001 (R_max + A_max) ||f_q||,
+// and tau_q and the row's own exact score come from fmaf chains of E terms. What rounding can move, relative to R_max ||y||:
+//   * the row's exact score against its real inner product: gamma_E = E u / (1 - E u), u = 2^-24 (one rounding per fmaf);
+//     tau_q itself is COMPARED as computed, not trusted as real, but the budget of round 2 charges a second chain for it;
+//   * the integer D is exact (|D| <= E 127^2 <= 12 387 072 < 2^24 for E <= 768), so the left side has three roundings
+//     (convert - exact -, multiply inside the fma, the product a_r * yt, the fma) and the right side three (subtract,
+//     multiply by 1/t_q, the margin's own sum), each of a quantity <= 1.35 R_max ||y|| / t_q (A_max <= 0.11 R_max and
+//     ||f_q|| <= 0.11 ||y|| at E <= 768: half a step times sqrt(E) against a largest component of 127 steps): < 16 u in all;
+//   * the norms ||y||, ||f_q||, a_r are sums of E squares in f32 (relative error < (E + 2) u / 2 each after the root):
+//     covered by their own 1.001 factors (1e-3 against < 2.3e-5).
+// Needed: (2 E + 16) u = 6.2e-5 at E = 512, 9.3e-5 at E = 768. The constant is 1e-4 * E / 512: 1e-4 at 512 (unchanged, bit for
+// bit), 1.5e-4 at 768 - the same 1.6 x head room at both widths instead of 1.08 x; it is < 1 % of the query half of the margin
+// (1.001 (R + A) ||f_q|| ~ 7.6e-3 R ||y|| on unit data), so the survivor count does not notice.
+// bf16: |c - s| <= (2 u9 + u9^2 + 2 E u) ||x|| ||y||, u9 = 2^-9: 0.0039712 at 512, 0.0040017 at 768 (no longer below the
+// 0.004 the header's argument rounds to). The constant is 0.0041 + 2 (E - 512) u: 0.0041 at 512 (unchanged), 0.0041305 at 768 -
+// the same 1.3e-4 of head room at both widths.
+template <int E>
+constexpr float i8_round_slack() { return 1e-4f * ((float)E / 512.0f); }
+template <int E>
+constexpr float bf16_margin_coef() { return 0.0041f + 2.0f * (float)(E - 512) * 5.9604644775390625e-8f; }
+static_assert(i8_round_slack<512>() == 1e-4f && bf16_margin_coef<512>() == 0.0041f, "E = 512 keeps its constants bit for bit");
+static_assert(768 * 127 * 127 < (1 << 24), "the int8 dot product must stay exact in f32");
+
+template <bool I8, int ET = 512>
 __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restrict__ q, int E, float rmax, float amax, int QA,
                                                           float* qmeta, uint4* qimage, unsigned* ctl, int nctl, int qs,
                                                           int wide = 0, int q2 = 0) {
-    constexpr int KS = 512 / (I8 ? 64 : 32);
+    constexpr int KS = ET / (I8 ? 64 : 32);         // k-steps of the 64-query image; E == ET (the wide image is 512-only)
     const int lane = threadIdx.x & 63;
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x == 0)
@@ -806,10 +836,12 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
     const int widx = ((qi >> 5) * 16 + (lane >> 1)) * 64 + (lane & 1) * 32 + (qi & 31);
     if (qi >= QA) {                                            // padding query of a used query group: zero image
         if (wide) { if (lane < 32) qimage[widx] = make_uint4(0u, 0u, 0u, 0u); }
-        else if (lane < KS * 4) {
-            qimage[(qg * KS + (lane >> 2)) * 64 + (lane & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
-            if (I8 && q2) qimage[COARSE_IMG2 + (qg * KS + (lane >> 2)) * 64 + (lane & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
-        }
+        else
+            // KS * 4 entries per query: 32 (int8) or 64 (bf16) at E = 512 - one round of the wave -, 48 or 96 at E = 768
+            for (int e = lane; e < KS * 4; e += 64) {
+                qimage[(qg * KS + (e >> 2)) * 64 + (e & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
+                if (I8 && q2) qimage[COARSE_IMG2 + (qg * KS + (e >> 2)) * 64 + (e & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
+            }
         return;
     }
     const float* y = q + (size_t)qi * E;
@@ -840,7 +872,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
     }
     if (lane == 0) {
         const float Y = sqrtf(ss), F = sqrtf(ff) * 1.001f;
-        float margin = I8 ? 1.001f * (rmax + amax) * F + 1e-4f * rmax * Y : 0.0041f * rmax * Y * 1.001f;
+        float margin = I8 ? 1.001f * (rmax + amax) * F + i8_round_slack<ET>() * rmax * Y : bf16_margin_coef<ET>() * rmax * Y * 1.001f;
         // A query with a NaN or infinite component has no usable coarse bound: its margin is +inf, which the selects turn into a
         // threshold of -inf whatever the K-th best is (inf - inf would be a NaN that passes nothing) - every row then passes, the
         // lists overflow and the exact fallback answers the call, as the contract promises for any data. The other two
@@ -871,8 +903,8 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
         }
         return;
     }
-    if (lane < KS * 4) {
-        const int s_ = lane >> 2, g_ = lane & 3;
+    for (int e = lane; e < KS * 4; e += 64) {          // one round at E = 512; 96 bf16 entries per query at E = 768 take two
+        const int s_ = e >> 2, g_ = e & 3;
         uint4 v;
         if (I8) {
             const float* p = y + 64 * s_ + 16 * g_;
@@ -908,7 +940,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
 // not a NaN (NaN -> -inf before the store). Never an fkey()-encoded key, never raw bits of an unchecked score: 0xffffffff is a NaN
 // pattern and would be read as "slot". tests/test_topk_gpu.py::test_non_finite_queries_through_the_permuted_int8_copy holds it.
 constexpr unsigned CAND_SLOT = 0xffffffffu;
-constexpr size_t RESCORE16_LDS = 512 * 4 + 4 * 16 * 68 * 4;      // rescore_pairs16_kernel: the query + four waves' tiles of 16 row chunks
+constexpr size_t RESCORE16_LDS = 512 * 4 + 4 * 16 * 68 * 4;      // rescore_pairs16_kernel (E = 512 only: the wide passes): the query + four waves' tiles of 16 row chunks
 
 struct CoarseArgs {
     const void* dbc;             // coarse copy of the matrix: bf16 [nrows][E] or int8 [nrows][E]
@@ -985,7 +1017,7 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
     // of f32 queries and quantise them again); here it is a 16-byte-per-lane copy, 8 loads in flight
     uint4* qimg = reinterpret_cast<uint4*>(smem);
     {
-        static_assert(NIMG % (8 * 256) == 0 || NIMG < 8 * 256, "image copy loop");
+        static_assert(NIMG % 256 == 0, "image copy loop: whole 256-entry rows, every one bounded by NIMG below");
         for (int base = tid; base < NIMG; base += 8 * 256) {
             uint4 v[8];
 #pragma unroll
@@ -1203,7 +1235,7 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
 }
 
 // Exact f32 re-scoring of the coarse survivors: (exact score bits, row id) for every entry of the candidate lists. A lane that
-// owns a (query, row) pair runs the SAME fmaf chain as the MFMA scan (t, c, g order) - one serial chain over the row's 512
+// owns a (query, row) pair runs the SAME fmaf chain as the MFMA scan (t, c, g order) - one serial chain over the row's E
 // components, so the score bits equal the exact kernel's and the oracle's; that chain is why a row cannot be split over lanes and
 // the rows go through a per-wave LDS tile: fetched COOPERATIVELY (4 rows x 256 B contiguous per wave-instruction), read back by
 // the owning lane. (A first version with one thread fetching its own 2-KB row: ~1 ms for 175 k pairs, 4 uncoalesced loads in flight.)
@@ -1276,7 +1308,8 @@ __global__ void __launch_bounds__(256) rescore_pairs16_kernel(const float* __res
 // (CLIPMI_RESCORE=16 / 64, development library; profiles/r04_search_rescore_ab.txt): its lists (2 500 / 1 500 / 700 pairs per
 // query) are gathered at the same ~5 TB/s by either form - 58.6 / 41.6 / 29.3 us against 58.1 / 47.8 / 27.2 at 10 M rows - and
 // with two calls in flight this one disturbs the other call's streaming scan less (0.976 against 1.005 ms per call).
-constexpr size_t RESCORE_LDS = 512 * 4 + 4 * 64 * 68 * 4;
+constexpr size_t rescore_lds(int E) { return (size_t)E * 4 + 4 * 64 * 68 * 4; }      // the query + four waves' tiles of 64 row chunks
+constexpr size_t RESCORE_LDS = rescore_lds(512);
 template <int E>
 __global__ void __launch_bounds__(256) rescore_pairs_kernel(const float* __restrict__ db, const float* __restrict__ q,
                                                             uint2* cand, const unsigned* __restrict__ gcnt, long long cap,
@@ -2123,7 +2156,7 @@ __global__ void __launch_bounds__(WAVES * 64) scan_coarse_wide_kernel(WideArgs a
 }
 
 struct Plan {
-    int C, waves, QA, QG, grid, grid_sample, wave_bytes, stage;
+    int C, waves, QA, QG, grid, grid_sample, wave_bytes, stage, E;
     size_t lds_scan, lds_sel;
     long long NL, NL_sample, cap, sample_rows;
     bool sample;
@@ -2134,6 +2167,7 @@ struct Plan {
 // side kernels fit on a CU beside a coarse scan workgroup of another batch in flight)
 bool make_plan(long long N, int E, int Q, int K, Plan& p, int lds_limit = LDS_LIMIT) {
     if (N < 0 || Q < 1 || K < 1 || (E != 512 && E != 768)) return false;
+    p.E = E;
     p.C = (int)align_up((size_t)K + 16, 16);
     p.waves = 0;
     // prefer 4 waves per block and as many queries per pass as LDS allows (32, else 16, else fewer)
@@ -2303,12 +2337,14 @@ constexpr int COARSE_Q = 64;                     // queries per coarse pass. (12
                                                  // leaves LDS for only 2 waves per CU = 2 of 4 SIMDs, and the pass turns
                                                  // MFMA-bound: 5.29 ms per 128 queries vs 2 x 2.21 ms)
 
-template <int QG, bool PREPASS, bool I8, bool Q2 = false>
-int launch_coarse(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
+template <int E, int QG, bool PREPASS, bool I8, bool Q2 = false>
+int launch_coarse_t(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
     static_assert(QG <= 4, "64 queries per pass at most");
+    static_assert(E == 512 || !Q2, "the two-digit query image (COARSE_IMG2) is laid out for E = 512");
     constexpr int WAVES = 4;
     // the final publication reuses the head of the query image for 3 * 16 QG counters: keep >= 1 KiB
-    size_t lds = (size_t)(Q2 ? 2 : 1) * QG * (512 / (I8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
+    // (image: 1 KiB per query group and k-step - E = 768: 48 KiB int8, 96 KiB bf16 at 64 queries; + 4 x 6 KiB of lists)
+    size_t lds = (size_t)(Q2 ? 2 : 1) * QG * (E / (I8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
     // The LAST segment's scan (3/4 of the rows) reserves COARSE_MAIN_LDS although it uses 56-88 KiB: with two batches in
     // flight on two streams, two such scans then cannot share a CU. Sharing halves each one's bandwidth, both finish
     // together and both batches run their latency-bound side kernels at the same time with HBM idle (1.06-1.08 ms per 64
@@ -2319,14 +2355,23 @@ int launch_coarse(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEven
     static const int wgs = [] { const int v = (int)dev_knob("CLIPMI_COARSE_WGS", 1); return v == 2 ? 2 : 1; }();
     if (!PREPASS && wgs == 1 && lds < (size_t)COARSE_MAIN_LDS) lds = COARSE_MAIN_LDS;
     if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_kernel<512, QG, PREPASS, I8, Q2>, lds)) return rc;
+    if (int rc = opt_in_lds((const void*)scan_coarse_kernel<E, QG, PREPASS, I8, Q2>, lds)) return rc;
     long long g_ = (nsteps + WAVES - 1) / WAVES;
     const int grid = (int)(g_ < (long long)NUM_CU * wgs ? g_ : (long long)NUM_CU * wgs);
     if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_kernel<512, QG, PREPASS, I8, Q2>), dim3(grid), dim3(WAVES * 64), lds, st, a);
+    hipLaunchKernelGGL((scan_coarse_kernel<E, QG, PREPASS, I8, Q2>), dim3(grid), dim3(WAVES * 64), lds, st, a);
     if (ev) (void)hipEventRecord(ev[1], st);
     CLIPMI_CHECK_LAUNCH("scan_coarse_kernel");
     return 0;
+}
+
+// E in {512, 768} (checked by the callers); the two-digit form (development library) exists at 512 only
+template <int QG, bool PREPASS, bool I8, bool Q2 = false>
+int launch_coarse(int E, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
+    if constexpr (!Q2)
+        if (E == 768) return launch_coarse_t<768, QG, PREPASS, I8, false>(a, nsteps, st, ev);
+    if (E != 512) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: E = %d", E);
+    return launch_coarse_t<512, QG, PREPASS, I8, Q2>(a, nsteps, st, ev);
 }
 
 constexpr int COARSE_CTL = 2 * COARSE_Q + 32 + COARSE_Q * LIVE_NB;     // fallback counters | coarse counters | overflow flag + 28 live-scan statistics | ladder
@@ -2357,19 +2402,25 @@ size_t carve_coarse(const Plan& p, void* base, size_t cap, CoarseWs* w) {
     x.tauc = ar.take<float>(COARSE_Q);
     x.last_m = ar.take<unsigned>(COARSE_Q);
     x.qmeta = ar.take<float>(4 * 64);
-    x.qimage = ar.take<uint4>(4 * 16 * 64);            // 64 KiB: the bf16 image of 64 queries (int8: half of it)
+    x.qimage = ar.take<uint4>((size_t)4 * (p.E / 32) * 64);      // the bf16 image of 64 queries, 64 KiB at E = 512, 96 KiB at 768 (int8: half of it)
     if (w) *w = x;
     return ar.off + 256;
 }
 
-inline int opt_in_rescore() {
+inline int opt_in_rescore(int E = 512) {
+    if (E == 768) return opt_in_lds((const void*)rescore_pairs_kernel<768>, rescore_lds(768));
     if (int rc = opt_in_lds((const void*)rescore_pairs_kernel<512>, RESCORE_LDS)) return rc;
     return opt_in_lds((const void*)rescore_pairs16_kernel<512>, RESCORE16_LDS);
 }
 
 // wide: the lists of a wide pass (up to 1 024 queries x ~500 pairs) go to the 16-pair form, the 64-query passes' to the 64-pair one
+// E = 768: the 64-pair form only (there is no wide pass; the 16-pair form would hold 4 x 12 row chunks = 192 VGPRs in flight)
 inline void launch_rescore(bool wide, dim3 grid, hipStream_t st, const float* db, const float* q, uint2* cand, const unsigned* gcnt,
-                           long long cap, const unsigned* slot_rows) {
+                           long long cap, const unsigned* slot_rows, int E = 512) {
+    if (E == 768) {
+        hipLaunchKernelGGL(rescore_pairs_kernel<768>, grid, dim3(256), rescore_lds(768), st, db, q, cand, gcnt, cap, slot_rows);
+        return;
+    }
 #ifdef CLIPMI_DEV
     static const int form = (int)dev_knob("CLIPMI_RESCORE", 0);            // 16 / 64: force one form (A/B)
     if (form == 16) wide = true;
@@ -2388,7 +2439,8 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
     if (!db_dev || !dbh_dev || !q_dev || !out_score_dev || !out_id_dev || !ws_dev || (i8 && !rmeta))
         return set_err(CLIPMI_EINVAL, "topk_ip_coarse: NULL pointer");
     if (i8 && !(amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", amax);
-    if (E != 512 || N < SAMPLE_MIN_N) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 and N >= %d", SAMPLE_MIN_N);
+    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N)
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
     if (!(rmax > 0.f) || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", rmax, (long long)N);
     Plan p;
     if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
@@ -2398,7 +2450,7 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
     carve_coarse(p, ws_dev, ws_bytes, &w);
     hipStream_t st = as_stream(stream);
     if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
-    if (int rc = opt_in_rescore()) return rc;
+    if (int rc = opt_in_rescore(E)) return rc;
     // int8: the rows the copy's slots hold, behind the block meta (quantize_rows_i8_kernel); bf16 copy: rows in order
     const unsigned* slot_rows = i8 ? i8_slot_rows(rmeta, N) : nullptr;
     // int8 copy, shards below 2^26 rows: the live-threshold scan - EXPERIMENTAL, off unless CLIPMI_LIVE=1. Bit-exact, ONE scan
@@ -2412,6 +2464,9 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
     // MFMA per fragment costs more than the re-scoring it saves - measured, development library only
     static const bool q2_on = dev_knob("CLIPMI_COARSE_Q2", 0) != 0;
     const bool q2 = i8 && q2_on && !live;
+    // both laboratory forms are built for E = 512 (LiveArgs rows of 512, COARSE_IMG2): asked for at 768 they refuse
+    if (E != 512 && i8 && (live_on || q2_on))
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse_i8: CLIPMI_LIVE / CLIPMI_COARSE_Q2 need E = 512 (E = %d)", E);
 #else
     constexpr bool live = false;
     constexpr bool q2 = false;
@@ -2424,9 +2479,15 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
         // what they consume): one launch per 64-query group
         {
             const int nq = (qa + 15) / 16 * 16;
-            if (i8)
+            if (i8 && E == 768)
+                hipLaunchKernelGGL((coarse_prep_kernel<true, 768>), dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
+                                   w.gcnt_e, COARSE_CTL, COARSE_QS, 0, 0);
+            else if (i8)
                 hipLaunchKernelGGL(coarse_prep_kernel<true>, dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
                                    w.gcnt_e, COARSE_CTL, COARSE_QS, 0, q2 ? 1 : 0);
+            else if (E == 768)
+                hipLaunchKernelGGL((coarse_prep_kernel<false, 768>), dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
+                                   w.gcnt_e, COARSE_CTL, COARSE_QS, 0, 0);
             else
                 hipLaunchKernelGGL(coarse_prep_kernel<false>, dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
                                    w.gcnt_e, COARSE_CTL, COARSE_QS);
@@ -2468,22 +2529,22 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
             int rc_;
 #ifdef CLIPMI_DEV
             if (i8 && q2)
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true, true>(c, nsteps, st, ev) : launch_coarse<1, false, true, true>(c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, true, true>(c, nsteps, st, ev) : launch_coarse<2, false, true, true>(c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, true, true>(c, nsteps, st, ev) : launch_coarse<4, false, true, true>(c, nsteps, st, ev));
+                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<1, false, true, true>(E, c, nsteps, st, ev))
+                    : qa <= 32 ? (pre ? launch_coarse<2, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<2, false, true, true>(E, c, nsteps, st, ev))
+                               : (pre ? launch_coarse<4, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<4, false, true, true>(E, c, nsteps, st, ev));
             else
 #endif
             if (i8)
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true>(c, nsteps, st, ev) : launch_coarse<1, false, true>(c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, true>(c, nsteps, st, ev) : launch_coarse<2, false, true>(c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, true>(c, nsteps, st, ev) : launch_coarse<4, false, true>(c, nsteps, st, ev));
+                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true>(E, c, nsteps, st, ev) : launch_coarse<1, false, true>(E, c, nsteps, st, ev))
+                    : qa <= 32 ? (pre ? launch_coarse<2, true, true>(E, c, nsteps, st, ev) : launch_coarse<2, false, true>(E, c, nsteps, st, ev))
+                               : (pre ? launch_coarse<4, true, true>(E, c, nsteps, st, ev) : launch_coarse<4, false, true>(E, c, nsteps, st, ev));
             else
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, false>(c, nsteps, st, ev) : launch_coarse<1, false, false>(c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, false>(c, nsteps, st, ev) : launch_coarse<2, false, false>(c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, false>(c, nsteps, st, ev) : launch_coarse<4, false, false>(c, nsteps, st, ev));
+                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, false>(E, c, nsteps, st, ev) : launch_coarse<1, false, false>(E, c, nsteps, st, ev))
+                    : qa <= 32 ? (pre ? launch_coarse<2, true, false>(E, c, nsteps, st, ev) : launch_coarse<2, false, false>(E, c, nsteps, st, ev))
+                               : (pre ? launch_coarse<4, true, false>(E, c, nsteps, st, ev) : launch_coarse<4, false, false>(E, c, nsteps, st, ev));
             if (rc_) return rc_;
             // ~1-3 k survivors per query = ~11 blocks of 256 pairs; a larger grid only queues idle blocks
-            launch_rescore(false, dim3(12, qa), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, COARSE_CAP, slot_rows);
+            launch_rescore(false, dim3(12, qa), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, COARSE_CAP, slot_rows, E);
             CLIPMI_CHECK_LAUNCH("rescore_pairs_kernel");
             // 4096 staged entries (32 KiB of LDS) cover these lists; a select block then fits on a CU even beside the
             // last segment's scan of ANOTHER batch in flight (104 KiB), which the 96-KiB staging of the sample select does not
@@ -2497,10 +2558,14 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
         // level 1 (exact, unfiltered, all <= 64 queries in one launch): scores of the first rows -> K-th best per query
         {
             const long long rows1 = two_level ? S1 : S2;
-            const size_t lds1 = (size_t)(512 / 16) * 1024;
-            if (int rc = opt_in_lds((const void*)sample_scores_kernel<512>, lds1)) return rc;
+            const size_t lds1 = (size_t)(E / 16) * 1024;           // the f32 image of 16 queries: 32 KiB, 48 KiB at E = 768
+            if (int rc = opt_in_lds(E == 768 ? (const void*)sample_scores_kernel<768> : (const void*)sample_scores_kernel<512>, lds1)) return rc;
             long long gs = ((rows1 + 15) / 16 + 3) / 4;
             if (gs > NUM_CU) gs = NUM_CU;
+            if (E == 768)
+                hipLaunchKernelGGL(sample_scores_kernel<768>, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), dim3(256), lds1, st, static_cast<const float*>(db_dev),
+                                   rows1, qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c);
+            else
             hipLaunchKernelGGL(sample_scores_kernel<512>, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), dim3(256), lds1, st, static_cast<const float*>(db_dev),
                                rows1, qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c);
             CLIPMI_CHECK_LAUNCH("sample_scores_kernel");
@@ -2961,7 +3026,9 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
     if (!db_dev || !db8_dev || !q_dev || !out_score_dev || !out_id_dev || !ws_dev || !rmeta)
         return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: NULL pointer");
     if (!(amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", amax);
-    if (E != 512 || N < SAMPLE_MIN_N) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 and N >= %d", SAMPLE_MIN_N);
+    // the wide passes are built for E = 512 (16 k-steps, 128-KiB tiles of 256 queries); clipmi_topk_ip_coarse_i8 sends E = 768
+    // through the 64-query passes
+    if (E != 512 || N < SAMPLE_MIN_N) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse (wide pass): needs E = 512 and N >= %d", SAMPLE_MIN_N);
     if (!(rmax > 0.f) || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", rmax, (long long)N);
     Plan p;
     if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
@@ -3084,12 +3151,13 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
 
 extern "C" size_t clipmi_topk_ip_coarse_workspace_bytes(int64_t N, int E, int Q, int K) {
     Plan p;
-    if (E != 512 || N < SAMPLE_MIN_N || !coarse_plan(N, E, Q, K, p)) {
-        set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512, N >= %d and a supported K", SAMPLE_MIN_N);
+    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N || !coarse_plan(N, E, Q, K, p)) {
+        set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: unsupported: needs E = 512 or 768, N >= %d and a supported K", SAMPLE_MIN_N);
         return 0;
     }
     size_t need = carve_coarse(p, nullptr, ~(size_t)0, nullptr);
-    if (Q > COARSE_Q) {                       // the int8 path takes a search of more than 64 queries as wide passes
+    // E = 768 has no wide pass: more than 64 queries run as 64-query passes inside the call, on the one 64-query workspace
+    if (Q > COARSE_Q && E == 512) {           // the int8 path takes a search of more than 64 queries as wide passes
         const size_t wide = carve_wide(p, Q < WIDE_MAX_Q ? Q : WIDE_MAX_Q, nullptr, ~(size_t)0, nullptr);
         need = wide > need ? wide : need;
     }
@@ -3356,7 +3424,7 @@ extern "C" int clipmi_rows_to_bf16(const float* db_dev, int64_t N, int E, void* 
 extern "C" int clipmi_topk_ip_coarse_i8(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax, int64_t N,
                                         int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
                                         float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-    if (Q > COARSE_Q && !wide_disabled())
+    if (Q > COARSE_Q && E == 512 && !wide_disabled())
         return topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K, id_base,
                               out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr, 0, nullptr);
     return topk_ip_coarse_impl(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q,

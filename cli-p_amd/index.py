@@ -51,6 +51,16 @@ def merge_lists_host(scores, ids, K):
     return out_s, out_i
 
 
+COARSE_DIMS = (512, 768)        # widths the coarse-then-exact paths are built for (csrc/topk.hip scan_coarse_kernel<E, ...>)
+COARSE_MIN_ROWS = 65536        # below this the library answers CLIPMI_EUNSUPPORTED (csrc/topk.hip SAMPLE_MIN_N)
+
+
+def coarse_eligible(coarse, d, ntotal):
+    """THE predicate of the coarse path: a coarse copy was asked for, the width has coarse kernels, the shard is large enough.
+    IndexFlatIP.uses_coarse(), repl.open_sharded and repl.main all decide with it."""
+    return coarse in ("bf16", "int8") and d in COARSE_DIMS and ntotal >= COARSE_MIN_ROWS
+
+
 class IndexFlatIP:
     """Exact inner-product index over f32 vectors resident in HBM."""
 
@@ -179,8 +189,8 @@ class IndexFlatIP:
         return self._db8 + (self._row_norm_max(),)
 
     def uses_coarse(self):
-        """True when searches go through a coarse-then-exact path (coarse copy requested, d = 512, N >= 65536)."""
-        return self.coarse in ("bf16", "int8") and self.d == 512 and self.ntotal >= 65536
+        """True when searches go through a coarse-then-exact path (coarse copy requested, d = 512 or 768, N >= 65536)."""
+        return coarse_eligible(self.coarse, self.d, self.ntotal)
 
     # -- query side ---------------------------------------------------------------------------
     def search_device(self, q, K, out=None, _one_pass=False):
@@ -201,13 +211,15 @@ class IndexFlatIP:
             dbh, rmax = self.matrix_bf16()
             coarse = rmax > 0.0 and np.isfinite(rmax)
         # more than 64 queries: the int8 path takes the whole search as wide passes inside the library (one stream of the
-        # copy per <= 1024 queries, csrc/topk.hip "Wide coarse pass"); the bf16 path pipelines its 64-query passes here
-        if coarse and self.coarse != "int8" and Q > self.PASS_Q and self.batches_in_flight > 1 and not _one_pass:
+        # copy per <= 1024 queries, csrc/topk.hip "Wide coarse pass"); the bf16 path pipelines its 64-query passes here, and so
+        # does the int8 path at d = 768, where the library has no wide pass (a 256-query tile of 768 bytes does not fit in LDS)
+        # and would run the 64-query passes one after the other on one stream
+        if coarse and (self.coarse != "int8" or self.d != 512) and Q > self.PASS_Q and self.batches_in_flight > 1 and not _one_pass:
             return self._search_pipelined(q, K, out, self.PASS_Q)
         # int8, more than one wide chunk (1024 queries): the chunks alternate between two streams the same way - one chunk's
         # re-scoring and selects run beside the other's matrix-bound scan (10 M rows, 2 x 1024 queries: 6.37 -> 6.07 ms per chunk,
         # 160.9 -> 168.8 k q/s; a single chunk cut in two halves gains nothing: 162.4 k)
-        if coarse and self.coarse == "int8" and Q > self.WIDE_Q and self.batches_in_flight > 1 and not _one_pass:
+        if coarse and self.coarse == "int8" and self.d == 512 and Q > self.WIDE_Q and self.batches_in_flight > 1 and not _one_pass:
             return self._search_pipelined(q, K, out, self.WIDE_Q)
         need = (L.clipmi_topk_ip_coarse_workspace_bytes if coarse else L.clipmi_topk_ip_workspace_bytes)(N, self.d, Q, K)
         if need == 0:
@@ -246,8 +258,8 @@ class IndexFlatIP:
     batches_in_flight = 2         # 64-query passes of ONE large search kept in flight on internal streams (1 = off)
 
     def _search_pipelined(self, q, K, out, chunk):
-        """A search of more than 64 queries on the bf16 coarse path (`chunk` = 64), or of more than 1024 on the int8 path (`chunk`
-        = 1024 = one wide pass): its passes alternate between the caller's stream and an
+        """A search of more than 64 queries on the bf16 coarse path or the int8 path at d = 768 (`chunk` = 64), or of more than 1024
+        on the int8 path at d = 512 (`chunk` = 1024 = one wide pass): its passes alternate between the caller's stream and an
         internal HIP stream (each with its own workspace), so one pass's latency-bound side kernels run beside the other's
         HBM-bound scan -
         what bench.py measures as "two batches in flight" (0.97-1.03 vs 1.09-1.10 ms per pass at 10 M rows). Same calls,

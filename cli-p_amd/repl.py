@@ -21,7 +21,7 @@ import time
 import numpy as np
 
 from . import store as vstore, tokenizer
-from .index import ShardedFlatIP, index_rows, read_index, shard_bounds
+from .index import ShardedFlatIP, coarse_eligible, index_rows, read_index, shard_bounds
 from .model import load
 from .ranks import Ranks
 
@@ -192,7 +192,7 @@ def open_sharded(path, ranks, coarse=None, local_search=None):
     if local_search is not None:
         return ShardedFlatIP(None, n, group=ranks.data, local_search=local_search)
     local = read_index(path, device=str(ranks.device), rows=(lo, hi))
-    if coarse in ("int8", "bf16") and local.d == 512 and local.ntotal >= 65536:
+    if coarse_eligible(coarse, local.d, local.ntotal):
         local.coarse = coarse
     return ShardedFlatIP(local, n, group=ranks.data)
 
@@ -211,7 +211,7 @@ def main():
         index = LeaderIndex(sharded, ranks)
     else:
         index = read_index("images.index", device=device)
-        if coarse in ("int8", "bf16") and index.d == 512 and index.ntotal >= 65536:
+        if coarse_eligible(coarse, index.d, index.ntotal):
             index.coarse = coarse
     model, _ = load(os.environ.get("CLIPMI_WEIGHTS", "ViT-B/32"), device=device, jit=False)
     model.eval()

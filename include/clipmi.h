@@ -157,7 +157,8 @@ int clipmi_topk_ip(const void* db_dev, int db_dtype, int64_t N, int E,
  * bf16 coarse scan of `db_bf16_dev` (the matrix rounded to bf16, [N][E]) that keeps a provable superset,
  * followed by exact f32 re-scoring of the survivors from `db_dev` (DESIGN.md "coarse path"). Half the HBM
  * bytes per pass and 64 queries per pass. `rmax` = an upper bound of the largest row L2 norm of db_dev.
- * E = 512, N >= 65536; if a candidate list overflows, the exact scan runs as a device-side fallback. */
+ * E = 512 or 768, N >= 65536 (anything else: CLIPMI_EUNSUPPORTED, a workspace size of 0); if a candidate list overflows,
+ * the exact scan runs as a device-side fallback. More than 64 queries are taken as 64-query passes inside the call. */
 size_t clipmi_topk_ip_coarse_workspace_bytes(int64_t N, int E, int Q, int K);
 int clipmi_topk_ip_coarse(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
                           const float* q_dev, int Q, int K, int64_t id_base,
@@ -175,8 +176,10 @@ int clipmi_topk_ip_coarse(const void* db_dev, const void* db_bf16_dev, int64_t N
  * score could reach the running K-th best, by |x.y - s t_q D| <= a_r ||y|| + (rmax + amax) ||y - t_q p_q||; survivors are
  * re-scored in exact f32 as above. `amax` >= every a_r, `rmax` >= every row norm. Up to 64 queries are one pass of the
  * copy (v_mfma_i32_16x16x64_i8, HBM-bound); MORE than 64 queries (query-index.py:111 is one call whatever Q) are taken
- * in chunks of <= 1024 as ONE pass each (v_mfma_i32_32x32x32_i8, query tiles of 256 resident in LDS, matrix-bound).
- * Workspace: clipmi_topk_ip_coarse_workspace_bytes. */
+ * in chunks of <= 1024 as ONE pass each at E = 512 (v_mfma_i32_32x32x32_i8, query tiles of 256 resident in LDS,
+ * matrix-bound); at E = 768, where such a tile (192 KiB) does not fit in LDS, as 64-query passes one after the other inside
+ * the call (a caller that wants them overlapped enqueues 64-query calls on two streams, as IndexFlatIP does).
+ * E = 512 or 768, N >= 65536. Workspace: clipmi_topk_ip_coarse_workspace_bytes. */
 /* Build-side helpers of the coarse copies (index load: query-index.py:60-75 reads every vector once and keeps the
  * matrix). clipmi_rows_stats writes stats2_dev[0] = the largest row norm of db (f64 accumulation, rounded up: a valid
  * `rmax`) and stats2_dev[1] = the largest a_r of an int8 copy's meta (`meta_dev` may be NULL: 0). clipmi_rows_to_bf16
