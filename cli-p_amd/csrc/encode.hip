@@ -35,6 +35,11 @@ struct Ws {
                               //          also the A operand of the LN-folded qkv / c_fc GEMMs
     float* ln_part;           //          row statistics of x as per-256-column (sum, sum of squares) [B*L][W/256][2]
     float* ln_leaf;           //          <= 128 rows (one prompt, one image): the statistics as per-4-column leaves [B*L][W/4][2]
+    // vision towers with bf16 weights: the class-token rows of the last block's tail (run_layers), compact
+    void* x3c;                // ln_fold: the B class-token rows of x3, [B][3 W bytes]
+    float* partc;             //          their statistics partials [B][W/256][2]
+    float* leafc;             //          B <= 128: or their statistics leaves [B][W/4][2]
+    float* xc;                // no ln_fold: the B class-token rows of x, f32 [B][W]
 };
 
 size_t carve(const clipmi_tower* t, int B, void* base, size_t cap, Ws* out) {
@@ -62,6 +67,15 @@ size_t carve(const clipmi_tower* t, int B, void* base, size_t cap, Ws* out) {
         w.x3 = ar.take<unsigned char>(rows * resid_row_bytes(W));
         w.ln_part = ar.take<float>(rows * 2 * (W / 256));
         if (rows <= (size_t)SKINNY_MAX_M) w.ln_leaf = ar.take<float>(rows * 2 * (W / 4));
+    }
+    if (t->kind == 0 && t->weight_format == 0) {
+        if (t->ln_fold) {
+            w.x3c = ar.take<unsigned char>((size_t)B * resid_row_bytes(W));
+            w.partc = ar.take<float>((size_t)B * 2 * (W / 256));
+            if (B <= SKINNY_MAX_M) w.leafc = ar.take<float>((size_t)B * 2 * (W / 4));
+        } else {
+            w.xc = ar.take<float>((size_t)B * W);
+        }
     }
     if (out) *out = w;
     return ar.off + 256;
@@ -97,14 +111,42 @@ const T* at(const void* blob, uint64_t off) {
     return reinterpret_cast<const T*>(static_cast<const char*>(blob) + off);
 }
 
+// The pruned tail of a vision tower (bf16 weights). encode_image reads only the class-token row of every image behind the
+// last block, and everything behind that block's attention is row-wise: out_proj, the residual adds, the LayerNorm
+// statistics, c_fc + QuickGELU and c_proj run over the B class-token rows instead of all B * L (ViT-B/32: 49 of 50 rows of
+// three of the twelve blocks' four GEMMs were computed to be thrown away). A row's bits depend neither on the batch size
+// nor on the kernel that computes it (gemm.hip), so the embeddings are the ones the full block gives.
+// At every batch size. With one or two ViT-B/32 images (all token rows on the skinny kernels) the tail is four launches in
+// place of three, and it still measured faster per call there; the CLIPMI_ENCODE_TAIL = 0 / 2 numbers are in DESIGN 4.7a.
+// CLIPMI_ENCODE_TAIL (development library): 0 = the last block over all rows; 1 = the product's rule and 2 = the tail at every
+// batch size, which are the same thing today.
+bool encode_tail() {
+    static const int mode = (int)dev_knob("CLIPMI_ENCODE_TAIL", 1);
+    return mode != 0;
+}
+
+// dst[b][:] = src[b * L][:], rows of row_bytes bytes (a multiple of 16): the class-token rows of the residual stream
+int launch_gather_rows(const void* src, void* dst, int B, int L, size_t row_bytes, hipStream_t st) {
+    if (row_bytes % 16 != 0) return set_err(CLIPMI_EINVAL, "gather_rows: %zu bytes per row", row_bytes);
+    const int row16 = (int)(row_bytes / 16);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)(((long long)B * row16 + 255) / 256)), dim3(256), 0, st,
+                       static_cast<const uint4*>(src), static_cast<uint4*>(dst), B, L, row16);
+    CLIPMI_CHECK_LAUNCH("gather_rows_kernel");
+    return 0;
+}
+
 // the 12 (or 24) residual attention blocks shared by both towers. weight_format 1 (BASELINE.json configs[4]): the
 // four linear layers of a block run on the FP8 matrix cores - weights are e4m3 with one scale per output channel
 // (packed by weights.py), the bf16 activation rows are quantised to e4m3 with one scale per row right before each
 // GEMM (quantize_rows_fp8_kernel), gemm256f8 applies both scales in its epilogue. LayerNorm, attention, the
 // residual stream, patch embedding and the final projection are unchanged.
-int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int causal, hipStream_t st, GemmProbe* probe) {
+// *pruned (vision towers): the last block ran its tail on the class-token rows, which are in w.x3c / w.xc, not w.x3 / w.x
+int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int causal, hipStream_t st, GemmProbe* probe,
+               bool* pruned = nullptr) {
     const int W = t->width, L = t->tokens, M = B * L;
     const bool fp8 = t->weight_format == 1;
+    const bool tail = pruned && !causal && !fp8 && (t->ln_fold ? w.x3c != nullptr : w.xc != nullptr) && encode_tail();
+    if (pruned) *pruned = tail;
     auto linear = [&](const unsigned short* A, int K, uint64_t w_off, uint64_t b_off, void* out, int N, int epi) -> int {
         GemmArgs g{};
         g.bias = at<float>(blob, b_off); g.out = out; g.M = M; g.N = N; g.K = K;
@@ -191,6 +233,32 @@ int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int 
         for (int l = 0; l < t->layers; ++l) {
             const uint64_t lb = lb_of(l);
             if (int rc = ln_linear(lb + t->lo_qkv_w, lb + t->lo_qkv_cb, lb + t->lo_qkv_colsum, 3 * W, EPI_LN_BIAS_BF16)) return rc;
+            if (tail && l == t->layers - 1) {
+                // the pruned tail: K and V of every token were needed, from here on only the class-token rows are. Their
+                // residual rows move to w.x3c (not in place: row b would land on rows another workgroup still reads), out_proj
+                // reads its A rows L apart in w.h, c_fc / c_proj use the head of w.big. No probe: bench.py's per-kernel times
+                // stay averages over launches of one shape. B <= 128: the skinny kernels with statistics leaves of their own.
+                const bool tleaf = w.leafc != nullptr && gemm_resid_writes_leaves(B, W, W) && gemm_resid_writes_leaves(B, W, 4 * W);
+                if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st)) return rc;
+                if (int rc = launch_gather_rows(w.x3, w.x3c, B, L, resid_row_bytes(W), st)) return rc;
+                auto tail_resid = [&](const unsigned short* A, unsigned lda_bytes, int K, uint64_t w_off, uint64_t b_off) -> int {
+                    GemmArgs g{};
+                    g.A = A; g.lda_bytes = lda_bytes; g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, b_off);
+                    g.M = B; g.N = W; g.K = K;
+                    g.x3 = w.x3c; g.ln_part = w.partc; g.tmp_f32 = w.x;
+                    if (tleaf) g.ln_leaf = w.leafc;
+                    return launch_gemm_algo(g, EPI_BIAS_RESID_LN_F32, 0, st, nullptr);
+                };
+                if (int rc = tail_resid(w.h, (unsigned)((size_t)L * W * 2), W, lb + t->lo_out_w, lb + t->lo_out_b)) return rc;
+                GemmArgs g{};
+                g.A = static_cast<const unsigned short*>(w.x3c); g.lda_bytes = (unsigned)resid_row_bytes(W);
+                g.W = at<unsigned short>(blob, lb + t->lo_fc_w); g.bias = at<float>(blob, lb + t->lo_fc_cb);
+                g.colsum = at<float>(blob, lb + t->lo_fc_colsum); g.ln_part_in = w.partc;
+                if (tleaf) g.ln_leaf_in = w.leafc;
+                g.out = w.big; g.M = B; g.N = 4 * W; g.K = W;
+                if (int rc = launch_gemm_algo(g, EPI_LN_BIAS_QGELU_BF16, 0, st, nullptr)) return rc;
+                return tail_resid(w.big, 0u, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b);     // the last block: done
+            }
             // (bench probe, mode 2: attention's own end stamp, so that out_proj gets a completion-to-completion time too)
             hipEvent_t* aev = nullptr;
             if (probe && probe->mode == 2 && probe->n < GemmProbe::MAX) {
@@ -254,6 +322,23 @@ int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int 
         if (int rc = launch_layernorm(ln, st)) return rc;
         if (int rc = linear(w.h, W, lb + t->lo_qkv_w, lb + t->lo_qkv_b, w.big, 3 * W, EPI_BIAS_BF16)) return rc;
         if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st)) return rc;
+        if (tail && l == t->layers - 1) {
+            // the pruned tail (see the LN-folded form above): the class-token rows of the f32 residual move to w.xc, ln_2
+            // writes its B rows to the head of w.h once out_proj has read the attention rows there
+            if (int rc = launch_gather_rows(w.x, w.xc, B, L, (size_t)W * 4, st)) return rc;
+            auto tail_linear = [&](const unsigned short* A, unsigned lda_bytes, int K, uint64_t w_off, uint64_t b_off, void* out, int N,
+                                   int epi) -> int {
+                GemmArgs g{};
+                g.A = A; g.lda_bytes = lda_bytes; g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, b_off);
+                g.out = out; g.M = B; g.N = N; g.K = K;
+                return launch_gemm_algo(g, epi, 0, st, nullptr);
+            };
+            if (int rc = tail_linear(w.h, (unsigned)((size_t)L * W * 2), W, lb + t->lo_out_w, lb + t->lo_out_b, w.xc, W, EPI_BIAS_RESID_F32)) return rc;
+            LnArgs ln2{w.xc, at<float>(blob, lb + t->lo_ln2_w), at<float>(blob, lb + t->lo_ln2_b), w.h, nullptr, 1, B, W, 1};
+            if (int rc = launch_layernorm(ln2, st)) return rc;
+            if (int rc = tail_linear(w.h, 0u, W, lb + t->lo_fc_w, lb + t->lo_fc_b, w.big, 4 * W, EPI_BIAS_QGELU_BF16)) return rc;
+            return tail_linear(w.big, 0u, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b, w.xc, W, EPI_BIAS_RESID_F32);     // the last block: done
+        }
         if (int rc = linear(w.h, W, lb + t->lo_out_w, lb + t->lo_out_b, w.x, W, EPI_BIAS_RESID_F32)) return rc;
         ln.w = at<float>(blob, lb + t->lo_ln2_w); ln.b = at<float>(blob, lb + t->lo_ln2_b);
         if (int rc = launch_layernorm(ln, st)) return rc;
@@ -325,7 +410,13 @@ static int encode_image_impl(const clipmi_tower* t, const void* blob_dev, const 
     if (fold8)     // FP8 tower with folded LayerNorms: the embedded rows' e4m3 image + statistics for the first qkv GEMM
         if (int rc = launch_rows_mx_stats(w.x, w.x8, w.x8_bs, w.ln_part, B * L, W, st)) return rc;
 #endif
-    if (int rc = run_layers(t, blob_dev, w, B, 0, st, probe)) return rc;
+    bool pruned = false;
+    if (int rc = run_layers(t, blob_dev, w, B, 0, st, probe, &pruned)) return rc;
+    if (pruned) {            // the class-token rows are compact
+        Ws wc = w;
+        wc.x = w.xc; wc.x3 = w.x3c;
+        return run_head(t, blob_dev, wc, B, nullptr, 1, out_dev, normalize, st);
+    }
     return run_head(t, blob_dev, w, B, nullptr, L, out_dev, normalize, st);
 }
 

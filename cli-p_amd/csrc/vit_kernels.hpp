@@ -134,6 +134,16 @@ static __global__ void __launch_bounds__(256) cls_rows_kernel(float* x, const fl
     x[(size_t)b * L * W + c] = cls[c] + pos[c];
 }
 
+// dst[b][:] = src[b * row_step][:], rows of row16 16-byte pieces: the class-token rows of the residual stream, compact, for
+// the last block's tail (encode.hip)
+static __global__ void __launch_bounds__(256) gather_rows_kernel(const uint4* __restrict__ src, uint4* __restrict__ dst, int B,
+                                                                 int row_step, int row16) {
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (long long)B * row16) return;
+    const int b = (int)(i / row16), c = (int)(i - (long long)b * row16);
+    dst[(size_t)b * row16 + c] = src[(size_t)b * row_step * row16 + c];
+}
+
 // x[q*L + t][:] = token_embedding[ids[q][t]] + positional_embedding[t]; one thread = 4 floats
 static __global__ void __launch_bounds__(256) text_embed_kernel(float* x, const int* ids, const float* tok, const float* pos,
                                                          int Q, int L, int W, int vocab) {

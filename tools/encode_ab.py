@@ -1,4 +1,6 @@
-"""Encode step A/B of env knobs (development aid): ms per step of B = 870, bf16, min of 3 x 8 steps."""
+"""Encode step A/B of env knobs (development aid): ms per step of B = 870 (or argv[1]), bf16, min of 3 x 8 steps.
+The line names the CLIPMI_* knobs the run was made with (e.g. CLIPMI_ENCODE_TAIL=0 / 2: the last block over all rows / the
+class-token tail at every batch size)."""
 import sys, os, time
 os.environ.setdefault("CLIPMI_DEV_LIB", "1")   # A/B knobs: development library only
 import torch
@@ -16,4 +18,5 @@ for _ in range(3):
     for _ in range(8): model.encode_image(x, normalize=True)
     torch.cuda.synchronize()
     best = min(best, (time.perf_counter() - t0) / 8)
-print(f"{os.environ.get('CLIPMI_GEMM_ST', 'default')}: {best * 1e3:.3f} ms per step, {B / best:.0f} images/s", flush=True)
+knobs = " ".join(f"{k}={v}" for k, v in sorted(os.environ.items()) if k.startswith("CLIPMI_") and k != "CLIPMI_DEV_LIB") or "default"
+print(f"{knobs}: B={B} {best * 1e3:.3f} ms per step, {B / best:.0f} images/s", flush=True)
