@@ -12,7 +12,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 DEV_LIB = os.environ.get("CLIPMI_DEV_LIB", "") not in ("", "0")
 LIB_PATH = os.path.join(HERE, "libclipmi_dev.so" if DEV_LIB else "libclipmi.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 F32, BF16, U8 = 0, 1, 2
 
 # every symbol include/clipmi.h declares (tests check the .so exports all of them)
@@ -22,6 +22,7 @@ SYMBOLS = [
     "clipmi_topk_ip_workspace_bytes", "clipmi_topk_ip",
     "clipmi_topk_ip_coarse_workspace_bytes", "clipmi_topk_ip_coarse", "clipmi_dbg_topk_coarse_scan_ms",
     "clipmi_rows_stats", "clipmi_rows_absmax", "clipmi_rows_order_workspace_bytes", "clipmi_rows_order_by_absmax", "clipmi_rows_to_bf16", "clipmi_i8_copy_bytes", "clipmi_i8_meta_bytes", "clipmi_quantize_rows_i8", "clipmi_topk_ip_coarse_i8", "clipmi_dbg_topk_coarse_i8_scan_ms",
+    "clipmi_topk_ip_wide_workspace_bytes", "clipmi_topk_ip_wide_i8", "clipmi_dbg_topk_wide_i8_scan_ms",
     "clipmi_dbg_quantize_rows_fp8", "clipmi_dbg_gemm_fp8",
     "clipmi_merge_topk_workspace_bytes", "clipmi_merge_topk", "clipmi_merge_topk_packed",
     "clipmi_l2_normalize_rows", "clipmi_resize_crop_rgb8", "clipmi_jpeg_workspace_bytes", "clipmi_jpeg_decode_rgb8", "clipmi_jpeg_progressive_workspace_bytes", "clipmi_jpeg_decode_progressive_rgb8", "clipmi_last_error", "clipmi_abi_version",
@@ -114,6 +115,14 @@ def lib():
     L.clipmi_dbg_topk_coarse_i8_scan_ms.restype = i32
     L.clipmi_dbg_topk_coarse_i8_scan_ms.argtypes = [vp, vp, vp, C.c_float, i64, i32, C.c_float, vp, i32, i32, vp, vp, vp, sz, vp,
                                                     i32, C.POINTER(C.c_float), C.POINTER(C.c_longlong)]
+    L.clipmi_topk_ip_wide_workspace_bytes.restype = sz
+    L.clipmi_topk_ip_wide_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.clipmi_topk_ip_wide_i8.restype = i32
+    L.clipmi_topk_ip_wide_i8.argtypes = [vp, vp, vp, C.c_float, i64, i32, C.c_float, vp, i32, i32, i64, vp, vp, vp, sz, vp]
+    L.clipmi_dbg_topk_wide_i8_scan_ms.restype = i32
+    L.clipmi_dbg_topk_wide_i8_scan_ms.argtypes = [vp, vp, vp, C.c_float, i64, i32, C.c_float, vp, i32, i32, vp, vp, vp, sz, vp,
+                                                  i32, C.POINTER(C.c_float), C.POINTER(C.c_longlong), C.POINTER(C.c_int),
+                                                  C.POINTER(C.c_int)]
     L.clipmi_dbg_topk_coarse_scan_ms.restype = i32
     L.clipmi_dbg_topk_coarse_scan_ms.argtypes = [vp, vp, i64, i32, C.c_float, vp, i32, i32, vp, vp, vp, sz, vp, i32,
                                                  C.POINTER(C.c_float), C.POINTER(C.c_longlong)]

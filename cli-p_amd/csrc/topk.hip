@@ -825,17 +825,18 @@ template <bool I8, int ET = 512>
 __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restrict__ q, int E, float rmax, float amax, int QA,
                                                           float* qmeta, uint4* qimage, unsigned* ctl, int nctl, int qs,
                                                           int wide = 0, int q2 = 0) {
-    constexpr int KS = ET / (I8 ? 64 : 32);         // k-steps of the 64-query image; E == ET (the wide image is 512-only)
+    constexpr int KS = ET / (I8 ? 64 : 32);         // k-steps of the 64-query image; E == ET
+    constexpr int KSW = ET / 32;                    // k-steps of the wide image: 16 at 512, 24 at 768 (2 KSW <= 64 lanes write it)
     const int lane = threadIdx.x & 63;
     const int qi = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (blockIdx.x == 0)
         for (int i = threadIdx.x; i < nctl; i += 256) ctl[i] = 0u;
     const int qg = qi >> 4, col = qi & 15;
-    // wide pass (int8): the B operand of v_mfma_i32_32x32x32_i8 - 32-query groups, 16 k-steps of 32 bytes, entry
-    // [(G*16 + s)*64 + h*32 + n] = bytes 32 s + 16 h .. + 15 of query 32 G + n
-    const int widx = ((qi >> 5) * 16 + (lane >> 1)) * 64 + (lane & 1) * 32 + (qi & 31);
+    // wide pass (int8): the B operand of v_mfma_i32_32x32x32_i8 - 32-query groups, KSW k-steps of 32 bytes, entry
+    // [(G*KSW + s)*64 + h*32 + n] = bytes 32 s + 16 h .. + 15 of query 32 G + n (lanes 0 .. 2 KSW - 1 hold (s, h) = (lane >> 1, lane & 1))
+    const int widx = ((qi >> 5) * KSW + (lane >> 1)) * 64 + (lane & 1) * 32 + (qi & 31);
     if (qi >= QA) {                                            // padding query of a used query group: zero image
-        if (wide) { if (lane < 32) qimage[widx] = make_uint4(0u, 0u, 0u, 0u); }
+        if (wide) { if (lane < 2 * KSW) qimage[widx] = make_uint4(0u, 0u, 0u, 0u); }
         else
             // KS * 4 entries per query: 32 (int8) or 64 (bf16) at E = 512 - one round of the wave -, 48 or 96 at E = 768
             for (int e = lane; e < KS * 4; e += 64) {
@@ -886,7 +887,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
         qmeta[3 * qs + qi] = margin;
     }
     if (I8 && wide) {
-        if (lane < 32) {
+        if (lane < 2 * KSW) {
             const float* p = y + 32 * (lane >> 1) + 16 * (lane & 1);
             unsigned w[4];
 #pragma unroll
@@ -1910,21 +1911,27 @@ inline const unsigned* i8_slot_rows(const float2* rmeta, int64_t N) {
 }
 
 constexpr int WIDE_MAX_Q = 1024;                 // queries of one wide launch (4 tiles of 256)
-constexpr int WIDE_TILE_SETS = 4;                // 64-query sets per tile: 4 x 32 KiB of image
+// E = 768 (scan_coarse_wide_kernel<4, 0, 24>, opt-in: clipmi_topk_ip_wide_i8): 1024 as well = 8 tiles of 128, eight workgroups of
+// an XCD on every block. The pass is matrix-bound, so the eight readers cost L2 hits the MFMAs hide, while 512 per launch would
+// stream the copy from HBM twice per 1024 queries and double the sample / re-score / select launches per query.
+constexpr int WIDE768_MAX_Q = 1024;
+constexpr int WIDE_TILE_SETS = 4;                // 64-query sets per tile: 4 x 32 KiB of image (E = 512)
+constexpr int WIDE768_TILE_SETS = 2;             // E = 768: 2 x 48 KiB
+inline int wide_max_q(int E) { return E == 768 ? WIDE768_MAX_Q : WIDE_MAX_Q; }
 constexpr int WIDE_FLUSH = 128;                  // pending pairs per wave that trigger a flush
 constexpr int WIDE_LIST = WIDE_FLUSH + 256;      // a (row tile, query group) block appends <= 256 behind a pending flush
 constexpr size_t WIDE_WAVE_BYTES = (size_t)WIDE_LIST * 8;
 constexpr long long WIDE_CAP = 1ll << 15;        // candidate slots per query of a wide pass (overflow arms the exact fallback)
 
 struct WideArgs {
-    const signed char* dbc;      // int8 copy, 32-row blocks of [16][64][16 B] (quantize_rows_i8_kernel)
+    const signed char* dbc;      // int8 copy, 32-row blocks of [E / 32][64][16 B] (quantize_rows_i8_kernel)
     const float2* rmeta;         // per row (block scale, error norm), padded to 32 rows
     const float2* bmeta;         // per 32-row block (scale, largest error norm)
     const float* qmeta;          // [4][qs]
-    const uint4* qimage;         // all queries' image, 64-query sets of 32 KiB (coarse_prep_kernel, wide form)
+    const uint4* qimage;         // all queries' image, 64-query sets of 32 KiB (48 KiB at E = 768; coarse_prep_kernel, wide form)
     long long row0, nrows;       // rows [row0, row0 + nrows), row0 % 32 == 0
     int Q, qs;
-    int nqt, spt;                // query tiles, 64-query sets per tile (<= WIDE_TILE_SETS)
+    int nqt, spt;                // query tiles, 64-query sets per tile (<= WIDE_TILE_SETS; WIDE768_TILE_SETS at E = 768)
     uint2* cand;                 // [Q][cap]
     unsigned* gcnt;              // [qs]
     long long cap;
@@ -1948,10 +1955,19 @@ __device__ __noinline__ void wide_flush(const uint2* list, int n, int qbase, uns
     wave_lds_sync();
 }
 
-template <int WAVES, int ABL = 0>      // ABL: development ablations (1 no compare, 2 few LDS reads, 3 no row loads)
+// KS = E / 32 k-steps: 16 (E = 512, 8 waves: this block's rows and the next one's, 2 x 64 registers, at two waves per SIMD) or
+// 24 (E = 768). At 768 the two row sets are 2 x 96 registers; with two accumulators (32) and the fragment ring (16) that is past
+// the 256 of a wave at two per SIMD, so the 768 form is the FOUR-wave workgroup: one wave per SIMD owns the SIMD's whole
+// register file (512: 256 VGPRs + 256 AGPRs), the allocator keeps what does not fit in VGPRs in AGPRs (MFMA reads its A operand
+// from either file) and nothing goes to scratch. The compare of group G - 1 already runs between group G's MFMAs inside one
+// wave; what the second wave per SIMD hid at 512 - the append path and the wait for the next block - is exposed here
+// (speed not measured).
+template <int WAVES, int ABL = 0, int KS = 16>      // ABL: development ablations (1 no compare, 2 few LDS reads, 3 no row loads)
 __global__ void __launch_bounds__(WAVES * 64) scan_coarse_wide_kernel(WideArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int KS = 16;                                    // k-steps of 32 bytes
+    static_assert(KS == 16 || (KS == 24 && WAVES == 4), "E = 512 (any WAVES) or E = 768 as the four-wave form");
+    static_assert(KS * 32 * 127 * 127 < (1 << 24), "the integer sums must be exact in f32 (pretest, append)");
+    constexpr int BLOCK_BYTES = 32 * 32 * KS;                 // one 32-row block of the copy
     constexpr int SET_ENTRIES = 2 * KS * 64;                  // 16-byte entries of one 64-query set's image (32 KiB)
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1982,7 +1998,7 @@ __global__ void __launch_bounds__(WAVES * 64) scan_coarse_wide_kernel(WideArgs a
                 if (base + i * WAVES * 64 < ne) qimg[base + i * WAVES * 64] = v[i];
         }
     }
-    float* ltau = reinterpret_cast<float*>(smem + (size_t)a.spt * SET_ENTRIES * 16);       // [256] scaled thresholds
+    float* ltau = reinterpret_cast<float*>(smem + (size_t)a.spt * SET_ENTRIES * 16);       // [256] scaled thresholds (128 used at E = 768)
     float* lyt = ltau + 64 * WIDE_TILE_SETS;                                               // [256] 1.001 ||y|| / t_q
     for (int i = tid; i < 64 * WIDE_TILE_SETS; i += WAVES * 64) {
         const bool act = i < nsets * 64 && qbase + i < a.Q;
@@ -2009,7 +2025,7 @@ __global__ void __launch_bounds__(WAVES * 64) scan_coarse_wide_kernel(WideArgs a
         const unsigned lane16 = (unsigned)lane * 16u;
         auto load_block = [&](int b_, uint4 (&dst)[KS]) {
             const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(
-                const_cast<signed char*>(a.dbc) + (size_t)b_ * (32 * 512), 0, 32 * 512, 0x00020000);
+                const_cast<signed char*>(a.dbc) + (size_t)b_ * BLOCK_BYTES, 0, BLOCK_BYTES, 0x00020000);
 #pragma unroll
             for (int s_ = 0; s_ < KS; ++s_)
                 dst[s_] = __builtin_bit_cast(uint4, __builtin_amdgcn_raw_buffer_load_b128(rs, lane16, s_ * 1024, (CLIPMI_NT_MASK & 2) ? 2 : 0));
@@ -2043,9 +2059,18 @@ __global__ void __launch_bounds__(WAVES * 64) scan_coarse_wide_kernel(WideArgs a
             }
             // The exact test of a (row, query) pair is  D s + a_r Y_q >= T_q  (T_q = (tau - margin) / t_q, Y_q = 1.001 ||y|| / t_q;
             // s the block's scale). Integer pre-test, one per lane (= query): no row of the block can pass unless
-            // D >= (T_q - amax_block Y_q) / s, rounded down with slack for the f32 roundings on both sides (|D| < 2^23 is exact
-            // in f32; each side rounds a few times at ~1e-7 relative) - so the lane's largest D decides, and the per-row test
-            // runs only where it can succeed. +inf thresholds (padding queries: any Q that is not a multiple of 32) are "never" by
+            // D >= (T_q - amax_block Y_q) / s, rounded down with slack for the f32 roundings on both sides (|D| <= 32 KS 127^2
+            // < 2^24 is exact in f32: 8.3e6 at 512, 1.24e7 at 768 - static_assert above) - so the lane's largest D decides, and the
+            // per-row test runs only where it can succeed.
+            // The slack, for |x| up to 1.3e7 (u = 2^-24): a row passes when fl(D s + fl(a Y)) >= T, i.e. D >= x* - u (|T| + a Y) / s
+            // with x* = (T - a Y) / s in real numbers. a / s <= 1.001 sqrt(E) / 2 (half a step per component) and Y <= 1.001 * 127
+            // sqrt(E), so a Y / s <= 4.9e4 at E = 768 and |T| / s <= |x*| + 4.9e4: D >= x* - u |x*| - 0.006. The computed
+            // xq = fl(fl(T - a Y) fl(1 / s)) has three roundings: |xq - x*| <= 3.0001 u |x*|. The two subtractions below round to
+            // half a unit each while |xq| < 2^24 (to u |xq| beyond). Needed: 1.006 + 4.1 u |x| = 1.006 + 2.5e-7 |x| (4.2 at
+            // |x| = 1.3e7); taken: 2 + 2e-6 |x| (28 there) - the constants of the 512 form, which needed 1.004 + 2.5e-7 |x|, hold
+            // at 768 unchanged. Past 2^24 no D exists: x* > 1.3e7 passes nothing and x* < -1.3e7 everything, and the relative
+            // slack (2e-6 against 6 u) keeps dmin on the right side of every possible D.
+            // +inf thresholds (padding queries: any Q that is not a multiple of 32) are "never" by
             // an explicit test - inf - inf below would be NaN = "always", and every block would then run the 16-ballot append
             // path for its padding lanes; an all-zero block (s = 0: inv_s = inf) clamps to +-1e9 by its sign;
             // -inf (no threshold yet) and NaN stay "always".
@@ -2414,7 +2439,7 @@ inline int opt_in_rescore(int E = 512) {
 }
 
 // wide: the lists of a wide pass (up to 1 024 queries x ~500 pairs) go to the 16-pair form, the 64-query passes' to the 64-pair one
-// E = 768: the 64-pair form only (there is no wide pass; the 16-pair form would hold 4 x 12 row chunks = 192 VGPRs in flight)
+// E = 768: the 64-pair form only, for the wide pass too (the 16-pair form would hold 4 x 12 row chunks = 192 VGPRs in flight)
 inline void launch_rescore(bool wide, dim3 grid, hipStream_t st, const float* db, const float* q, uint2* cand, const unsigned* gcnt,
                            long long cap, const unsigned* slot_rows, int E = 512) {
     if (E == 768) {
@@ -2693,7 +2718,7 @@ size_t carve_wide(const Plan& p, int Qc, void* base, size_t cap, WideWs* w) {
     x.thr0 = ar.take<float>(qs);
     x.last_m = ar.take<unsigned>(qs);
     x.qmeta = ar.take<float>(4 * qs);
-    x.qimage = ar.take<uint4>(qs / 64 * 2048);        // 32 KiB per 64-query set
+    x.qimage = ar.take<uint4>(qs / 64 * (size_t)(4 * p.E));     // 2 (E / 32) 64 entries per 64-query set: 32 KiB, 48 KiB at E = 768
     if (w) *w = x;
     return ar.off + 256;
 }
@@ -2984,13 +3009,15 @@ int launch_wide2(const WideArgs& a, hipStream_t st, hipEvent_t* ev, int ng) {
     return ng == 2 ? launch_wide2_t<NB, 2>(a, st, ev) : launch_wide2_t<NB, 1>(a, st, ev);
 }
 
-template <int WAVES, int ABL = 0>
+template <int WAVES, int ABL = 0, int KS = 16>
 int launch_wide_t(const WideArgs& a, hipStream_t st, hipEvent_t* ev) {
-    const size_t lds = (size_t)a.spt * 32768 + 2048 + WAVES * WIDE_WAVE_BYTES;
+    // image (2 KiB per k-step and 64-query set) | thresholds | lists: 8 waves 154 KiB at E = 512, 4 waves 110 KiB at E = 768
+    if (a.spt > (KS == 24 ? WIDE768_TILE_SETS : WIDE_TILE_SETS)) return set_err(CLIPMI_EINVAL, "scan_coarse_wide: %d sets per tile", a.spt);
+    const size_t lds = (size_t)a.spt * (KS * 2048) + 2048 + WAVES * WIDE_WAVE_BYTES;
     if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse_wide: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_wide_kernel<WAVES, ABL>, lds)) return rc;
+    if (int rc = opt_in_lds((const void*)scan_coarse_wide_kernel<WAVES, ABL, KS>, lds)) return rc;
     if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_wide_kernel<WAVES, ABL>), dim3(NUM_CU), dim3(WAVES * 64), lds, st, a);
+    hipLaunchKernelGGL((scan_coarse_wide_kernel<WAVES, ABL, KS>), dim3(NUM_CU), dim3(WAVES * 64), lds, st, a);
     if (ev) (void)hipEventRecord(ev[1], st);
     CLIPMI_CHECK_LAUNCH("scan_coarse_wide_kernel");
     return 0;
@@ -3019,20 +3046,23 @@ int wide_segments(long long N, int K, long long S1, long long* b) {
     return n;
 }
 
-// int8 coarse-then-exact search of 64 < Q queries: chunks of <= WIDE_MAX_Q queries, each ONE pass of the copy in segments
+// int8 coarse-then-exact search of 64 < Q queries: chunks of <= WIDE_MAX_Q queries, each ONE pass of the copy in segments.
+// E = 768 (clipmi_topk_ip_wide_i8 only): the same sequence with the four-wave scan (tiles of 128 queries), the sample and the
+// 64-pair re-scoring at 768; chunks of WIDE768_MAX_Q.
 int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta, float amax, int64_t N, int E, float rmax,
                    const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev, void* ws_dev,
                    size_t ws_bytes, void* stream, hipEvent_t* scan_ev, int max_ev, int* n_ev) {
     if (!db_dev || !db8_dev || !q_dev || !out_score_dev || !out_id_dev || !ws_dev || !rmeta)
         return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: NULL pointer");
     if (!(amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", amax);
-    // the wide passes are built for E = 512 (16 k-steps, 128-KiB tiles of 256 queries); clipmi_topk_ip_coarse_i8 sends E = 768
-    // through the 64-query passes
-    if (E != 512 || N < SAMPLE_MIN_N) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse (wide pass): needs E = 512 and N >= %d", SAMPLE_MIN_N);
+    // clipmi_topk_ip_coarse_i8 sends E = 768 through the 64-query passes; clipmi_topk_ip_wide_i8 here
+    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N)
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse (wide pass): needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
     if (!(rmax > 0.f) || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", rmax, (long long)N);
     Plan p;
     if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
-    const int qc_max = Q < WIDE_MAX_Q ? Q : WIDE_MAX_Q;
+    const int chunk = wide_max_q(E), tile_sets = E == 768 ? WIDE768_TILE_SETS : WIDE_TILE_SETS;
+    const int qc_max = Q < chunk ? Q : chunk;
     if (ws_bytes < carve_wide(p, qc_max, nullptr, ~(size_t)0, nullptr))
         return set_err(CLIPMI_EWORKSPACE, "topk_ip_coarse_i8: workspace %zu too small", ws_bytes);
     WideWs w;
@@ -3041,15 +3071,19 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
     hipStream_t st = as_stream(stream);
     const unsigned* slot_rows = i8_slot_rows(rmeta, N);
     if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
-    if (int rc = opt_in_rescore()) return rc;
-    const size_t lds1 = (size_t)(512 / 16) * 1024;
-    if (int rc = opt_in_lds((const void*)sample_scores_kernel<512>, lds1)) return rc;
+    if (int rc = opt_in_rescore(E)) return rc;
+    const size_t lds1 = (size_t)(E / 16) * 1024;               // the f32 image of 16 queries: 32 KiB, 48 KiB at E = 768
+    if (int rc = opt_in_lds(E == 768 ? (const void*)sample_scores_kernel<768> : (const void*)sample_scores_kernel<512>, lds1)) return rc;
     int ev_used = 0;
 
-    for (int q0 = 0; q0 < Q; q0 += WIDE_MAX_Q) {
-        const int qc = (Q - q0) < WIDE_MAX_Q ? (Q - q0) : WIDE_MAX_Q;
+    for (int q0 = 0; q0 < Q; q0 += chunk) {
+        const int qc = (Q - q0) < chunk ? (Q - q0) : chunk;
         const float* qg = q_dev + (size_t)q0 * E;
         const int nsets = (qc + 63) / 64;
+        if (E == 768)
+            hipLaunchKernelGGL((coarse_prep_kernel<true, 768>), dim3(nsets * 16), dim3(256), 0, st, qg, E, rmax, amax, qc, w.qmeta,
+                               w.qimage, w.gcnt_e, 2 * qs + 4, qs, 1, 0);
+        else
         hipLaunchKernelGGL(coarse_prep_kernel<true>, dim3(nsets * 16), dim3(256), 0, st, qg, E, rmax, amax, qc, w.qmeta, w.qimage,
                            w.gcnt_e, 2 * qs + 4, qs, 1);
         CLIPMI_CHECK_LAUNCH("coarse_prep_kernel(wide)");
@@ -3064,6 +3098,17 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
             static const int sqg = (int)dev_knob("CLIPMI_WIDE_SAMPLE_QG", 2);
             const int ngroups = (qc + 16 * sqg - 1) / (16 * sqg);
             if (ngroups >= 8 / sqg && gs > sdiv) gs = (gs + sdiv - 1) / sdiv;
+            if (E == 768) {
+                // QG = 2 at 768 as well: 48 row registers more than at 512, inside the 512 of a 256-thread workgroup (resource
+                // table, DESIGN 4.1l: no scratch)
+                if (sqg == 2) {
+                    if (int rc = opt_in_lds((const void*)sample_scores_kernel<768, 2>, 2 * lds1)) return rc;
+                    hipLaunchKernelGGL((sample_scores_kernel<768, 2>), dim3((unsigned)gs, (unsigned)ngroups), dim3(256), 2 * lds1, st,
+                                       static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
+                } else
+                hipLaunchKernelGGL(sample_scores_kernel<768>, dim3((unsigned)gs, (unsigned)ngroups), dim3(256), lds1, st,
+                                   static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
+            } else
             if (sqg == 2) {
                 if (int rc = opt_in_lds((const void*)sample_scores_kernel<512, 2>, 2 * lds1)) return rc;
                 hipLaunchKernelGGL((sample_scores_kernel<512, 2>), dim3((unsigned)gs, (unsigned)ngroups), dim3(256), 2 * lds1, st,
@@ -3083,7 +3128,7 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
         c.dbc = static_cast<const signed char*>(db8_dev); c.rmeta = rmeta; c.qmeta = w.qmeta; c.qimage = w.qimage;
         c.bmeta = rmeta + i8_row_meta_entries(N);
         c.Q = qc; c.qs = qs;
-        c.nqt = (nsets + WIDE_TILE_SETS - 1) / WIDE_TILE_SETS;
+        c.nqt = (nsets + tile_sets - 1) / tile_sets;
         c.spt = (nsets + c.nqt - 1) / c.nqt;
         c.cand = w.cand_c; c.gcnt = w.gcnt_c; c.cap = WIDE_CAP; c.overflow = w.flag;
         {
@@ -3101,6 +3146,9 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
             c.row0 = r0;
             c.nrows = bnd[sgi] - r0;
             hipEvent_t* ev = (scan_ev && ev_used + 2 <= max_ev) ? scan_ev + ev_used : nullptr;
+            if (E == 768) {
+                if (int rc = (launch_wide_t<4, 0, 24>(c, st, ev))) return rc;
+            } else {
 #ifdef CLIPMI_DEV
             static const int abl = (int)dev_knob("CLIPMI_WIDE_ABL", 0);        // ablations + the 4-wave form: development build only
             // CLIPMI_WIDE2=0: never the second form (A/B); CLIPMI_WIDE2_MINQ: smallest query count that takes it
@@ -3116,8 +3164,9 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
 #else
             if (int rc = qc >= W2_MIN_Q ? launch_wide2<4>(c, st, ev, wide2_groups(qc)) : launch_wide_t<8>(c, st, ev)) return rc;
 #endif
+            }
             if (ev) ev_used += 2;
-            launch_rescore(true, dim3(12, qc), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, WIDE_CAP, slot_rows);
+            launch_rescore(true, dim3(12, qc), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, WIDE_CAP, slot_rows, E);
             CLIPMI_CHECK_LAUNCH("rescore_pairs16_kernel(wide)");
             // keep: bit 0 = the K best stay at the head of the list for the next segment; bit 1 = add to the survivor count
             const int keep = (last ? 0 : 1) | (sgi > 0 ? 2 : 0);
@@ -3429,6 +3478,87 @@ extern "C" int clipmi_topk_ip_coarse_i8(const void* db_dev, const void* db_i8_de
                               out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr, 0, nullptr);
     return topk_ip_coarse_impl(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q,
                                K, id_base, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr);
+}
+
+// The opt-in pair (ABI 8): clipmi_topk_ip_coarse_i8 with a wide pass at E = 768 as well. E = 512 and Q <= 64 ARE that function
+// (and its workspace); E = 768 with more than 64 queries runs chunks of <= WIDE768_MAX_Q as one pass of the copy each.
+extern "C" size_t clipmi_topk_ip_wide_workspace_bytes(int64_t N, int E, int Q, int K) {
+    size_t need = clipmi_topk_ip_coarse_workspace_bytes(N, E, Q, K);          // 0 + `unsupported` under its conditions
+    if (need == 0 || E != 768 || Q <= COARSE_Q) return need;
+    Plan p;
+    if (!coarse_plan(N, E, Q, K, p)) return need;
+    const size_t wide = carve_wide(p, Q < WIDE768_MAX_Q ? Q : WIDE768_MAX_Q, nullptr, ~(size_t)0, nullptr);
+    return wide > need ? wide : need;
+}
+
+extern "C" int clipmi_topk_ip_wide_i8(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax, int64_t N,
+                                      int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
+                                      float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    if (Q > COARSE_Q && E == 768)
+        return topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K, id_base,
+                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr, 0, nullptr);
+    return clipmi_topk_ip_coarse_i8(db_dev, db_i8_dev, meta_dev, amax, N, E, rmax, q_dev, Q, K, id_base, out_score_dev, out_id_dev,
+                                    ws_dev, ws_bytes, stream);
+}
+
+// Measurement hook of the wide passes (64 < Q, E = 512 or 768): the call `reps` times, chunk by chunk, with events around every
+// wide scan launch; synchronises after each chunk to read its survivor counts and overflow flag (both are per-chunk state of the
+// workspace). Everything reported is the LAST repetition's.
+extern "C" int clipmi_dbg_topk_wide_i8_scan_ms(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax,
+                                               int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
+                                               float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
+                                               void* stream, int reps, float* scan_ms, long long* survivors, int* scan_launches,
+                                               int* fallback_armed) {
+    if (!scan_ms || reps < 1 || Q <= COARSE_Q || (E != 512 && E != 768) || !q_dev || !out_score_dev || !out_id_dev)
+        return set_err(CLIPMI_EINVAL, "dbg_topk_wide_i8_scan_ms: bad arguments (64 < Q, E = 512 or 768)");
+    Plan p;
+    if (N < SAMPLE_MIN_N || !coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EUNSUPPORTED, "dbg_topk_wide_i8_scan_ms: unsupported N=%lld K=%d", (long long)N, K);
+    const int chunk = wide_max_q(E);
+    constexpr int NEV = 2 * WIDE_MAX_SEGS;
+    hipEvent_t ev[NEV];
+    for (int i = 0; i < NEV; ++i)
+        if (hipEventCreate(&ev[i]) != hipSuccess) return set_err(CLIPMI_EHIP, "hipEventCreate");
+    unsigned host[WIDE_MAX_Q > WIDE768_MAX_Q ? WIDE_MAX_Q : WIDE768_MAX_Q];
+    hipStream_t st = as_stream(stream);
+    int rc = 0, launches = 0, armed = 0;
+    long long tot = 0;
+    double total = 0.0;
+    for (int r = 0; r < reps && rc == 0; ++r) {
+        launches = 0; armed = 0; tot = 0; total = 0.0;
+        for (int q0 = 0; q0 < Q && rc == 0; q0 += chunk) {
+            const int qc = (Q - q0) < chunk ? (Q - q0) : chunk;
+            int n_ev = 0;
+            // a chunk of <= 64 queries (the tail of Q = k chunk + 1 ...) is still a wide pass inside a whole call: keep it one here
+            rc = topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev + (size_t)q0 * E,
+                                qc, K, 0, out_score_dev + (size_t)q0 * K, out_id_dev + (size_t)q0 * K, ws_dev, ws_bytes, stream, ev,
+                                NEV, &n_ev);
+            if (rc) break;
+            if (hipStreamSynchronize(st) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipStreamSynchronize"); break; }
+            for (int j = 0; j + 1 < n_ev; j += 2) {
+                float ms = 0.f;
+                (void)hipEventElapsedTime(&ms, ev[j], ev[j + 1]);
+                total += ms;
+            }
+            launches += n_ev / 2;
+            WideWs w;
+            carve_wide(p, qc, ws_dev, ws_bytes, &w);
+            unsigned flag = 0;
+            if (hipMemcpy(host, w.last_m, sizeof(unsigned) * qc, hipMemcpyDeviceToHost) != hipSuccess ||
+                hipMemcpy(&flag, w.flag, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) {
+                rc = set_err(CLIPMI_EHIP, "hipMemcpy(wide counters)");
+                break;
+            }
+            for (int i = 0; i < qc; ++i) tot += host[i] < WIDE_CAP ? host[i] : WIDE_CAP;
+            armed |= flag != 0;
+        }
+    }
+    for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
+    if (rc) return rc;
+    *scan_ms = (float)total;
+    if (survivors) *survivors = tot;
+    if (scan_launches) *scan_launches = launches;
+    if (fallback_armed) *fallback_armed = armed;
+    return 0;
 }
 
 // Measurement hook: clipmi_topk_ip_coarse `reps` times with events around the bf16 scan kernel (Q <= 64).

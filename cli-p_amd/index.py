@@ -64,16 +64,22 @@ def coarse_eligible(coarse, d, ntotal):
 class IndexFlatIP:
     """Exact inner-product index over f32 vectors resident in HBM."""
 
-    def __init__(self, d, device="cuda:0", coarse=None):
+    def __init__(self, d, device="cuda:0", coarse=None, wide_768=None):
         """coarse="bf16": keep a bf16 copy of the matrix beside the f32 one (+50 % HBM) and search through
         clipmi_topk_ip_coarse — a bf16-MFMA scan that keeps a provable superset, then exact f32
         re-scoring: same bit-exact results, half the bytes per pass, 64 queries per pass.
         coarse="int8": the same with a per-row-scaled int8 copy (+25 % HBM + 8 B per row): a quarter of the
         f32 bytes per pass; the superset bound uses each row's exact quantisation-error norm, so rows with
-        one dominant component loosen it (more survivors, or the exact fallback) but never change results."""
+        one dominant component loosen it (more survivors, or the exact fallback) but never change results.
+        wide_768 (opt-in; d = 768 with coarse="int8" only, ignored otherwise): searches of more than 64 queries go through
+        clipmi_topk_ip_wide_i8 - one pass of the int8 copy per <= 1024 queries instead of one per 64. Same bit-exact
+        results. None takes $CLIPMI_WIDE_768 ("" or "0": off, anything else: on); the default is off."""
         if coarse not in (None, "bf16", "int8"):
             raise ValueError("IndexFlatIP: coarse must be None, 'bf16' or 'int8'")
         self.coarse = coarse
+        if wide_768 is None:
+            wide_768 = os.environ.get("CLIPMI_WIDE_768", "") not in ("", "0")
+        self.wide_768 = bool(wide_768)
         self._dbh = None
         self._rmax = None
         self._db8 = None
@@ -212,16 +218,22 @@ class IndexFlatIP:
             coarse = rmax > 0.0 and np.isfinite(rmax)
         # more than 64 queries: the int8 path takes the whole search as wide passes inside the library (one stream of the
         # copy per <= 1024 queries, csrc/topk.hip "Wide coarse pass"); the bf16 path pipelines its 64-query passes here, and so
-        # does the int8 path at d = 768, where the library has no wide pass (a 256-query tile of 768 bytes does not fit in LDS)
-        # and would run the 64-query passes one after the other on one stream
-        if coarse and (self.coarse != "int8" or self.d != 512) and Q > self.PASS_Q and self.batches_in_flight > 1 and not _one_pass:
+        # does the int8 path at d = 768 by default: clipmi_topk_ip_coarse_i8 has no wide pass there (a 256-query tile of 768
+        # bytes does not fit in LDS) and would run the 64-query passes one after the other on one stream
+        # (opt-in at d = 768, `wide_768`: the library's wide pass there - clipmi_topk_ip_wide_i8 -, chunks of WIDE_Q_768 queries)
+        wide768 = bool(coarse) and self._wide_768_on() and Q > self.PASS_Q
+        if coarse and (self.coarse != "int8" or self.d != 512) and not wide768 and Q > self.PASS_Q and self.batches_in_flight > 1 \
+                and not _one_pass:
             return self._search_pipelined(q, K, out, self.PASS_Q)
         # int8, more than one wide chunk (1024 queries): the chunks alternate between two streams the same way - one chunk's
         # re-scoring and selects run beside the other's matrix-bound scan (10 M rows, 2 x 1024 queries: 6.37 -> 6.07 ms per chunk,
         # 160.9 -> 168.8 k q/s; a single chunk cut in two halves gains nothing: 162.4 k)
         if coarse and self.coarse == "int8" and self.d == 512 and Q > self.WIDE_Q and self.batches_in_flight > 1 and not _one_pass:
             return self._search_pipelined(q, K, out, self.WIDE_Q)
-        need = (L.clipmi_topk_ip_coarse_workspace_bytes if coarse else L.clipmi_topk_ip_workspace_bytes)(N, self.d, Q, K)
+        if wide768 and Q > self.WIDE_Q_768 and self.batches_in_flight > 1 and not _one_pass:
+            return self._search_pipelined(q, K, out, self.WIDE_Q_768)
+        need = (L.clipmi_topk_ip_wide_workspace_bytes if wide768 else L.clipmi_topk_ip_coarse_workspace_bytes if coarse
+                else L.clipmi_topk_ip_workspace_bytes)(N, self.d, Q, K)
         if need == 0:
             raise _lib.ClipmiError("topk_ip: " + _lib.last_error())
         # the workspace belongs to the stream the call is enqueued on (torch's current stream): two batches in flight on
@@ -235,6 +247,12 @@ class IndexFlatIP:
             out_i = torch.empty((Q, K), dtype=torch.int64, device=self.device)
         else:
             out_s, out_i = out
+        if wide768:
+            rc = L.clipmi_topk_ip_wide_i8(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, self.d, rmax, q.data_ptr(),
+                                          Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
+                                          ws.numel(), _lib.stream_ptr(self.device))
+            _lib.check(rc, "clipmi_topk_ip_wide_i8")
+            return out_s, out_i
         if coarse and self.coarse == "int8":
             rc = L.clipmi_topk_ip_coarse_i8(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, self.d, rmax, q.data_ptr(),
                                             Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
@@ -255,11 +273,16 @@ class IndexFlatIP:
 
     PASS_Q = 64                   # queries of one coarse pass (csrc/topk.hip COARSE_Q)
     WIDE_Q = 1024                 # queries of one wide pass of the int8 copy (csrc/topk.hip WIDE_MAX_Q)
+    WIDE_Q_768 = 1024             # ... at d = 768, when `wide_768` is on (csrc/topk.hip WIDE768_MAX_Q)
     batches_in_flight = 2         # 64-query passes of ONE large search kept in flight on internal streams (1 = off)
+
+    def _wide_768_on(self):
+        """The opt-in wide pass applies: asked for, d = 768, int8 copy (the flag is inert anywhere else)."""
+        return self.wide_768 and self.d == 768 and self.coarse == "int8"
 
     def _search_pipelined(self, q, K, out, chunk):
         """A search of more than 64 queries on the bf16 coarse path or the int8 path at d = 768 (`chunk` = 64), or of more than 1024
-        on the int8 path at d = 512 (`chunk` = 1024 = one wide pass): its passes alternate between the caller's stream and an
+        on the int8 path at d = 512 or - with `wide_768` - at d = 768 (`chunk` = 1024 = one wide pass): its passes alternate between the caller's stream and an
         internal HIP stream (each with its own workspace), so one pass's latency-bound side kernels run beside the other's
         HBM-bound scan -
         what bench.py measures as "two batches in flight" (0.97-1.03 vs 1.09-1.10 ms per pass at 10 M rows). Same calls,
@@ -490,7 +513,7 @@ def _read_faiss_ivfflat(f, path):
     return d, mat
 
 
-def read_index(path, device="cuda:0", rows=None, coarse=None):
+def read_index(path, device="cuda:0", rows=None, coarse=None, wide_768=None):
     """faiss.read_index stand-in (query-index.py:29): reads both formats write_index produces and the
     IndexIVFFlat file the reference's build-index.py writes (rows come back in id order and are searched
     exactly; `nprobe` is accepted and ignored).
@@ -528,7 +551,7 @@ def read_index(path, device="cuda:0", rows=None, coarse=None):
             raise ValueError(f"{path}: not a clipmi, faiss IndexFlatIP or faiss IndexIVFFlat file")
     if data.size != (hi - lo) * d:
         raise ValueError(f"{path}: truncated ({data.size} of {(hi - lo) * d} floats)")
-    idx = IndexFlatIP(d, device=device, coarse=coarse)
+    idx = IndexFlatIP(d, device=device, coarse=coarse, wide_768=wide_768)
     if hi > lo:
         idx.add(data.reshape(hi - lo, d))
     idx.id_base = lo

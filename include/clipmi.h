@@ -27,7 +27,7 @@
 extern "C" {
 #endif
 
-#define CLIPMI_ABI_VERSION 7
+#define CLIPMI_ABI_VERSION 8
 
 enum {
     CLIPMI_OK = 0,
@@ -214,6 +214,18 @@ int clipmi_topk_ip_coarse_i8(const void* db_dev, const void* db_i8_dev, const fl
                              int64_t N, int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
                              float* out_score_dev, int64_t* out_id_dev,
                              void* ws_dev, size_t ws_bytes, void* stream);
+/* ---- ABI 8. The same search with a ONE-PASS wide scan at E = 768 as well - opt-in: clipmi_topk_ip_coarse_i8 and its workspace
+ * function keep their behaviour byte for byte. Arguments, contract (asynchronous, no allocation, exact for any data and any row
+ * permutation, exact fallback when a list overflows) and results are those of clipmi_topk_ip_coarse_i8.
+ * E = 512, or Q <= 64: it IS that function, and the workspace size is clipmi_topk_ip_coarse_workspace_bytes'.
+ * E = 768, Q > 64: chunks of <= 1024 queries, each ONE pass of the copy on `stream` (v_mfma_i32_32x32x32_i8, 24 k-steps, query
+ * tiles of 128 = 96 KiB resident in LDS, four-wave workgroups); the workspace is the larger of the 64-query one and the wide
+ * pass's for min(Q, 1024) queries. Returns 0 / CLIPMI_EUNSUPPORTED under the conditions of the functions above. */
+size_t clipmi_topk_ip_wide_workspace_bytes(int64_t N, int E, int Q, int K);
+int clipmi_topk_ip_wide_i8(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax,
+                           int64_t N, int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
+                           float* out_score_dev, int64_t* out_id_dev,
+                           void* ws_dev, size_t ws_bytes, void* stream);
 
 /* ---- multi-GPU merge of per-shard partial results (no reference counterpart: the reference
  * is single-process). Inputs are R lists per query as gathered by one
@@ -364,6 +376,17 @@ int clipmi_dbg_topk_coarse_i8_scan_ms(const void* db_dev, const void* db_i8_dev,
                                       int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
                                       float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
                                       void* stream, int reps, float* scan_ms, long long* survivors);
+
+/* The wide passes of clipmi_topk_ip_wide_i8 (64 < Q; E = 512 or 768; workspace: clipmi_topk_ip_wide_workspace_bytes) `reps`
+ * times with HIP events around every wide scan launch; synchronises. Of the last repetition: *scan_ms = the summed duration of
+ * the wide scan launches, *survivors = the exactly re-scored (query, row) pairs, *scan_launches = the number of wide scan
+ * launches (segments x chunks: the copy is streamed once per chunk), *fallback_armed = 1 if a list overflowed (the exact
+ * fallback answered). The last three may be NULL. */
+int clipmi_dbg_topk_wide_i8_scan_ms(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax,
+                                    int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
+                                    float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
+                                    void* stream, int reps, float* scan_ms, long long* survivors, int* scan_launches,
+                                    int* fallback_armed);
 
 /* the FP8 path's two kernels alone: bf16 [M][K] -> e4m3 [M][K] + f32 row scales; C = a_scale w_scale (A8 W8^T) + epilogue
  * `epi` (0 bias -> bf16, 1 bias + QuickGELU -> bf16, 2 bias + residual into f32 out, 3 f32) */

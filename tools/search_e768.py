@@ -1,17 +1,28 @@
 """Search of a 768-wide index (ViT-L/14): exact f32 scan (coarse=None - what every 768 index ran before the coarse paths took that width) against the int8 and bf16 coarse paths, ONE process, same rows. usage: python tools/search_e768.py [N] [calls]
 Device events around `calls` (>= 40) calls after warm-up, the three forms alternated three times (best round reported, all rounds printed): K = 51,
 Q = 1, 16, 64 with one call in flight and with two on two streams, one call of Q = 1024; per coarse kind the scan time of
-the measurement hook, GB/s on N (E + 8) resp. N 2 E bytes, exactly re-scored rows per query. Results asserted identical."""
+the measurement hook, GB/s on N (E + 8) resp. N 2 E bytes, exactly re-scored rows per query. Results asserted identical.
+Many-query legs (Q = 128, 256, 512, 1024, int8 copy): the opt-in one-pass wide call (IndexFlatIP(wide_768=True) ->
+clipmi_topk_ip_wide_i8) against the pipelined 64-query form (the default), alternated in three rounds on ONE index copy, `calls`
+calls per round; per Q the wide scan launches' summed duration and the re-scored rows per query from the hook.
+--many-only: only those legs (and only the int8 copy is built). --out PATH: the many-query lines are also written to PATH
+(profiles/r06_search_wide768.txt is the record DESIGN 4.1l quotes)."""
 import sys, os, ctypes as C
 import torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clipmi
 L = clipmi._lib.lib()
 dev = torch.device("cuda:0")
-N = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000
-CALLS = max(40, int(sys.argv[2])) if len(sys.argv) > 2 else 40
+argv = [a for a in sys.argv[1:] if not a.startswith("--")]
+MANY_ONLY = "--many-only" in sys.argv
+OUT = None
+if "--out" in sys.argv:
+    OUT = sys.argv[sys.argv.index("--out") + 1]
+    argv.remove(OUT)
+N = int(argv[0]) if len(argv) > 0 else 10_000_000
+CALLS = max(40, int(argv[1])) if len(argv) > 1 else 40
 E, K = 768, 51
-FORMS = (None, "int8", "bf16")
+FORMS = ("int8",) if MANY_ONLY else (None, "int8", "bf16")
 g = torch.Generator(device=dev); g.manual_seed(1)
 db = torch.empty((N, E), dtype=torch.float32, device=dev)
 for lo in range(0, N, 1 << 20):
@@ -23,7 +34,8 @@ for kind in FORMS:
     idx[kind] = clipmi.IndexFlatIP(E, device=dev, coarse=kind)
     idx[kind].add(db)
     assert idx[kind].uses_coarse() == (kind is not None)
-idx["int8"].matrix_i8(); idx["bf16"].matrix_bf16()
+idx["int8"].matrix_i8()
+if not MANY_ONLY: idx["bf16"].matrix_bf16()
 cur, side = clipmi._lib.side_stream(dev)
 torch.cuda.synchronize()
 
@@ -42,6 +54,64 @@ def timed(ix, q, calls, two):
     torch.cuda.synchronize()
     return e0.elapsed_time(e1) / calls, out
 
+
+def many_query_legs():
+    """The wide call against the pipelined 64-query form, same process, same int8 copy."""
+    lines = []
+
+    def log(t):
+        print(t, flush=True)
+        lines.append(t)
+
+    pipe = idx["int8"]
+    wide = clipmi.IndexFlatIP(E, device=dev, coarse="int8", wide_768=True)
+    wide.add(db)
+    wide._db8, wide._rmax = pipe._db8, pipe._rmax                      # one copy for both forms
+    forms = (("pipelined-64", pipe), ("wide", wide))
+    qs = {}
+    for Q in (128, 256, 512, 1024):
+        q = torch.randn((Q, E), generator=g, device=dev)
+        qs[Q] = q / q.norm(dim=1, keepdim=True)
+    bestm, outs = {}, {}
+    for rnd in range(3):
+        for Q in qs:
+            for name, ix in forms:
+                if rnd == 0:
+                    for _ in range(2): ix.search_device(qs[Q], K)
+                    torch.cuda.synchronize()
+                ms, out = timed(ix, qs[Q], CALLS, False)
+                bestm[(name, Q)] = min(bestm.get((name, Q), 1e30), ms)
+                outs[(name, Q)] = (out[0].clone(), out[1].clone())
+                log(f"round {rnd} {name:12s} Q={Q:4d}: {ms:8.3f} ms per call = {Q / ms * 1e3:9.0f} q/s")
+    for Q in qs:
+        a, b = outs[("pipelined-64", Q)], outs[("wide", Q)]
+        assert torch.equal(a[0].view(torch.int32), b[0].view(torch.int32)) and torch.equal(a[1], b[1]), Q
+    log("results identical, wide vs pipelined 64-query form at Q = 128, 256, 512, 1024: True")
+    log(f"N = {N} x {E}, K = {K}: best of 3 alternated rounds, {CALLS} calls each")
+    d8, meta, amax, rmax = pipe.matrix_i8()
+    for Q in qs:
+        p_, w_ = bestm[("pipelined-64", Q)], bestm[("wide", Q)]
+        ws = torch.empty(L.clipmi_topk_ip_wide_workspace_bytes(N, E, Q, K), dtype=torch.uint8, device=dev)
+        sm, sv, nl, fa = C.c_float(0), C.c_longlong(0), C.c_int(0), C.c_int(0)
+        os_ = torch.empty((Q, K), dtype=torch.float32, device=dev)
+        oi_ = torch.empty((Q, K), dtype=torch.int64, device=dev)
+        rc = L.clipmi_dbg_topk_wide_i8_scan_ms(db.data_ptr(), d8.data_ptr(), meta.data_ptr(), amax, N, E, rmax, qs[Q].data_ptr(), Q, K,
+                                               os_.data_ptr(), oi_.data_ptr(), ws.data_ptr(), ws.numel(), None, 5, C.byref(sm),
+                                               C.byref(sv), C.byref(nl), C.byref(fa))
+        clipmi._lib.check(rc, "wide scan hook")
+        assert torch.equal(oi_, outs[("wide", Q)][1])
+        log(f"Q={Q:4d}: pipelined-64 {p_:8.3f} ms {Q / p_ * 1e3:8.0f} q/s | wide {w_:8.3f} ms {Q / w_ * 1e3:8.0f} q/s ({p_ / w_:5.2f} x) | "
+            f"wide scans {sm.value:.3f} ms in {nl.value} launches = {2.0 * N * Q * E / sm.value / 1e9:.0f} int8 TOP/s, "
+            f"re-scored rows per query {sv.value / Q:.0f}, fallback armed {fa.value}")
+        del ws
+    if OUT:
+        with open(OUT, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
+if MANY_ONLY:
+    many_query_legs()
+    sys.exit(0)
 
 best, results = {}, {}
 shapes = [(1, False), (1, True), (16, False), (16, True), (64, False), (64, True), (1024, False)]
@@ -96,3 +166,4 @@ for kind in ("int8", "bf16"):
         torch.cuda.synchronize()
         assert torch.equal(oi_, results[(None, Q)][1])
         print(f"{kind} Q={Q:2d}: scans {sm.value:.3f} ms = {byt / sm.value / 1e6:.0f} GB/s on {byt / 1e9:.2f} GB; exactly re-scored rows per query {sv.value / Q:.0f}", flush=True)
+many_query_legs()
