@@ -173,7 +173,10 @@ def parse(data, keep_stuffing=False):
     i += 2 + L
     out.ri, out.starts, out.stuffed = ri, None, 0
     if keep_stuffing and not ri and n - i >= 2 and data[n - 2] == 0xFF and data[n - 1] == 0xD9:
-        out.stream = data[i:n - 2]
+        j = n - 2
+        while j > i and data[j - 1] == 0xFF:                 # fill bytes in front of EOI (a data 0xFF has its 0x00 behind it): not
+            j -= 1                                           # the segment's - the device would take them for a marker inside it
+        out.stream = data[i:j]
         out.stuffed = 1
     elif ri:
         # restart intervals: RSTn markers, numbered 0..7 in turn (jdmarker.c read_restart_marker), separate them; every
@@ -182,20 +185,27 @@ def parse(data, keep_stuffing=False):
         if want > MAX_INTERVALS:
             raise Unsupported("too many restart intervals")
         parts, count, seg = [], 0, i
-        for m_ in _MARKER.finditer(data, i):
-            j = m_.start()
+        while True:
+            m_ = _MARKER.search(data, seg)
+            if m_ is None:
+                raise Unsupported("no end of image")
+            j = e = m_.start()
+            while j + 1 < n and data[j + 1] == 0xFF:         # fill bytes in front of a marker: rare, walk them
+                j += 1
+            if j + 1 >= n:
+                raise Unsupported("no end of image")
             nxt = data[j + 1]
+            if nxt == 0:
+                raise Unsupported("fill bytes inside the scan")
             if nxt == 0xD0 + (count & 7) and count + 1 < want:
-                parts.append(data[seg:j].replace(b"\xff\x00", b"\xff"))
+                parts.append(data[seg:e].replace(b"\xff\x00", b"\xff"))
                 count += 1
                 seg = j + 2
                 continue
             if nxt != 0xD9 or count + 1 != want:
                 raise Unsupported("marker inside the scan")
-            parts.append(data[seg:j].replace(b"\xff\x00", b"\xff"))
+            parts.append(data[seg:e].replace(b"\xff\x00", b"\xff"))
             break
-        else:
-            raise Unsupported("no end of image")
         lens = np.fromiter((len(x) for x in parts), dtype=np.int64, count=len(parts))
         out.starts = (np.cumsum(lens) - lens).astype(np.uint32)
         out.stream = b"".join(parts)
@@ -203,7 +213,7 @@ def parse(data, keep_stuffing=False):
         m_ = _MARKER.search(data, i)
         if m_ is None:
             raise Unsupported("no end of image")
-        j = m_.start()
+        j = e = m_.start()
         nxt = data[j + 1]
         if nxt == 0xFF:                                      # fill bytes in front of a marker: rare, walk them
             while j + 1 < n and data[j + 1] == 0xFF:
@@ -215,7 +225,7 @@ def parse(data, keep_stuffing=False):
                 raise Unsupported("fill bytes inside the scan")
         if nxt != 0xD9:
             raise Unsupported("marker inside the scan")         # further scans
-        out.stream = data[i:j].replace(b"\xff\x00", b"\xff")
+        out.stream = data[i:e].replace(b"\xff\x00", b"\xff")   # (the fill bytes are not the segment's)
     if len(out.stream) >= MAX_STREAM:
         raise Unsupported("too large")
     return out

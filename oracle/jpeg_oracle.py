@@ -139,21 +139,28 @@ def parse(data):
     # numbered 0..7 in turn) separate the restart intervals and are dropped
     parts, j, count = [], i, 0
     while True:
-        j = data.find(b"\xff", j)
+        j = e = data.find(b"\xff", j)
         if j < 0 or j + 1 >= n:
             raise Unsupported("no EOI")
         nxt = data[j + 1]
         if nxt == 0:
             j += 2
             continue
+        while nxt == 0xFF:                               # fill bytes in front of a marker (jdhuff.c jpeg_fill_bit_buffer skips them)
+            j += 1
+            if j + 1 >= n:
+                raise Unsupported("no EOI")
+            nxt = data[j + 1]
+        if nxt == 0:
+            raise Unsupported("fill bytes inside the scan")
         if ri and nxt == 0xD0 + (count & 7):
-            parts.append(data[i:j].replace(b"\xff\x00", b"\xff"))
+            parts.append(data[i:e].replace(b"\xff\x00", b"\xff"))
             count += 1
             i = j = j + 2
             continue
         if nxt != 0xD9:
             raise Unsupported("marker inside the scan")
-        parts.append(data[i:j].replace(b"\xff\x00", b"\xff"))
+        parts.append(data[i:e].replace(b"\xff\x00", b"\xff"))
         break
     starts = [0]
     for part in parts[:-1]:

@@ -389,10 +389,11 @@ def _seg(m, payload):
     return bytes([0xFF, m]) + (len(payload) + 2).to_bytes(2, "big") + payload
 
 
-def write(blob, script, tamper=None):
+def write(blob, script, tamper=None, tables=None):
     """Baseline JPEG file + scan script [(component indices, Ss, Se, Ah, Al), ...] -> progressive file with the same quantised
     coefficients. Every scan gets its own optimal tables (a DHT in front of it). tamper(scan index, scan, events) -> events:
-    rewrites a scan's symbols before its tables are built (malformed files whose codes are all valid)."""
+    rewrites a scan's symbols before its tables are built (malformed files whose codes are all valid). tables: a length profile
+    of jpeg_baseline.profile_table instead of the optimal one (codes no encoder writes: all at 16 bits, ...)."""
     info = jpeg_oracle.parse(blob)
     coef, _ = jpeg_oracle.decode_coefficients(info)
     geom = _Geom(info)
@@ -417,7 +418,11 @@ def write(blob, script, tamper=None):
             for e in ev:
                 if e[0] == "h" and e[1] == key:
                     freq[e[2]] = freq.get(e[2], 0) + 1
-            bits, vals = optimal_table(freq)
+            if tables is None:
+                bits, vals = optimal_table(freq)
+            else:
+                from jpeg_baseline import profile_table
+                bits, vals = profile_table(tables, 0 if ss == 0 else 1, freq)
             codes[key] = _codes(bits, vals)
             dht += bytes([(0 if ss == 0 else 0x10) | key]) + bytes(bits) + bytes(vals)
         if dht:
