@@ -4,7 +4,7 @@
 // through - 8-bit baseline / extended-sequential Huffman, one interleaved scan, grey or YCbCr with luma sampling 1x1 /
 // 2x1 / 2x2 and 1x1 chroma, with or without restart intervals - and produces Pillow's bytes (tests/test_jpeg_gpu.py compares with
 // Pillow itself; oracle/jpeg_oracle.py is the CPU restatement, pinned against Pillow in tests/test_jpeg.py).
-// Everything else (progressive, CMYK, PNG, ...) stays with Pillow in the decode workers.
+// Everything else (CMYK, ...) stays with Pillow in the decode workers; PNG files have png.hip.
 //
 // Kernels, one batch of images per call:
 //   jpeg_build_luts_kernel   canonical Huffman codes of the batch's distinct DHT tables -> 10-bit look-up + slow-path arrays

@@ -141,7 +141,7 @@ JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then t
 _plans = {}
 
 
-def stage_jpeg(path, n_px, region):
+def stage_jpeg(path, n_px, region, data=None):
     """For the decode on the device (csrc/jpeg.hip): read the file, walk its markers (jpeg_parse.parse) and lay out in `region`
     [header | quantisation steps | Huffman tables | resize plan coefficients | entropy-coded segment without byte stuffing, followed
     by >= 16 zero bytes]. -> (w, h, bytes used); raises jpeg_parse.Unsupported for files Pillow has to decode, returns None when
@@ -150,8 +150,9 @@ def stage_jpeg(path, n_px, region):
         from . import jpeg_parse
     except ImportError:
         import jpeg_parse
-    with open(path, "rb") as f:
-        data = f.read()
+    if data is None:
+        with open(path, "rb") as f:
+            data = f.read()
     p = jpeg_parse.parse(data, keep_stuffing=True)     # (a plain slice where the file allows: the device removes the byte stuffing)
     key = (p.width, p.height, n_px)
     plan = _plans.get(key)
@@ -185,7 +186,7 @@ def stage_jpeg(path, n_px, region):
 PROG_SCAN_BYTES = 64      # one scan record in a progressive region: jpeg.SCAN's layout (clipmi_jpeg_scan), offsets region-relative
 
 
-def stage_jpeg_progressive(path, n_px, region):
+def stage_jpeg_progressive(path, n_px, region, data=None):
     """For the progressive decode on the device (csrc/jpeg.hip jpeg_progressive_kernel): read the file, walk its markers
     (jpeg_parse.parse_progressive) and lay out in `region` [header | quantisation steps | resize plan coefficients | scan records |
     the scans' Huffman tables | the scans' entropy-coded segments without byte stuffing, each 16-byte aligned and followed by
@@ -197,8 +198,9 @@ def stage_jpeg_progressive(path, n_px, region):
         from . import jpeg_parse
     except ImportError:
         import jpeg_parse
-    with open(path, "rb") as f:
-        data = f.read()
+    if data is None:
+        with open(path, "rb") as f:
+            data = f.read()
     p = jpeg_parse.parse_progressive(data)
     key = (p.width, p.height, n_px)
     plan = _plans.get(key)
@@ -249,10 +251,55 @@ def stage_jpeg_progressive(path, n_px, region):
     return p.width, p.height, total
 
 
+PNG_MAX_RAW = 16 << 20      # filtered scanlines of a file the device takes: one wave inflates one image (~30 ms per MB of literals,
+                            # DESIGN 4.9), so a larger file would hold up its batch on the side stream; Pillow decodes those
+
+
+def stage_png(path, n_px, region, data=None):
+    """For the PNG decode on the device (csrc/png.hip): read the file, walk its chunks (png_parse.parse) and lay out in `region`
+    [header | resize plan coefficients | DEFLATE stream without the zlib header, 16-byte aligned and followed by >= 16 zero
+    bytes]. The header is stage_jpeg's, with kind 6: 6 w h channels 0 0 stream_bytes 0 | the resize plan's ten fields | stream
+    offset, coefficient offset. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises
+    png_parse.Unsupported for files Pillow has to decode, among them files of more than PNG_MAX_RAW bytes of scanlines.
+    data: the file's contents, when the caller has read them."""
+    try:
+        from . import png_parse
+    except ImportError:
+        import png_parse
+    if data is None:
+        with open(path, "rb") as f:
+            data = f.read()
+    p = png_parse.parse(data)
+    if p.raw_bytes() > PNG_MAX_RAW:
+        raise png_parse.Unsupported("more than PNG_MAX_RAW bytes of scanlines")
+    key = (p.width, p.height, n_px)
+    plan = _plans.get(key)
+    if plan is None:
+        if len(_plans) > 256:
+            _plans.clear()
+        plan = _plans[key] = resize_plan(p.width, p.height, n_px)
+    nh, nv = plan["hcoef"].size, plan["vcoef"].size
+    o_stream = (JPEG_COEF_OFF + 4 * (nh + nv) + 15) // 16 * 16
+    total = (o_stream + len(p.stream) + 16 + 15) // 16 * 16
+    if total > region.size:
+        return p.width, p.height, -total
+    ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
+    ints[:] = [6, p.width, p.height, p.channels, 0, 0, len(p.stream), 0, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
+               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, o_stream, JPEG_COEF_OFF] + [0] * 12
+    if nh + nv:
+        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
+        co[:nh] = plan["hcoef"]
+        co[nh:] = plan["vcoef"]
+    region[o_stream:o_stream + len(p.stream)] = np.frombuffer(p.stream, np.uint8)
+    region[o_stream + len(p.stream):total] = 0
+    return p.width, p.height, total
+
+
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (bits: 1 full-size pixels, 2 a parsed baseline JPEG file, 4 a parsed progressive JPEG file) |
+         what the region may take (bits: 1 full-size pixels, 2 a parsed baseline JPEG file, 4 a parsed progressive JPEG file,
+         8 a parsed PNG file) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
@@ -260,7 +307,9 @@ def serve(fin, fout):
               b"3" + <iiq (w, h, bytes)>: a baseline JPEG file, parsed, with its resize plan, in the region (stage_jpeg) |
               b"4" + <iiq (w, h, bytes)>: a progressive JPEG file, parsed, with its resize plan, in the region
               (stage_jpeg_progressive) |
-              b"5" + <iiq (w, h, bytes)>: as b"1", and the file would have been a b"3" or b"4" with a region of that many bytes."""
+              b"5" + <iiq (w, h, bytes)>: as b"1", and the file would have been a b"3", b"4" or b"6" with a region of that many
+              bytes |
+              b"6" + <iiq (w, h, bytes)>: a PNG file, parsed, with its resize plan, in the region (stage_png)."""
     import mmap
     import os
     import struct
@@ -292,24 +341,29 @@ def serve(fin, fout):
             if big_name != b"-":
                 region = np.frombuffer(mapped(big_name.decode()), dtype=np.uint8, count=int(big_cap_s), offset=int(big_off_s))
                 full = None
-                if mode & 2:
+                # the file is read once and its first bytes choose the parser (a PNG file used to be read by each of them in turn)
+                data = kind = None
+                if mode & 14:
                     try:
-                        full = stage_jpeg(fname, n_px, region)
-                    except Exception:                          # not a file for the device decoder (or unreadable: Pillow reports it)
+                        with open(fname, "rb") as f:
+                            data = f.read()
+                    except OSError:                            # unreadable: Pillow reports it
+                        data = None
+                    if data is not None:
+                        kind = "png" if data[:8] == b"\x89PNG\r\n\x1a\n" else "jpeg" if data[:2] == b"\xff\xd8" else None
+                for bit, want_kind, stager, tag in ((2, "jpeg", stage_jpeg, b"3"), (4, "jpeg", stage_jpeg_progressive, b"4"),
+                                                    (8, "png", stage_png, b"6")):
+                    if full is not None or wanted is not None or not mode & bit or kind != want_kind:
+                        continue
+                    try:
+                        full = stager(fname, n_px, region, data)
+                    except Exception:                          # not a file for this device decoder: the next one, or Pillow
                         full = None
                     if full is not None and full[2] < 0:
                         full, wanted = None, (full[0], full[1], -full[2])
                     if full is not None:
-                        reply = b"3" + struct.pack("<iiq", *full)
-                if full is None and wanted is None and mode & 4:
-                    try:
-                        full = stage_jpeg_progressive(fname, n_px, region)
-                    except Exception:                          # not a progressive file for the device (or unreadable)
-                        full = None
-                    if full is not None and full[2] < 0:
-                        full, wanted = None, (full[0], full[1], -full[2])
-                    if full is not None:
-                        reply = b"4" + struct.pack("<iiq", *full)
+                        reply = tag + struct.pack("<iiq", *full)
+                data = None
                 if full is None and mode & 1:
                     full = decode_full(fname, n_px, region)
                     if full is not None:

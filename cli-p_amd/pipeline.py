@@ -124,7 +124,7 @@ class DecodePool:
         """Worker w decodes its share of the batch: (slot, path) pairs -> (slot, status) with status False (failed), True
         (the transform's pixels are in the slot) or (kind, w, h, bytes): the image is in its region of the big segment -
         kind 2 at full size, for the resize on the device; kind 3 as a parsed JPEG file, for the decode on the device; kind 4 as
-        a parsed progressive JPEG file. If the worker process dies (a file that crashes the decoder, an OOM kill), that
+        a parsed progressive JPEG file; kind 6 as a parsed PNG file. If the worker process dies (a file that crashes the decoder, an OOM kill), that
         file is reported as failed and the rest of the share - and of every later batch - is decoded in this process: no
         program is spawned once the GPU may have been initialised."""
         import struct
@@ -148,7 +148,7 @@ class DecodePool:
                 raw = p.stdout.read(17 * len(jobs))
                 for k in range(len(raw) // 17):
                     st = raw[17 * k:17 * k + 1]
-                    if st == b"2" or st == b"3" or st == b"4":
+                    if st == b"2" or st == b"3" or st == b"4" or st == b"6":
                         ok.append((jobs[k][0], (int(st),) + struct.unpack_from("<iiq", raw, 17 * k + 1)))
                     elif st == b"5":                       # Pillow decoded it; a larger region would have taken the file itself
                         self.jpeg_wanted = max(self.jpeg_wanted, struct.unpack_from("<iiq", raw, 17 * k + 1)[2])
@@ -181,7 +181,7 @@ class DecodePool:
         resize on the device; the result is then ((slots view, good mask, big view, {slot: (kind, w, h, bytes)}), ok, bad).
         full_mode: what a region may take - bit 0 full-size pixels (kind 2), bit 1 baseline JPEG files parsed for the decode on
         the device (kind 3: decode_worker.stage_jpeg), bit 2 progressive JPEG files parsed for it (kind 4:
-        decode_worker.stage_jpeg_progressive)."""
+        decode_worker.stage_jpeg_progressive), bit 3 PNG files parsed for the decode on the device (kind 6: decode_worker.stage_png)."""
         n = len(paths)
         per = 3 * n_px * n_px
         seg = self._segment(max(1, n * per), segment)
@@ -332,8 +332,37 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
     return recs, scans, tables, jobs, out_sz, blocks, len(pool_t)
 
 
+def png_records(bigview, n, cap, slots, comp, n_px):
+    """jpeg_records for PNG files (decode_worker.stage_png wrote the regions). -> (clipmi_png_image records with stream offsets into
+    the segment and the scanline and output buffers laid out back to back, clipmi_resize_job records whose sources are the decoder's
+    outputs, output bytes per image, scanline bytes per image, each rounded up to 16)"""
+    from . import png as P
+    from .decode_worker import JPEG_HDR_INTS
+    from .resize import JOB
+    slots = np.asarray(slots, dtype=np.int64)
+    n6 = len(slots)
+    st = np.lib.stride_tricks.as_strided
+    H = st(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[slots].astype(np.int64)
+    w, h, ch, nrows = H[:, 1], H[:, 2], H[:, 3], H[:, 9]
+    recs = np.zeros(n6, dtype=P.IMAGE)
+    out_sz = (w * h * 3 + 15) // 16 * 16
+    raw_sz = (h * (1 + w * ch) + 15) // 16 * 16
+    out_off = np.cumsum(out_sz) - out_sz
+    recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + H[:, 18], np.cumsum(raw_sz) - raw_sz, out_off
+    recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = H[:, 6], w, h, ch
+    jobs = np.zeros(n6, dtype=JOB)
+    jobs["src_off"], jobs["w"], jobs["h"], jobs["r0"], jobs["nrows"], jobs["out_index"] = out_off, w, h, H[:, 8], nrows, np.asarray(comp)[slots]
+    jobs["need_h"], jobs["need_v"], jobs["left"], jobs["top"], jobs["hk"], jobs["vk"] = (H[:, 10], H[:, 11], H[:, 12], H[:, 13],
+                                                                                      H[:, 14], H[:, 15])
+    jobs["hcoef_off"] = (slots * cap + H[:, 19]) // 4
+    jobs["vcoef_off"] = jobs["hcoef_off"] + H[:, 16]
+    tmp = nrows * n_px * 3
+    jobs["tmp_off"] = np.cumsum(tmp) - tmp
+    return recs, jobs, out_sz, raw_sz
+
+
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
-                 jpeg_group_mb=32768, device_progressive=None):
+                 jpeg_group_mb=32768, device_progressive=None, device_png=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -348,11 +377,17 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     device_progressive (default $CLIPMI_DEVICE_PROGRESSIVE, else off; "1" = on; needs the JPEG decode on the device above):
     progressive JPEG files take the device too (jpeg_parse.parse_progressive in the workers, clipmi_jpeg_decode_progressive_rgb8
     + clipmi_resize_crop_rgb8 beside the baseline decode), the same bytes as Pillow's; files it reports go back to Pillow.
+    device_png (default $CLIPMI_DEVICE_PNG, else off; "1" = on; needs the JPEG decode on the device above, whose regions it
+    shares): 8-bit grey and RGB PNG files that are not interlaced and hold at most decode_worker.PNG_MAX_RAW (16 MiB) of
+    scanlines take the device too (png_parse.parse in the workers,
+    clipmi_png_decode_rgb8 + clipmi_resize_crop_rgb8 on the side stream beside the JPEG decodes, grouped under jpeg_group_mb
+    like them), the same bytes as Pillow's; every other PNG file and every file the device reports goes back to Pillow. With
+    the flag off nothing changes for any file.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
     shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoder (jpeg_files;
-    progressive ones: jpeg_progressive_files)."""
+    progressive ones: jpeg_progressive_files; PNG files the device decoded and did not hand back: png_files)."""
     import os
     import time
     n_px = model.visual.input_resolution
@@ -395,7 +430,10 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     full_cap = [max(resize_cap, jpeg_now)]               # bytes per region of the big segment; [0]: mutable (may be switched off)
     if device_progressive is None:
         device_progressive = os.environ.get("CLIPMI_DEVICE_PROGRESSIVE", "0") not in ("", "0")
-    full_mode = (1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0)
+    if device_png is None:
+        device_png = os.environ.get("CLIPMI_DEVICE_PNG", "0") not in ("", "0")
+    full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
+                 (8 if jpeg_cap and device_png else 0))
 
     # three pinned staging buffers used in turn (GPU): batch i may still be in its H2D copy while batch i+1 is filled;
     # a buffer is reused only after the copy that read it has finished. Pixels go shared memory -> pinned -> device:
@@ -430,7 +468,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         of the segment where it lies (it is page-locked: no packing copy on the host - packing 1 GB per batch of photo-sized
         images with one thread was slower than Pillow's resize), then clipmi_resize_crop_rgb8 for the full-size images (kind 2)
         and clipmi_jpeg_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed JPEG files (kind 3), and
-        clipmi_jpeg_decode_progressive_rgb8 + clipmi_resize_crop_rgb8 for the parsed progressive ones (kind 4).
+        clipmi_jpeg_decode_progressive_rgb8 + clipmi_resize_crop_rgb8 for the parsed progressive ones (kind 4), and
+        clipmi_png_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed PNG files (kind 6).
         The copy stream carries the copies only; the kernels go to the process's ONE side stream (_lib.side_stream: this ROCm gives a
         process three hardware queues) behind an event, so that the next batch's copy runs beside this batch's kernels instead of
         behind them, and the consumer finds them queued in front of its encode step.
@@ -448,6 +487,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         e2 = sorted((s_, v) for s_, v in full.items() if v[0] == 2)
         e3 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 3), dtype=np.int64)
         e4 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 4), dtype=np.int64)
+        e6 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 6), dtype=np.int64)
+        n_status = len(e3) + len(e4) + len(e6)              # one status tensor: baseline files, progressive files, PNG files
         if not pool.pin_segment(2 + seg_index[0]):
             # the segment could not be page-locked (locked-memory limit?): this batch goes through a pinned copy of it, the
             # following ones take the host path
@@ -458,10 +499,13 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         else:
             slot = None
             src = torch.from_numpy(bigview[:used])
-        pending = {"keep": [], "status": None, "launch": []}
+        pending = {"keep": [], "status": None, "launch": [], "n_png": len(e6)}
         with torch.cuda.stream(copy_stream):
             dbig = src.to(dev, non_blocking=True)
             base = dbig.data_ptr()
+            if n_status:
+                pending["status"] = torch.empty(n_status, dtype=torch.int32, device=dev)
+                pending["slots"] = np.concatenate([e3, e4, e6])
             if e2:
                 jobs = np.zeros(len(e2), dtype=JOB)
                 toff, max_rows = 0, 1
@@ -501,7 +545,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                         lo, acc = k, 0
                     acc += int(need[k])
                 groups.append((lo, len(e3)))
-                status = torch.empty(len(e3) + len(e4), dtype=torch.int32, device=dev)
+                status = pending["status"]
                 calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
                 for lo, hi in groups:
                     recs, tables, jobs, out_sz, blocks, nt = jpeg_records(bigview, n, cap, e3[lo:hi], comp, n_px)
@@ -536,7 +580,6 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
 
                 pending["launch"].append(decode_jpeg)
                 pending["keep"] += [ws, rgb, scratch3]
-                pending["status"], pending["slots"] = status, e3
             if len(e4):
                 # progressive files: the same grouping, their own records and workspace, behind the baseline decode on the side stream;
                 # their statuses follow the baseline files' in one tensor
@@ -550,7 +593,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                         lo, acc = k, 0
                     acc += int(need[k])
                 groups.append((lo, len(e4)))
-                status = pending["status"] if pending["status"] is not None else torch.empty(len(e4), dtype=torch.int32, device=dev)
+                status = pending["status"]
                 calls4, ws_max, rgb_max, tmp_max = [], 0, 0, 0
                 for lo, hi in groups:
                     recs, scans, tables, jobs, out_sz, blocks, nt = progressive_records(bigview, n, cap, e4[lo:hi], comp, n_px)
@@ -588,7 +631,52 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
 
                 pending["launch"].append(decode_progressive)
                 pending["keep"] += [ws4, rgb4, scratch4]
-                pending["status"], pending["slots"] = status, np.concatenate([e3, e4])
+            if len(e6):
+                # PNG files: the same grouping by what a group holds in HBM (scanlines, RGB rows, the resize's rows), their own
+                # workspace, behind the JPEG decodes on the side stream; their statuses come last in the tensor
+                st_ = np.lib.stride_tricks.as_strided
+                H6 = st_(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[e6].astype(np.int64)
+                need = H6[:, 2] * (1 + H6[:, 1] * H6[:, 3]) + (H6[:, 1] * H6[:, 2] * 3 + 15) // 16 * 16 + H6[:, 9] * n_px * 3
+                groups, lo, acc = [], 0, 0
+                for k in range(len(e6)):
+                    if k > lo and acc + need[k] > jpeg_group_bytes:
+                        groups.append((lo, k))
+                        lo, acc = k, 0
+                    acc += int(need[k])
+                groups.append((lo, len(e6)))
+                status = pending["status"]
+                calls6, ws_max, rgb_max, tmp_max = [], 0, 0, 0
+                for lo, hi in groups:
+                    recs, jobs, out_sz, raw_sz = png_records(bigview, n, cap, e6[lo:hi], comp, n_px)
+                    nrows = jobs["nrows"].astype(np.int64)
+                    o_job = (recs.nbytes + 15) // 16 * 16
+                    small = np.zeros(o_job + jobs.nbytes, np.uint8)
+                    small[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
+                    small[o_job:] = jobs.view(np.uint8).reshape(-1)
+                    dsmall = torch.from_numpy(small).to(dev)
+                    total_raw = int(raw_sz.sum())
+                    ws_bytes = int(L.clipmi_png_workspace_bytes(hi - lo, total_raw))
+                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
+                    tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
+                    calls6.append((dsmall, o_job, hi - lo, total_raw, int(raw_sz.max()), int(nrows.max()), ws_bytes,
+                                   len(e3) + len(e4) + lo))
+                    pending["keep"].append(dsmall)
+                ws6 = torch.empty(ws_max, dtype=torch.uint8, device=dev)
+                rgb6 = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
+                scratch6 = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
+
+                def decode_png(status=status):
+                    for dsmall, o_job, n6, total_raw, max_raw, mr, ws_bytes, lo in calls6:
+                        sb = dsmall.data_ptr()
+                        rc = L.clipmi_png_decode_rgb8(base, sb, n6, total_raw, max_raw, rgb6.data_ptr(), status.data_ptr() + 4 * lo,
+                                                      ws6.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
+                        _lib.check(rc, "clipmi_png_decode_rgb8")
+                        rc = L.clipmi_resize_crop_rgb8(rgb6.data_ptr(), sb + o_job, n6, mr, base, n_px, devt.data_ptr(), scratch6.data_ptr(),
+                                                       _lib.stream_ptr(dev))
+                        _lib.check(rc, "clipmi_resize_crop_rgb8")
+
+                pending["launch"].append(decode_png)
+                pending["keep"] += [ws6, rgb6, scratch6]
             ev_copy = torch.cuda.Event()
             ev_copy.record(copy_stream)
         side = _lib.side_stream(dev)[1]
@@ -655,7 +743,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
             pending["chunk"], pending["good"] = chunk, good.copy()
         if jpeg_cap and full_cap[0]:
             # the next batches' JPEG regions: 1.25 x the largest file this batch held or turned away
-            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] in (3, 4)] + [pool.jpeg_wanted])
+            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] in (3, 4, 6)] + [pool.jpeg_wanted])
             pool.jpeg_wanted = 0
             if used3:
                 pool.jpeg_cap_hint = min(jpeg_cap, max(1 << 16, (used3 + used3 // 4 + 65535) // 65536 * 65536))
@@ -712,6 +800,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
             feats = model.encode_image(devt, normalize=True).cpu().numpy().astype("float32")
             if pending is not None and pending["status"] is not None:
                 stc = pending["status"].cpu().numpy()         # (behind the encode step: nothing waits for it in the common case)
+                if stats is not None and pending["n_png"]:
+                    stats["png_files"] = stats.get("png_files", 0) + int((stc[-pending["n_png"]:] == 0).sum())
                 if stc.any():
                     ok, bad, devt = redo_on_host([int(s_) for s_ in pending["slots"][stc != 0]], pending["chunk"],
                                                  pending["good"], ok, bad, devt)

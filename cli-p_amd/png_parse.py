@@ -1,0 +1,149 @@
+"""Host side of the PNG decode on the device (csrc/png.hip): walk the chunks and hand over the DEFLATE stream.
+
+`parse(data)` lets through 8-bit grey (colour type 0) and RGB (colour type 2) files that are not interlaced and carry no
+`tRNS` and no APNG chunk, and returns the IDAT payloads joined, without the 2-byte zlib header; the Adler-32 and anything
+behind it stay in place (the device finds the trailer behind the final block itself). Everything else raises `Unsupported`
+and stays with Pillow: palette, alpha, 16-bit and 1/2/4-bit files (the transform resamples those modes differently), Adam7
+files, and any file whose chunks this parser cannot vouch for - in front of the image data AND behind it: Pillow's load_end()
+runs its chunk handlers on everything up to IEND, and a handler that raises there makes `convert("RGB")` fail although the
+pixels are complete. Pure Python plus zlib.crc32, no Pillow: decode_worker.py imports it under both import forms, like jpeg_parse.
+"""
+import re
+import struct
+import zlib
+
+SIGNATURE = b"\x89PNG\r\n\x1a\n"
+# Pillow warns from this many pixels on (Image.MAX_IMAGE_PIXELS) and refuses at twice as many; such a file is Pillow's to judge.
+# Below it the filtered data (height x (1 + width x channels) bytes) stays far under 2^31 - 1.
+MAX_PIXELS = 89478485
+MAX_TEXT_BYTES = 1 << 20
+# The unfilter kernel keeps a band's last row in LDS (48 KiB): rows of up to this many pixels; wider files are Pillow's.
+MAX_WIDTH = 16384
+
+# Chunks allowed in front of the first IDAT, with the length Pillow's handler needs (None: any), and why each can change
+# neither mode nor size nor pixels of `Image.open(f).convert("RGB")` (PIL/PngImagePlugin.py, PngStream.chunk_*):
+ALLOWED_BEFORE_IDAT = {
+    b"gAMA": 4,      # stored as info["gamma"]; Pillow never applies a gamma (a shorter chunk would raise in i32)
+    b"cHRM": 32,     # stored as info["chromaticity"] only
+    b"sRGB": 1,      # stored as info["srgb"] only (an empty chunk raises "Truncated sRGB chunk")
+    b"pHYs": 9,      # stored as info["dpi"] / info["aspect"]; no resampling follows from it
+    b"tEXt": None,   # stored as info / text entries; Pillow refuses more than 64 MiB of text, so the total is capped here
+    b"tIME": None,   # no handler: read, CRC checked and dropped
+    b"sBIT": None,   # no handler: Pillow does not shift samples by the significant bits
+    b"bKGD": None,   # no handler: there is no alpha to composite over a background in colour types 0 and 2
+}
+# Behind the IDAT run Pillow (load_end) checks no CRC, stops at IEND, at a chunk type that is not four word characters and
+# where fewer than 8 bytes are left, skips chunks it has no handler for (if they fit the file) and calls its handler for the
+# rest. Let through there: the chunks of the list above under the same length rule (their handlers raise on other lengths:
+# "Truncated sRGB chunk", struct.error, ...; text counts towards the same cap) and chunks Pillow has no handler for. A chunk
+# that runs past the end of the file ("Truncated File Read") and every other chunk with a handler are refused.
+PILLOW_HANDLERS = (b"IHDR", b"IDAT", b"IEND", b"PLTE", b"tRNS", b"gAMA", b"cHRM", b"sRGB", b"pHYs", b"tEXt", b"zTXt", b"iTXt",
+                   b"iCCP", b"eXIf", b"acTL", b"fcTL", b"fdAT")
+_CID = re.compile(rb"\w\w\w\w")                                # Pillow's is_cid
+
+# not in the list on purpose: PLTE / tRNS (change the mode or the pixels), iCCP / zTXt / iTXt (decompressed while opening, may
+# raise), eXIf (kept as is, but an orientation tag is a caller's business), acTL / fcTL / fdAT (APNG), unknown chunks.
+
+
+class Unsupported(Exception):
+    """Not a file for the device decoder: Pillow decodes it (or reports it)."""
+
+
+class Parsed:
+    __slots__ = ("width", "height", "channels", "stream")
+
+    def __init__(self, width, height, channels, stream):
+        self.width, self.height, self.channels, self.stream = width, height, channels, stream
+
+    def raw_bytes(self):
+        """size of the filtered scanlines the stream has to produce"""
+        return self.height * (1 + self.width * self.channels)
+
+
+def parse(data):
+    """PNG file contents -> Parsed(width, height, channels, stream); raises Unsupported(reason)."""
+    data = bytes(data)
+    if data[:8] != SIGNATURE:
+        raise Unsupported("not a PNG file")
+    pos, n = 8, len(data)
+    first = True
+    text = 0
+    pieces = None
+    while True:
+        if pos + 8 > n:
+            if pieces is not None:
+                break                                          # Pillow reads no further than the image data: no IEND is fine
+            raise Unsupported("file ends before the image data")
+        length, cid = struct.unpack_from(">I4s", data, pos)
+        body = pos + 8
+        if pieces is not None:
+            if cid != b"IDAT":
+                break                                          # the IDAT run is over; Pillow stops reading here as well
+            if body + length > n:
+                raise Unsupported("IDAT chunk runs past the end of the file")
+            pieces.append(data[body:body + length])            # (CRC not checked: Pillow does not, the Adler-32 guards the data)
+            pos = body + length + 4
+            continue
+        if body + length + 4 > n:
+            raise Unsupported("chunk runs past the end of the file")
+        if cid == b"IDAT":
+            if first:
+                raise Unsupported("IDAT before IHDR")
+            pieces = []
+            continue
+        if zlib.crc32(data[pos + 4:body + length]) != struct.unpack_from(">I", data, body + length)[0]:
+            raise Unsupported("bad CRC in %r" % cid)
+        if first:
+            if cid != b"IHDR" or length != 13:
+                raise Unsupported("IHDR is not the first chunk")
+            width, height, depth, ctype, comp, filt, lace = struct.unpack_from(">IIBBBBB", data, body)
+            if depth != 8 or ctype not in (0, 2):
+                raise Unsupported("bit depth %d, colour type %d" % (depth, ctype))
+            if comp != 0 or filt != 0:
+                raise Unsupported("unknown compression or filter method")
+            if lace != 0:
+                raise Unsupported("interlaced")
+            if width < 1 or height < 1:
+                raise Unsupported("empty image")
+            if width * height > MAX_PIXELS:
+                raise Unsupported("too many pixels")
+            if width > MAX_WIDTH:
+                raise Unsupported("rows too wide")
+            channels = 3 if ctype == 2 else 1
+            first = False
+        else:
+            want = ALLOWED_BEFORE_IDAT.get(cid, -1)
+            if want == -1 or (want is not None and length != want):
+                raise Unsupported("chunk %r in front of the image data" % cid)
+            if cid == b"tEXt":
+                text += length
+                if text > MAX_TEXT_BYTES:
+                    raise Unsupported("too much text")
+        pos = body + length + 4
+    # behind the IDAT run: what Pillow's load_end() walks (see PILLOW_HANDLERS above)
+    while pos + 8 <= n:
+        length, cid = struct.unpack_from(">I4s", data, pos)
+        if not _CID.fullmatch(cid) or cid == b"IEND":
+            break                                              # Pillow stops reading here
+        if pos + 8 + length > n:
+            raise Unsupported("chunk %r behind the image data runs past the end of the file" % cid)
+        want = ALLOWED_BEFORE_IDAT.get(cid, -1)
+        if want == -1:
+            if cid in PILLOW_HANDLERS:
+                raise Unsupported("chunk %r behind the image data" % cid)
+        elif want is not None and length != want:
+            raise Unsupported("chunk %r of %d bytes behind the image data" % (cid, length))
+        if cid == b"tEXt":
+            text += length
+            if text > MAX_TEXT_BYTES:
+                raise Unsupported("too much text")
+        pos += 12 + length
+    stream = b"".join(pieces)
+    if len(stream) < 2:
+        raise Unsupported("no zlib header")
+    cmf, flg = stream[0], stream[1]
+    if cmf & 15 != 8 or cmf >> 4 > 7 or (cmf * 256 + flg) % 31 or flg & 0x20:
+        raise Unsupported("bad zlib header")
+    if len(stream) - 2 >= 1 << 31:
+        raise Unsupported("stream too large")
+    return Parsed(width, height, channels, stream[2:])

@@ -341,6 +341,34 @@ int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* ima
                                         int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
                                         void* stream);
 
+/* ---- PNG files on the device (an addition to ABI 8: two new entry points and one new record, nothing existing changes, so
+ * CLIPMI_ABI_VERSION stays 8). The same bytes as Pillow's `Image.open(f).convert("RGB")` for the files the host parser lets
+ * through (cli-p_amd/png_parse.py: 8-bit grey or RGB, not interlaced, at most 16384 pixels wide, no tRNS, no APNG chunk, and no
+ * chunk in front of or behind the image data that makes Pillow refuse the file - the device sees the image data only). Per image one record. stream_off:
+ * the IDAT payloads joined, WITHOUT the 2-byte zlib header, the Adler-32 and whatever follows it left in place, 16-byte aligned
+ * and followed by at least 16 zero bytes. raw_off: where the image's filtered scanlines (height x (1 + width x channels) bytes)
+ * go in the workspace's scanline buffer, a multiple of 16; total_raw_bytes = the sum of the images' scanline sizes, each rounded
+ * up to 16, max_raw_bytes = the largest single one. out_dev: per image height rows of width*3 RGB bytes at out_off (grey
+ * replicated) - the layout clipmi_resize_crop_rgb8 takes.
+ * status_dev[i]: 0 decoded - the DEFLATE data is valid, ends with its final block's end-of-block code having produced exactly
+ * the scanlines' bytes, every filter byte is <= 4, and the 4 bytes behind the byte-aligned end of the stream equal the Adler-32
+ * of the produced bytes; 1 invalid DEFLATE data (a bad block type, stored length, code set, code or distance) or a record
+ * outside the limits above; 2 the stream ended early, produced too little or wants to produce more, or fewer than 4 bytes follow
+ * it; 3 a filter byte above 4; 4 the Adler-32 differs. A file with a non-zero status goes back to Pillow, whose error handling
+ * is the reference's; its bytes in out_dev are undefined. */
+typedef struct clipmi_png_image {
+    int64_t stream_off;           /* bytes from streams_dev */
+    int64_t raw_off;              /* bytes into the workspace's scanline buffer */
+    int64_t out_off;              /* bytes from out_dev */
+    int32_t stream_bytes;
+    int32_t width, height;
+    int32_t channels;             /* 1 (grey) or 3 (RGB) */
+    int32_t reserved[2];
+} clipmi_png_image;
+int64_t clipmi_png_workspace_bytes(int n, int64_t total_raw_bytes);
+int clipmi_png_decode_rgb8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes, int64_t max_raw_bytes,
+                           void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* thread-local message of the last failing call on this thread ("" if none) */
 const char* clipmi_last_error(void);
 int clipmi_abi_version(void);
