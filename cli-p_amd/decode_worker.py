@@ -13,8 +13,15 @@ imported through the package, so a worker never imports torch or touches the GPU
 Protocol: see serve(). A file that does not decode is answered b"0" and reported per file like build-index.py:55-58.
 """
 import sys
+from collections import namedtuple
 
 import numpy as np
+
+try:
+    from . import jpeg_parse, png_parse
+except ImportError:                                        # started by path (a worker): the parsers lie beside this file
+    import jpeg_parse
+    import png_parse
 
 
 def load_uint8(path, n_px, out=None):
@@ -132,54 +139,100 @@ def decode_full(path, n_px, region):
     return w, h, total
 
 
-JPEG_HDR_INTS = 32        # header of a JPEG region (stage_jpeg): 3 w h ncomp hs vs stream_bytes blocks | r0 nrows need_h need_v left top hk vk
-                          # n_hcoef n_vcoef | stream offset, coefficient offset (bytes from the region's start) | restart interval,
-                          # number of intervals, offset of their uint32 byte offsets into the segment | 1: the segment keeps its stuffing
+JPEG_HDR_INTS = 32        # header of a region that holds a parsed file (stage_jpeg, stage_jpeg_progressive, stage_png): int32, see HDR
 JPEG_QUANT_OFF = 128      # 3 x 64 quantisation steps, natural order
 JPEG_TABLES_OFF = 320     # six raw Huffman tables (jpeg_parse.TABLE_BYTES each): DC, AC per component
-JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then the entropy-coded segment (16-byte aligned)
+JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then what the format stores (16-byte aligned)
+
+
+class HDR:
+    """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, pipeline.py reads them
+    through these names); [24..31] are zero. Offsets count bytes from the region's start."""
+    KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE or KIND_PNG
+    NCOMP, HS, VS = 3, 4, 5   # components (PNG: channels), luma sampling factors (PNG: 0 0)
+    COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
+    BLOCKS = 7                # 8 x 8 blocks of the image (PNG: 0)
+    PLAN = slice(8, 16)       # resize_plan's r0 nrows need_h need_v left top hk vk: the order of resize.JOB and of decode_full's header
+    NROWS = 9
+    N_HCOEF, N_VCOEF = 16, 17                                       # ints in the horizontal and the vertical coefficient block
+    DATA_OFF, COEF_OFF = 18, 19                                     # the format's data behind the coefficient blocks; the blocks
+    RESTART_INTERVAL, N_INTERVALS, INTERVALS_OFF, STUFFED = 20, 21, 22, 23     # baseline: DRI, number of intervals, offset of their
+    #                                                                 uint32 byte offsets into the segment, 1: the segment keeps its stuffing
+    TABLES_OFF, N_TABLES = 20, 21                                   # progressive: the scans' Huffman tables
+
+
+KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
 _plans = {}
 
 
-def stage_jpeg(path, n_px, region, data=None):
-    """For the decode on the device (csrc/jpeg.hip): read the file, walk its markers (jpeg_parse.parse) and lay out in `region`
-    [header | quantisation steps | Huffman tables | resize plan coefficients | entropy-coded segment without byte stuffing, followed
-    by >= 16 zero bytes]. -> (w, h, bytes used); raises jpeg_parse.Unsupported for files Pillow has to decode, returns None when
-    the file does not fit the region."""
-    try:
-        from . import jpeg_parse
-    except ImportError:
-        import jpeg_parse
+def _contents(path, data):
     if data is None:
         with open(path, "rb") as f:
             data = f.read()
-    p = jpeg_parse.parse(data, keep_stuffing=True)     # (a plain slice where the file allows: the device removes the byte stuffing)
-    key = (p.width, p.height, n_px)
+    return data
+
+
+def _plan(w, h, n_px):
+    key = (w, h, n_px)
     plan = _plans.get(key)
     if plan is None:
         if len(_plans) > 256:
             _plans.clear()
-        plan = _plans[key] = resize_plan(p.width, p.height, n_px)
+        plan = _plans[key] = resize_plan(w, h, n_px)
+    return plan
+
+
+def _data_off(plan):
+    """The first free 16-aligned offset behind the header, the tables and the plan's coefficient blocks"""
+    return (JPEG_COEF_OFF + 4 * (plan["hcoef"].size + plan["vcoef"].size) + 15) // 16 * 16
+
+
+def _no_room(p, total):
+    return p.width, p.height, -total                      # the file does not fit its region: what it would need
+
+
+def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0)):
+    """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23]) and the plan's coefficient blocks"""
     nh, nv = plan["hcoef"].size, plan["vcoef"].size
-    o_stream = (JPEG_COEF_OFF + 4 * (nh + nv) + 15) // 16 * 16
-    o_int = (o_stream + len(p.stream) + 16 + 15) // 16 * 16
-    n_int = len(p.starts) if p.ri else 0
-    total = (o_int + 4 * n_int + 15) // 16 * 16
-    if total > region.size:
-        return p.width, p.height, -total
     ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
-    ints[:] = [3, p.width, p.height, p.ncomp, p.hs, p.vs, len(p.stream), p.blocks(), plan["r0"], plan["nrows"], plan["need_h"],
-               plan["need_v"], plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, o_stream, JPEG_COEF_OFF, p.ri, n_int, o_int, p.stuffed] + [0] * 8
-    region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
-    region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 6 * jpeg_parse.TABLE_BYTES] = np.frombuffer(b"".join(p.tables), np.uint8)
+    ints[:] = [kind, p.width, p.height, *sampling, count, blocks, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
+               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific] + [0] * 8
     if nh + nv:
         co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
         co[:nh] = plan["hcoef"]
         co[nh:] = plan["vcoef"]
-    region[o_stream:o_stream + len(p.stream)] = np.frombuffer(p.stream, np.uint8)
-    region[o_stream + len(p.stream):total] = 0
+
+
+def _stream_end(off, nbytes):
+    return (off + nbytes + 16 + 15) // 16 * 16
+
+
+def _write_stream(region, off, stream):
+    """The stream at `off` and zeros behind it: at least 16, up to the next 16-byte boundary (_stream_end)"""
+    region[off:off + len(stream)] = np.frombuffer(stream, np.uint8)
+    region[off + len(stream):_stream_end(off, len(stream))] = 0
+
+
+def stage_jpeg(path, n_px, region, data=None):
+    """For the decode on the device (csrc/jpeg.hip): read the file, walk its markers (jpeg_parse.parse) and lay out in `region`
+    [header | quantisation steps | Huffman tables | resize plan coefficients | entropy-coded segment, followed by >= 16 zero
+    bytes | the restart intervals' offsets]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit the region;
+    raises jpeg_parse.Unsupported for files Pillow has to decode."""
+    p = jpeg_parse.parse(_contents(path, data), keep_stuffing=True)     # (a plain slice where the file allows: the device removes the byte stuffing)
+    plan = _plan(p.width, p.height, n_px)
+    o_stream = _data_off(plan)
+    o_int = _stream_end(o_stream, len(p.stream))
+    n_int = len(p.starts) if p.ri else 0
+    total = (o_int + 4 * n_int + 15) // 16 * 16
+    if total > region.size:
+        return _no_room(p, total)
+    _write_head(region, KIND_BASELINE, p, (p.ncomp, p.hs, p.vs), len(p.stream), p.blocks(), plan, (p.ri, n_int, o_int, p.stuffed))
+    region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
+    region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 6 * jpeg_parse.TABLE_BYTES] = np.frombuffer(b"".join(p.tables), np.uint8)
+    _write_stream(region, o_stream, p.stream)
     if n_int:
         np.frombuffer(region, dtype=np.uint32, count=n_int, offset=o_int)[:] = p.starts
+        region[o_int + 4 * n_int:total] = 0
     return p.width, p.height, total
 
 
@@ -190,50 +243,27 @@ def stage_jpeg_progressive(path, n_px, region, data=None):
     """For the progressive decode on the device (csrc/jpeg.hip jpeg_progressive_kernel): read the file, walk its markers
     (jpeg_parse.parse_progressive) and lay out in `region` [header | quantisation steps | resize plan coefficients | scan records |
     the scans' Huffman tables | the scans' entropy-coded segments without byte stuffing, each 16-byte aligned and followed by
-    >= 16 zero bytes]. The header is stage_jpeg's, with kind 4, the number of scans at [6], and at [18] / [20] / [21] the offsets
-    of the scan records and of the tables and the number of tables. A scan record's stream_off counts from the region's start
-    and its table indices from the region's first table. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not
-    fit; raises jpeg_parse.Unsupported for files Pillow has to decode."""
-    try:
-        from . import jpeg_parse
-    except ImportError:
-        import jpeg_parse
-    if data is None:
-        with open(path, "rb") as f:
-            data = f.read()
-    p = jpeg_parse.parse_progressive(data)
-    key = (p.width, p.height, n_px)
-    plan = _plans.get(key)
-    if plan is None:
-        if len(_plans) > 256:
-            _plans.clear()
-        plan = _plans[key] = resize_plan(p.width, p.height, n_px)
-    nh, nv = plan["hcoef"].size, plan["vcoef"].size
+    >= 16 zero bytes]. A scan record's stream_off counts from the region's start and its table indices from the region's first
+    table. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises jpeg_parse.Unsupported for files
+    Pillow has to decode."""
+    p = jpeg_parse.parse_progressive(_contents(path, data))
+    plan = _plan(p.width, p.height, n_px)
     tables = {}
     for sc in p.scans:
         for t in (sc.dc if sc.ss == 0 else sc.ac):
             if t is not None:
                 tables.setdefault(t, len(tables))
-    o_scans = (JPEG_COEF_OFF + 4 * (nh + nv) + 15) // 16 * 16
+    o_scans = _data_off(plan)
     o_tab = o_scans + PROG_SCAN_BYTES * len(p.scans)
-    o = o_tab + jpeg_parse.TABLE_BYTES * len(tables)
+    total = (o_tab + jpeg_parse.TABLE_BYTES * len(tables) + 15) // 16 * 16
     offs = []
     for sc in p.scans:
-        o = (o + 15) // 16 * 16
-        offs.append(o)
-        o += len(sc.stream) + 16
-    total = (o + 15) // 16 * 16
+        offs.append(total)
+        total = _stream_end(total, len(sc.stream))
     if total > region.size:
-        return p.width, p.height, -total
-    ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
-    ints[:] = [4, p.width, p.height, p.ncomp, p.hs, p.vs, len(p.scans), p.blocks(), plan["r0"], plan["nrows"], plan["need_h"],
-               plan["need_v"], plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, o_scans, JPEG_COEF_OFF, o_tab, len(tables),
-               0, 0] + [0] * 8
+        return _no_room(p, total)
+    _write_head(region, KIND_PROGRESSIVE, p, (p.ncomp, p.hs, p.vs), len(p.scans), p.blocks(), plan, (o_tab, len(tables), 0, 0))
     region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
-    if nh + nv:
-        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
-        co[:nh] = plan["hcoef"]
-        co[nh:] = plan["vcoef"]
     rec = np.frombuffer(region, dtype=np.int32, count=PROG_SCAN_BYTES // 4 * len(p.scans), offset=o_scans).reshape(len(p.scans), -1)
     rec[:] = 0
     for k, sc in enumerate(p.scans):
@@ -246,8 +276,7 @@ def stage_jpeg_progressive(path, n_px, region, data=None):
     for t, j in tables.items():
         region[o_tab + j * jpeg_parse.TABLE_BYTES:o_tab + (j + 1) * jpeg_parse.TABLE_BYTES] = np.frombuffer(t, np.uint8)
     for sc, off in zip(p.scans, offs):
-        region[off:off + len(sc.stream)] = np.frombuffer(sc.stream, np.uint8)
-        region[off + len(sc.stream):(off + len(sc.stream) + 16 + 15) // 16 * 16] = 0
+        _write_stream(region, off, sc.stream)
     return p.width, p.height, total
 
 
@@ -258,58 +287,48 @@ PNG_MAX_RAW = 16 << 20      # filtered scanlines of a file the device takes: one
 def stage_png(path, n_px, region, data=None):
     """For the PNG decode on the device (csrc/png.hip): read the file, walk its chunks (png_parse.parse) and lay out in `region`
     [header | resize plan coefficients | DEFLATE stream without the zlib header, 16-byte aligned and followed by >= 16 zero
-    bytes]. The header is stage_jpeg's, with kind 6: 6 w h channels 0 0 stream_bytes 0 | the resize plan's ten fields | stream
-    offset, coefficient offset. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises
-    png_parse.Unsupported for files Pillow has to decode, among them files of more than PNG_MAX_RAW bytes of scanlines.
+    bytes]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises png_parse.Unsupported for files
+    Pillow has to decode, among them files of more than PNG_MAX_RAW bytes of scanlines.
     data: the file's contents, when the caller has read them."""
-    try:
-        from . import png_parse
-    except ImportError:
-        import png_parse
-    if data is None:
-        with open(path, "rb") as f:
-            data = f.read()
-    p = png_parse.parse(data)
+    p = png_parse.parse(_contents(path, data))
     if p.raw_bytes() > PNG_MAX_RAW:
         raise png_parse.Unsupported("more than PNG_MAX_RAW bytes of scanlines")
-    key = (p.width, p.height, n_px)
-    plan = _plans.get(key)
-    if plan is None:
-        if len(_plans) > 256:
-            _plans.clear()
-        plan = _plans[key] = resize_plan(p.width, p.height, n_px)
-    nh, nv = plan["hcoef"].size, plan["vcoef"].size
-    o_stream = (JPEG_COEF_OFF + 4 * (nh + nv) + 15) // 16 * 16
-    total = (o_stream + len(p.stream) + 16 + 15) // 16 * 16
+    plan = _plan(p.width, p.height, n_px)
+    o_stream = _data_off(plan)
+    total = _stream_end(o_stream, len(p.stream))
     if total > region.size:
-        return p.width, p.height, -total
-    ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
-    ints[:] = [6, p.width, p.height, p.channels, 0, 0, len(p.stream), 0, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
-               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, o_stream, JPEG_COEF_OFF] + [0] * 12
-    if nh + nv:
-        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
-        co[:nh] = plan["hcoef"]
-        co[nh:] = plan["vcoef"]
-    region[o_stream:o_stream + len(p.stream)] = np.frombuffer(p.stream, np.uint8)
-    region[o_stream + len(p.stream):total] = 0
+        return _no_room(p, total)
+    _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan)
+    _write_stream(region, o_stream, p.stream)
     return p.width, p.height, total
+
+
+# One way a file can sit in a region of the big segment for the device. kind: the worker's reply tag (b"%d" % kind), HDR.KIND and
+# the first entry of DecodePool's (kind, w, h, bytes); bit: the bit of the request's mode that allows it; magic: which files the
+# stager is tried on (serve() looks at the first bytes); stat: encode_files' stats key - "staged" counts the files a worker laid
+# out, "decoded" those of them the device did not report.
+Kind = namedtuple("Kind", "kind bit magic stager stat counts")
+FULL_SIZE = Kind(2, 1, None, decode_full, None, None)         # decoded pixels at full size, for the resize on the device
+# the parsed files, in the order serve() tries them and the device's statuses are laid out (pipeline.device_stage)
+PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
+          Kind(KIND_PROGRESSIVE, 4, "jpeg", stage_jpeg_progressive, "jpeg_progressive_files", "staged"),
+          Kind(KIND_PNG, 8, "png", stage_png, "png_files", "decoded"))
+PARSED_KINDS = frozenset(k.kind for k in PARSED)
+REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + PARSED)
+WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
 
 
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (bits: 1 full-size pixels, 2 a parsed baseline JPEG file, 4 a parsed progressive JPEG file,
-         8 a parsed PNG file) |
+         what the region may take (the bits of FULL_SIZE and PARSED) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
-              b"2" + <iiq (w, h, bytes)>: the image sits at full size, with its resize plan, in the region (decode_full) |
-              b"3" + <iiq (w, h, bytes)>: a baseline JPEG file, parsed, with its resize plan, in the region (stage_jpeg) |
-              b"4" + <iiq (w, h, bytes)>: a progressive JPEG file, parsed, with its resize plan, in the region
-              (stage_jpeg_progressive) |
-              b"5" + <iiq (w, h, bytes)>: as b"1", and the file would have been a b"3", b"4" or b"6" with a region of that many
-              bytes |
-              b"6" + <iiq (w, h, bytes)>: a PNG file, parsed, with its resize plan, in the region (stage_png)."""
+              a Kind's tag (FULL_SIZE, PARSED) + <iiq (w, h, bytes)>: the file sits in the region as that kind's stager left it,
+              with its resize plan |
+              WANTED_TAG + <iiq (w, h, bytes)>: as b"1", and the file would have been one of PARSED with a region of that many
+              bytes."""
     import mmap
     import os
     import struct
@@ -342,32 +361,30 @@ def serve(fin, fout):
                 region = np.frombuffer(mapped(big_name.decode()), dtype=np.uint8, count=int(big_cap_s), offset=int(big_off_s))
                 full = None
                 # the file is read once and its first bytes choose the parser (a PNG file used to be read by each of them in turn)
-                data = kind = None
-                if mode & 14:
+                data = magic = None
+                if mode & sum(k.bit for k in PARSED):
                     try:
-                        with open(fname, "rb") as f:
-                            data = f.read()
+                        data = _contents(fname, None)
                     except OSError:                            # unreadable: Pillow reports it
                         data = None
                     if data is not None:
-                        kind = "png" if data[:8] == b"\x89PNG\r\n\x1a\n" else "jpeg" if data[:2] == b"\xff\xd8" else None
-                for bit, want_kind, stager, tag in ((2, "jpeg", stage_jpeg, b"3"), (4, "jpeg", stage_jpeg_progressive, b"4"),
-                                                    (8, "png", stage_png, b"6")):
-                    if full is not None or wanted is not None or not mode & bit or kind != want_kind:
+                        magic = "png" if data[:8] == b"\x89PNG\r\n\x1a\n" else "jpeg" if data[:2] == b"\xff\xd8" else None
+                for k in PARSED:
+                    if full is not None or wanted is not None or not mode & k.bit or magic != k.magic:
                         continue
                     try:
-                        full = stager(fname, n_px, region, data)
+                        full = k.stager(fname, n_px, region, data)
                     except Exception:                          # not a file for this device decoder: the next one, or Pillow
                         full = None
                     if full is not None and full[2] < 0:
                         full, wanted = None, (full[0], full[1], -full[2])
                     if full is not None:
-                        reply = tag + struct.pack("<iiq", *full)
+                        reply = b"%d" % k.kind + struct.pack("<iiq", *full)
                 data = None
-                if full is None and mode & 1:
+                if full is None and mode & FULL_SIZE.bit:
                     full = decode_full(fname, n_px, region)
                     if full is not None:
-                        reply = b"2" + struct.pack("<iiq", *full)
+                        reply = b"%d" % FULL_SIZE.kind + struct.pack("<iiq", *full)
                 region = None
             if reply is None:
                 if shm_name == b"-":
@@ -376,7 +393,7 @@ def serve(fin, fout):
                     slot = np.frombuffer(mapped(shm_name.decode()), dtype=np.uint8, count=3 * n_px * n_px, offset=off)
                     load_uint8(fname, n_px, out=slot.reshape(3, n_px, n_px))
                     slot = None                                # no view may outlive the request (close() refuses then)
-                    reply = b"1" if wanted is None else b"5" + struct.pack("<iiq", *wanted)
+                    reply = b"1" if wanted is None else WANTED_TAG + struct.pack("<iiq", *wanted)
         except KeyboardInterrupt:
             break
         except Exception:

@@ -13,7 +13,9 @@ import numpy as np
 import torch
 
 
-from .decode_worker import load_uint8  # noqa: E402,F401  (the Pillow part of the transform lives beside its worker script)
+# the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
+from .decode_worker import (FULL_SIZE, HDR, KIND_BASELINE, KIND_PNG, KIND_PROGRESSIVE, PARSED, PARSED_KINDS, PLAN_INTS,  # noqa: E402,F401
+                            REGION_TAGS, WANTED_TAG, load_uint8)
 
 
 class DecodePool:
@@ -122,9 +124,8 @@ class DecodePool:
 
     def _run(self, w, jobs, n_px, name, seg, big=None):
         """Worker w decodes its share of the batch: (slot, path) pairs -> (slot, status) with status False (failed), True
-        (the transform's pixels are in the slot) or (kind, w, h, bytes): the image is in its region of the big segment -
-        kind 2 at full size, for the resize on the device; kind 3 as a parsed JPEG file, for the decode on the device; kind 4 as
-        a parsed progressive JPEG file; kind 6 as a parsed PNG file. If the worker process dies (a file that crashes the decoder, an OOM kill), that
+        (the transform's pixels are in the slot) or (kind, w, h, bytes): the image is in its region of the big segment, as one
+        of decode_worker's FULL_SIZE and PARSED kinds. If the worker process dies (a file that crashes the decoder, an OOM kill), that
         file is reported as failed and the rest of the share - and of every later batch - is decoded in this process: no
         program is spawned once the GPU may have been initialised."""
         import struct
@@ -148,9 +149,9 @@ class DecodePool:
                 raw = p.stdout.read(17 * len(jobs))
                 for k in range(len(raw) // 17):
                     st = raw[17 * k:17 * k + 1]
-                    if st == b"2" or st == b"3" or st == b"4" or st == b"6":
+                    if st in REGION_TAGS:
                         ok.append((jobs[k][0], (int(st),) + struct.unpack_from("<iiq", raw, 17 * k + 1)))
-                    elif st == b"5":                       # Pillow decoded it; a larger region would have taken the file itself
+                    elif st == WANTED_TAG:                 # Pillow decoded it; a larger region would have taken the file itself
                         self.jpeg_wanted = max(self.jpeg_wanted, struct.unpack_from("<iiq", raw, 17 * k + 1)[2])
                         ok.append((jobs[k][0], True))
                     else:
@@ -179,9 +180,7 @@ class DecodePool:
         full_cap > 0 (with copy=False): 8-bit RGB images that need resampling and fit full_cap bytes are delivered at FULL
         size in a second segment, one region of full_cap bytes per slot (tmpfs pages exist only where written), for the
         resize on the device; the result is then ((slots view, good mask, big view, {slot: (kind, w, h, bytes)}), ok, bad).
-        full_mode: what a region may take - bit 0 full-size pixels (kind 2), bit 1 baseline JPEG files parsed for the decode on
-        the device (kind 3: decode_worker.stage_jpeg), bit 2 progressive JPEG files parsed for it (kind 4:
-        decode_worker.stage_jpeg_progressive), bit 3 PNG files parsed for the decode on the device (kind 6: decode_worker.stage_png)."""
+        full_mode: what a region may take - the bits of decode_worker's FULL_SIZE and PARSED kinds."""
         n = len(paths)
         per = 3 * n_px * n_px
         seg = self._segment(max(1, n * per), segment)
@@ -244,6 +243,41 @@ def _load_safe(args):
         return None
 
 
+def _headers(bigview, n, cap, slots):
+    """The region headers (decode_worker.HDR) of `slots` as int64 [len(slots)][JPEG_HDR_INTS]: one strided gather out of the
+    segment (uint8, n regions of cap bytes)"""
+    from .decode_worker import JPEG_HDR_INTS
+    hd = np.lib.stride_tricks.as_strided(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))
+    return hd[slots].astype(np.int64)
+
+
+def _resize_jobs(src_off, w, h, plan, n_hcoef, hcoef_off, out_index, n_px):
+    """clipmi_resize_job records. plan: [n][8] r0 nrows need_h need_v left top hk vk (HDR.PLAN); hcoef_off: where each image's
+    horizontal coefficient block starts, in ints from the segment's start - the vertical block follows it; the rows the
+    vertical pass leaves for the horizontal one lie back to back in the scratch buffer (tmp_off)."""
+    from .resize import JOB
+    jobs = np.zeros(len(w), dtype=JOB)
+    jobs["src_off"], jobs["w"], jobs["h"], jobs["out_index"] = src_off, w, h, out_index
+    for k, f in enumerate(("r0", "nrows", "need_h", "need_v", "left", "top", "hk", "vk")):
+        jobs[f] = plan[:, k]
+    jobs["hcoef_off"] = hcoef_off
+    jobs["vcoef_off"] = jobs["hcoef_off"] + n_hcoef
+    tmp = plan[:, 1] * n_px * 3
+    jobs["tmp_off"] = np.cumsum(tmp) - tmp
+    return jobs
+
+
+def _decoded_jobs(hd, cap, slots, comp, n_px):
+    """-> (the resize jobs of parsed files whose decoded RGB rows lie back to back, 16-byte aligned, in the decoder's output: the
+    order of `slots`; their offsets there; their sizes)"""
+    w, h = hd[:, HDR.W], hd[:, HDR.H]
+    out_sz = (w * h * 3 + 15) // 16 * 16
+    out_off = np.cumsum(out_sz) - out_sz
+    jobs = _resize_jobs(out_off, w, h, hd[:, HDR.PLAN], hd[:, HDR.N_HCOEF], (slots * cap + hd[:, HDR.COEF_OFF]) // 4,
+                        np.asarray(comp)[slots], n_px)
+    return jobs, out_off, out_sz
+
+
 def jpeg_records(bigview, n, cap, slots, comp, n_px):
     """The device decoder's records out of a batch's regions of the big segment (decode_worker.stage_jpeg wrote them): every field
     comes out of the regions' headers as one strided numpy gather - no Python per image except the table-set look-up.
@@ -251,21 +285,19 @@ def jpeg_records(bigview, n, cap, slots, comp, n_px):
     batch's tensor. -> (clipmi_jpeg_image records with offsets into the segment, distinct raw Huffman tables uint8, clipmi_resize_job
     records whose sources are the decoder's outputs laid out back to back, output bytes per image, blocks per image, number of tables)"""
     from . import jpeg as J
-    from .decode_worker import JPEG_COEF_OFF, JPEG_HDR_INTS, JPEG_QUANT_OFF, JPEG_TABLES_OFF
-    from .resize import JOB
+    from .decode_worker import JPEG_QUANT_OFF, JPEG_TABLES_OFF
     slots = np.asarray(slots, dtype=np.int64)
     n3 = len(slots)
     st = np.lib.stride_tricks.as_strided
-    H = st(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[slots].astype(np.int64)
-    w, h, blocks, nrows = H[:, 1], H[:, 2], H[:, 7], H[:, 9]
+    hd = _headers(bigview, n, cap, slots)
+    jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px)
+    blocks = hd[:, HDR.BLOCKS]
     recs = np.zeros(n3, dtype=J.IMAGE)
-    out_sz = (w * h * 3 + 15) // 16 * 16
-    out_off = np.cumsum(out_sz) - out_sz
-    recs["stream_off"], recs["coef_off"], recs["out_off"] = slots * cap + H[:, 18], np.cumsum(blocks) - blocks, out_off
-    recs["stream_bytes"], recs["width"], recs["height"] = H[:, 6], w, h
-    recs["ncomp"], recs["hs"], recs["vs"] = H[:, 3], H[:, 4], H[:, 5]
-    recs["restart_interval"], recs["n_intervals"], recs["intervals_off"] = H[:, 20], H[:, 21], slots * cap + H[:, 22]
-    recs["stuffed"] = H[:, 23]
+    recs["stream_off"], recs["coef_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(blocks) - blocks, out_off
+    recs["stream_bytes"], recs["width"], recs["height"] = hd[:, HDR.COUNT], hd[:, HDR.W], hd[:, HDR.H]
+    recs["ncomp"], recs["hs"], recs["vs"] = hd[:, HDR.NCOMP], hd[:, HDR.HS], hd[:, HDR.VS]
+    recs["restart_interval"], recs["n_intervals"] = hd[:, HDR.RESTART_INTERVAL], hd[:, HDR.N_INTERVALS]
+    recs["intervals_off"], recs["stuffed"] = slots * cap + hd[:, HDR.INTERVALS_OFF], hd[:, HDR.STUFFED]
     recs["quant"] = st(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n3, 3, 64)
     # the Huffman tables: distinct six-table sets first (files of one encoder share theirs), then distinct tables
     tabs = st(bigview[JPEG_TABLES_OFF:], shape=(n, 6 * J.TABLE_BYTES), strides=(cap, 1))[slots]
@@ -278,14 +310,6 @@ def jpeg_records(bigview, n, cap, slots, comp, n_px):
         set_idx[k] = idx
     recs["dc_tbl"], recs["ac_tbl"] = set_idx[:, 0::2], set_idx[:, 1::2]
     tables = np.frombuffer(b"".join(pool_t), np.uint8)
-    jobs = np.zeros(n3, dtype=JOB)
-    jobs["src_off"], jobs["w"], jobs["h"], jobs["r0"], jobs["nrows"], jobs["out_index"] = out_off, w, h, H[:, 8], nrows, np.asarray(comp)[slots]
-    jobs["need_h"], jobs["need_v"], jobs["left"], jobs["top"], jobs["hk"], jobs["vk"] = (H[:, 10], H[:, 11], H[:, 12], H[:, 13],
-                                                                                      H[:, 14], H[:, 15])
-    jobs["hcoef_off"] = (slots * cap + JPEG_COEF_OFF) // 4
-    jobs["vcoef_off"] = jobs["hcoef_off"] + H[:, 16]
-    tmp = nrows * n_px * 3
-    jobs["tmp_off"] = np.cumsum(tmp) - tmp
     return recs, tables, jobs, out_sz, blocks, len(pool_t)
 
 
@@ -294,25 +318,22 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
     records, clipmi_jpeg_scan records with offsets into the segment, distinct raw Huffman tables uint8, clipmi_resize_job records
     whose sources are the decoder's outputs laid out back to back, output bytes per image, blocks per image, number of tables)"""
     from . import jpeg as J
-    from .decode_worker import JPEG_HDR_INTS, JPEG_QUANT_OFF, PROG_SCAN_BYTES
-    from .resize import JOB
+    from .decode_worker import JPEG_QUANT_OFF, PROG_SCAN_BYTES
     slots = np.asarray(slots, dtype=np.int64)
     n4 = len(slots)
-    st = np.lib.stride_tricks.as_strided
-    H = st(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[slots].astype(np.int64)
-    w, h, nscans, blocks, nrows = H[:, 1], H[:, 2], H[:, 6], H[:, 7], H[:, 9]
+    hd = _headers(bigview, n, cap, slots)
+    jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px)
+    nscans, blocks = hd[:, HDR.COUNT], hd[:, HDR.BLOCKS]
     recs = np.zeros(n4, dtype=J.PIMAGE)
-    out_sz = (w * h * 3 + 15) // 16 * 16
-    out_off = np.cumsum(out_sz) - out_sz
-    recs["coef_off"], recs["out_off"], recs["width"], recs["height"] = np.cumsum(blocks) - blocks, out_off, w, h
-    recs["ncomp"], recs["hs"], recs["vs"] = H[:, 3], H[:, 4], H[:, 5]
+    recs["coef_off"], recs["out_off"], recs["width"], recs["height"] = np.cumsum(blocks) - blocks, out_off, hd[:, HDR.W], hd[:, HDR.H]
+    recs["ncomp"], recs["hs"], recs["vs"] = hd[:, HDR.NCOMP], hd[:, HDR.HS], hd[:, HDR.VS]
     recs["first_scan"], recs["n_scans"] = np.cumsum(nscans) - nscans, nscans
-    recs["quant"] = st(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n4, 3, 64)
+    recs["quant"] = np.lib.stride_tricks.as_strided(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n4, 3, 64)
     scans = np.zeros(int(nscans.sum()), dtype=J.SCAN)
     pool_t = {}
     for k in range(n4):
         base = int(slots[k]) * cap
-        o_scans, o_tab, nt = int(H[k, 18]), int(H[k, 20]), int(H[k, 21])
+        o_scans, o_tab, nt = int(hd[k, HDR.DATA_OFF]), int(hd[k, HDR.TABLES_OFF]), int(hd[k, HDR.N_TABLES])
         local = bigview[base + o_scans:base + o_scans + PROG_SCAN_BYTES * int(nscans[k])].copy().view(J.SCAN)
         remap = np.array([pool_t.setdefault(bigview[base + o_tab + t * J.TABLE_BYTES:base + o_tab + (t + 1) * J.TABLE_BYTES].tobytes(),
                                             len(pool_t)) for t in range(nt)] + [-1], dtype=np.int32)
@@ -321,14 +342,6 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
         f = int(recs["first_scan"][k])
         scans[f:f + len(local)] = local
     tables = np.frombuffer(b"".join(pool_t), np.uint8)
-    jobs = np.zeros(n4, dtype=JOB)
-    jobs["src_off"], jobs["w"], jobs["h"], jobs["r0"], jobs["nrows"], jobs["out_index"] = out_off, w, h, H[:, 8], nrows, np.asarray(comp)[slots]
-    jobs["need_h"], jobs["need_v"], jobs["left"], jobs["top"], jobs["hk"], jobs["vk"] = (H[:, 10], H[:, 11], H[:, 12], H[:, 13],
-                                                                                      H[:, 14], H[:, 15])
-    jobs["hcoef_off"] = (slots * cap + H[:, 19]) // 4
-    jobs["vcoef_off"] = jobs["hcoef_off"] + H[:, 16]
-    tmp = nrows * n_px * 3
-    jobs["tmp_off"] = np.cumsum(tmp) - tmp
     return recs, scans, tables, jobs, out_sz, blocks, len(pool_t)
 
 
@@ -337,28 +350,74 @@ def png_records(bigview, n, cap, slots, comp, n_px):
     the segment and the scanline and output buffers laid out back to back, clipmi_resize_job records whose sources are the decoder's
     outputs, output bytes per image, scanline bytes per image, each rounded up to 16)"""
     from . import png as P
-    from .decode_worker import JPEG_HDR_INTS
-    from .resize import JOB
     slots = np.asarray(slots, dtype=np.int64)
-    n6 = len(slots)
-    st = np.lib.stride_tricks.as_strided
-    H = st(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[slots].astype(np.int64)
-    w, h, ch, nrows = H[:, 1], H[:, 2], H[:, 3], H[:, 9]
-    recs = np.zeros(n6, dtype=P.IMAGE)
-    out_sz = (w * h * 3 + 15) // 16 * 16
+    hd = _headers(bigview, n, cap, slots)
+    jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px)
+    w, h, ch = hd[:, HDR.W], hd[:, HDR.H], hd[:, HDR.NCOMP]
+    recs = np.zeros(len(slots), dtype=P.IMAGE)
     raw_sz = (h * (1 + w * ch) + 15) // 16 * 16
-    out_off = np.cumsum(out_sz) - out_sz
-    recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + H[:, 18], np.cumsum(raw_sz) - raw_sz, out_off
-    recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = H[:, 6], w, h, ch
-    jobs = np.zeros(n6, dtype=JOB)
-    jobs["src_off"], jobs["w"], jobs["h"], jobs["r0"], jobs["nrows"], jobs["out_index"] = out_off, w, h, H[:, 8], nrows, np.asarray(comp)[slots]
-    jobs["need_h"], jobs["need_v"], jobs["left"], jobs["top"], jobs["hk"], jobs["vk"] = (H[:, 10], H[:, 11], H[:, 12], H[:, 13],
-                                                                                      H[:, 14], H[:, 15])
-    jobs["hcoef_off"] = (slots * cap + H[:, 19]) // 4
-    jobs["vcoef_off"] = jobs["hcoef_off"] + H[:, 16]
-    tmp = nrows * n_px * 3
-    jobs["tmp_off"] = np.cumsum(tmp) - tmp
+    recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(raw_sz) - raw_sz, out_off
+    recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = hd[:, HDR.COUNT], w, h, ch
     return recs, jobs, out_sz, raw_sz
+
+
+def _groups(need, budget):
+    """[lo, hi) ranges of consecutive files whose `need` sums stay within the budget: a group closes when the next file would
+    exceed it, and a file above the budget is a group of its own. No files, no group."""
+    groups, lo, acc = [], 0, 0
+    for k in range(len(need)):
+        if k > lo and acc + need[k] > budget:
+            groups.append((lo, k))
+            lo, acc = k, 0
+        acc += int(need[k])
+    return groups + [(lo, len(need))] if len(need) else groups
+
+
+def _pack16(arrays):
+    """Arrays -> (one uint8 buffer that holds their bytes at 16-byte-aligned offsets, the offsets)"""
+    offs, end = [], 0
+    for a in arrays:
+        offs.append((end + 15) // 16 * 16)
+        end = offs[-1] + a.nbytes
+    buf = np.zeros(end, np.uint8)
+    for a, o in zip(arrays, offs):
+        buf[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
+    return buf, offs
+
+
+def _baseline_group(L, r):
+    recs, tables, jobs, out_sz, blocks, nt = r
+    total, most, pixels = int(blocks.sum()), int(blocks.max()), int((recs["width"].astype(np.int64) * recs["height"]).max())
+    ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total, nt))
+    return [recs, tables, jobs], out_sz, ws_bytes, "clipmi_jpeg_decode_rgb8", lambda base, sb, offs, rgb, status, ws, stream: (
+        L.clipmi_jpeg_decode_rgb8(base, sb, len(recs), sb + offs[1], nt, total, most, pixels, rgb, status, ws, ws_bytes, stream))
+
+
+def _progressive_group(L, r):
+    recs, scans, tables, jobs, out_sz, blocks, nt = r
+    total, most, pixels = int(blocks.sum()), int(blocks.max()), int((recs["width"].astype(np.int64) * recs["height"]).max())
+    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(recs), total, nt))
+    return [recs, scans, tables, jobs], out_sz, ws_bytes, "clipmi_jpeg_decode_progressive_rgb8", (
+        lambda base, sb, offs, rgb, status, ws, stream: L.clipmi_jpeg_decode_progressive_rgb8(
+            base, sb, len(recs), sb + offs[1], len(scans), sb + offs[2], nt, total, most, pixels, rgb, status, ws, ws_bytes, stream))
+
+
+def _png_group(L, r):
+    recs, jobs, out_sz, raw_sz = r
+    total, most = int(raw_sz.sum()), int(raw_sz.max())
+    ws_bytes = int(L.clipmi_png_workspace_bytes(len(recs), total))
+    return [recs, jobs], out_sz, ws_bytes, "clipmi_png_decode_rgb8", lambda base, sb, offs, rgb, status, ws, stream: (
+        L.clipmi_png_decode_rgb8(base, sb, len(recs), total, most, rgb, status, ws, ws_bytes, stream))
+
+
+# What differs between the parsed kinds in device_stage, by decode_worker.Kind.kind:
+#   the records function |
+#   the bytes of HBM a file's decoder needs beside its RGB rows and the resize's rows, out of the headers (coefficients; scanlines) |
+#   (library, what the records function returned) -> (the arrays that travel to the device, 16-byte aligned in this order, the
+#   resize jobs last; output bytes per image; workspace bytes; the decode entry's name; its call, given where things lie)
+_FORMATS = {KIND_BASELINE: (jpeg_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _baseline_group),
+            KIND_PROGRESSIVE: (progressive_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _progressive_group),
+            KIND_PNG: (png_records, lambda hd: hd[:, HDR.H] * (1 + hd[:, HDR.W] * hd[:, HDR.NCOMP]), _png_group)}
 
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
@@ -386,8 +445,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
-    shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoder (jpeg_files;
-    progressive ones: jpeg_progressive_files; PNG files the device decoded and did not hand back: png_files)."""
+    shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoders, under the
+    keys of decode_worker.PARSED (jpeg_files, jpeg_progressive_files: files staged for the device; png_files: files it decoded and
+    did not hand back)."""
     import os
     import time
     n_px = model.visual.input_resolution
@@ -466,29 +526,23 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     def device_stage(devt, bigview, full, good):
         """The batch's regions of the big segment -> their rows of devt, on the copy stream behind devt's own copy: ONE H2D copy
         of the segment where it lies (it is page-locked: no packing copy on the host - packing 1 GB per batch of photo-sized
-        images with one thread was slower than Pillow's resize), then clipmi_resize_crop_rgb8 for the full-size images (kind 2)
-        and clipmi_jpeg_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed JPEG files (kind 3), and
-        clipmi_jpeg_decode_progressive_rgb8 + clipmi_resize_crop_rgb8 for the parsed progressive ones (kind 4), and
-        clipmi_png_decode_rgb8 + clipmi_resize_crop_rgb8 for the parsed PNG files (kind 6).
+        images with one thread was slower than Pillow's resize), then clipmi_resize_crop_rgb8 for the full-size images
+        (decode_worker.FULL_SIZE) and, for each kind of parsed file in decode_worker.PARSED's order, its decode entry (_FORMATS) +
+        clipmi_resize_crop_rgb8.
         The copy stream carries the copies only; the kernels go to the process's ONE side stream (_lib.side_stream: this ROCm gives a
         process three hardware queues) behind an event, so that the next batch's copy runs beside this batch's kernels instead of
         behind them, and the consumer finds them queued in front of its encode step.
         -> (event behind the kernels, pending: what the consumer checks afterwards - the decoder's per-file status). Returns when the
         segment has been copied (it is decoded into again two batches later)."""
         from . import _lib
-        from . import jpeg as J
-        from .decode_worker import JPEG_COEF_OFF, JPEG_HDR_INTS, JPEG_QUANT_OFF, JPEG_TABLES_OFF, PLAN_INTS
-        from .resize import JOB
         L = _lib.lib()
         n = len(good)
         comp = np.cumsum(good) - 1                           # slot -> row of devt
         cap = bigview.size // n
         used = (max(full) + 1) * cap
-        e2 = sorted((s_, v) for s_, v in full.items() if v[0] == 2)
-        e3 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 3), dtype=np.int64)
-        e4 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 4), dtype=np.int64)
-        e6 = np.array(sorted(s_ for s_, v in full.items() if v[0] == 6), dtype=np.int64)
-        n_status = len(e3) + len(e4) + len(e6)              # one status tensor: baseline files, progressive files, PNG files
+        e2 = np.array(sorted(s_ for s_, v in full.items() if v[0] == FULL_SIZE.kind), dtype=np.int64)
+        parsed = [np.array(sorted(s_ for s_, v in full.items() if v[0] == k.kind), dtype=np.int64) for k in PARSED]
+        n_status = sum(len(slots) for slots in parsed)      # one status tensor: the kinds in PARSED's order
         if not pool.pin_segment(2 + seg_index[0]):
             # the segment could not be page-locked (locked-memory limit?): this batch goes through a pinned copy of it, the
             # following ones take the host path
@@ -499,184 +553,70 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         else:
             slot = None
             src = torch.from_numpy(bigview[:used])
-        pending = {"keep": [], "status": None, "launch": [], "n_png": len(e6)}
+        pending = {"keep": [], "status": None, "launch": [], "count_ok": []}
         with torch.cuda.stream(copy_stream):
             dbig = src.to(dev, non_blocking=True)
             base = dbig.data_ptr()
             if n_status:
                 pending["status"] = torch.empty(n_status, dtype=torch.int32, device=dev)
-                pending["slots"] = np.concatenate([e3, e4, e6])
-            if e2:
-                jobs = np.zeros(len(e2), dtype=JOB)
-                toff, max_rows = 0, 1
-                for t, (s_, (_, w, h, nb)) in enumerate(e2):
-                    base_ = s_ * cap
-                    o_hdr = (w * h * 3 + 15) // 16 * 16
-                    hd = np.frombuffer(bigview, dtype=np.int32, count=PLAN_INTS, offset=base_ + o_hdr)
-                    j = jobs[t]
-                    j["src_off"], j["w"], j["h"], j["r0"], j["nrows"], j["out_index"] = base_, w, h, hd[2], hd[3], comp[s_]
-                    j["need_h"], j["need_v"], j["left"], j["top"], j["hk"], j["vk"] = hd[4], hd[5], hd[6], hd[7], hd[8], hd[9]
-                    j["hcoef_off"] = (base_ + o_hdr) // 4 + PLAN_INTS
-                    j["vcoef_off"] = j["hcoef_off"] + hd[10]
-                    j["tmp_off"] = toff
-                    toff += int(hd[3]) * n_px * 3
-                    max_rows = max(max_rows, int(hd[3]))
+                pending["slots"] = np.concatenate(parsed)
+
+            def resize_into_devt(src_ptr, jobs_ptr, n_jobs, max_rows, scratch):
+                rc = L.clipmi_resize_crop_rgb8(src_ptr, jobs_ptr, n_jobs, max_rows, base, n_px, devt.data_ptr(), scratch.data_ptr(),
+                                               _lib.stream_ptr(dev))
+                _lib.check(rc, "clipmi_resize_crop_rgb8")
+
+            if len(e2):
+                # decode_full's regions: [pixels | pad to 16 | PLAN_INTS header: w h, the plan, n_hcoef n_vcoef | coefficient blocks]
+                wh = np.array([full[s_][1:3] for s_ in e2], dtype=np.int64)
+                o_hdr = e2 * cap + (wh[:, 0] * wh[:, 1] * 3 + 15) // 16 * 16
+                hd = np.stack([np.frombuffer(bigview, dtype=np.int32, count=PLAN_INTS, offset=int(o)) for o in o_hdr]).astype(np.int64)
+                jobs = _resize_jobs(e2 * cap, wh[:, 0], wh[:, 1], hd[:, 2:10], hd[:, 10], o_hdr // 4 + PLAN_INTS, comp[e2], n_px)
                 djobs = torch.from_numpy(jobs.view(np.uint8).reshape(-1).copy()).to(dev)
-                scratch = torch.empty(max(toff, 1), dtype=torch.uint8, device=dev)
+                scratch = torch.empty(max(int((hd[:, 3] * n_px * 3).sum()), 1), dtype=torch.uint8, device=dev)
                 pending["keep"] += [djobs, scratch]
 
-                def resize_full(djobs=djobs, scratch=scratch, n2=len(e2), max_rows=max_rows):
-                    rc = L.clipmi_resize_crop_rgb8(base, djobs.data_ptr(), n2, max_rows, base, n_px, devt.data_ptr(),
-                                                   scratch.data_ptr(), _lib.stream_ptr(dev))
-                    _lib.check(rc, "clipmi_resize_crop_rgb8")
+                def resize_full(djobs=djobs, scratch=scratch, n2=len(e2), max_rows=max(1, int(hd[:, 3].max()))):
+                    resize_into_devt(base, djobs.data_ptr(), n2, max_rows, scratch)
 
                 pending["launch"].append(resize_full)
-            if len(e3):
-                # groups of files whose decoded form (coefficients, sample planes, RGB rows: ~22 bytes per pixel) fits a budget: a
-                # batch of thumbnails is one group, a batch of 12-megapixel photos many - they run one after the other through
-                # ONE workspace (the side stream is in order), so that HBM holds a group, not a batch, of decoded photos
-                st_ = np.lib.stride_tricks.as_strided
-                H3 = st_(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[e3].astype(np.int64)
-                need = H3[:, 7] * 192 + (H3[:, 1] * H3[:, 2] * 3 + 15) // 16 * 16 + H3[:, 9] * n_px * 3
-                groups, lo, acc = [], 0, 0
-                for k in range(len(e3)):
-                    if k > lo and acc + need[k] > jpeg_group_bytes:
-                        groups.append((lo, k))
-                        lo, acc = k, 0
-                    acc += int(need[k])
-                groups.append((lo, len(e3)))
-                status = pending["status"]
+            status_at = 0                                    # where this kind's statuses start in the tensor
+            for kind, slots in zip(PARSED, parsed):
+                if not len(slots):
+                    continue
+                # groups of files whose decoded form (for JPEG coefficients, sample planes, RGB rows: ~22 bytes per pixel; for PNG
+                # scanlines and RGB rows) fits a budget: a batch of thumbnails is one group, a batch of 12-megapixel photos many -
+                # they run one after the other through ONE workspace per kind (the side stream is in order), so that HBM holds a
+                # group, not a batch, of decoded photos. The kinds follow each other on the side stream in PARSED's order.
+                records, decoder_bytes, group = _FORMATS[kind.kind]
+                hd = _headers(bigview, n, cap, slots)
+                need = decoder_bytes(hd) + (hd[:, HDR.W] * hd[:, HDR.H] * 3 + 15) // 16 * 16 + hd[:, HDR.NROWS] * n_px * 3
                 calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
-                for lo, hi in groups:
-                    recs, tables, jobs, out_sz, blocks, nt = jpeg_records(bigview, n, cap, e3[lo:hi], comp, n_px)
-                    w, h, nrows = recs["width"].astype(np.int64), recs["height"].astype(np.int64), jobs["nrows"].astype(np.int64)
-                    o_tab = (recs.nbytes + 15) // 16 * 16
-                    o_job = (o_tab + tables.nbytes + 15) // 16 * 16
-                    small = np.zeros(o_job + jobs.nbytes, np.uint8)
-                    small[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-                    small[o_tab:o_tab + tables.nbytes] = tables
-                    small[o_job:] = jobs.view(np.uint8).reshape(-1)
+                for lo, hi in _groups(need, jpeg_group_bytes):
+                    arrays, out_sz, ws_bytes, name, decode = group(L, records(bigview, n, cap, slots[lo:hi], comp, n_px))
+                    small, offs = _pack16(arrays)
                     dsmall = torch.from_numpy(small).to(dev)
-                    total_blocks = int(blocks.sum())
-                    ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, nt))
+                    nrows = arrays[-1]["nrows"].astype(np.int64)
                     ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
                     tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
-                    calls.append((dsmall, o_tab, o_job, hi - lo, nt, total_blocks, int(blocks.max()), int((w * h).max()), int(nrows.max()),
-                                  ws_bytes, lo))
+                    calls.append((dsmall, offs, hi - lo, int(nrows.max()), name, decode, 4 * (status_at + lo)))
                     pending["keep"].append(dsmall)
                 ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
                 rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
-                scratch3 = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
+                scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
 
-                def decode_jpeg():
-                    for dsmall, o_tab, o_job, n3, nt, total_blocks, mb, mp, mr, ws_bytes, lo in calls:
+                def decode_kind(calls=calls, ws=ws, rgb=rgb, scratch=scratch, status=pending["status"]):
+                    for dsmall, offs, n_files, max_rows, name, decode, status_off in calls:
                         sb = dsmall.data_ptr()
-                        rc = L.clipmi_jpeg_decode_rgb8(base, sb, n3, sb + o_tab, nt, total_blocks, mb, mp, rgb.data_ptr(),
-                                                       status.data_ptr() + 4 * lo, ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_jpeg_decode_rgb8")
-                        rc = L.clipmi_resize_crop_rgb8(rgb.data_ptr(), sb + o_job, n3, mr, base, n_px, devt.data_ptr(), scratch3.data_ptr(),
-                                                       _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_resize_crop_rgb8")
+                        _lib.check(decode(base, sb, offs, rgb.data_ptr(), status.data_ptr() + status_off, ws.data_ptr(),
+                                          _lib.stream_ptr(dev)), name)
+                        resize_into_devt(rgb.data_ptr(), sb + offs[-1], n_files, max_rows, scratch)
 
-                pending["launch"].append(decode_jpeg)
-                pending["keep"] += [ws, rgb, scratch3]
-            if len(e4):
-                # progressive files: the same grouping, their own records and workspace, behind the baseline decode on the side stream;
-                # their statuses follow the baseline files' in one tensor
-                st_ = np.lib.stride_tricks.as_strided
-                H4 = st_(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[e4].astype(np.int64)
-                need = H4[:, 7] * 192 + (H4[:, 1] * H4[:, 2] * 3 + 15) // 16 * 16 + H4[:, 9] * n_px * 3
-                groups, lo, acc = [], 0, 0
-                for k in range(len(e4)):
-                    if k > lo and acc + need[k] > jpeg_group_bytes:
-                        groups.append((lo, k))
-                        lo, acc = k, 0
-                    acc += int(need[k])
-                groups.append((lo, len(e4)))
-                status = pending["status"]
-                calls4, ws_max, rgb_max, tmp_max = [], 0, 0, 0
-                for lo, hi in groups:
-                    recs, scans, tables, jobs, out_sz, blocks, nt = progressive_records(bigview, n, cap, e4[lo:hi], comp, n_px)
-                    w, h, nrows = recs["width"].astype(np.int64), recs["height"].astype(np.int64), jobs["nrows"].astype(np.int64)
-                    o_scan = (recs.nbytes + 15) // 16 * 16
-                    o_tab = (o_scan + scans.nbytes + 15) // 16 * 16
-                    o_job = (o_tab + tables.nbytes + 15) // 16 * 16
-                    small = np.zeros(o_job + jobs.nbytes, np.uint8)
-                    small[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-                    small[o_scan:o_scan + scans.nbytes] = scans.view(np.uint8).reshape(-1)
-                    small[o_tab:o_tab + tables.nbytes] = tables
-                    small[o_job:] = jobs.view(np.uint8).reshape(-1)
-                    dsmall = torch.from_numpy(small).to(dev)
-                    total_blocks = int(blocks.sum())
-                    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(hi - lo, total_blocks, nt))
-                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
-                    tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
-                    calls4.append((dsmall, o_scan, len(scans), o_tab, o_job, hi - lo, nt, total_blocks, int(blocks.max()), int((w * h).max()),
-                                   int(nrows.max()), ws_bytes, len(e3) + lo))
-                    pending["keep"].append(dsmall)
-                ws4 = torch.empty(ws_max, dtype=torch.uint8, device=dev)
-                rgb4 = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
-                scratch4 = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
-
-                def decode_progressive(status=status):
-                    for dsmall, o_scan, ns, o_tab, o_job, n4, nt, total_blocks, mb, mp, mr, ws_bytes, lo in calls4:
-                        sb = dsmall.data_ptr()
-                        rc = L.clipmi_jpeg_decode_progressive_rgb8(base, sb, n4, sb + o_scan, ns, sb + o_tab, nt, total_blocks, mb, mp,
-                                                                   rgb4.data_ptr(), status.data_ptr() + 4 * lo, ws4.data_ptr(), ws_bytes,
-                                                                   _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_jpeg_decode_progressive_rgb8")
-                        rc = L.clipmi_resize_crop_rgb8(rgb4.data_ptr(), sb + o_job, n4, mr, base, n_px, devt.data_ptr(), scratch4.data_ptr(),
-                                                       _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_resize_crop_rgb8")
-
-                pending["launch"].append(decode_progressive)
-                pending["keep"] += [ws4, rgb4, scratch4]
-            if len(e6):
-                # PNG files: the same grouping by what a group holds in HBM (scanlines, RGB rows, the resize's rows), their own
-                # workspace, behind the JPEG decodes on the side stream; their statuses come last in the tensor
-                st_ = np.lib.stride_tricks.as_strided
-                H6 = st_(bigview[:4 * JPEG_HDR_INTS].view(np.int32), shape=(n, JPEG_HDR_INTS), strides=(cap, 4))[e6].astype(np.int64)
-                need = H6[:, 2] * (1 + H6[:, 1] * H6[:, 3]) + (H6[:, 1] * H6[:, 2] * 3 + 15) // 16 * 16 + H6[:, 9] * n_px * 3
-                groups, lo, acc = [], 0, 0
-                for k in range(len(e6)):
-                    if k > lo and acc + need[k] > jpeg_group_bytes:
-                        groups.append((lo, k))
-                        lo, acc = k, 0
-                    acc += int(need[k])
-                groups.append((lo, len(e6)))
-                status = pending["status"]
-                calls6, ws_max, rgb_max, tmp_max = [], 0, 0, 0
-                for lo, hi in groups:
-                    recs, jobs, out_sz, raw_sz = png_records(bigview, n, cap, e6[lo:hi], comp, n_px)
-                    nrows = jobs["nrows"].astype(np.int64)
-                    o_job = (recs.nbytes + 15) // 16 * 16
-                    small = np.zeros(o_job + jobs.nbytes, np.uint8)
-                    small[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-                    small[o_job:] = jobs.view(np.uint8).reshape(-1)
-                    dsmall = torch.from_numpy(small).to(dev)
-                    total_raw = int(raw_sz.sum())
-                    ws_bytes = int(L.clipmi_png_workspace_bytes(hi - lo, total_raw))
-                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
-                    tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
-                    calls6.append((dsmall, o_job, hi - lo, total_raw, int(raw_sz.max()), int(nrows.max()), ws_bytes,
-                                   len(e3) + len(e4) + lo))
-                    pending["keep"].append(dsmall)
-                ws6 = torch.empty(ws_max, dtype=torch.uint8, device=dev)
-                rgb6 = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
-                scratch6 = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
-
-                def decode_png(status=status):
-                    for dsmall, o_job, n6, total_raw, max_raw, mr, ws_bytes, lo in calls6:
-                        sb = dsmall.data_ptr()
-                        rc = L.clipmi_png_decode_rgb8(base, sb, n6, total_raw, max_raw, rgb6.data_ptr(), status.data_ptr() + 4 * lo,
-                                                      ws6.data_ptr(), ws_bytes, _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_png_decode_rgb8")
-                        rc = L.clipmi_resize_crop_rgb8(rgb6.data_ptr(), sb + o_job, n6, mr, base, n_px, devt.data_ptr(), scratch6.data_ptr(),
-                                                       _lib.stream_ptr(dev))
-                        _lib.check(rc, "clipmi_resize_crop_rgb8")
-
-                pending["launch"].append(decode_png)
-                pending["keep"] += [ws6, rgb6, scratch6]
+                pending["launch"].append(decode_kind)
+                pending["keep"] += [ws, rgb, scratch]
+                if kind.counts == "decoded":
+                    pending["count_ok"].append((kind.stat, status_at, status_at + len(slots)))
+                status_at += len(slots)
             ev_copy = torch.cuda.Event()
             ev_copy.record(copy_stream)
         side = _lib.side_stream(dev)[1]
@@ -743,7 +683,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
             pending["chunk"], pending["good"] = chunk, good.copy()
         if jpeg_cap and full_cap[0]:
             # the next batches' JPEG regions: 1.25 x the largest file this batch held or turned away
-            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] in (3, 4, 6)] + [pool.jpeg_wanted])
+            used3 = max([int(v[3]) for v in (full or {}).values() if v[0] in PARSED_KINDS] + [pool.jpeg_wanted])
             pool.jpeg_wanted = 0
             if used3:
                 pool.jpeg_cap_hint = min(jpeg_cap, max(1 << 16, (used3 + used3 // 4 + 65535) // 65536 * 65536))
@@ -800,8 +740,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
             feats = model.encode_image(devt, normalize=True).cpu().numpy().astype("float32")
             if pending is not None and pending["status"] is not None:
                 stc = pending["status"].cpu().numpy()         # (behind the encode step: nothing waits for it in the common case)
-                if stats is not None and pending["n_png"]:
-                    stats["png_files"] = stats.get("png_files", 0) + int((stc[-pending["n_png"]:] == 0).sum())
+                if stats is not None:
+                    for key, lo, hi in pending["count_ok"]:
+                        stats[key] = stats.get(key, 0) + int((stc[lo:hi] == 0).sum())
                 if stc.any():
                     ok, bad, devt = redo_on_host([int(s_) for s_ in pending["slots"][stc != 0]], pending["chunk"],
                                                  pending["good"], ok, bad, devt)
@@ -834,9 +775,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                 if stats is not None:
                     stats["copy_s"] = stats.get("copy_s", 0.0) + time.perf_counter() - t0
                     if len(dec_[0]) == 4:
-                        stats["jpeg_files"] = stats.get("jpeg_files", 0) + sum(1 for v in dec_[0][3].values() if v[0] == 3)
-                        stats["jpeg_progressive_files"] = stats.get("jpeg_progressive_files", 0) + sum(1 for v in dec_[0][3].values()
-                                                                                                       if v[0] == 4)
+                        for k in PARSED:
+                            if k.counts == "staged":
+                                stats[k.stat] = stats.get(k.stat, 0) + sum(1 for v in dec_[0][3].values() if v[0] == k.kind)
                 return r
 
             def submit(j):

@@ -211,3 +211,46 @@ def test_stage_png_round_trips_a_file_through_a_region(tmp_path):
     Image.fromarray(png_cases.noise(rng, 8, 8, 4), "RGBA").save(bad)
     with pytest.raises(png_parse.Unsupported):
         decode_worker.stage_png(str(bad), 224, np.zeros(1 << 16, np.uint8))
+
+
+def test_worker_regions_and_the_png_records_built_from_them(tmp_path):
+    """What a decode worker lays out for PNG files (decode_worker.stage_png) and what the parent builds out of a batch's regions
+    (pipeline.png_records) is, field for field, what png.pack builds from the parsed files, with the streams in place in the
+    segment; the resize jobs are resize_plan's, with the coefficient blocks where the jobs point."""
+    from clipmi import decode_worker as dw, pipeline
+    rng = np.random.default_rng(7)
+    specs = [(64, 96, 3), (260, 300, 1), (224, 224, 3), (300, 260, 1)]          # (h, w, channels)
+    n, cap, n_px = len(specs) + 2, 256 << 10, 224
+    big = np.full(n * cap, 0xAB, np.uint8)
+    slots, items = [], []
+    for k, (h, w, ch) in enumerate(specs):
+        blob = png_cases.write(png_cases.smooth(rng, h, w, ch), "cycle")
+        path = tmp_path / f"f{k}.png"
+        path.write_bytes(blob)
+        slot = k + (1 if k >= 2 else 0)                           # slot 2 holds no PNG file: a gap in the batch
+        got = dw.stage_png(str(path), n_px, big[slot * cap:(slot + 1) * cap])
+        assert got[:2] == (w, h) and 0 < got[2] <= cap
+        slots.append(slot)
+        items.append(png_parse.parse(blob))
+    comp = np.arange(n)
+    recs, jobs, out_sz, raw_sz = pipeline.png_records(big, n, cap, slots, comp, n_px)
+    ref = png.pack(items)[0]
+    for f in ("stream_bytes", "width", "height", "channels", "raw_off", "out_off"):
+        assert np.array_equal(recs[f], ref[f]), f
+    assert list(out_sz) == [(it.width * it.height * 3 + 15) // 16 * 16 for it in items]
+    assert list(raw_sz) == [(it.raw_bytes() + 15) // 16 * 16 for it in items]
+    for k, (r, it, slot) in enumerate(zip(recs, items, slots)):
+        o, nb = int(r["stream_off"]), int(r["stream_bytes"])
+        assert slot * cap <= o and o + nb + 16 <= (slot + 1) * cap and o % 16 == 0
+        assert big[o:o + nb].tobytes() == it.stream and not big[o + nb:o + nb + 16].any()
+        plan = dw.resize_plan(it.width, it.height, n_px)
+        j = jobs[k]
+        assert (int(j["w"]), int(j["h"]), int(j["r0"]), int(j["nrows"]), int(j["need_h"]), int(j["need_v"]), int(j["left"]), int(j["top"]),
+                int(j["hk"]), int(j["vk"])) == (it.width, it.height, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"], plan["left"],
+                                                plan["top"], plan["hk"], plan["vk"])
+        assert int(j["src_off"]) == int(r["out_off"]) and int(j["out_index"]) == slot
+        hc = np.frombuffer(big, np.int32, count=plan["hcoef"].size, offset=4 * int(j["hcoef_off"]))
+        vc = np.frombuffer(big, np.int32, count=plan["vcoef"].size, offset=4 * int(j["vcoef_off"]))
+        assert np.array_equal(hc, plan["hcoef"]) and np.array_equal(vc, plan["vcoef"])
+    tmp = jobs["nrows"].astype(np.int64) * n_px * 3
+    assert np.array_equal(jobs["tmp_off"], np.cumsum(tmp) - tmp)
