@@ -375,40 +375,57 @@ extern "C" size_t clipmi_encode_image_workspace_bytes(const clipmi_tower* t, int
     return carve(t, B, nullptr, ~(size_t)0, nullptr);
 }
 
-static int encode_image_impl(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype,
-                             int B, float* out_dev, int normalize, void* ws_dev, size_t ws_bytes, void* stream, GemmProbe* probe) {
-    if (int rc = check_tower(t, 0, "encode_image")) return rc;
-    if (!blob_dev || !pixels_dev || !out_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "encode_image: NULL pointer");
-    if (B < 1) return set_err(CLIPMI_EINVAL, "encode_image: B=%d", B);
-    if (pix_dtype != CLIPMI_F32 && pix_dtype != CLIPMI_BF16 && pix_dtype != CLIPMI_U8)
-        return set_err(CLIPMI_EINVAL, "encode_image: pix_dtype %d", pix_dtype);
-    const int grid = t->res / t->patch, np = grid * grid;
-    if (np + 1 != t->tokens || t->patch_k % 64 != 0 || t->patch_k < 3 * t->patch * t->patch)
-        return set_err(CLIPMI_EINVAL, "encode_image: inconsistent tower (res %d patch %d tokens %d patch_k %d)", t->res,
-                       t->patch, t->tokens, t->patch_k);
-    const size_t need = clipmi_encode_image_workspace_bytes(t, B);
-    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "encode_image: workspace %zu < %zu", ws_bytes, need);
-    Ws w;
-    carve(t, B, ws_dev, ws_bytes, &w);
-    hipStream_t st = as_stream(stream);
+// The embedding front end of the vision tower, everything in front of the first block: patches -> patch GEMM (+ positional
+// rows, EPI_PATCH_F32; `algo` as in launch_gemm_algo, 0 in the product) -> class-token rows -> ln_pre (skipped when
+// !with_ln_pre: the test hook's view of the rows in front of it). Shared by clipmi_encode_image and clipmi_dbg_embed_image.
+static int embed_image(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype, int B, const Ws& w,
+                       int algo, bool with_ln_pre, hipStream_t st) {
     const int W = t->width, L = t->tokens;
-
+    const int grid = t->res / t->patch, np = grid * grid;
     PatchArgs pa{pixels_dev, w.patches, pix_dtype, B, t->res, t->patch, grid, np, t->patch_k};
     if (int rc = launch_patchify(pa, st)) return rc;
     GemmArgs g{};
     g.A = w.patches; g.W = at<unsigned short>(blob_dev, t->off_patch_w); g.bias = nullptr; g.out = w.x;
     g.M = B * np; g.N = W; g.K = t->patch_k; g.pos = at<float>(blob_dev, t->off_pos); g.np = np; g.L = L;
-    if (int rc = launch_gemm_algo(g, EPI_PATCH_F32, 0, st)) return rc;
+    if (int rc = launch_gemm_algo(g, EPI_PATCH_F32, algo, st)) return rc;
     hipLaunchKernelGGL(cls_rows_kernel, dim3((unsigned)(((long long)B * W + 255) / 256)), dim3(256), 0, st, w.x,
                        at<float>(blob_dev, t->off_cls), at<float>(blob_dev, t->off_pos), B, L, W);
     CLIPMI_CHECK_LAUNCH("cls_rows_kernel");
+    if (!with_ln_pre) return 0;
     LnArgs ln{w.x, at<float>(blob_dev, t->off_ln_pre_w), at<float>(blob_dev, t->off_ln_pre_b), w.x, nullptr, 1, B * L, W, 0};
     const bool fold8 = t->ln_fold && t->weight_format == 1;
     if (t->ln_fold && !fold8) { ln.out_x3 = w.x3; ln.out_part = w.ln_part; }     // straight into the split residual
-    if (int rc = launch_layernorm(ln, st)) return rc;       // ln_pre (ln_fold 0 / FP8: in place, each wave owns its row)
+    return launch_layernorm(ln, st);       // ln_pre (ln_fold 0 / FP8: in place, each wave owns its row)
+}
+
+// arguments of clipmi_encode_image and of its test hook (`who` names the entry point in the message)
+static int check_image_args(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype, int B,
+                            bool have_out, const void* ws_dev, size_t ws_bytes, const char* who) {
+    if (int rc = check_tower(t, 0, who)) return rc;
+    if (!blob_dev || !pixels_dev || !have_out || !ws_dev) return set_err(CLIPMI_EINVAL, "%s: NULL pointer", who);
+    if (B < 1) return set_err(CLIPMI_EINVAL, "%s: B=%d", who, B);
+    if (pix_dtype != CLIPMI_F32 && pix_dtype != CLIPMI_BF16 && pix_dtype != CLIPMI_U8)
+        return set_err(CLIPMI_EINVAL, "%s: pix_dtype %d", who, pix_dtype);
+    const int grid = t->res / t->patch, np = grid * grid;
+    if (np + 1 != t->tokens || t->patch_k % 64 != 0 || t->patch_k < 3 * t->patch * t->patch)
+        return set_err(CLIPMI_EINVAL, "%s: inconsistent tower (res %d patch %d tokens %d patch_k %d)", who, t->res,
+                       t->patch, t->tokens, t->patch_k);
+    const size_t need = clipmi_encode_image_workspace_bytes(t, B);
+    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    return 0;
+}
+
+static int encode_image_impl(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype,
+                             int B, float* out_dev, int normalize, void* ws_dev, size_t ws_bytes, void* stream, GemmProbe* probe) {
+    if (int rc = check_image_args(t, blob_dev, pixels_dev, pix_dtype, B, out_dev != nullptr, ws_dev, ws_bytes, "encode_image")) return rc;
+    Ws w;
+    carve(t, B, ws_dev, ws_bytes, &w);
+    hipStream_t st = as_stream(stream);
+    const int L = t->tokens;
+    if (int rc = embed_image(t, blob_dev, pixels_dev, pix_dtype, B, w, 0, true, st)) return rc;
 #ifdef CLIPMI_DEV
-    if (fold8)     // FP8 tower with folded LayerNorms: the embedded rows' e4m3 image + statistics for the first qkv GEMM
-        if (int rc = launch_rows_mx_stats(w.x, w.x8, w.x8_bs, w.ln_part, B * L, W, st)) return rc;
+    if (t->ln_fold && t->weight_format == 1)     // FP8 tower with folded LayerNorms: the embedded rows' e4m3 image + statistics for the first qkv GEMM
+        if (int rc = launch_rows_mx_stats(w.x, w.x8, w.x8_bs, w.ln_part, B * L, t->width, st)) return rc;
 #endif
     bool pruned = false;
     if (int rc = run_layers(t, blob_dev, w, B, 0, st, probe, &pruned)) return rc;
@@ -431,16 +448,10 @@ extern "C" size_t clipmi_encode_text_workspace_bytes(const clipmi_tower* t, int 
     return carve(t, Q, nullptr, ~(size_t)0, nullptr);
 }
 
-extern "C" int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q,
-                                  float* out_dev, int normalize, void* ws_dev, size_t ws_bytes, void* stream) {
-    if (int rc = check_tower(t, 1, "encode_text")) return rc;
-    if (!blob_dev || !ids_dev || !out_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "encode_text: NULL pointer");
-    if (Q < 1) return set_err(CLIPMI_EINVAL, "encode_text: Q=%d", Q);
-    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
-    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "encode_text: workspace %zu < %zu", ws_bytes, need);
-    Ws w;
-    carve(t, Q, ws_dev, ws_bytes, &w);
-    hipStream_t st = as_stream(stream);
+// The embedding front end of the text tower: token + positional embedding, the EOT rows and, for LN-folded towers, the split
+// rows with their statistics - in one launch where the fused kernel exists. Shared by clipmi_encode_text and
+// clipmi_dbg_embed_text.
+static int embed_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q, const Ws& w, hipStream_t st) {
     const int W = t->width, L = t->tokens;
     const long long n4 = (long long)Q * L * (W / 4);
     const bool fold8_ = t->ln_fold && t->weight_format == 1;
@@ -450,8 +461,7 @@ extern "C" int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev, c
                            at<float>(blob_dev, t->off_tok_emb), at<float>(blob_dev, t->off_pos), w.x3, w.ln_part, w.rowidx, Q, L, W,
                            t->vocab);
         CLIPMI_CHECK_LAUNCH("text_embed_split_kernel");
-        if (int rc = run_layers(t, blob_dev, w, Q, 1, st, nullptr)) return rc;
-        return run_head(t, blob_dev, w, Q, w.rowidx, 1, out_dev, normalize, st);
+        return 0;
     }
     hipLaunchKernelGGL(text_embed_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, st, w.x, ids_dev,
                        at<float>(blob_dev, t->off_tok_emb), at<float>(blob_dev, t->off_pos), Q, L, W, t->vocab);
@@ -466,8 +476,78 @@ extern "C" int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev, c
     if (t->ln_fold) {
         if (int rc = launch_split_stats(w.x, false, w.x3, w.ln_part, Q * L, W, st)) return rc;
     }
+    return 0;
+}
+
+extern "C" int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q,
+                                  float* out_dev, int normalize, void* ws_dev, size_t ws_bytes, void* stream) {
+    if (int rc = check_tower(t, 1, "encode_text")) return rc;
+    if (!blob_dev || !ids_dev || !out_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "encode_text: NULL pointer");
+    if (Q < 1) return set_err(CLIPMI_EINVAL, "encode_text: Q=%d", Q);
+    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
+    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "encode_text: workspace %zu < %zu", ws_bytes, need);
+    Ws w;
+    carve(t, Q, ws_dev, ws_bytes, &w);
+    hipStream_t st = as_stream(stream);
+    if (int rc = embed_text(t, blob_dev, ids_dev, Q, w, st)) return rc;
     if (int rc = run_layers(t, blob_dev, w, Q, 1, st, nullptr)) return rc;
     return run_head(t, blob_dev, w, Q, w.rowidx, 1, out_dev, normalize, st);
+}
+
+// Test hooks of the embedding front ends: the product's own launch sequence (embed_image / embed_text above) in the tower's
+// ordinary workspace, then copies of what it left there, on the same stream. Every output pointer is optional.
+static int copy_out(void* dst, const void* src, size_t bytes, hipStream_t st, const char* who) {
+    if (!dst) return 0;
+    if (hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: hipMemcpyAsync", who);
+    return 0;
+}
+
+extern "C" int clipmi_dbg_embed_image(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype, int B,
+                                      int algo, int with_ln_pre, void* patches_out_dev, float* rows_out_dev, void* x3_out_dev,
+                                      float* part_out_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    const char* who = "dbg_embed_image";
+    if (int rc = check_image_args(t, blob_dev, pixels_dev, pix_dtype, B, true, ws_dev, ws_bytes, who)) return rc;
+    const int W = t->width, L = t->tokens, np = L - 1;
+    if (algo < 0 || algo > 2) return set_err(CLIPMI_EINVAL, "%s: algo %d (0 = by shape, 1 = 128 x 128, 2 = 256 x 256)", who, algo);
+    if (algo == 2 && (W % 256 != 0 || t->patch_k < 128))
+        return set_err(CLIPMI_EINVAL, "%s: algo 2 needs width %% 256 == 0 and patch_k >= 128 (width %d, patch_k %d)", who, W, t->patch_k);
+    // the form the rows have behind ln_pre: split rows + partials (bf16 LN-folded towers) or f32 rows
+    const bool split = with_ln_pre && t->ln_fold && t->weight_format == 0;
+    if (split ? rows_out_dev != nullptr : (x3_out_dev != nullptr || part_out_dev != nullptr))
+        return set_err(CLIPMI_EINVAL, "%s: this tower's rows are %s here", who, split ? "split rows + partials" : "f32 rows");
+    Ws w;
+    carve(t, B, ws_dev, ws_bytes, &w);
+    hipStream_t st = as_stream(stream);
+    if (int rc = embed_image(t, blob_dev, pixels_dev, pix_dtype, B, w, algo, with_ln_pre != 0, st)) return rc;
+    const size_t rows = (size_t)B * L;
+    if (int rc = copy_out(patches_out_dev, w.patches, (size_t)B * np * t->patch_k * 2, st, who)) return rc;
+    if (int rc = copy_out(rows_out_dev, w.x, rows * W * 4, st, who)) return rc;
+    if (int rc = copy_out(x3_out_dev, w.x3, rows * resid_row_bytes(W), st, who)) return rc;
+    return copy_out(part_out_dev, w.ln_part, rows * 2 * (W / 256) * 4, st, who);
+}
+
+extern "C" int clipmi_dbg_embed_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q, float* rows_out_dev,
+                                     void* x3_out_dev, float* part_out_dev, int32_t* rowidx_out_dev, void* ws_dev, size_t ws_bytes,
+                                     void* stream) {
+    const char* who = "dbg_embed_text";
+    if (int rc = check_tower(t, 1, who)) return rc;
+    if (!blob_dev || !ids_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "%s: NULL pointer", who);
+    if (Q < 1) return set_err(CLIPMI_EINVAL, "%s: Q=%d", who, Q);
+    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
+    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    const bool split = t->ln_fold && t->weight_format == 0;
+    if (split ? rows_out_dev != nullptr : (x3_out_dev != nullptr || part_out_dev != nullptr))
+        return set_err(CLIPMI_EINVAL, "%s: this tower's rows are %s", who, split ? "split rows + partials" : "f32 rows");
+    Ws w;
+    carve(t, Q, ws_dev, ws_bytes, &w);
+    hipStream_t st = as_stream(stream);
+    if (int rc = embed_text(t, blob_dev, ids_dev, Q, w, st)) return rc;
+    const int W = t->width;
+    const size_t rows = (size_t)Q * t->tokens;
+    if (int rc = copy_out(rows_out_dev, w.x, rows * W * 4, st, who)) return rc;
+    if (int rc = copy_out(x3_out_dev, w.x3, rows * resid_row_bytes(W), st, who)) return rc;
+    if (int rc = copy_out(part_out_dev, w.ln_part, rows * 2 * (W / 256) * 4, st, who)) return rc;
+    return copy_out(rowidx_out_dev, w.rowidx, (size_t)Q * 4, st, who);
 }
 
 // Measurement hook (bench.py roofline): clipmi_encode_image `reps` times per estimator with HIP events around the launches

@@ -375,10 +375,15 @@ int clipmi_abi_version(void);
 
 /* ---- test/bench hooks: the individual kernels behind encode_*, exported so that parity
  * tests and bench.py can launch and time them one at a time. Not part of the drop-in surface.
+ * (clipmi_dbg_embed_image / clipmi_dbg_embed_text are additions to ABI 8 in the sense of the PNG note above: nothing existing
+ * changes, CLIPMI_ABI_VERSION stays 8.)
  */
 /* C[M][N] = A[M][K](bf16) . W[N][K]^T(bf16) with fused epilogue `epi`:
  *   0: out bf16 = acc + bias        1: out bf16 = quickgelu(acc + bias)
- *   2: out f32 += acc + bias (residual, in place)    3: out f32 = acc (bias may be NULL)  */
+ *   2: out f32 += acc + bias (residual, in place)    3: out f32 = acc (bias may be NULL)
+ * `epi` bits 8-10 force a kernel (1 = 128 x 128 tiles, 2 = 256 x 256, 3 = the persistent 256 x 256 kernel). Epilogue 4 (the patch
+ * GEMM: row b*np + p goes to row b*L + 1 + p with the positional row 1 + p added) needs a tower's geometry and is refused here; it
+ * is tested in its three kernels through clipmi_dbg_embed_image below (tests/test_embed_gpu.py); 5-8 have hooks of their own. */
 int clipmi_dbg_gemm_bf16(const void* a_dev, const void* w_dev, const float* bias_dev,
                          void* out_dev, int M, int N, int K, int epi, void* stream);
 /* rows of f32 x[M][W] -> LayerNorm(eps 1e-5) -> bf16 (out_bf16 != 0) or f32 */
@@ -452,6 +457,27 @@ int clipmi_dbg_gemm_ln_leaf(const void* x3_dev, const void* wg_dev, const float*
                             const float* leaf_dev, void* out_dev, int M, int N, int K, int epi, void* stream);
 int clipmi_dbg_gemm_resid_ln(const void* a_dev, const void* w_dev, const float* bias_dev, void* x3_dev, float* part_dev,
                              float* tmp_dev, int M, int N, int K, int algo, void* stream);
+
+/* The embedding front ends of the two towers - everything in front of the first block - as clipmi_encode_image /
+ * clipmi_encode_text enqueue them (the same function runs in both), in the tower's ordinary workspace
+ * (clipmi_encode_*_workspace_bytes), followed by copies of the results on the same stream. Every `*_out_dev` pointer may be NULL.
+ * clipmi_dbg_embed_image: patchify (pix_dtype as clipmi_encode_image) -> patch GEMM with the positional rows (`algo`: 0 = the
+ * product's choice by shape, 1 / 2 = force the 128 x 128 / 256 x 256 kernel; 2 needs width % 256 == 0) -> class-token rows ->
+ * ln_pre when with_ln_pre != 0.
+ *   patches_out_dev : bf16 [B*np][patch_k], the patch matrix (np = tokens - 1)
+ *   rows_out_dev    : f32 [B*L][W] - with_ln_pre == 0: the rows in front of ln_pre; with_ln_pre != 0: the rows behind it, for
+ *                     towers that keep f32 rows there (ln_fold 0, FP8 weights)
+ *   x3_out_dev, part_out_dev : with_ln_pre != 0 and a bf16 LN-folded tower: the split rows [B*L][3 W bytes] and their statistics
+ *                     partials f32 [B*L][W/256][2] (clipmi_dbg_split_stats' layout)
+ * An output the tower does not produce in that form (rows_out_dev for split rows and the reverse) is CLIPMI_EINVAL.
+ * clipmi_dbg_embed_text: token + positional embedding and the EOT rows; rows_out_dev f32 [Q*L][W] (towers without folded
+ * LayerNorms) or x3_out_dev + part_out_dev (LN-folded towers), rowidx_out_dev int32 [Q] = q*L + first argmax of ids[q][:]. */
+int clipmi_dbg_embed_image(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype, int B,
+                           int algo, int with_ln_pre, void* patches_out_dev, float* rows_out_dev, void* x3_out_dev,
+                           float* part_out_dev, void* ws_dev, size_t ws_bytes, void* stream);
+int clipmi_dbg_embed_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q, float* rows_out_dev,
+                          void* x3_out_dev, float* part_out_dev, int32_t* rowidx_out_dev, void* ws_dev, size_t ws_bytes,
+                          void* stream);
 
 /* clipmi_encode_image `reps` times with HIP events around every launch of the GEMM whose
  * epilogue is `probe_epi` (1 = MLP c_fc + QuickGELU), on `stream`; synchronises;
