@@ -1,4 +1,6 @@
-// png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8).
+// png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8), and
+// the file's own-mode pixels for alpha, palette and low-depth files (clipmi_png_decode_px8: the same inflate and Adler-32
+// kernels, png_unfilter_px_kernel with a filter unit of 1, 2 or 4 bytes and an "alpha" or "index" store).
 // The host (cli-p_amd/png_parse.py) lets through 8-bit grey and RGB files that are not interlaced and hands over the DEFLATE
 // stream behind the zlib header. Three kernels:
 //   png_inflate_kernel   one wave per image: RFC 1951 inflate into the workspace's scanline buffer, with zlib's own table checks
@@ -29,6 +31,28 @@ constexpr unsigned PNG_FLUSH = 8192;        // flush to HBM from this many waiti
 constexpr int PNG_LIT_BITS = 10, PNG_DIST_BITS = 9, PNG_CL_BITS = 7;
 constexpr int PNG_PAD = 16;                 // zero bytes behind every stream
 constexpr int PNG_MAX_WIDTH = 16384;        // the unfilter kernel holds one row in LDS (48 KiB); png_parse.MAX_WIDTH
+constexpr int PNG_MAX_ROW = 49152;          // ... that many bytes: what bounds the rows of clipmi_png_decode_px8; png_parse.MAX_ROW_BYTES
+
+// The bytes of one scanline without its filter byte, and whether the record is one its entry takes. modes == 0
+// (clipmi_png_decode_rgb8): 8-bit grey or RGB, `reserved` not looked at. modes == 1 (clipmi_png_decode_px8): reserved[0] =
+// colour type << 8 | bit depth, reserved[1] = palette entries; RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4.
+__device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int64_t& row) {
+    if (im.width < 1 || im.width > PNG_MAX_WIDTH) return false;
+    if (!modes) {
+        row = (int64_t)im.width * im.channels;
+        return im.channels == 1 || im.channels == 3;
+    }
+    const int ctype = im.reserved[0] >> 8, depth = im.reserved[0] & 255;
+    const bool low = depth == 1 || depth == 2 || depth == 4;
+    int samples;
+    if (ctype == 6 && depth == 8) samples = 4;
+    else if (ctype == 4 && depth == 8) samples = 2;
+    else if (ctype == 3 && (low || depth == 8) && im.reserved[1] >= 1 && im.reserved[1] <= (1 << depth)) samples = 1;
+    else if (ctype == 0 && low) samples = 1;
+    else return false;
+    row = ((int64_t)im.width * samples * depth + 7) >> 3;
+    return im.channels == samples && row <= PNG_MAX_ROW;
+}
 
 __constant__ unsigned char png_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
 
@@ -133,7 +157,7 @@ struct PngBits {
 // barriers sit in uniform control flow; only the copies into the ring and out of it are spread over the lanes.
 __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char* __restrict__ streams, const PngImage* __restrict__ images,
                                                             int64_t total_raw, int64_t max_raw, unsigned char* __restrict__ rawbuf,
-                                                            unsigned* __restrict__ adler_want, int32_t* __restrict__ status) {
+                                                            unsigned* __restrict__ adler_want, int32_t* __restrict__ status, int modes) {
     __shared__ __attribute__((aligned(16))) unsigned char ring[PNG_RING];
     __shared__ unsigned short lit_lut[1 << PNG_LIT_BITS], dist_lut[1 << PNG_DIST_BITS], cl_lut[1 << PNG_CL_BITS];
     __shared__ unsigned short lit_sorted[288], dist_sorted[32], cl_sorted[19];
@@ -141,8 +165,10 @@ __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char*
     __shared__ unsigned char lens[320], cl_lens[19];
     const int lane = threadIdx.x;
     const PngImage im = images[blockIdx.x];
-    const int64_t raw_bytes64 = (int64_t)im.height * (1 + (int64_t)im.width * im.channels);
-    if (im.width < 1 || im.width > PNG_MAX_WIDTH || im.height < 1 || (im.channels != 1 && im.channels != 3) || im.stream_bytes < 0 || im.stream_off < 0 ||
+    int64_t row_bytes = 0;
+    const bool known = png_row_bytes(im, modes, row_bytes);
+    const int64_t raw_bytes64 = (int64_t)im.height * (1 + row_bytes);
+    if (!known || im.height < 1 || im.stream_bytes < 0 || im.stream_off < 0 ||
         raw_bytes64 > 0x7fffffffLL || raw_bytes64 > max_raw || im.raw_off < 0 || (im.raw_off & 15) ||
         im.raw_off + raw_bytes64 > total_raw) {
         if (lane == 0) status[blockIdx.x] = 1;
@@ -337,10 +363,13 @@ __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char*
 // (`prev`, PNG_MAX_WIDTH pixels: the host parser refuses wider files) and lane 0 of the next band takes them from there, so
 // the kernel never reads back what it stored to HBM. Within a band lane 63 writes word index t - 63 while lane 0 reads index
 // t: every word is read before it is overwritten, and the barrier between two bands orders the rest.
-template <int CH>
-__device__ void png_unfilter_image(const unsigned char* __restrict__ raw, unsigned char* __restrict__ out, unsigned* prev, int w, int h,
-                                   int lane, bool& bad) {
-    constexpr int PX = 4, NW = CH;                      // 4 pixels a step: CH words of 4 bytes
+// The filter works on units of CH bytes: CH = 3 or 1 for the 8-bit RGB and grey rows of clipmi_png_decode_rgb8; for
+// clipmi_png_decode_px8 4 (RGBA), 2 (grey + alpha) or 1 (8-bit palette rows and every depth below 8, which PNG filters byte by
+// byte). `w` counts units. What becomes of a step's finished bytes is the store's business: store.put(row, x0, words) gets the
+// units x0 .. x0 + 3 of the row (those below w are valid), packed as they lie in the file.
+template <int CH, class Store>
+__device__ void png_unfilter_image(const unsigned char* __restrict__ raw, Store& store, unsigned* prev, int w, int h, int lane, bool& bad) {
+    constexpr int PX = 4, NW = CH;                      // 4 units a step: CH words of 4 bytes
     const int64_t stride = 1 + (int64_t)w * CH;
     const int steps = (w + PX - 1) / PX;
     for (int r0 = 0; r0 < h; r0 += PNG_T) {
@@ -349,7 +378,6 @@ __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, unsign
         int ft = active ? raw[row * stride] : 0;
         if (ft > 4) { bad = true; ft = 0; }
         const unsigned char* src = raw + row * stride + 1;
-        unsigned char* drow = out + (int64_t)row * w * 3;
         unsigned res[NW];
         int a[CH], c[CH];
 #pragma unroll
@@ -388,12 +416,8 @@ __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, unsign
                     c[k] = b;
                     a[k] = v;
                     res[q >> 2] |= (unsigned)v << (8 * (q & 3));
-                    const int x = x0 + q / CH;
-                    if (x < w) {
-                        if (CH == 3) drow[(int64_t)x * 3 + k] = (unsigned char)v;
-                        else drow[(int64_t)x * 3] = drow[(int64_t)x * 3 + 1] = drow[(int64_t)x * 3 + 2] = (unsigned char)v;
-                    }
                 }
+                store.put(row, x0, res);
                 if (lane == PNG_T - 1) {
 #pragma unroll
                     for (int k = 0; k < NW; k++) prev[m * NW + k] = res[k];
@@ -404,6 +428,25 @@ __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, unsign
     }
 }
 
+// rows of width * 3 RGB bytes, grey replicated: what clipmi_png_decode_rgb8 leaves
+template <int CH>
+struct PngRgbStore {
+    unsigned char* out;
+    int w;
+    __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
+        unsigned char* drow = out + (int64_t)row * w * 3;
+#pragma unroll
+        for (int q = 0; q < 4 * CH; q++) {
+            const int x = x0 + q / CH, k = q % CH;
+            const unsigned char v = (unsigned char)(res[q >> 2] >> (8 * (q & 3)));
+            if (x < w) {
+                if (CH == 3) drow[(int64_t)x * 3 + k] = v;
+                else drow[(int64_t)x * 3] = drow[(int64_t)x * 3 + 1] = drow[(int64_t)x * 3 + 2] = v;
+            }
+        }
+    }
+};
+
 __global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
                                                              unsigned char* __restrict__ out, int32_t* status) {
     __shared__ unsigned prev[(PNG_MAX_WIDTH + 3) / 4 * 3];      // a band's last row: 4 pixels = 3 words (RGB) or 1 word (grey)
@@ -411,9 +454,77 @@ __global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __r
     const PngImage im = images[blockIdx.x];            // (width <= PNG_MAX_WIDTH: png_inflate_kernel gave status 1 otherwise)
     const int lane = threadIdx.x;
     bool bad = false;
-    if (im.channels == 3) png_unfilter_image<3>(rawbuf + im.raw_off, out + im.out_off, prev, im.width, im.height, lane, bad);
-    else png_unfilter_image<1>(rawbuf + im.raw_off, out + im.out_off, prev, im.width, im.height, lane, bad);
+    if (im.channels == 3) {
+        PngRgbStore<3> store{out + im.out_off, im.width};
+        png_unfilter_image<3>(rawbuf + im.raw_off, store, prev, im.width, im.height, lane, bad);
+    } else {
+        PngRgbStore<1> store{out + im.out_off, im.width};
+        png_unfilter_image<1>(rawbuf + im.raw_off, store, prev, im.width, im.height, lane, bad);
+    }
     if (__syncthreads_or(bad ? 1 : 0) && lane == 0) status[blockIdx.x] = 3;
+}
+
+// What clipmi_png_decode_px8 leaves, by colour type and depth. "alpha": rows of width * 4 bytes R G B A - RGBA as it is, grey +
+// alpha as L L L A, grey at depth 2 / 4 as v*85 / v*17 three times and 255 (Pillow opens those files as L with these values).
+// "index": rows of width bytes, one unpacked sample each, for palette files and 1-bit grey; the most significant bits of a
+// byte come first, the padding bits at a row's end are dropped, and a sample >= `entries` sets over (status 5).
+struct PngPxStore {
+    unsigned char* out;
+    int width, ctype, depth, entries;
+    bool over;
+    __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
+        if (ctype == 6 || ctype == 4) {
+            unsigned* drow = reinterpret_cast<unsigned*>(out) + (int64_t)row * width;    // (out_off is a multiple of 16)
+#pragma unroll
+            for (int p = 0; p < 4; p++) {
+                if (x0 + p >= width) break;
+                unsigned v;
+                if (ctype == 6) v = res[p];
+                else {
+                    const unsigned la = res[p >> 1] >> (16 * (p & 1));
+                    v = (la & 255u) * 0x010101u | (la & 0xff00u) << 16;
+                }
+                drow[x0 + p] = v;
+            }
+            return;
+        }
+        const int per = 8 / depth;                                  // samples in a byte: 1, 2, 4 or 8
+        const unsigned mask = (1u << depth) - 1u;
+        for (int q = 0; q < 4; q++) {                               // the step's 4 bytes (ctype 0 and 3 filter with unit 1)
+            const unsigned byte = (res[0] >> (8 * q)) & 255u;
+            const int64_t px0 = ((int64_t)x0 + q) * per;
+            for (int s = 0; s < per; s++) {
+                const int64_t px = px0 + s;
+                if (px >= width) return;
+                const unsigned v = (byte >> (8 - depth * (s + 1))) & mask;
+                if (ctype == 0 && depth != 1) {
+                    reinterpret_cast<unsigned*>(out)[(int64_t)row * width + px] = v * (depth == 2 ? 85u : 17u) * 0x010101u | 0xff000000u;
+                } else {
+                    if ((int)v >= entries) over = true;
+                    out[(int64_t)row * width + px] = (unsigned char)v;
+                }
+            }
+        }
+    }
+};
+
+__global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
+                                                                unsigned char* __restrict__ out, int32_t* status) {
+    __shared__ unsigned prev[PNG_MAX_ROW / 4];         // a band's last row: PNG_MAX_ROW bytes (png_inflate_kernel refused longer rows)
+    if (status[blockIdx.x] != 0) return;
+    const PngImage im = images[blockIdx.x];
+    const int lane = threadIdx.x;
+    int64_t row_bytes = 0;
+    if (!png_row_bytes(im, 1, row_bytes)) return;      // (not reached: png_inflate_kernel gave status 1)
+    const int ctype = im.reserved[0] >> 8, depth = im.reserved[0] & 255;
+    PngPxStore store{out + im.out_off, im.width, ctype, depth, ctype == 3 ? im.reserved[1] : 2, false};
+    const unsigned char* raw = rawbuf + im.raw_off;
+    bool bad = false;
+    if (ctype == 6) png_unfilter_image<4>(raw, store, prev, (int)row_bytes / 4, im.height, lane, bad);
+    else if (ctype == 4) png_unfilter_image<2>(raw, store, prev, (int)row_bytes / 2, im.height, lane, bad);
+    else png_unfilter_image<1>(raw, store, prev, (int)row_bytes, im.height, lane, bad);
+    const int is_bad = __syncthreads_or(bad ? 1 : 0), is_over = __syncthreads_or(store.over ? 1 : 0);
+    if (lane == 0 && (is_bad || is_over)) status[blockIdx.x] = is_bad ? 3 : 5;
 }
 
 // ---- Adler-32 of the scanlines. With d_0 .. d_{n-1} the bytes: s1 = 1 + sum d_i, s2 = n + sum (n - i) d_i (mod 65521), which is
@@ -423,11 +534,13 @@ constexpr int PNG_ADLER_T = 256;
 constexpr unsigned long long PNG_ADLER_MOD = 65521ull;
 
 __global__ void __launch_bounds__(PNG_ADLER_T) png_adler_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
-                                                                const unsigned* __restrict__ adler_want, int32_t* status) {
+                                                                const unsigned* __restrict__ adler_want, int32_t* status, int modes) {
     __shared__ unsigned long long red1[PNG_ADLER_T], red2[PNG_ADLER_T];
     if (status[blockIdx.x] != 0) return;
     const PngImage im = images[blockIdx.x];
-    const unsigned n = (unsigned)((int64_t)im.height * (1 + (int64_t)im.width * im.channels));
+    int64_t row_bytes = 0;
+    png_row_bytes(im, modes, row_bytes);
+    const unsigned n = (unsigned)((int64_t)im.height * (1 + row_bytes));
     const unsigned char* raw = rawbuf + im.raw_off;
     const int tid = threadIdx.x;
     unsigned long long s1 = 0, s2 = 0;
@@ -477,17 +590,17 @@ extern "C" int64_t clipmi_png_workspace_bytes(int n, int64_t total_raw_bytes) {
     return (int64_t)align_up((size_t)total_raw_bytes, 256) + (int64_t)align_up((size_t)n * sizeof(unsigned), 256);
 }
 
-extern "C" int clipmi_png_decode_rgb8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes,
-                                      int64_t max_raw_bytes, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
-                                      void* stream) {
+// the three launches behind both entries; modes: 0 clipmi_png_decode_rgb8, 1 clipmi_png_decode_px8
+static int png_decode(const char* who, int modes, const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes,
+                      int64_t max_raw_bytes, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
     static_assert(sizeof(PngImage) == sizeof(clipmi_png_image) && sizeof(PngImage) == 48, "clipmi_png_image layout");
     if (!streams_dev || !images_dev || !out_dev || !status_dev || !ws_dev || n < 1 || total_raw_bytes < 1 || max_raw_bytes < 1 ||
         max_raw_bytes > total_raw_bytes || max_raw_bytes > 0x7fffffffLL || (reinterpret_cast<uintptr_t>(ws_dev) & 15))
-        return set_err(CLIPMI_EINVAL, "png_decode_rgb8: bad arguments");
+        return set_err(CLIPMI_EINVAL, "%s: bad arguments", who);
     if (n > 0x7fffffff / 2)
-        return set_err(CLIPMI_EINVAL, "png_decode_rgb8: batch too large for one launch");
+        return set_err(CLIPMI_EINVAL, "%s: batch too large for one launch", who);
     if (ws_bytes < clipmi_png_workspace_bytes(n, total_raw_bytes))
-        return set_err(CLIPMI_EWORKSPACE, "png_decode_rgb8: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+        return set_err(CLIPMI_EWORKSPACE, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
                        (long long)clipmi_png_workspace_bytes(n, total_raw_bytes));
     hipStream_t st = as_stream(stream);
     Arena ar(ws_dev, (size_t)ws_bytes);
@@ -495,12 +608,36 @@ extern "C" int clipmi_png_decode_rgb8(const void* streams_dev, const void* image
     unsigned* want = ar.take<unsigned>((size_t)n);
     const PngImage* images = static_cast<const PngImage*>(images_dev);
     hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, static_cast<const unsigned char*>(streams_dev), images,
-                       total_raw_bytes, max_raw_bytes, raw, want, status_dev);
+                       total_raw_bytes, max_raw_bytes, raw, want, status_dev, modes);
     CLIPMI_CHECK_LAUNCH("png_inflate_kernel");
-    hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw, static_cast<unsigned char*>(out_dev),
-                       status_dev);
-    CLIPMI_CHECK_LAUNCH("png_unfilter_kernel");
-    hipLaunchKernelGGL(png_adler_kernel, dim3((unsigned)n), dim3(PNG_ADLER_T), 0, st, images, raw, want, status_dev);
+    if (modes) {
+        hipLaunchKernelGGL(png_unfilter_px_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw, static_cast<unsigned char*>(out_dev),
+                           status_dev);
+        CLIPMI_CHECK_LAUNCH("png_unfilter_px_kernel");
+    } else {
+        hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw, static_cast<unsigned char*>(out_dev),
+                           status_dev);
+        CLIPMI_CHECK_LAUNCH("png_unfilter_kernel");
+    }
+    hipLaunchKernelGGL(png_adler_kernel, dim3((unsigned)n), dim3(PNG_ADLER_T), 0, st, images, raw, want, status_dev, modes);
     CLIPMI_CHECK_LAUNCH("png_adler_kernel");
     return 0;
+}
+
+extern "C" int clipmi_png_decode_rgb8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes,
+                                      int64_t max_raw_bytes, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                      void* stream) {
+    return png_decode("png_decode_rgb8", 0, streams_dev, images_dev, n, total_raw_bytes, max_raw_bytes, out_dev, status_dev, ws_dev,
+                      ws_bytes, stream);
+}
+
+extern "C" int64_t clipmi_png_px8_workspace_bytes(int n, int64_t total_raw_bytes) {
+    return clipmi_png_workspace_bytes(n, total_raw_bytes);
+}
+
+extern "C" int clipmi_png_decode_px8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes,
+                                     int64_t max_raw_bytes, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                     void* stream) {
+    return png_decode("png_decode_px8", 1, streams_dev, images_dev, n, total_raw_bytes, max_raw_bytes, out_dev, status_dev, ws_dev,
+                      ws_bytes, stream);
 }

@@ -109,6 +109,28 @@ def resize_plan(w, h, n_px):
     return plan
 
 
+def nearest_window(in_size, out_size, o0, n_out):
+    """Pillow's NEAREST resize (ImagingScaleAffine, what Image.resize does to palette and 1-bit images whatever filter is asked
+    for): the source index of outputs o0 .. o0 + n_out - 1 of an axis scaled from in_size to out_size. The source coordinate starts
+    at half a step and grows by SEQUENTIAL float64 additions of in_size / out_size, not by multiplication. -> int32 [n_out]"""
+    step = in_size / out_size
+    at = np.cumsum(np.concatenate([[0.5 * step], np.full(out_size - 1, step)]))       # (cumsum adds in order)
+    return np.minimum(at[o0:o0 + n_out].astype(np.int64), in_size - 1).astype(np.int32)
+
+
+def nearest_plan(w, h, n_px):
+    """resize_plan for images Pillow resizes with NEAREST (modes P and 1): the same sizes and crop window; in place of the
+    coefficient blocks the source column of each of the n_px output columns ("hcoef") and the source row of each output row
+    ("vcoef"), what clipmi_nearest_crop_p8 takes; r0 / nrows span the rows the window reads."""
+    plan = dict(resize_plan(w, h, n_px))
+    plan["hcoef"] = nearest_window(w, plan["nw"], plan["left"], n_px)
+    plan["vcoef"] = nearest_window(h, plan["nh"], plan["top"], n_px)
+    plan["hk"] = plan["vk"] = 0
+    plan["r0"] = int(plan["vcoef"].min())
+    plan["nrows"] = int(plan["vcoef"].max()) - plan["r0"] + 1
+    return plan
+
+
 PLAN_INTS = 16            # header of a full-size image's region: w h r0 nrows need_h need_v left top hk vk n_hcoef n_vcoef
 
 
@@ -148,8 +170,8 @@ JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then w
 class HDR:
     """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, pipeline.py reads them
     through these names); [24..31] are zero. Offsets count bytes from the region's start."""
-    KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE or KIND_PNG
-    NCOMP, HS, VS = 3, 4, 5   # components (PNG: channels), luma sampling factors (PNG: 0 0)
+    KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA or KIND_PNG_INDEX
+    NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
     COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
     BLOCKS = 7                # 8 x 8 blocks of the image (PNG: 0)
     PLAN = slice(8, 16)       # resize_plan's r0 nrows need_h need_v left top hk vk: the order of resize.JOB and of decode_full's header
@@ -159,9 +181,12 @@ class HDR:
     RESTART_INTERVAL, N_INTERVALS, INTERVALS_OFF, STUFFED = 20, 21, 22, 23     # baseline: DRI, number of intervals, offset of their
     #                                                                 uint32 byte offsets into the segment, 1: the segment keeps its stuffing
     TABLES_OFF, N_TABLES = 20, 21                                   # progressive: the scans' Huffman tables
+    DEPTH, CTYPE, ENTRIES = 20, 21, 22                              # KIND_PNG_ALPHA, KIND_PNG_INDEX: bit depth, colour type, palette
+    #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF
 
 
 KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
+KIND_PNG_ALPHA, KIND_PNG_INDEX = 7, 8                     # png_parse's kinds "alpha" and "index" (clipmi_png_decode_px8)
 _plans = {}
 
 
@@ -172,13 +197,13 @@ def _contents(path, data):
     return data
 
 
-def _plan(w, h, n_px):
-    key = (w, h, n_px)
+def _plan(w, h, n_px, nearest=False):
+    key = (w, h, n_px, nearest)
     plan = _plans.get(key)
     if plan is None:
         if len(_plans) > 256:
             _plans.clear()
-        plan = _plans[key] = resize_plan(w, h, n_px)
+        plan = _plans[key] = (nearest_plan if nearest else resize_plan)(w, h, n_px)
     return plan
 
 
@@ -284,23 +309,45 @@ PNG_MAX_RAW = 16 << 20      # filtered scanlines of a file the device takes: one
                             # DESIGN 4.9), so a larger file would hold up its batch on the side stream; Pillow decodes those
 
 
-def stage_png(path, n_px, region, data=None):
+def stage_png(path, n_px, region, data=None, modes=False):
     """For the PNG decode on the device (csrc/png.hip): read the file, walk its chunks (png_parse.parse) and lay out in `region`
     [header | resize plan coefficients | DEFLATE stream without the zlib header, 16-byte aligned and followed by >= 16 zero
     bytes]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises png_parse.Unsupported for files
     Pillow has to decode, among them files of more than PNG_MAX_RAW bytes of scanlines.
+    modes: the request allows alpha, palette and low-depth files (png_parse.parse(modes=True)). Their regions have the same
+    layout under the kinds KIND_PNG_ALPHA and KIND_PNG_INDEX (HDR.KIND), with depth, colour type and palette entries in the
+    header (HDR.DEPTH ..); an index file's palette lies at JPEG_TABLES_OFF and its "coefficient blocks" are nearest_plan's two
+    tables. Without it such a file raises Unsupported, as ever.
     data: the file's contents, when the caller has read them."""
-    p = png_parse.parse(_contents(path, data))
+    p = png_parse.parse(_contents(path, data), modes=modes)
     if p.raw_bytes() > PNG_MAX_RAW:
         raise png_parse.Unsupported("more than PNG_MAX_RAW bytes of scanlines")
-    plan = _plan(p.width, p.height, n_px)
+    plan = _plan(p.width, p.height, n_px, nearest=p.kind == "index")
     o_stream = _data_off(plan)
     total = _stream_end(o_stream, len(p.stream))
     if total > region.size:
         return _no_room(p, total)
-    _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan)
+    if p.kind == "rgb":
+        _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan)
+    else:
+        _write_head(region, KIND_PNG_INDEX if p.kind == "index" else KIND_PNG_ALPHA, p, (p.channels, 0, 0), len(p.stream), 0, plan,
+                    (p.depth, p.ctype, p.n_entries, 0))
+        if p.kind == "index":
+            region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 768] = p.palette.reshape(-1)
     _write_stream(region, o_stream, p.stream)
     return p.width, p.height, total
+
+
+def _stage_png_kind(kind):
+    """stage_png(modes=True) for the files of one of the new kinds only: a launch group holds one kind (PARSED)"""
+    def stage(path, n_px, region, data=None):
+        data = _contents(path, data)
+        ctype, depth = data[25], data[24]                         # IHDR, before any work: which kind the file would be
+        index = ctype == 3 or (ctype == 0 and depth == 1)
+        if (ctype, depth) in ((0, 8), (2, 8)) or index != (kind == KIND_PNG_INDEX):
+            raise png_parse.Unsupported("a file of another kind")
+        return stage_png(path, n_px, region, data, modes=True)
+    return stage
 
 
 # One way a file can sit in a region of the big segment for the device. kind: the worker's reply tag (b"%d" % kind), HDR.KIND and
@@ -312,7 +359,10 @@ FULL_SIZE = Kind(2, 1, None, decode_full, None, None)         # decoded pixels a
 # the parsed files, in the order serve() tries them and the device's statuses are laid out (pipeline.device_stage)
 PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
           Kind(KIND_PROGRESSIVE, 4, "jpeg", stage_jpeg_progressive, "jpeg_progressive_files", "staged"),
-          Kind(KIND_PNG, 8, "png", stage_png, "png_files", "decoded"))
+          Kind(KIND_PNG, 8, "png", stage_png, "png_files", "decoded"),
+          # alpha, palette and low-depth PNG files: one bit of the mode for both kinds, one stats key
+          Kind(KIND_PNG_ALPHA, 16, "png", _stage_png_kind(KIND_PNG_ALPHA), "png_mode_files", "decoded"),
+          Kind(KIND_PNG_INDEX, 16, "png", _stage_png_kind(KIND_PNG_INDEX), "png_mode_files", "decoded"))
 PARSED_KINDS = frozenset(k.kind for k in PARSED)
 REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + PARSED)
 WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
@@ -362,7 +412,7 @@ def serve(fin, fout):
                 full = None
                 # the file is read once and its first bytes choose the parser (a PNG file used to be read by each of them in turn)
                 data = magic = None
-                if mode & sum(k.bit for k in PARSED):
+                if any(mode & k.bit for k in PARSED):
                     try:
                         data = _contents(fname, None)
                     except OSError:                            # unreadable: Pillow reports it

@@ -14,7 +14,7 @@ import torch
 
 
 # the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
-from .decode_worker import (FULL_SIZE, HDR, KIND_BASELINE, KIND_PNG, KIND_PROGRESSIVE, PARSED, PARSED_KINDS, PLAN_INTS,  # noqa: E402,F401
+from .decode_worker import (FULL_SIZE, HDR, KIND_BASELINE, KIND_PNG, KIND_PNG_ALPHA, KIND_PNG_INDEX, KIND_PROGRESSIVE, PARSED, PARSED_KINDS, PLAN_INTS,  # noqa: E402,F401
                             REGION_TAGS, WANTED_TAG, load_uint8)
 
 
@@ -251,10 +251,10 @@ def _headers(bigview, n, cap, slots):
     return hd[slots].astype(np.int64)
 
 
-def _resize_jobs(src_off, w, h, plan, n_hcoef, hcoef_off, out_index, n_px):
+def _resize_jobs(src_off, w, h, plan, n_hcoef, hcoef_off, out_index, n_px, px=3):
     """clipmi_resize_job records. plan: [n][8] r0 nrows need_h need_v left top hk vk (HDR.PLAN); hcoef_off: where each image's
     horizontal coefficient block starts, in ints from the segment's start - the vertical block follows it; the rows the
-    vertical pass leaves for the horizontal one lie back to back in the scratch buffer (tmp_off)."""
+    vertical pass leaves for the horizontal one lie back to back in the scratch buffer (tmp_off), px bytes a pixel."""
     from .resize import JOB
     jobs = np.zeros(len(w), dtype=JOB)
     jobs["src_off"], jobs["w"], jobs["h"], jobs["out_index"] = src_off, w, h, out_index
@@ -262,19 +262,29 @@ def _resize_jobs(src_off, w, h, plan, n_hcoef, hcoef_off, out_index, n_px):
         jobs[f] = plan[:, k]
     jobs["hcoef_off"] = hcoef_off
     jobs["vcoef_off"] = jobs["hcoef_off"] + n_hcoef
-    tmp = plan[:, 1] * n_px * 3
+    tmp = plan[:, 1] * n_px * px
     jobs["tmp_off"] = np.cumsum(tmp) - tmp
     return jobs
 
 
-def _decoded_jobs(hd, cap, slots, comp, n_px):
-    """-> (the resize jobs of parsed files whose decoded RGB rows lie back to back, 16-byte aligned, in the decoder's output: the
-    order of `slots`; their offsets there; their sizes)"""
+def _decoded_jobs(hd, cap, slots, comp, n_px, px=3):
+    """-> (the transform's jobs for parsed files whose decoded rows, px bytes a pixel, lie back to back, 16-byte aligned, in the
+    decoder's output: the order of `slots`; their offsets there; their sizes). px 3 and 4: clipmi_resize_job records; px 1 (index
+    rows): clipmi_nearest_job records that point at the palette and the two tables in the file's region."""
     w, h = hd[:, HDR.W], hd[:, HDR.H]
-    out_sz = (w * h * 3 + 15) // 16 * 16
+    out_sz = (w * h * px + 15) // 16 * 16
     out_off = np.cumsum(out_sz) - out_sz
+    if px == 1:
+        from .decode_worker import JPEG_TABLES_OFF
+        from .resize import NEAREST_JOB
+        jobs = np.zeros(len(w), dtype=NEAREST_JOB)
+        jobs["src_off"], jobs["w"], jobs["h"], jobs["out_index"] = out_off, w, h, np.asarray(comp)[slots]
+        jobs["pal_off"] = slots * cap + JPEG_TABLES_OFF
+        jobs["col_off"] = (slots * cap + hd[:, HDR.COEF_OFF]) // 4
+        jobs["row_off"] = jobs["col_off"] + hd[:, HDR.N_HCOEF]
+        return jobs, out_off, out_sz
     jobs = _resize_jobs(out_off, w, h, hd[:, HDR.PLAN], hd[:, HDR.N_HCOEF], (slots * cap + hd[:, HDR.COEF_OFF]) // 4,
-                        np.asarray(comp)[slots], n_px)
+                        np.asarray(comp)[slots], n_px, px)
     return jobs, out_off, out_sz
 
 
@@ -361,6 +371,24 @@ def png_records(bigview, n, cap, slots, comp, n_px):
     return recs, jobs, out_sz, raw_sz
 
 
+def _png_mode_records(px):
+    """png_records for the files of one of png_parse's other kinds (decode_worker.stage_png(modes=True) wrote the regions): px bytes
+    per decoded pixel - 4 "alpha", 1 "index"; the records carry colour type, depth and palette entries for clipmi_png_decode_px8"""
+    def records(bigview, n, cap, slots, comp, n_px):
+        from . import png as P
+        slots = np.asarray(slots, dtype=np.int64)
+        hd = _headers(bigview, n, cap, slots)
+        jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px, px)
+        w, h, ch, depth = hd[:, HDR.W], hd[:, HDR.H], hd[:, HDR.NCOMP], hd[:, HDR.DEPTH]
+        recs = np.zeros(len(slots), dtype=P.IMAGE)
+        raw_sz = (h * (1 + (w * ch * depth + 7) // 8) + 15) // 16 * 16
+        recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(raw_sz) - raw_sz, out_off
+        recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = hd[:, HDR.COUNT], w, h, ch
+        recs["reserved"] = np.stack([hd[:, HDR.CTYPE] << 8 | depth, hd[:, HDR.ENTRIES]], axis=1)
+        return recs, jobs, out_sz, raw_sz
+    return records
+
+
 def _groups(need, budget):
     """[lo, hi) ranges of consecutive files whose `need` sums stay within the budget: a group closes when the next file would
     exceed it, and a file above the budget is a group of its own. No files, no group."""
@@ -410,18 +438,34 @@ def _png_group(L, r):
         L.clipmi_png_decode_rgb8(base, sb, len(recs), total, most, rgb, status, ws, ws_bytes, stream))
 
 
+def _png_mode_group(L, r):
+    recs, jobs, out_sz, raw_sz = r
+    total, most = int(raw_sz.sum()), int(raw_sz.max())
+    ws_bytes = int(L.clipmi_png_px8_workspace_bytes(len(recs), total))
+    return [recs, jobs], out_sz, ws_bytes, "clipmi_png_decode_px8", lambda base, sb, offs, rgb, status, ws, stream: (
+        L.clipmi_png_decode_px8(base, sb, len(recs), total, most, rgb, status, ws, ws_bytes, stream))
+
+
 # What differs between the parsed kinds in device_stage, by decode_worker.Kind.kind:
 #   the records function |
 #   the bytes of HBM a file's decoder needs beside its RGB rows and the resize's rows, out of the headers (coefficients; scanlines) |
 #   (library, what the records function returned) -> (the arrays that travel to the device, 16-byte aligned in this order, the
-#   resize jobs last; output bytes per image; workspace bytes; the decode entry's name; its call, given where things lie)
-_FORMATS = {KIND_BASELINE: (jpeg_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _baseline_group),
-            KIND_PROGRESSIVE: (progressive_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _progressive_group),
-            KIND_PNG: (png_records, lambda hd: hd[:, HDR.H] * (1 + hd[:, HDR.W] * hd[:, HDR.NCOMP]), _png_group)}
+#   resize jobs last; output bytes per image; workspace bytes; the decode entry's name; its call, given where things lie) |
+#   the bytes per decoded pixel | the transform entry that takes them (clipmi_nearest_crop_p8 needs no scratch rows)
+def _png_mode_scanlines(hd):
+    return hd[:, HDR.H] * (1 + (hd[:, HDR.W] * hd[:, HDR.NCOMP] * hd[:, HDR.DEPTH] + 7) // 8)
+
+
+_FORMATS = {KIND_BASELINE: (jpeg_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _baseline_group, 3, "clipmi_resize_crop_rgb8"),
+            KIND_PROGRESSIVE: (progressive_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _progressive_group, 3, "clipmi_resize_crop_rgb8"),
+            KIND_PNG: (png_records, lambda hd: hd[:, HDR.H] * (1 + hd[:, HDR.W] * hd[:, HDR.NCOMP]), _png_group, 3,
+                       "clipmi_resize_crop_rgb8"),
+            KIND_PNG_ALPHA: (_png_mode_records(4), _png_mode_scanlines, _png_mode_group, 4, "clipmi_resize_crop_rgba8"),
+            KIND_PNG_INDEX: (_png_mode_records(1), _png_mode_scanlines, _png_mode_group, 1, "clipmi_nearest_crop_p8")}
 
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
-                 jpeg_group_mb=32768, device_progressive=None, device_png=None):
+                 jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -442,12 +486,16 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     clipmi_png_decode_rgb8 + clipmi_resize_crop_rgb8 on the side stream beside the JPEG decodes, grouped under jpeg_group_mb
     like them), the same bytes as Pillow's; every other PNG file and every file the device reports goes back to Pillow. With
     the flag off nothing changes for any file.
+    device_png_modes (default $CLIPMI_DEVICE_PNG_MODES, else off; "1" = on; takes effect only with device_png on): RGBA, grey +
+    alpha, palette (depth 1/2/4/8, with or without tRNS) and grey depth 1/2/4 files that are not interlaced take the device as
+    well (png_parse.parse(modes=True), clipmi_png_decode_px8, then clipmi_resize_crop_rgba8 or clipmi_nearest_crop_p8: Pillow
+    resamples such files in their own mode), the same bytes as Pillow's. Off, such files stay with Pillow as before.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
     shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoders, under the
     keys of decode_worker.PARSED (jpeg_files, jpeg_progressive_files: files staged for the device; png_files: files it decoded and
-    did not hand back)."""
+    did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only)."""
     import os
     import time
     n_px = model.visual.input_resolution
@@ -492,8 +540,10 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         device_progressive = os.environ.get("CLIPMI_DEVICE_PROGRESSIVE", "0") not in ("", "0")
     if device_png is None:
         device_png = os.environ.get("CLIPMI_DEVICE_PNG", "0") not in ("", "0")
+    if device_png_modes is None:
+        device_png_modes = os.environ.get("CLIPMI_DEVICE_PNG_MODES", "0") not in ("", "0")
     full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
-                 (8 if jpeg_cap and device_png else 0))
+                 (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0))
 
     # three pinned staging buffers used in turn (GPU): batch i may still be in its H2D copy while batch i+1 is filled;
     # a buffer is reused only after the copy that read it has finished. Pixels go shared memory -> pinned -> device:
@@ -561,10 +611,13 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                 pending["status"] = torch.empty(n_status, dtype=torch.int32, device=dev)
                 pending["slots"] = np.concatenate(parsed)
 
-            def resize_into_devt(src_ptr, jobs_ptr, n_jobs, max_rows, scratch):
-                rc = L.clipmi_resize_crop_rgb8(src_ptr, jobs_ptr, n_jobs, max_rows, base, n_px, devt.data_ptr(), scratch.data_ptr(),
-                                               _lib.stream_ptr(dev))
-                _lib.check(rc, "clipmi_resize_crop_rgb8")
+            def resize_into_devt(src_ptr, jobs_ptr, n_jobs, max_rows, scratch, entry="clipmi_resize_crop_rgb8"):
+                if entry == "clipmi_nearest_crop_p8":
+                    rc = L.clipmi_nearest_crop_p8(src_ptr, jobs_ptr, n_jobs, base, n_px, devt.data_ptr(), _lib.stream_ptr(dev))
+                else:
+                    rc = getattr(L, entry)(src_ptr, jobs_ptr, n_jobs, max_rows, base, n_px, devt.data_ptr(), scratch.data_ptr(),
+                                           _lib.stream_ptr(dev))
+                _lib.check(rc, entry)
 
             if len(e2):
                 # decode_full's regions: [pixels | pad to 16 | PLAN_INTS header: w h, the plan, n_hcoef n_vcoef | coefficient blocks]
@@ -588,29 +641,30 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                 # scanlines and RGB rows) fits a budget: a batch of thumbnails is one group, a batch of 12-megapixel photos many -
                 # they run one after the other through ONE workspace per kind (the side stream is in order), so that HBM holds a
                 # group, not a batch, of decoded photos. The kinds follow each other on the side stream in PARSED's order.
-                records, decoder_bytes, group = _FORMATS[kind.kind]
+                records, decoder_bytes, group, px, entry = _FORMATS[kind.kind]
+                tmp_px = 0 if entry == "clipmi_nearest_crop_p8" else px      # scratch bytes per pixel of the rows between the passes
                 hd = _headers(bigview, n, cap, slots)
-                need = decoder_bytes(hd) + (hd[:, HDR.W] * hd[:, HDR.H] * 3 + 15) // 16 * 16 + hd[:, HDR.NROWS] * n_px * 3
+                need = decoder_bytes(hd) + (hd[:, HDR.W] * hd[:, HDR.H] * px + 15) // 16 * 16 + hd[:, HDR.NROWS] * n_px * tmp_px
                 calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
                 for lo, hi in _groups(need, jpeg_group_bytes):
                     arrays, out_sz, ws_bytes, name, decode = group(L, records(bigview, n, cap, slots[lo:hi], comp, n_px))
                     small, offs = _pack16(arrays)
                     dsmall = torch.from_numpy(small).to(dev)
-                    nrows = arrays[-1]["nrows"].astype(np.int64)
+                    nrows = hd[lo:hi, HDR.NROWS]
                     ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
-                    tmp_max = max(tmp_max, int((nrows * n_px * 3).sum()))
+                    tmp_max = max(tmp_max, int((nrows * n_px * tmp_px).sum()))
                     calls.append((dsmall, offs, hi - lo, int(nrows.max()), name, decode, 4 * (status_at + lo)))
                     pending["keep"].append(dsmall)
                 ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
                 rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
                 scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
 
-                def decode_kind(calls=calls, ws=ws, rgb=rgb, scratch=scratch, status=pending["status"]):
+                def decode_kind(calls=calls, ws=ws, rgb=rgb, scratch=scratch, status=pending["status"], entry=entry):
                     for dsmall, offs, n_files, max_rows, name, decode, status_off in calls:
                         sb = dsmall.data_ptr()
                         _lib.check(decode(base, sb, offs, rgb.data_ptr(), status.data_ptr() + status_off, ws.data_ptr(),
                                           _lib.stream_ptr(dev)), name)
-                        resize_into_devt(rgb.data_ptr(), sb + offs[-1], n_files, max_rows, scratch)
+                        resize_into_devt(rgb.data_ptr(), sb + offs[-1], n_files, max_rows, scratch, entry)
 
                 pending["launch"].append(decode_kind)
                 pending["keep"] += [ws, rgb, scratch]

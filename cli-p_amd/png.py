@@ -2,7 +2,9 @@
 
 The host walks the chunks (png_parse.parse) and lets through 8-bit grey and RGB files that are not interlaced; the device
 inflates the IDAT stream (one wave per image), undoes the scanline filters and checks the Adler-32, and leaves Pillow's
-bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_crop_rgb8` takes. PNG is lossless, so there is
+bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_crop_rgb8` takes. With `modes=True` alpha,
+palette and low-depth files decode too, to the pixels of their own mode (clipmi_png_decode_px8; status 5: a palette index beyond
+the palette), and `transform_files` runs the transform of each kind on the device. PNG is lossless, so there is
 no tolerance: a file comes back with exactly Pillow's pixels (status 0) or goes back to Pillow - every file the parser
 refuses (`Unsupported`) and every file the device reports (1 invalid DEFLATE data, 2 the stream ended early, produced too
 little or wants to produce more, 3 a filter byte above 4, 4 the Adler-32 differs), so that Pillow's error handling stays the
@@ -19,8 +21,12 @@ IMAGE = np.dtype([("stream_off", "<i8"), ("raw_off", "<i8"), ("out_off", "<i8"),
 assert IMAGE.itemsize == 48
 
 
+PX_BYTES = {"rgb": 3, "alpha": 4, "index": 1}          # bytes per decoded pixel, by Parsed.kind
+
+
 def pack(items):
-    """Parsed records -> (IMAGE array, streams uint8, out_bytes, total_raw_bytes, max_raw_bytes)"""
+    """Parsed records -> (IMAGE array, streams uint8, out_bytes, total_raw_bytes, max_raw_bytes). Records of the kinds "alpha" and
+    "index" (clipmi_png_decode_px8) carry colour type, depth and palette entries in `reserved`."""
     recs = np.zeros(len(items), dtype=IMAGE)
     soff = roff = ooff = 0
     max_raw = 1
@@ -29,24 +35,32 @@ def pack(items):
         r = recs[k]
         r["stream_off"], r["raw_off"], r["out_off"], r["stream_bytes"] = soff, roff, ooff, len(it.stream)
         r["width"], r["height"], r["channels"] = it.width, it.height, it.channels
+        if it.kind != "rgb":
+            r["reserved"] = (it.ctype << 8 | it.depth, it.n_entries)
         pad = (-len(it.stream)) % 16 + 16
         pieces.append(it.stream)
         pieces.append(b"\0" * pad)
         soff += len(it.stream) + pad
         raw = it.raw_bytes()
         roff += (raw + 15) // 16 * 16
-        ooff += (it.width * it.height * 3 + 15) // 16 * 16
+        ooff += (it.width * it.height * PX_BYTES[it.kind] + 15) // 16 * 16
         max_raw = max(max_raw, raw)
     return recs, np.frombuffer(b"".join(pieces), np.uint8), ooff, roff, max_raw
 
 
 def decode_device(items, device, stream=None):
-    """Parsed records -> (out uint8 device tensor, records, status int32 device tensor): the RGB rows of image k start at
-    records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is."""
+    """Parsed records, all of kind "rgb" or none of them -> (out uint8 device tensor, records, status int32 device tensor): the
+    decoded rows of image k (PX_BYTES of its kind per pixel) start at records[k]["out_off"]. Asynchronous on torch's current
+    stream of `device`; status is valid once that stream is."""
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.ClipmiError("png.decode_device needs the HIP path (no CPU fallback)")
     L = _lib.lib()
+    px8 = bool(items) and items[0].kind != "rgb"
+    if any((it.kind != "rgb") != px8 for it in items):
+        raise ValueError("png.decode_device: \"rgb\" files and files of the other kinds go to different entries")
+    size_of, decode, name = ((L.clipmi_png_px8_workspace_bytes, L.clipmi_png_decode_px8, "clipmi_png_decode_px8") if px8 else
+                             (L.clipmi_png_workspace_bytes, L.clipmi_png_decode_rgb8, "clipmi_png_decode_rgb8"))
     recs, streams, out_bytes, total_raw, max_raw = pack(items)
     n = len(items)
     out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=device)
@@ -59,37 +73,122 @@ def decode_device(items, device, stream=None):
     hv[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
     hv[o_str:] = streams
     dev = host.to(device, non_blocking=True)
-    ws_bytes = int(L.clipmi_png_workspace_bytes(n, total_raw))
+    ws_bytes = int(size_of(n, total_raw))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
-    rc = L.clipmi_png_decode_rgb8(base + o_str, base, n, total_raw, max_raw, out.data_ptr(), status.data_ptr(), ws.data_ptr(),
-                                  ws_bytes, _lib.stream_ptr(device))
-    _lib.check(rc, "clipmi_png_decode_rgb8")
+    rc = decode(base + o_str, base, n, total_raw, max_raw, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
+                _lib.stream_ptr(device))
+    _lib.check(rc, name)
     cur = torch.cuda.current_stream(device)
     dev.record_stream(cur)
     ws.record_stream(cur)
     return out, recs, status
 
 
-def decode_files(blobs, device):
-    """PNG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
-    device reported it). Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM."""
-    items, where = [], []
+def _parsed(blobs, modes):
+    """-> [(position, Parsed)] of the files the parser lets through, split into the "rgb" files and the others"""
+    rgb, px8 = [], []
     for k, b in enumerate(blobs):
         try:
-            items.append(parse(b))
-            where.append(k)
+            it = parse(b, modes=modes)
         except Unsupported:
-            pass
+            continue
+        (rgb if it.kind == "rgb" else px8).append((k, it))
+    return rgb, px8
+
+
+def decode_files(blobs, device, modes=False):
+    """PNG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
+    device reported it). modes=True: alpha, palette and low-depth files decode too (png_parse.parse(modes=True)) - files of kind
+    "alpha" come back as uint8 [H,W,4], files of kind "index" as (uint8 [H,W], palette uint8 [256,3]).
+    Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM."""
     res = [None] * len(blobs)
-    if not items:
-        return res
-    out, recs, status = decode_device(items, device)
-    st = status.cpu().numpy()
+    for group in _parsed(blobs, modes):
+        if not group:
+            continue
+        out, recs, status = decode_device([it for _, it in group], device)
+        st = status.cpu().numpy()
+        host = out.cpu().numpy()
+        for t, (k, it) in enumerate(group):
+            if st[t] == 0:
+                h, w, o = it.height, it.width, int(recs[t]["out_off"])
+                if it.kind == "index":
+                    res[k] = (host[o:o + h * w].reshape(h, w), it.palette)
+                else:
+                    res[k] = host[o:o + h * w * PX_BYTES[it.kind]].reshape(h, w, PX_BYTES[it.kind])
+    return res
+
+
+def transform_device(items, out_rows, n_px, out, decoded, recs, device):
+    """The transform of decoded files on the device: the rows of `decoded` (decode_device's buffer, records `recs`) of the Parsed
+    `items`, all of one kind -> out[out_rows[k]] uint8 [3,n_px,n_px], through the entry of that kind: clipmi_resize_crop_rgb8,
+    clipmi_resize_crop_rgba8 or clipmi_nearest_crop_p8."""
+    from .decode_worker import nearest_plan, resize_plan
+    from .resize import JOB, NEAREST_JOB
+    L = _lib.lib()
+    kind = items[0].kind
+    px = PX_BYTES[kind]
+    n = len(items)
+    if kind == "index":
+        jobs = np.zeros(n, dtype=NEAREST_JOB)
+        tabs = np.zeros(n * (768 + 8 * n_px), np.uint8)            # per file: palette | column table | row table
+        for k, it in enumerate(items):
+            plan = nearest_plan(it.width, it.height, n_px)
+            o = k * (768 + 8 * n_px)
+            tabs[o:o + 768] = it.palette.reshape(-1)
+            tabs[o + 768:o + 768 + 8 * n_px].view(np.int32)[:] = np.concatenate([plan["hcoef"], plan["vcoef"]])
+            j = jobs[k]
+            j["src_off"], j["w"], j["h"], j["out_index"] = int(recs[k]["out_off"]), it.width, it.height, out_rows[k]
+            j["pal_off"], j["col_off"], j["row_off"] = o, (o + 768) // 4, (o + 768) // 4 + n_px
+        small = np.concatenate([jobs.view(np.uint8).reshape(-1), tabs])
+        dsmall = torch.from_numpy(small).to(device)
+        rc = L.clipmi_nearest_crop_p8(decoded.data_ptr(), dsmall.data_ptr(), n, dsmall.data_ptr() + jobs.nbytes, n_px, out.data_ptr(),
+                                      _lib.stream_ptr(device))
+        _lib.check(rc, "clipmi_nearest_crop_p8")
+        return
+    jobs = np.zeros(n, dtype=JOB)
+    coefs, coff, toff, max_rows = [], 0, 0, 1
+    for k, it in enumerate(items):
+        p = resize_plan(it.width, it.height, n_px)
+        j = jobs[k]
+        j["src_off"], j["w"], j["h"], j["r0"], j["nrows"], j["out_index"] = int(recs[k]["out_off"]), it.width, it.height, p["r0"], p["nrows"], out_rows[k]
+        j["need_h"], j["need_v"], j["left"], j["top"], j["hk"], j["vk"] = p["need_h"], p["need_v"], p["left"], p["top"], p["hk"], p["vk"]
+        j["hcoef_off"], j["vcoef_off"], j["tmp_off"] = coff, coff + p["hcoef"].size, toff
+        coefs += [p["hcoef"], p["vcoef"]]
+        coff += p["hcoef"].size + p["vcoef"].size
+        toff += p["nrows"] * n_px * px
+        max_rows = max(max_rows, p["nrows"])
+    coef = np.concatenate(coefs + [np.zeros(1, np.int32)]).astype(np.int32)
+    small = np.concatenate([jobs.view(np.uint8).reshape(-1), coef.view(np.uint8)])
+    dsmall = torch.from_numpy(small).to(device)
+    scratch = torch.empty(max(toff, 1), dtype=torch.uint8, device=device)
+    name = "clipmi_resize_crop_rgba8" if kind == "alpha" else "clipmi_resize_crop_rgb8"
+    rc = getattr(L, name)(decoded.data_ptr(), dsmall.data_ptr(), n, max_rows, dsmall.data_ptr() + jobs.nbytes, n_px, out.data_ptr(),
+                          scratch.data_ptr(), _lib.stream_ptr(device))
+    _lib.check(rc, name)
+
+
+def transform_files(blobs, n_px, device):
+    """PNG file contents -> per file the transform's pixels, uint8 [3,n_px,n_px] as decode_worker.load_uint8 gives them (None
+    where the file is not for the device or the device reported it): decode on the device + the transform entry of the file's
+    kind, "rgb" included. Synchronises; a convenience for tests and tools like decode_files."""
+    device = torch.device(device)
+    res = [None] * len(blobs)
+    rgb, px8 = _parsed(blobs, True)
+    groups = [rgb, [e for e in px8 if e[1].kind == "alpha"], [e for e in px8 if e[1].kind == "index"]]
+    out = torch.zeros((max(len(blobs), 1), 3, n_px, n_px), dtype=torch.uint8, device=device)
+    keep = []
+    for group in groups:
+        if not group:
+            continue
+        items = [it for _, it in group]
+        decoded, recs, status = decode_device(items, device)
+        transform_device(items, [k for k, _ in group], n_px, out, decoded, recs, device)
+        keep.append((group, status))
     host = out.cpu().numpy()
-    for t, k in enumerate(where):
-        if st[t] == 0:
-            r = recs[t]
-            h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
-            res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
+    for group, status in keep:
+        st = status.cpu().numpy()
+        for t, (k, _) in enumerate(group):
+            if st[t] == 0:
+                res[k] = host[k]
     return res

@@ -1,7 +1,8 @@
 """Host side of the PNG decode on the device (csrc/png.hip): walk the chunks and hand over the DEFLATE stream.
 
 `parse(data)` lets through 8-bit grey (colour type 0) and RGB (colour type 2) files that are not interlaced and carry no
-`tRNS` and no APNG chunk, and returns the IDAT payloads joined, without the 2-byte zlib header; the Adler-32 and anything
+`tRNS` and no APNG chunk (`parse(data, modes=True)` also RGBA, grey + alpha, palette files at depth 1/2/4/8, with or without
+`tRNS`, and grey files at depth 1/2/4: kinds "alpha" and "index", see Parsed), and returns the IDAT payloads joined, without the 2-byte zlib header; the Adler-32 and anything
 behind it stay in place (the device finds the trailer behind the final block itself). Everything else raises `Unsupported`
 and stays with Pillow: palette, alpha, 16-bit and 1/2/4-bit files (the transform resamples those modes differently), Adam7
 files, and any file whose chunks this parser cannot vouch for - in front of the image data AND behind it: Pillow's load_end()
@@ -19,6 +20,7 @@ MAX_PIXELS = 89478485
 MAX_TEXT_BYTES = 1 << 20
 # The unfilter kernel keeps a band's last row in LDS (48 KiB): rows of up to this many pixels; wider files are Pillow's.
 MAX_WIDTH = 16384
+MAX_ROW_BYTES = 49152      # ... and, for the modes behind `modes=True`, of up to this many bytes: RGBA rows of at most 12288 pixels
 
 # Chunks allowed in front of the first IDAT, with the length Pillow's handler needs (None: any), and why each can change
 # neither mode nor size nor pixels of `Image.open(f).convert("RGB")` (PIL/PngImagePlugin.py, PngStream.chunk_*):
@@ -50,18 +52,38 @@ class Unsupported(Exception):
 
 
 class Parsed:
-    __slots__ = ("width", "height", "channels", "stream")
+    """kind: what the device decodes the file to - "rgb" (3 bytes per pixel, clipmi_png_decode_rgb8), "alpha" (4 bytes per pixel:
+    RGBA, grey + alpha, grey at depth 2/4) or "index" (1 byte per pixel: palette files, 1-bit grey), both clipmi_png_decode_px8.
+    channels: samples per pixel; palette: uint8 [256][3], zero beyond the n_entries entries (None for "rgb" and "alpha"; 1-bit grey
+    is the two-entry palette black, white)."""
+    __slots__ = ("width", "height", "channels", "stream", "kind", "depth", "ctype", "palette", "n_entries")
 
-    def __init__(self, width, height, channels, stream):
+    def __init__(self, width, height, channels, stream, kind="rgb", depth=8, ctype=None, palette=None, n_entries=0):
         self.width, self.height, self.channels, self.stream = width, height, channels, stream
+        self.kind, self.depth, self.ctype = kind, depth, (2 if channels == 3 else 0) if ctype is None else ctype
+        self.palette, self.n_entries = palette, n_entries
+
+    def row_bytes(self):
+        return (self.width * self.channels * self.depth + 7) // 8
 
     def raw_bytes(self):
         """size of the filtered scanlines the stream has to produce"""
-        return self.height * (1 + self.width * self.channels)
+        return self.height * (1 + self.row_bytes())
 
 
-def parse(data):
-    """PNG file contents -> Parsed(width, height, channels, stream); raises Unsupported(reason)."""
+# colour type -> (samples per pixel, the depths taken under modes=True); 16-bit files stay Pillow's
+_MODES = {6: (4, (8,)), 4: (2, (8,)), 3: (1, (1, 2, 4, 8)), 0: (1, (1, 2, 4))}
+
+
+def _palette(body, n_entries):
+    import numpy as np
+    pal = np.zeros((256, 3), np.uint8)
+    pal[:n_entries] = np.frombuffer(body, np.uint8).reshape(n_entries, 3)
+    return pal
+
+
+def parse(data, modes=False):
+    """PNG file contents -> Parsed; raises Unsupported(reason). modes: also let the files of kinds "alpha" and "index" through."""
     data = bytes(data)
     if data[:8] != SIGNATURE:
         raise Unsupported("not a PNG file")
@@ -69,6 +91,8 @@ def parse(data):
     first = True
     text = 0
     pieces = None
+    plte = None                                                # the PLTE chunk's body (colour type 3 under modes=True)
+    seen_trns = False
     while True:
         if pos + 8 > n:
             if pieces is not None:
@@ -97,7 +121,8 @@ def parse(data):
             if cid != b"IHDR" or length != 13:
                 raise Unsupported("IHDR is not the first chunk")
             width, height, depth, ctype, comp, filt, lace = struct.unpack_from(">IIBBBBB", data, body)
-            if depth != 8 or ctype not in (0, 2):
+            rgb = depth == 8 and ctype in (0, 2)
+            if not rgb and not (modes and ctype in _MODES and depth in _MODES[ctype][1]):
                 raise Unsupported("bit depth %d, colour type %d" % (depth, ctype))
             if comp != 0 or filt != 0:
                 raise Unsupported("unknown compression or filter method")
@@ -109,8 +134,20 @@ def parse(data):
                 raise Unsupported("too many pixels")
             if width > MAX_WIDTH:
                 raise Unsupported("rows too wide")
-            channels = 3 if ctype == 2 else 1
+            channels = (3 if ctype == 2 else 1) if rgb else _MODES[ctype][0]
+            if (width * channels * depth + 7) // 8 > MAX_ROW_BYTES:
+                raise Unsupported("rows too wide")
             first = False
+        elif not rgb and ctype == 3 and cid == b"PLTE":
+            # exactly one, 1 .. 1 << depth whole entries (Pillow takes the palette as it comes; a longer one is its to judge)
+            if plte is not None or seen_trns or length % 3 or not 3 <= length <= 768 or length > 3 << depth:
+                raise Unsupported("PLTE chunk")
+            plte = data[body:body + length]
+        elif not rgb and ctype == 3 and cid == b"tRNS":
+            # behind the palette, at most one alpha per entry: it sets info["transparency"] and changes no pixel of convert("RGB")
+            if plte is None or seen_trns or length > len(plte) // 3:
+                raise Unsupported("tRNS chunk")
+            seen_trns = True
         else:
             want = ALLOWED_BEFORE_IDAT.get(cid, -1)
             if want == -1 or (want is not None and length != want):
@@ -146,4 +183,12 @@ def parse(data):
         raise Unsupported("bad zlib header")
     if len(stream) - 2 >= 1 << 31:
         raise Unsupported("stream too large")
-    return Parsed(width, height, channels, stream[2:])
+    if rgb:
+        return Parsed(width, height, channels, stream[2:])
+    if ctype == 3:
+        if plte is None:
+            raise Unsupported("no PLTE chunk")
+        return Parsed(width, height, 1, stream[2:], "index", depth, 3, _palette(plte, len(plte) // 3), len(plte) // 3)
+    if ctype == 0 and depth == 1:
+        return Parsed(width, height, 1, stream[2:], "index", 1, 0, _palette(b"\0\0\0\xff\xff\xff", 2), 2)
+    return Parsed(width, height, channels, stream[2:], "alpha", depth, ctype)

@@ -17,6 +17,9 @@ JOB = np.dtype([("src_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("r0", "<i4"), (
                 ("need_h", "<i4"), ("need_v", "<i4"), ("left", "<i4"), ("top", "<i4"), ("hk", "<i4"), ("vk", "<i4"),
                 ("hcoef_off", "<i8"), ("vcoef_off", "<i8"), ("tmp_off", "<i8")], align=True)
 assert JOB.itemsize == 80
+NEAREST_JOB = np.dtype([("src_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("out_index", "<i4"), ("reserved", "<i4"), ("pal_off", "<i8"),
+                        ("col_off", "<i8"), ("row_off", "<i8")], align=True)      # clipmi_nearest_job
+assert NEAREST_JOB.itemsize == 48
 
 
 def pack_jobs(shapes, n_px, plans=None):

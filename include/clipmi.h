@@ -369,6 +369,45 @@ int64_t clipmi_png_workspace_bytes(int n, int64_t total_raw_bytes);
 int clipmi_png_decode_rgb8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes, int64_t max_raw_bytes,
                            void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- Alpha, palette and low-depth PNG files on the device (a further addition to ABI 8 in the sense of the note above: new
+ * entry points and one new record, nothing existing changes). clipmi_png_decode_px8 takes the stream layout, the records, the
+ * workspace and the arguments of clipmi_png_decode_rgb8 and leaves the file's own-mode pixels, which Pillow's transform
+ * resamples before it converts to RGB. A record carries in reserved[0] colour type << 8 | bit depth, in reserved[1] the palette's
+ * entry count (colour type 3: 1 .. 1 << depth; otherwise ignored), and in `channels` the samples per pixel (4, 2, 1, 1).
+ * Taken: colour type 6 and 4 at depth 8, colour type 3 at depth 1/2/4/8, colour type 0 at depth 1/2/4; a scanline holds
+ * ceil(width x channels x depth / 8) bytes behind its filter byte, at most 49152 (the sizes and offsets count these scanlines).
+ * out_dev, per image at out_off (a multiple of 16), one of two layouts:
+ *   "alpha" (colour types 6 and 4, colour type 0 at depth 2/4): rows of width*4 bytes R G B A; grey + alpha as L L L A, grey at
+ *           depth 2 / 4 as v*85 / v*17 three times, then 255 - the layout clipmi_resize_crop_rgba8 takes;
+ *   "index" (colour type 3, colour type 0 at depth 1): rows of width bytes, one sample each, the most significant bits of a byte
+ *           first, the padding bits at a row's end dropped - the layout clipmi_nearest_crop_p8 takes.
+ * status_dev[i]: 0..4 as clipmi_png_decode_rgb8; 5 an "index" image holds a sample >= its entry count (1-bit grey has 2). */
+int64_t clipmi_png_px8_workspace_bytes(int n, int64_t total_raw_bytes);
+int clipmi_png_decode_px8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes, int64_t max_raw_bytes,
+                          void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream);
+
+/* The transform for those pixels, bit for bit what Pillow's resize (in the file's mode) + crop + convert("RGB") gives.
+ * clipmi_resize_crop_rgba8: arguments and jobs of clipmi_resize_crop_rgb8 with 4 bytes per source and scratch pixel (rows of
+ * w*4 bytes; nrows*n_px*4 scratch bytes per job, tmp_off a multiple of 4). A job that resamples an axis premultiplies each
+ * pixel as it is loaded (t = c*a + 128; c' = ((t >> 8) + t) >> 8), resamples four channels and un-premultiplies in front of the
+ * store (a 0 or 255: c'; else min(255, 255*c' / a)); a job that resamples neither axis crops and drops alpha.
+ * clipmi_nearest_crop_p8: "index" rows -> palette colours of the source pixel each output takes. tabs_dev (4-byte aligned)
+ * holds, per job, the palette (256 x 3 bytes, pal_off in bytes) and two int32 tables (col_off, row_off: int32 offsets) with the
+ * source column of each of the n_px output columns and the source row of each output row, computed by the host with Pillow's
+ * float64 accumulation (cli-p_amd/decode_worker.py nearest_window). Both write out_dev as clipmi_resize_crop_rgb8 does. */
+typedef struct clipmi_nearest_job {
+    int64_t src_off;              /* bytes from raw_dev to the image's first sample (rows of w bytes) */
+    int32_t w, h;                 /* source size */
+    int32_t out_index;
+    int32_t reserved;
+    int64_t pal_off;              /* bytes from tabs_dev */
+    int64_t col_off, row_off;     /* int32 offsets from tabs_dev */
+} clipmi_nearest_job;
+int clipmi_resize_crop_rgba8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
+                             int n_px, void* out_dev, void* scratch_dev, void* stream);
+int clipmi_nearest_crop_p8(const void* raw_dev, const void* jobs_dev, int njobs, const void* tabs_dev, int n_px, void* out_dev,
+                           void* stream);
+
 /* thread-local message of the last failing call on this thread ("" if none) */
 const char* clipmi_last_error(void);
 int clipmi_abi_version(void);

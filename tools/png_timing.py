@@ -6,6 +6,10 @@ each reported (other people's work shares the host, so the minimum is the figure
            each (its choice per block; the block kinds were not counted), so the file is as large as its scanlines
   smooth   photo-like: low-frequency waves plus a little noise, literals and short matches
   screen   screenshot-like: flat areas, text-like edges, long matches
+and, for the alpha, palette and low-depth files `device_png_modes` adds, variants of smooth and screen (`--sets modes` runs the
+eight of them): `<kind>_rgba` with an alpha plane (smooth: a slow wave; screen: opaque but for a few transparent boxes) and
+`<kind>_p4`, quantised to a 16-colour palette and saved at 4 bits. For these the two settings are `device_png` on with
+`device_png_modes` off (Pillow decodes them in the workers) and on.
 Prints one JSON line per set and a table. usage: python tools/png_timing.py [--rounds N] [--sets noise:small,screen:big,...]
 Under `rocprofv3 --kernel-trace --stats -- python tools/png_timing.py --rounds 1 --sets ...` the three png_* kernels' own
 times are in the statistics file."""
@@ -25,6 +29,7 @@ SIZES = {"small": (224, 224, 435, 87), "big": (1500, 2000, 58, 12)}          # h
 
 def picture(kind, seed, h, w):
     rng = np.random.default_rng(seed)
+    kind, _, variant = kind.partition("_")
     if kind == "noise":
         a = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
     elif kind == "smooth":
@@ -41,7 +46,21 @@ def picture(kind, seed, h, w):
             xs = rng.integers(0, 2, w // 3 + 1).repeat(3)[:w].astype(bool)
             a[y0:y0 + 7:2, xs] = 30
     buf = io.BytesIO()
-    Image.fromarray(a).save(buf, format="PNG")
+    img = Image.fromarray(a)
+    kw = {}
+    if variant == "rgba":
+        if kind == "smooth":
+            y, x = np.mgrid[0:h, 0:w].astype(np.float32)
+            alpha = np.clip(160 + 110 * np.sin(x / 70 + y / 110), 0, 255).astype(np.uint8)
+        else:
+            alpha = np.full((h, w), 255, np.uint8)
+            for _ in range(max(1, h * w // 20000)):
+                y0, x0 = int(rng.integers(0, h)), int(rng.integers(0, w))
+                alpha[y0:y0 + int(rng.integers(1, 60)), x0:x0 + int(rng.integers(1, 200))] = 0
+        img.putalpha(Image.fromarray(alpha))
+    elif variant == "p4":
+        img, kw = img.quantize(16), {"bits": 4}
+    img.save(buf, format="PNG", **kw)
     return buf.getvalue()
 
 
@@ -51,6 +70,8 @@ def main():
     rounds = int(sys.argv[sys.argv.index("--rounds") + 1]) if "--rounds" in sys.argv else 3
     sets = (sys.argv[sys.argv.index("--sets") + 1].split(",") if "--sets" in sys.argv else
             [f"{k}:{s}" for s in ("small", "big") for k in ("noise", "smooth", "screen")])
+    if sets == ["modes"]:
+        sets = [f"{k}_{v}:{s}" for s in ("small", "big") for k in ("screen", "smooth") for v in ("rgba", "p4")]
     import clipmi
     pool = clipmi.pipeline.DecodePool(16)                    # before the GPU is touched
     d = tempfile.mkdtemp(prefix="clipmi_png_")
@@ -69,19 +90,21 @@ def main():
                 with open(paths[-1], "wb") as f:
                     f.write(blobs[k % distinct])
             kw = dict(batch=n, pool=pool, device_jpeg_kb=16384)
+            modes = "_" in s                                 # a variant for device_png_modes: that flag is what goes off and on
+            flags = (lambda on: dict(device_png=True, device_png_modes=on)) if modes else (lambda on: dict(device_png=on))
             best, kept, stage = {False: 1e9, True: 1e9}, {}, {}
             for on in (False, True):                         # warm-up: region sizes, workspaces, page-locked segments
-                for _ in clipmi.pipeline.encode_files(model, paths, device_png=on, **kw):
+                for _ in clipmi.pipeline.encode_files(model, paths, **flags(on), **kw):
                     pass
             for _ in range(rounds):
                 for on in (False, True):
                     st = {}
                     t0 = time.perf_counter()
-                    got = sum(len(ok) for ok, _, _ in clipmi.pipeline.encode_files(model, paths, device_png=on, stats=st, **kw))
+                    got = sum(len(ok) for ok, _, _ in clipmi.pipeline.encode_files(model, paths, stats=st, **flags(on), **kw))
                     dt = time.perf_counter() - t0             # (every batch's vectors were copied to the host: the device is done)
                     assert got == len(paths)
                     if dt < best[on]:
-                        best[on], kept[on] = dt, st.get("png_files", 0)
+                        best[on], kept[on] = dt, st.get("png_mode_files" if modes else "png_files", 0)
                         stage[on] = {k: round(v, 2) for k, v in st.items() if k.endswith("_s")}
             row = dict(set=s, files=len(paths), size=[w, h], mean_file_kb=round(sum(map(len, blobs)) / distinct / 1024, 1), rounds=rounds,
                        pillow_images_per_s=round(len(paths) / best[False], 1), device_images_per_s=round(len(paths) / best[True], 1),
@@ -91,9 +114,9 @@ def main():
     finally:
         pool.close()
         shutil.rmtree(d, ignore_errors=True)
-    print(f"{'set':14s} {'files':>6s} {'KB/file':>8s} {'Pillow img/s':>13s} {'device img/s':>13s} {'on device':>10s}")
+    print(f"{'set':18s} {'files':>6s} {'KB/file':>8s} {'Pillow img/s':>13s} {'device img/s':>13s} {'on device':>10s}")
     for r in rows:
-        print(f"{r['set']:14s} {r['files']:6d} {r['mean_file_kb']:8.1f} {r['pillow_images_per_s']:13.1f} {r['device_images_per_s']:13.1f} "
+        print(f"{r['set']:18s} {r['files']:6d} {r['mean_file_kb']:8.1f} {r['pillow_images_per_s']:13.1f} {r['device_images_per_s']:13.1f} "
               f"{r['device_png_files']:10d}")
 
 
