@@ -1,8 +1,6 @@
 // gemm.hip — instantiation and launch of the bf16 NT GEMM (see gemm.hpp).
 #include "gemm256p.hpp"
 #include "gemm_skinny.hpp"
-#ifdef CLIPMI_DEV
-#endif
 #include "gemm256f8.hpp"
 #include <hip/hip_ext.h>
 #include <cstdlib>
@@ -35,43 +33,33 @@ static int launch_epi(const GemmArgs& g, hipStream_t st, GemmProbe* probe) {
     return 0;
 }
 
-template <int EPI>
-static int launch_epi256(const GemmArgs& g, hipStream_t st, GemmProbe* probe) {
+// gemm256 / gemm256f8 (gemm256.hpp, gemm256f8.hpp), one workgroup per tile. KERNEL keys the LDS opt-in slots: `lds_max` is
+// opted in once per instantiation and device, `lds` is this launch's. opt_err / name: the texts of a failed opt-in and of a
+// failed launch. Only the bf16 form passes a probe.
+template <auto KERNEL>
+static int launch_g256(const GemmArgs& g, hipStream_t st, int lds_max, int lds, const char* opt_err, const char* name,
+                       GemmProbe* probe = nullptr, int epi = 0) {
     const int grid = (g.N / 256) * ((g.M + 255) / 256);
     static thread_local int opted[64];
-    if (!lds_opted(opted)) {
-        if (hipFuncSetAttribute((const void*)gemm256_bf16_nt_kernel<EPI>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G256_LDS) != hipSuccess)
-            return set_err(CLIPMI_EHIP, "hipFuncSetAttribute(gemm256, %d B LDS)", G256_LDS);
-    }
-    if (probe && probe->wants(EPI)) {
+    if (!lds_opted(opted) &&
+        hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess)
+        return set_err(CLIPMI_EHIP, opt_err, lds_max);
+    if (probe && probe->wants(epi)) {
         GemmProbe& p = *probe;
-        const int i = p.begin(EPI, 1, st, g.K);
-        hipExtLaunchKernelGGL(gemm256_bf16_nt_kernel<EPI>, dim3(grid), dim3(512), G256_LDS, st, p.ev[2 * i],
-                              p.ev[2 * i + 1], 0, g);
+        const int i = p.begin(epi, 1, st, g.K);
+        hipExtLaunchKernelGGL(KERNEL, dim3(grid), dim3(512), lds, st, p.ev[2 * i], p.ev[2 * i + 1], 0, g);
     } else {
-        hipLaunchKernelGGL(gemm256_bf16_nt_kernel<EPI>, dim3(grid), dim3(512), G256_LDS, st, g);
+        hipLaunchKernelGGL(KERNEL, dim3(grid), dim3(512), lds, st, g);
     }
-    CLIPMI_CHECK_LAUNCH("gemm256_bf16_nt_kernel");
+    CLIPMI_CHECK_LAUNCH(name);
     return 0;
 }
 
-#ifdef CLIPMI_DEV
-// development: the W-direct form of gemm256 (gemm256.hpp WD = true), algo 5 of the test hooks
-template <int EPI, int WD = 1>
-static int launch_epi256wd(const GemmArgs& g, hipStream_t st) {
-    const int grid = (g.N / 256) * ((g.M + 255) / 256);
-    static thread_local int opted[64];
-    if (!lds_opted(opted)) {
-        if (hipFuncSetAttribute((const void*)gemm256_bf16_nt_kernel<EPI, WD>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G256_LDS) != hipSuccess)
-            return set_err(CLIPMI_EHIP, "hipFuncSetAttribute(gemm256 WD, %d B LDS)", G256_LDS);
-    }
-    hipLaunchKernelGGL((gemm256_bf16_nt_kernel<EPI, WD>), dim3(grid), dim3(512), G256_LDS, st, g);
-    CLIPMI_CHECK_LAUNCH("gemm256_bf16_nt_kernel<WD>");
-    return 0;
+template <int EPI>
+static int launch_epi256(const GemmArgs& g, hipStream_t st, GemmProbe* probe) {
+    return launch_g256<gemm256_bf16_nt_kernel<EPI>>(g, st, G256_LDS, G256_LDS, "hipFuncSetAttribute(gemm256, %d B LDS)",
+                                                    "gemm256_bf16_nt_kernel", probe, EPI);
 }
-#endif
 
 // persistent, role-split 256x256 kernel (gemm256p.hpp): pure-store epilogues only
 static int persist_mode() {
@@ -172,17 +160,11 @@ int launch_gemm_algo(const GemmArgs& g, int epi, int algo, hipStream_t st, GemmP
         return set_err(CLIPMI_EINVAL, "gemm: EPI_BIAS_RESID_LN_F32 needs x3 (16-byte aligned), ln_part, tmp_f32 and N %% 256 == 0, N <= 1024");
     if (g.lda_bytes && (g.lda_bytes % 16 != 0 || g.lda_bytes < 2u * (unsigned)g.K))
         return set_err(CLIPMI_EINVAL, "gemm: lda_bytes %u (need a multiple of 16, >= 2 K)", g.lda_bytes);
+    if (algo == 5)
+        return set_err(CLIPMI_EUNSUPPORTED, "algo 5 (W-direct gemm256, DESIGN 4.4h) was removed: measured 33-40 %% slower in round 4, commit 9acf8e2 last carried it");
 #ifndef CLIPMI_DEV
-    if (algo == 4 || algo == 5) return set_err(CLIPMI_EUNSUPPORTED, "algo %d exists in the development build only (libclipmi_dev.so)", algo);
+    if (algo == 4) return set_err(CLIPMI_EUNSUPPORTED, "algo %d exists in the development build only (libclipmi_dev.so)", algo);
 #else
-    if (algo == 5) {
-        if (g.N % 256 != 0 || g.K % 64 != 0 || g.K < 128 || g.M < 1 || !g.A || !g.W || !g.out)
-            return set_err(CLIPMI_EINVAL, "gemm256 WD: N %% 256 == 0, K %% 64 == 0, K >= 128");
-        if (epi == EPI_BIAS_BF16) return launch_epi256wd<EPI_BIAS_BF16>(g, st);
-        if (epi == EPI_BIAS_QGELU_BF16) return launch_epi256wd<EPI_BIAS_QGELU_BF16>(g, st);
-        if (epi == EPI_F32) return launch_epi256wd<EPI_F32>(g, st);
-        return set_err(CLIPMI_EINVAL, "gemm256 WD: epilogue %d", epi);
-    }
     if (algo == 4) return set_err(CLIPMI_EUNSUPPORTED, "algo 4 (gemm2w, DESIGN 4.4g) was removed in round 5: measured slower in round 3, its sources are in the history");
 #endif
     const bool ok256 = g.N % 256 == 0 && g.K % 64 == 0 && g.K >= 128;
@@ -289,33 +271,17 @@ int launch_gemm_algo(const GemmArgs& g, int epi, int algo, hipStream_t st, GemmP
 
 template <int EPI, bool MX>
 static int launch_epi256f8(const GemmArgs& g, hipStream_t st) {
-    const int grid = (g.N / 256) * ((g.M + 255) / 256);
-    static thread_local int opted[64];
-    if (!lds_opted(opted)) {
-        if (hipFuncSetAttribute((const void*)gemm256f8_nt_kernel<EPI, MX>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G256_LDS) != hipSuccess)
-            return set_err(CLIPMI_EHIP, "hipFuncSetAttribute(gemm256f8, %d B LDS)", G256_LDS);
-    }
-    hipLaunchKernelGGL((gemm256f8_nt_kernel<EPI, MX>), dim3(grid), dim3(512), G256_LDS, st, g);
-    CLIPMI_CHECK_LAUNCH("gemm256f8_nt_kernel");
-    return 0;
+    return launch_g256<gemm256f8_nt_kernel<EPI, MX>>(g, st, G256_LDS, G256_LDS, "hipFuncSetAttribute(gemm256f8, %d B LDS)",
+                                                     "gemm256f8_nt_kernel");
 }
 
 // block-scaled activations (gemm256f8.hpp BSA): the tile's 256 x K/32 scale bytes sit behind the K-tile buffers
 constexpr int G256F8_BSA_MAX_K = 4096;           // 32 KiB of scale bytes per tile: 160 KiB of LDS in all
 template <int EPI>
 static int launch_epi256f8_bsa(const GemmArgs& g, hipStream_t st) {
-    const int grid = (g.N / 256) * ((g.M + 255) / 256);
-    const int lds = G256_LDS + 256 * (g.K / 32);
-    static thread_local int opted[64];
-    if (!lds_opted(opted)) {
-        if (hipFuncSetAttribute((const void*)gemm256f8_nt_kernel<EPI, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                G256_LDS + 256 * (G256F8_BSA_MAX_K / 32)) != hipSuccess)
-            return set_err(CLIPMI_EHIP, "hipFuncSetAttribute(gemm256f8 block-scaled)");
-    }
-    hipLaunchKernelGGL((gemm256f8_nt_kernel<EPI, true, true>), dim3(grid), dim3(512), lds, st, g);
-    CLIPMI_CHECK_LAUNCH("gemm256f8_nt_kernel(block-scaled A)");
-    return 0;
+    return launch_g256<gemm256f8_nt_kernel<EPI, true, true>>(g, st, G256_LDS + 256 * (G256F8_BSA_MAX_K / 32), G256_LDS + 256 * (g.K / 32),
+                                                             "hipFuncSetAttribute(gemm256f8 block-scaled)",
+                                                             "gemm256f8_nt_kernel(block-scaled A)");
 }
 
 // true when launch_gemm_fp8(.., EPI_BIAS_QGELU_BF16, ..) of this shape runs on the persistent kernel, whose store pass can

@@ -1,6 +1,7 @@
 """W fragments straight from L2 (gemm256 WD) against the LDS-DMA form of the SAME kernel (development aid):
 bit-identity of the outputs, then interleaved timing rounds in one process on the encode step's GEMM shapes.
-algo 2 = gemm256 (both operands by LDS-DMA), 5 = gemm256 WD, 3 = the persistent role-split kernel (for scale)."""
+algo 2 = gemm256 (both operands by LDS-DMA), 5 = gemm256 WD, 3 = the persistent role-split kernel (for scale).
+The WD arm (algo 5) was removed, measured 33-40 % slower (profiles/r04_wdirect_ab.txt): commit 9acf8e2 last carried it, run this there."""
 import sys, os
 os.environ.setdefault("CLIPMI_DEV_LIB", "1")
 import torch

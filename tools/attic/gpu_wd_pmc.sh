@@ -1,6 +1,7 @@
 #!/bin/bash
 # PMC evidence for DESIGN 4.4h (W fragments straight from L2): the c_fc shape on gemm256 (algo 2), its W-direct form
 # (algo 5) and the persistent kernel (algo 3) under rocprofv3 counter passes (own runs, --kernel-trace only).
+# The WD arm (algo 5) was removed, measured 33-40 % slower (profiles/r04_wdirect_ab.txt): commit 9acf8e2 last carried it, run this there.
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}; cd "$ROOT"; mkdir -p gpurun_out/wd
 export TMPDIR=/tmp CLIPMI_DEV_LIB=1
 rocprofv3 -L > gpurun_out/wd/counters.txt 2>&1
