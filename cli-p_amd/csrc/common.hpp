@@ -50,6 +50,10 @@ constexpr long long dev_knob(const char*, long long dflt) { return dflt; }
 constexpr bool dev_knob_set(const char*) { return false; }
 #endif
 
+// resize.hip: resize_v_kernel over clipmi_resize_job records (the second pass of clipmi_resize_crop_rgb8)
+int launch_resize_v_rgb8(const void* jobs_dev, int njobs, const int32_t* coef_dev, int n_px, const void* scratch_dev, void* out_dev,
+                         hipStream_t st);
+
 constexpr int NUM_CU = 256;           // MI355X
 constexpr int LDS_BYTES = 160 * 1024; // per CU
 

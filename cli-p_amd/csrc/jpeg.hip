@@ -26,6 +26,9 @@
 //                            outside the range where libjpeg-turbo's IDCT provably equals it is reported (status 4)
 //   jpeg_color_kernel        jdsample.c's fancy (triangle) upsampling with jdmainct.c's edge rows + jdcolor.c's
 //                            16-bit fixed-point YCbCr -> RGB; rows of width*3 bytes, as Pillow's array
+//   jpeg_color_resize_h_kernel   the transform entries' form of the last step: the same upsampling and colour conversion fused with
+//                            Pillow's horizontal resampling pass (resize.hip's resize_h_kernel), over the rows and columns the
+//                            transform's window needs only - the full-size RGB rows are never written
 #include "common.hpp"
 
 namespace clipmi {
@@ -755,6 +758,228 @@ __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __rest
     o[2] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
 }
 
+// ---- jpeg_color_kernel + resize_h_kernel (resize.hip) in one pass, for the transform entries: the full-size RGB image is never
+// written. Only the source rows [r0, r0 + nrows) and the source columns under the n_px-wide window are converted, from the
+// sample planes jpeg_idct_kernel left, and what reaches memory is what resize_h_kernel writes: the 8-bit rows between Pillow's
+// two passes, scratch[tmp_off + (row * n_px + x) * 3 + c]. The arithmetic per output is that of the two kernels, in their order.
+//
+// A workgroup takes a job and a band of JF_ROWS source rows and walks the window in chunks of output columns. A chunk is as
+// many outputs as fit its three LDS pieces: JF_SPAN source columns, JF_COEF coefficients, JF_T outputs. Per chunk:
+//   stage     the band's luma bytes and the chroma rows and columns the chunk's source columns read (for 2x2 the neighbouring
+//             chroma rows too), 8 bytes per load (plane rows are multiples of 8 bytes at 64-byte aligned bases), and the chunk's
+//             first taps, tap counts and coefficients
+//   convert   every staged source pixel once: upsampled chroma + YCbCr -> RGB into an LDS row of R | G << 8 | B << 16
+//   resample  one thread per (row, output): the dot product over LDS pixels and LDS coefficients, three byte stores
+// LDS use does not depend on the image's width. An output whose taps do not fit a chunk by themselves (more than JF_SPAN source
+// columns or JF_COEF coefficients under ONE output: a shorter side beyond 100 x n_px) is computed tap by tap from the planes in
+// memory (jf_pixel_global), as is any output whose first tap and count do not lie inside the staged span.
+constexpr int JF_T = 256;
+constexpr int JF_ROWS = 8;                 // source rows per workgroup; 2x2 chroma needs JF_ROWS / 2 + 3 <= JF_ROWS rows
+constexpr int JF_SPAN = 512;               // source columns per chunk
+constexpr int JF_COEF = 3072;              // coefficients per chunk
+constexpr int JF_TILE_W = JF_SPAN + 16;    // staged bytes per row: the span, widened to multiples of 8 at both ends
+
+__device__ __forceinline__ unsigned jf_rgb(int Y, int cbs, int crs) {          // jdcolor.c, as jpeg_color_kernel
+    const int cb = cbs - 128, cr = crs - 128;
+    int r = Y + ((91881 * cr + 32768) >> 16);
+    int g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
+    int b = Y + ((116130 * cb + 32768) >> 16);
+    r = r < 0 ? 0 : (r > 255 ? 255 : r);
+    g = g < 0 ? 0 : (g > 255 ? 255 : g);
+    b = b < 0 ? 0 : (b > 255 ? 255 : b);
+    return (unsigned)r | ((unsigned)g << 8) | ((unsigned)b << 16);
+}
+
+// The chroma sample of source column x (jdsample.c's fancy upsampling, as jpeg_color_kernel): r0 = the chroma row of the pixel's
+// own row, r1 = the context row (2x2 only), both indexed by chroma column - `off`. mode 0: 1x1 (copy), 1: h2v1, 2: h2v2
+__device__ __forceinline__ int jf_chroma(const unsigned char* r0, const unsigned char* r1, int off, int x, int dw, int mode) {
+    if (mode == 0) return r0[x - off];
+    const int cx = x >> 1, i = cx - off;
+    if (mode == 1) {
+        const int p = r0[i];
+        if (x & 1) return cx == dw - 1 ? p : (3 * p + r0[i + 1] + 2) >> 2;
+        return cx == 0 ? p : (3 * p + r0[i - 1] + 1) >> 2;
+    }
+    const int s = 3 * r0[i] + r1[i];
+    if (x & 1) return cx == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * r0[i + 1] + r1[i + 1] + 7) >> 4;
+    return cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * r0[i - 1] + r1[i - 1] + 8) >> 4;
+}
+
+struct JfGeom {                // an image's planes, as jpeg_idct_kernel lays them out
+    const unsigned char* py;
+    const unsigned char* pc[2];
+    int W, H, yw, cw, dw, dh, mode;
+    bool color;
+};
+
+__device__ __forceinline__ int jf_context_row(const JfGeom& g, int y) {        // h2v2: the other chroma row of source row y
+    const int cy = y >> 1;
+    return (y & 1) ? (cy + 1 < g.dh ? cy + 1 : g.dh - 1) : (cy > 0 ? cy - 1 : 0);
+}
+
+// One pixel straight from the planes in memory, coordinates clamped into the image
+__device__ __forceinline__ unsigned jf_pixel_global(const JfGeom& g, int x, int y) {
+    x = x < 0 ? 0 : (x >= g.W ? g.W - 1 : x);
+    y = y < 0 ? 0 : (y >= g.H ? g.H - 1 : y);
+    const int Y = g.py[(size_t)y * g.yw + x];
+    if (!g.color) return (unsigned)Y * 0x010101u;
+    int cc[2];
+    const int cy = g.mode == 2 ? y >> 1 : y, oy = g.mode == 2 ? jf_context_row(g, y) : y;
+#pragma unroll
+    for (int c = 0; c < 2; ++c) cc[c] = jf_chroma(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, g.mode);
+    return jf_rgb(Y, cc[0], cc[1]);
+}
+
+__global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegImage* __restrict__ images,
+                                                                   const unsigned char* __restrict__ planes,
+                                                                   const clipmi_resize_job* __restrict__ jobs,
+                                                                   const int* __restrict__ coef, int n_px,
+                                                                   unsigned char* __restrict__ scratch) {
+    __shared__ __attribute__((aligned(16))) unsigned char s_y[JF_ROWS][JF_TILE_W];
+    __shared__ __attribute__((aligned(16))) unsigned char s_c[2][JF_ROWS][JF_TILE_W];
+    __shared__ unsigned s_rgb[JF_ROWS][JF_SPAN];
+    __shared__ int s_coef[JF_COEF];
+    __shared__ int s_xmin[JF_T], s_cnt[JF_T];
+    __shared__ int s_end;
+    const JpegImage& im = images[blockIdx.y];
+    const clipmi_resize_job j = jobs[blockIdx.y];
+    const int tid = threadIdx.x;
+    const int row0 = blockIdx.x * JF_ROWS;
+    JfGeom g;
+    g.W = im.width;
+    g.H = im.height;
+    if (row0 >= j.nrows || g.W < 1 || g.H < 1) return;                      // (the whole workgroup)
+    const int nr = j.nrows - row0 < JF_ROWS ? j.nrows - row0 : JF_ROWS;
+    g.color = im.ncomp != 1;
+    const int hs = g.color ? im.hs : 1, vs = g.color ? im.vs : 1;
+    const int mx = (g.W + 8 * hs - 1) / (8 * hs), my = (g.H + 8 * vs - 1) / (8 * vs);
+    g.mode = hs == 1 ? 0 : (vs == 1 ? 1 : 2);
+    g.yw = mx * hs * 8;
+    g.cw = mx * 8;
+    g.dw = (g.W + 1) >> 1;
+    g.dh = (g.H + 1) >> 1;
+    g.py = planes + im.coef_off * 64;
+    g.pc[0] = g.py + (size_t)mx * my * hs * vs * 64;
+    g.pc[1] = g.pc[0] + (size_t)mx * my * 64;
+    const int hk = j.hk > 0 ? j.hk : 0;
+    const int* cf = coef + j.hcoef_off;
+    unsigned char* dst = scratch + j.tmp_off + (size_t)row0 * n_px * 3;
+    // the band's source rows (consecutive; clamped into the image whatever the job says)
+    const int ylo = min(max(j.r0 + row0, 0), g.H - 1), yhi = min(max(j.r0 + row0 + nr - 1, 0), g.H - 1);
+    const int cylo = g.mode == 2 ? max((ylo >> 1) - 1, 0) : ylo;                       // first staged chroma row
+    const int ncr = g.mode == 2 ? min((yhi >> 1) + 1, g.dh - 1) - cylo + 1 : nr;      // staged chroma rows (2x2: <= JF_ROWS / 2 + 3)
+
+    for (int x0 = 0; x0 < n_px;) {
+        // ---- the chunk: outputs [x0, x1) read the source columns [sx0, sx1)
+        int x1, sx0, sx1;
+        if (j.need_h) {
+            sx0 = cf[x0];
+            const int c = x0 + tid;                                             // the chunk may end behind output c
+            int end = 0;
+            bool fits = false;
+            if (c < n_px) {
+                end = cf[c] + cf[n_px + c];
+                fits = cf[c] >= sx0 && end - sx0 <= JF_SPAN && (long long)(tid + 1) * hk <= JF_COEF;
+            }
+            // (first taps and ends do not decrease along an axis, so `fits` holds for a prefix of the threads; a table that breaks
+            // this only sends outputs to jf_pixel_global below)
+            const int n = __syncthreads_count(fits);
+            if (fits && tid == n - 1) s_end = end;
+            __syncthreads();
+            x1 = x0 + (n > 0 ? n : 1);
+            sx1 = n > 0 ? s_end : sx0;                                          // (n == 0: nothing staged, output x0 from memory)
+        } else {
+            x1 = min(x0 + JF_SPAN, n_px);
+            sx0 = j.left + x0;
+            sx1 = j.left + x1;
+        }
+        sx0 = min(max(sx0, 0), g.W);
+        sx1 = min(max(sx1, sx0), min(g.W, sx0 + JF_SPAN));
+        const int span = sx1 - sx0, nx = x1 - x0;
+        // ---- stage
+        const int yb = sx0 & ~7, ye = min((sx1 + 7) & ~7, g.yw);
+        int cb = yb, ce = ye;
+        if (g.mode) {
+            cb = max((sx0 >> 1) - 1, 0) & ~7;
+            ce = min((min(((sx1 - 1) >> 1) + 1, g.dw - 1) + 8) & ~7, g.cw);
+        }
+        if (span > 0) {
+            const int nu = (ye - yb) >> 3;
+            for (int i = tid; i < nr * nu; i += JF_T) {
+                const int r = i / nu, u = i - r * nu;
+                *reinterpret_cast<uint2*>(&s_y[r][8 * u]) = *reinterpret_cast<const uint2*>(g.py + (size_t)min(ylo + r, g.H - 1) * g.yw + yb + 8 * u);
+            }
+            if (g.color) {
+                const int nc = (ce - cb) >> 3;
+                for (int i = tid; i < 2 * ncr * nc; i += JF_T) {
+                    const int c = i / (ncr * nc), t = i - c * ncr * nc, r = t / nc, u = t - r * nc;
+                    const int cy = g.mode == 2 ? cylo + r : min(ylo + r, g.H - 1);
+                    *reinterpret_cast<uint2*>(&s_c[c][r][8 * u]) = *reinterpret_cast<const uint2*>((c ? g.pc[1] : g.pc[0]) + (size_t)cy * g.cw + cb + 8 * u);
+                }
+            }
+            if (j.need_h) {
+                if (tid < nx) {
+                    s_xmin[tid] = cf[x0 + tid];
+                    s_cnt[tid] = cf[n_px + x0 + tid];
+                }
+                const int* kk = cf + 2 * (size_t)n_px + (size_t)x0 * hk;
+                for (int i = tid; i < nx * hk; i += JF_T) s_coef[i] = kk[i];
+            }
+        }
+        __syncthreads();
+        // ---- convert
+        for (int r = 0; r < nr; ++r) {
+            const int y = min(ylo + r, g.H - 1);
+            const int t0 = g.mode == 2 ? (y >> 1) - cylo : r, t1 = g.mode == 2 ? jf_context_row(g, y) - cylo : r;
+            for (int p = tid; p < span; p += JF_T) {
+                const int x = sx0 + p;
+                const int Y = s_y[r][x - yb];
+                unsigned v = (unsigned)Y * 0x010101u;
+                if (g.color) v = jf_rgb(Y, jf_chroma(s_c[0][t0], s_c[0][t1], cb, x, g.dw, g.mode), jf_chroma(s_c[1][t0], s_c[1][t1], cb, x, g.dw, g.mode));
+                s_rgb[r][p] = v;
+            }
+        }
+        __syncthreads();
+        // ---- resample
+        for (int i = tid; i < nr * nx; i += JF_T) {
+            const int r = i / nx, xo = i - r * nx;
+            unsigned char* o = dst + ((size_t)r * n_px + x0 + xo) * 3;
+            if (!j.need_h) {
+                const int x = j.left + x0 + xo;
+                const unsigned v = x >= sx0 && x < sx1 ? s_rgb[r][x - sx0] : jf_pixel_global(g, x, ylo + r);
+                o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16);
+                continue;
+            }
+            int a0 = 1 << 21, a1 = a0, a2 = a0;                  // Pillow: from 2^(PRECISION_BITS - 1), as resize_h_kernel
+            if (span > 0 && s_xmin[xo] >= sx0 && s_cnt[xo] >= 0 && s_cnt[xo] <= hk && s_xmin[xo] + s_cnt[xo] <= sx1) {
+                const unsigned* px = &s_rgb[r][s_xmin[xo] - sx0];
+                const int* kk = &s_coef[xo * hk];
+                const int cnt = s_cnt[xo];
+                for (int k = 0; k < cnt; ++k) {
+                    const unsigned v = px[k];
+                    const int c = kk[k];
+                    a0 += (int)(v & 255u) * c; a1 += (int)((v >> 8) & 255u) * c; a2 += (int)(v >> 16) * c;
+                }
+            } else {
+                const int xmin = cf[x0 + xo], cnt = min(max(cf[n_px + x0 + xo], 0), hk);
+                const int* kk = cf + 2 * (size_t)n_px + (size_t)(x0 + xo) * hk;
+                for (int k = 0; k < cnt; ++k) {
+                    const unsigned v = jf_pixel_global(g, xmin + k, ylo + r);
+                    const int c = kk[k];
+                    a0 += (int)(v & 255u) * c; a1 += (int)((v >> 8) & 255u) * c; a2 += (int)(v >> 16) * c;
+                }
+            }
+            a0 >>= 22; a1 >>= 22; a2 >>= 22;
+            // three byte stores, as resize_h_kernel: the packed form has been miscompiled (resize_h_rgba_kernel's comment)
+            o[0] = (unsigned char)(a0 < 0 ? 0 : (a0 > 255 ? 255 : a0));
+            o[1] = (unsigned char)(a1 < 0 ? 0 : (a1 > 255 ? 255 : a1));
+            o[2] = (unsigned char)(a2 < 0 ? 0 : (a2 > 255 ? 255 : a2));
+        }
+        __syncthreads();                                         // the next chunk rewrites every LDS piece
+        x0 = x1;
+    }
+}
+
 
 // ---- Progressive files (SOF2, Huffman; ITU T.81 Annex G as libjpeg's jdphuff.c decodes it). The host (jpeg_parse.parse_progressive)
 // hands over only files whose scan script is complete - every coefficient of every component at Al = 0 by EOI - so that
@@ -1111,20 +1336,15 @@ extern "C" int64_t clipmi_jpeg_workspace_bytes(int64_t total_blocks, int ntables
            (int64_t)align_up((size_t)total_blocks * 64, 256);
 }
 
-extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
-                                       int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
-                                       void* ws_dev, int64_t ws_bytes, void* stream) {
+// The baseline decode up to the sample planes (shared by the decode and the transform entry) -> 0 and the planes, or an error
+static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                                int64_t total_blocks, int64_t max_blocks, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                hipStream_t st, unsigned char** planes_out) {
     static_assert(sizeof(JpegImage) == sizeof(clipmi_jpeg_image) && sizeof(JpegImage) == 288, "clipmi_jpeg_image layout");
-    if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || ntables < 1 || total_blocks < 1 ||
-        max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: bad arguments");
     if (ws_bytes < clipmi_jpeg_workspace_bytes(total_blocks, ntables))
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+        return set_err(CLIPMI_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
                        (long long)clipmi_jpeg_workspace_bytes(total_blocks, ntables));
-    if ((max_blocks + 127) / 128 > 0x7fffffffLL || (max_pixels + 255) / 256 > 0x7fffffffLL || n > 65535)
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: batch too large for one launch");
-    hipStream_t st = as_stream(stream);
+    if ((max_blocks + 127) / 128 > 0x7fffffffLL || n > 65535) return set_err(CLIPMI_EINVAL, "%s: batch too large for one launch", who);
     Arena ar(ws_dev, (size_t)ws_bytes);
     JpLut* luts = ar.take<JpLut>((size_t)ntables);
     short* coef = ar.take<short>((size_t)total_blocks * 64);
@@ -1132,7 +1352,7 @@ extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int 
     JpegImage* images = static_cast<JpegImage*>(images_dev);
     hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3((unsigned)n), dim3(256), 0, st, static_cast<unsigned char*>(streams_dev), images);
     CLIPMI_CHECK_LAUNCH("jpeg_unstuff_kernel");
-    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "jpeg_decode_rgb8: memset");
+    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: memset", who);
     hipLaunchKernelGGL(jpeg_build_luts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
     CLIPMI_CHECK_LAUNCH("jpeg_build_luts_kernel");
     hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n), dim3(JP_T), 0, st, static_cast<const unsigned char*>(streams_dev), images,
@@ -1143,10 +1363,59 @@ extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int 
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
                        status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
-                       static_cast<unsigned char*>(out_dev));
+    *planes_out = planes;
+    return 0;
+}
+
+extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                                       int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
+                                       void* ws_dev, int64_t ws_bytes, void* stream) {
+    if (n == 0) return 0;
+    if (!streams_dev || !images_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || ntables < 1 || total_blocks < 1 ||
+        max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: bad arguments");
+    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: batch too large for one launch");
+    hipStream_t st = as_stream(stream);
+    unsigned char* planes = nullptr;
+    if (int rc = jpeg_baseline_planes("jpeg_decode_rgb8", streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks,
+                                      status_dev, ws_dev, ws_bytes, st, &planes))
+        return rc;
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st,
+                       static_cast<const JpegImage*>(images_dev), planes, static_cast<unsigned char*>(out_dev));
     CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
     return 0;
+}
+
+// The transform entries' tail: the fused colour conversion + horizontal pass over the planes, then resize.hip's vertical pass
+static int jpeg_transform_tail(const JpegImage* images, const unsigned char* planes, int n, const void* jobs_dev,
+                               int max_rows, const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev, hipStream_t st) {
+    static_assert(sizeof(clipmi_resize_job) == 80, "clipmi_resize_job layout");
+    hipLaunchKernelGGL(jpeg_color_resize_h_kernel, dim3((unsigned)((max_rows + JF_ROWS - 1) / JF_ROWS), (unsigned)n), dim3(JF_T), 0, st,
+                       images, planes, static_cast<const clipmi_resize_job*>(jobs_dev), coef_dev, n_px,
+                       static_cast<unsigned char*>(scratch_dev));
+    CLIPMI_CHECK_LAUNCH("jpeg_color_resize_h_kernel");
+    return launch_resize_v_rgb8(jobs_dev, n, coef_dev, n_px, scratch_dev, out_dev, st);
+}
+
+static bool jpeg_transform_args_ok(const void* jobs_dev, int max_rows, const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev) {
+    return jobs_dev && coef_dev && out_dev && scratch_dev && n_px >= 1 && n_px <= 4096 && max_rows >= 1;
+}
+
+extern "C" int clipmi_jpeg_decode_transform_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                                                 int64_t total_blocks, int64_t max_blocks, const void* jobs_dev, int max_rows,
+                                                 const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev, int32_t* status_dev,
+                                                 void* ws_dev, int64_t ws_bytes, void* stream) {
+    if (n == 0) return 0;
+    if (!streams_dev || !images_dev || !tables_dev || !status_dev || !ws_dev || n < 0 || ntables < 1 || total_blocks < 1 ||
+        max_blocks < 1 || max_blocks > total_blocks || !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_transform_rgb8: bad arguments");
+    hipStream_t st = as_stream(stream);
+    unsigned char* planes = nullptr;
+    if (int rc = jpeg_baseline_planes("jpeg_decode_transform_rgb8", streams_dev, images_dev, n, tables_dev, ntables, total_blocks,
+                                      max_blocks, status_dev, ws_dev, ws_bytes, st, &planes))
+        return rc;
+    return jpeg_transform_tail(static_cast<const JpegImage*>(images_dev), planes, n, jobs_dev, max_rows, coef_dev, n_px, out_dev,
+                               scratch_dev, st);
 }
 
 extern "C" int64_t clipmi_jpeg_progressive_workspace_bytes(int n, int64_t total_blocks, int ntables) {
@@ -1155,30 +1424,24 @@ extern "C" int64_t clipmi_jpeg_progressive_workspace_bytes(int n, int64_t total_
            (int64_t)align_up((size_t)total_blocks * 128, 256) + (int64_t)align_up((size_t)total_blocks * 64, 256);
 }
 
-extern "C" int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev, int nscans,
-                                                   const void* tables_dev, int ntables, int64_t total_blocks, int64_t max_blocks,
-                                                   int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
-                                                   void* stream) {
+// The progressive decode up to the sample planes -> 0, the planes and the records jpeg_progressive_kernel wrote for the later kernels
+static int jpeg_progressive_planes(const char* who, const void* streams_dev, const void* images_dev, int n, const void* scans_dev,
+                                   int nscans, const void* tables_dev, int ntables, int64_t total_blocks, int64_t max_blocks,
+                                   int32_t* status_dev, void* ws_dev, int64_t ws_bytes, hipStream_t st, unsigned char** planes_out,
+                                   JpegImage** images_out) {
     static_assert(sizeof(JpegScan) == sizeof(clipmi_jpeg_scan) && sizeof(JpegScan) == 64, "clipmi_jpeg_scan layout");
     static_assert(sizeof(JpegProgImage) == sizeof(clipmi_jpeg_progressive_image) && sizeof(JpegProgImage) == 256,
                   "clipmi_jpeg_progressive_image layout");
-    if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 ||
-        ntables < 1 || total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: bad arguments");
     if (ws_bytes < clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, ntables))
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: workspace of %lld bytes, %lld needed", (long long)ws_bytes,
+        return set_err(CLIPMI_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
                        (long long)clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, ntables));
-    if ((max_blocks + 127) / 128 > 0x7fffffffLL || (max_pixels + 255) / 256 > 0x7fffffffLL || n > 65535)
-        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: batch too large for one launch");
-    hipStream_t st = as_stream(stream);
+    if ((max_blocks + 127) / 128 > 0x7fffffffLL || n > 65535) return set_err(CLIPMI_EINVAL, "%s: batch too large for one launch", who);
     Arena ar(ws_dev, (size_t)ws_bytes);
     JppLut* luts = ar.take<JppLut>((size_t)ntables);
     JpegImage* images = ar.take<JpegImage>((size_t)n);
     short* coef = ar.take<short>((size_t)total_blocks * 64);
     unsigned char* planes = ar.take<unsigned char>((size_t)total_blocks * 64);
-    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess)
-        return set_err(CLIPMI_EHIP, "jpeg_decode_progressive_rgb8: memset");
+    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: memset", who);
     hipLaunchKernelGGL(jpeg_build_pluts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
     CLIPMI_CHECK_LAUNCH("jpeg_build_pluts_kernel");
     hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)n), dim3(JPP_T), 0, st, static_cast<const unsigned char*>(streams_dev),
@@ -1188,8 +1451,47 @@ extern "C" int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, cons
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
                        status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
+    *planes_out = planes;
+    *images_out = images;
+    return 0;
+}
+
+extern "C" int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev, int nscans,
+                                                   const void* tables_dev, int ntables, int64_t total_blocks, int64_t max_blocks,
+                                                   int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
+                                                   void* stream) {
+    if (n == 0) return 0;
+    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 ||
+        ntables < 1 || total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: bad arguments");
+    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: batch too large for one launch");
+    hipStream_t st = as_stream(stream);
+    unsigned char* planes = nullptr;
+    JpegImage* images = nullptr;
+    if (int rc = jpeg_progressive_planes("jpeg_decode_progressive_rgb8", streams_dev, images_dev, n, scans_dev, nscans, tables_dev, ntables,
+                                         total_blocks, max_blocks, status_dev, ws_dev, ws_bytes, st, &planes, &images))
+        return rc;
     hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
                        static_cast<unsigned char*>(out_dev));
     CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
     return 0;
+}
+
+extern "C" int clipmi_jpeg_decode_progressive_transform_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev,
+                                                             int nscans, const void* tables_dev, int ntables, int64_t total_blocks,
+                                                             int64_t max_blocks, const void* jobs_dev, int max_rows,
+                                                             const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev,
+                                                             int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
+    if (n == 0) return 0;
+    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 || ntables < 1 ||
+        total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks ||
+        !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_transform_rgb8: bad arguments");
+    hipStream_t st = as_stream(stream);
+    unsigned char* planes = nullptr;
+    JpegImage* images = nullptr;
+    if (int rc = jpeg_progressive_planes("jpeg_decode_progressive_transform_rgb8", streams_dev, images_dev, n, scans_dev, nscans, tables_dev,
+                                         ntables, total_blocks, max_blocks, status_dev, ws_dev, ws_bytes, st, &planes, &images))
+        return rc;
+    return jpeg_transform_tail(images, planes, n, jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev, st);
 }

@@ -192,6 +192,17 @@ __global__ void __launch_bounds__(256) nearest_p8_kernel(const unsigned char* __
 }  // namespace
 }  // namespace clipmi
 
+// the vertical pass by itself: jpeg.hip's transform entries run it behind their own horizontal pass
+int clipmi::launch_resize_v_rgb8(const void* jobs_dev, int njobs, const int32_t* coef_dev, int n_px, const void* scratch_dev, void* out_dev,
+                                 hipStream_t st) {
+    const long long per_v = (long long)n_px * n_px;
+    hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)((per_v + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
+                       static_cast<const ResizeJob*>(jobs_dev), coef_dev, n_px, static_cast<const unsigned char*>(scratch_dev),
+                       static_cast<unsigned char*>(out_dev));
+    CLIPMI_CHECK_LAUNCH("resize_v_kernel");
+    return 0;
+}
+
 using namespace clipmi;
 
 extern "C" int clipmi_resize_crop_rgb8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
@@ -201,16 +212,12 @@ extern "C" int clipmi_resize_crop_rgb8(const void* raw_dev, const void* jobs_dev
     if (!raw_dev || !jobs_dev || !coef_dev || !out_dev || !scratch_dev || njobs < 0 || n_px < 1 || n_px > 4096 || max_rows < 1)
         return set_err(CLIPMI_EINVAL, "resize_crop_rgb8: bad arguments");
     hipStream_t st = as_stream(stream);
-    const long long per_h = (long long)max_rows * n_px, per_v = (long long)n_px * n_px;
+    const long long per_h = (long long)max_rows * n_px;
     hipLaunchKernelGGL(resize_h_kernel, dim3((unsigned)((per_h + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
                        static_cast<const unsigned char*>(raw_dev), static_cast<const ResizeJob*>(jobs_dev), coef_dev, n_px,
                        static_cast<unsigned char*>(scratch_dev));
     CLIPMI_CHECK_LAUNCH("resize_h_kernel");
-    hipLaunchKernelGGL(resize_v_kernel, dim3((unsigned)((per_v + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
-                       static_cast<const ResizeJob*>(jobs_dev), coef_dev, n_px, static_cast<const unsigned char*>(scratch_dev),
-                       static_cast<unsigned char*>(out_dev));
-    CLIPMI_CHECK_LAUNCH("resize_v_kernel");
-    return 0;
+    return launch_resize_v_rgb8(jobs_dev, njobs, coef_dev, n_px, scratch_dev, out_dev, st);
 }
 
 extern "C" int clipmi_resize_crop_rgba8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,

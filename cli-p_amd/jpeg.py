@@ -8,6 +8,8 @@ JPEG) raise `Unsupported` and stay with Pillow in the decode workers - that is a
 on the host from the file's own header; a file the device then reports (status != 0: 1 an invalid Huffman code, 2 the data
 ended early or ran over, 3 a marker inside a segment handed over with its stuffing, 4 a block whose IDCT leaves the range where
 libjpeg-turbo's provably equals the device's) goes the same way, so that Pillow's error handling stays the reference's.
+`transform_files` goes one step further: decode and the CLIP transform's resize + crop in one library call, without the full-size
+RGB rows in between (clipmi_jpeg_decode_transform_rgb8, opt-in in the pipeline: encode_files(jpeg_fused=True)).
 """
 import numpy as np
 import torch
@@ -215,3 +217,102 @@ def decode_progressive_files(blobs, device):
             h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
             res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
     return res
+
+
+# ---- decode + the transform in one call (csrc/jpeg.hip jpeg_color_resize_h_kernel): baseline and progressive files straight to
+# the uint8 [3, n_px, n_px] pixels `transform` computes before its float tail, the same bytes as decode + resize_crop_rgb8.
+class Staged:
+    """A batch of files parsed, planned and on the device (stage_transform), for run_transform"""
+    __slots__ = ("n", "n_px", "device", "groups", "keep")
+
+
+def stage_transform(blobs, n_px, device, keep_stuffing=False):
+    """JPEG file contents (or records parse / parse_progressive returned) -> Staged: the records of both kinds packed, the
+    transform planned with decode_worker's planner (resize.pack_jobs: job k writes block k of the output, whichever kind file k
+    is), everything copied to the device, workspaces allocated. Raises Unsupported for a file neither parser takes."""
+    from . import resize
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise _lib.ClipmiError("jpeg.stage_transform needs the HIP path (no CPU fallback)")
+    L = _lib.lib()
+    kinds = ([], [])                                      # (position, record) of the baseline and of the progressive files
+    for k, b in enumerate(blobs):
+        if not isinstance(b, (Parsed, Progressive)):
+            try:
+                b = parse(b, keep_stuffing=keep_stuffing)
+            except Unsupported:
+                b = parse_progressive(b)
+        kinds[isinstance(b, Progressive)].append((k, b))
+    st = Staged()
+    st.n, st.n_px, st.device, st.groups, st.keep = len(blobs), n_px, device, [], []
+    for progressive, members in enumerate(kinds):
+        if not members:
+            continue
+        items = [it for _, it in members]
+        if progressive:
+            recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items)
+            arrays = [recs, scans, tables]
+            ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(items), total_blocks, len(tables)))
+        else:
+            recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items)
+            arrays = [recs, tables]
+            ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, len(tables)))
+        jobs, coef, _, scratch_bytes, max_rows = resize.pack_jobs([(it.height, it.width) for it in items], n_px)
+        jobs["out_index"] = [k for k, _ in members]
+        jobs["src_off"] = recs["out_off"]                 # (the decoder's rows: what the unfused form's resize reads)
+        arrays += [jobs, coef, streams]
+        offs, end = [], 0
+        for a in arrays:
+            offs.append((end + 15) // 16 * 16)
+            end = offs[-1] + a.nbytes
+        host = torch.empty(max(end, 16), dtype=torch.uint8).pin_memory()
+        hv = host.numpy()
+        for a, o in zip(arrays, offs):
+            hv[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
+        dev = host.to(device, non_blocking=True)
+        st.keep.append(host)
+        st.groups.append(dict(progressive=bool(progressive), n=len(items), dev=dev, offs=offs, nscans=len(scans) if progressive else 0,
+                              ntables=len(tables), total_blocks=total_blocks, max_blocks=max_blocks, max_pixels=max_pixels,
+                              out_bytes=out_bytes, max_rows=max_rows, ws_bytes=ws_bytes,
+                              ws=torch.empty(ws_bytes, dtype=torch.uint8, device=device),
+                              scratch=torch.empty(scratch_bytes, dtype=torch.uint8, device=device),
+                              where=torch.tensor([k for k, _ in members], dtype=torch.long, device=device)))
+    return st
+
+
+def run_transform(st, fused=True):
+    """Staged -> (uint8 [n][3][n_px][n_px] device tensor, int32 [n] status device tensor; a file with a non-zero status has
+    unspecified pixels). fused: clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8; not fused: the decode
+    entries into full-size RGB rows, then clipmi_resize_crop_rgb8 over them. Asynchronous on torch's current stream."""
+    L = _lib.lib()
+    out = torch.empty((st.n, 3, st.n_px, st.n_px), dtype=torch.uint8, device=st.device)
+    status = torch.zeros(max(st.n, 1), dtype=torch.int32, device=st.device)
+    stream = _lib.stream_ptr(st.device)
+    for g in st.groups:
+        base, o = g["dev"].data_ptr(), g["offs"]
+        gst = torch.zeros(g["n"], dtype=torch.int32, device=st.device)
+        head = (base + o[-1], base, g["n"]) + ((base + o[1], g["nscans"], base + o[2]) if g["progressive"] else (base + o[1],))
+        head += (g["ntables"], g["total_blocks"], g["max_blocks"])
+        jobs, coef = base + o[-3], base + o[-2]
+        tail = (gst.data_ptr(), g["ws"].data_ptr(), g["ws_bytes"], stream)
+        if fused:
+            name = "clipmi_jpeg_decode_progressive_transform_rgb8" if g["progressive"] else "clipmi_jpeg_decode_transform_rgb8"
+            rc = getattr(L, name)(*head, jobs, g["max_rows"], coef, st.n_px, out.data_ptr(), g["scratch"].data_ptr(), *tail)
+            _lib.check(rc, name)
+        else:
+            name = "clipmi_jpeg_decode_progressive_rgb8" if g["progressive"] else "clipmi_jpeg_decode_rgb8"
+            rgb = torch.empty(max(g["out_bytes"], 16), dtype=torch.uint8, device=st.device)
+            _lib.check(getattr(L, name)(*head, g["max_pixels"], rgb.data_ptr(), *tail), name)
+            rc = L.clipmi_resize_crop_rgb8(rgb.data_ptr(), jobs, g["n"], g["max_rows"], coef, st.n_px, out.data_ptr(),
+                                           g["scratch"].data_ptr(), stream)
+            _lib.check(rc, "clipmi_resize_crop_rgb8")
+            rgb.record_stream(torch.cuda.current_stream(st.device))
+        status.index_copy_(0, g["where"], gst)
+    return out, status[:st.n]
+
+
+def transform_files(blobs, n_px, device, fused=True):
+    """JPEG file contents, baseline and progressive alike -> (uint8 [n][3][n_px][n_px] device tensor: Pillow's decode + bicubic resize
+    of the shorter side to n_px + centre crop, as decode_worker.load_uint8; int32 [n] status device tensor, as the decode entries').
+    fused=False computes the same through the decode entries and clipmi_resize_crop_rgb8, with the full-size RGB rows between."""
+    return run_transform(stage_transform(blobs, n_px, device), fused)

@@ -430,6 +430,27 @@ def _progressive_group(L, r):
             base, sb, len(recs), sb + offs[1], len(scans), sb + offs[2], nt, total, most, pixels, rgb, status, ws, ws_bytes, stream))
 
 
+def _baseline_fused_group(L, r):
+    """_baseline_group for clipmi_jpeg_decode_transform_rgb8: the call also takes tr = (the group's largest nrows, n_px, the batch's
+    tensor, the scratch rows) and no RGB rows; the jobs' coefficient offsets count from the segment's start, as for the resize entry"""
+    recs, tables, jobs, out_sz, blocks, nt = r
+    total, most = int(blocks.sum()), int(blocks.max())
+    ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total, nt))
+    return [recs, tables, jobs], out_sz, ws_bytes, "clipmi_jpeg_decode_transform_rgb8", lambda base, sb, offs, rgb, status, ws, stream, tr: (
+        L.clipmi_jpeg_decode_transform_rgb8(base, sb, len(recs), sb + offs[1], nt, total, most, sb + offs[2], tr[0], base, tr[1], tr[2],
+                                            tr[3], status, ws, ws_bytes, stream))
+
+
+def _progressive_fused_group(L, r):
+    recs, scans, tables, jobs, out_sz, blocks, nt = r
+    total, most = int(blocks.sum()), int(blocks.max())
+    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(recs), total, nt))
+    return [recs, scans, tables, jobs], out_sz, ws_bytes, "clipmi_jpeg_decode_progressive_transform_rgb8", (
+        lambda base, sb, offs, rgb, status, ws, stream, tr: L.clipmi_jpeg_decode_progressive_transform_rgb8(
+            base, sb, len(recs), sb + offs[1], len(scans), sb + offs[2], nt, total, most, sb + offs[3], tr[0], base, tr[1], tr[2], tr[3],
+            status, ws, ws_bytes, stream))
+
+
 def _png_group(L, r):
     recs, jobs, out_sz, raw_sz = r
     total, most = int(raw_sz.sum()), int(raw_sz.max())
@@ -464,8 +485,35 @@ _FORMATS = {KIND_BASELINE: (jpeg_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _b
             KIND_PNG_INDEX: (_png_mode_records(1), _png_mode_scanlines, _png_mode_group, 1, "clipmi_nearest_crop_p8")}
 
 
+# With jpeg_fused the two JPEG kinds go through the entries that decode and transform in one call (transform entry None: the
+# decode entry's call did it): no full-size RGB rows exist for them.
+_FUSED_FORMATS = {KIND_BASELINE: _FORMATS[KIND_BASELINE][:2] + (_baseline_fused_group, 3, None),
+                  KIND_PROGRESSIVE: _FORMATS[KIND_PROGRESSIVE][:2] + (_progressive_fused_group, 3, None)}
+
+
+def formats(jpeg_fused=False):
+    """_FORMATS, with the fused rows in place of the two JPEG kinds' when jpeg_fused"""
+    return {**_FORMATS, **_FUSED_FORMATS} if jpeg_fused else _FORMATS
+
+
+def jpeg_fused_default():
+    """$CLIPMI_DEVICE_JPEG_FUSED ("1" = on), off when unset"""
+    import os
+    return os.environ.get("CLIPMI_DEVICE_JPEG_FUSED", "0") not in ("", "0")
+
+
+def file_need(hd, fmt, n_px):
+    """Bytes of HBM each file of one kind needs while its group is decoded, out of the region headers hd ([n][JPEG_HDR_INTS]) and the
+    kind's row fmt of formats(): what its decoder needs, its full-size decoded rows (none where the decode entry transforms too)
+    and the rows between the resize's two passes. device_stage sizes its groups by it."""
+    records, decoder_bytes, group, px, entry = fmt
+    tmp_px = 0 if entry == "clipmi_nearest_crop_p8" else px      # scratch bytes per pixel of the rows between the passes
+    rows = 0 if entry is None else (hd[:, HDR.W] * hd[:, HDR.H] * px + 15) // 16 * 16
+    return decoder_bytes(hd) + rows + hd[:, HDR.NROWS] * n_px * tmp_px
+
+
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
-                 jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None):
+                 jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -490,6 +538,10 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     alpha, palette (depth 1/2/4/8, with or without tRNS) and grey depth 1/2/4 files that are not interlaced take the device as
     well (png_parse.parse(modes=True), clipmi_png_decode_px8, then clipmi_resize_crop_rgba8 or clipmi_nearest_crop_p8: Pillow
     resamples such files in their own mode), the same bytes as Pillow's. Off, such files stay with Pillow as before.
+    jpeg_fused (default $CLIPMI_DEVICE_JPEG_FUSED, else off; "1" = on): baseline and progressive files on the device go through
+    clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8, which convert and resample straight from
+    the decoder's sample planes: the same bytes, and no full-size RGB rows (3 bytes per pixel) in HBM, so that a group under
+    jpeg_group_mb holds more files. Off, nothing changes for any file.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
@@ -542,6 +594,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         device_png = os.environ.get("CLIPMI_DEVICE_PNG", "0") not in ("", "0")
     if device_png_modes is None:
         device_png_modes = os.environ.get("CLIPMI_DEVICE_PNG_MODES", "0") not in ("", "0")
+    if jpeg_fused is None:
+        jpeg_fused = jpeg_fused_default()
+    kind_formats = formats(jpeg_fused)
     full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
                  (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0))
 
@@ -641,27 +696,31 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                 # scanlines and RGB rows) fits a budget: a batch of thumbnails is one group, a batch of 12-megapixel photos many -
                 # they run one after the other through ONE workspace per kind (the side stream is in order), so that HBM holds a
                 # group, not a batch, of decoded photos. The kinds follow each other on the side stream in PARSED's order.
-                records, decoder_bytes, group, px, entry = _FORMATS[kind.kind]
+                records, decoder_bytes, group, px, entry = kind_formats[kind.kind]
                 tmp_px = 0 if entry == "clipmi_nearest_crop_p8" else px      # scratch bytes per pixel of the rows between the passes
                 hd = _headers(bigview, n, cap, slots)
-                need = decoder_bytes(hd) + (hd[:, HDR.W] * hd[:, HDR.H] * px + 15) // 16 * 16 + hd[:, HDR.NROWS] * n_px * tmp_px
+                need = file_need(hd, kind_formats[kind.kind], n_px)
                 calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
                 for lo, hi in _groups(need, jpeg_group_bytes):
                     arrays, out_sz, ws_bytes, name, decode = group(L, records(bigview, n, cap, slots[lo:hi], comp, n_px))
                     small, offs = _pack16(arrays)
                     dsmall = torch.from_numpy(small).to(dev)
                     nrows = hd[lo:hi, HDR.NROWS]
-                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()))
+                    ws_max, rgb_max = max(ws_max, ws_bytes), max(rgb_max, int(out_sz.sum()) if entry is not None else 0)
                     tmp_max = max(tmp_max, int((nrows * n_px * tmp_px).sum()))
                     calls.append((dsmall, offs, hi - lo, int(nrows.max()), name, decode, 4 * (status_at + lo)))
                     pending["keep"].append(dsmall)
                 ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
-                rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev)
+                rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev) if entry is not None else None
                 scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
 
                 def decode_kind(calls=calls, ws=ws, rgb=rgb, scratch=scratch, status=pending["status"], entry=entry):
                     for dsmall, offs, n_files, max_rows, name, decode, status_off in calls:
                         sb = dsmall.data_ptr()
+                        if entry is None:                    # (the decode entry transforms too: no full-size rows)
+                            _lib.check(decode(base, sb, offs, None, status.data_ptr() + status_off, ws.data_ptr(), _lib.stream_ptr(dev),
+                                              (max_rows, n_px, devt.data_ptr(), scratch.data_ptr())), name)
+                            continue
                         _lib.check(decode(base, sb, offs, rgb.data_ptr(), status.data_ptr() + status_off, ws.data_ptr(),
                                           _lib.stream_ptr(dev)), name)
                         resize_into_devt(rgb.data_ptr(), sb + offs[-1], n_files, max_rows, scratch, entry)

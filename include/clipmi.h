@@ -341,6 +341,25 @@ int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, const void* ima
                                         int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
                                         void* stream);
 
+/* ---- Baseline and progressive JPEG files straight to the transform's pixels (a further addition to ABI 8 in the sense of the
+ * PNG note below: two new entry points, nothing existing changes). The decode entries above followed by clipmi_resize_crop_rgb8,
+ * without the full-size RGB image between them: the colour conversion and the horizontal pass read the decoder's sample planes
+ * in the workspace, for the source rows and columns the n_px-wide window needs only, and clipmi_resize_crop_rgb8's vertical pass
+ * finishes. The arguments of the decode entries with the transform's in place of out_dev and max_pixels: jobs_dev, max_rows,
+ * coef_dev, n_px, out_dev (uint8 [.][3][n_px][n_px], block job.out_index) and scratch_dev as clipmi_resize_crop_rgb8 takes them.
+ * Job k belongs to image k; its w and h are the image's; its src_off and the image record's out_off are ignored. Workspace
+ * sizes: clipmi_jpeg_workspace_bytes / clipmi_jpeg_progressive_workspace_bytes. status_dev: as the decode entries; a file with a
+ * non-zero status leaves unspecified bytes in its block of out_dev and in its scratch rows, and nothing outside them. */
+int clipmi_jpeg_decode_transform_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                                      int64_t total_blocks, int64_t max_blocks, const void* jobs_dev, int max_rows,
+                                      const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev, int32_t* status_dev,
+                                      void* ws_dev, int64_t ws_bytes, void* stream);
+int clipmi_jpeg_decode_progressive_transform_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev,
+                                                  int nscans, const void* tables_dev, int ntables, int64_t total_blocks,
+                                                  int64_t max_blocks, const void* jobs_dev, int max_rows, const int32_t* coef_dev,
+                                                  int n_px, void* out_dev, void* scratch_dev, int32_t* status_dev, void* ws_dev,
+                                                  int64_t ws_bytes, void* stream);
+
 /* ---- PNG files on the device (an addition to ABI 8: two new entry points and one new record, nothing existing changes, so
  * CLIPMI_ABI_VERSION stays 8). The same bytes as Pillow's `Image.open(f).convert("RGB")` for the files the host parser lets
  * through (cli-p_amd/png_parse.py: 8-bit grey or RGB, not interlaced, at most 16384 pixels wide, no tRNS, no APNG chunk, and no
