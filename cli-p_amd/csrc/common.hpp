@@ -41,13 +41,11 @@ struct Arena {
 
 // Development knobs. The CLIPMI_* environment variables that A/B runs and tools/ use exist only in the -DCLIPMI_DEV build
 // (libclipmi_dev.so: cli-p_amd/build.py --dev); the product library reads no environment variable on any path, and the
-// laboratory kernels (live-threshold scan, gemm2w, the scan ablations) are not compiled into it.
+// laboratory kernels (the wide scan's ablations and four-wave form, the folded-LayerNorm FP8 tower) are not compiled into it.
 #ifdef CLIPMI_DEV
 inline long long dev_knob(const char* name, long long dflt) { const char* e = getenv(name); return e && *e ? atoll(e) : dflt; }
-inline bool dev_knob_set(const char* name) { return getenv(name) != nullptr; }
 #else
 constexpr long long dev_knob(const char*, long long dflt) { return dflt; }
-constexpr bool dev_knob_set(const char*) { return false; }
 #endif
 
 // resize.hip: resize_v_kernel over clipmi_resize_job records (the second pass of clipmi_resize_crop_rgb8)

@@ -405,42 +405,54 @@ __host__ __device__ constexpr int sel_stage_entries(int K, int limit = LDS_LIMIT
 // the block copies it into LDS once (loads batched four deep) and every pass runs out of LDS: the per-pass loop
 // (load, LDS atomic, next load) otherwise pays one L2 round trip per 512 entries, ~17 us for a 7 k-entry list
 // against ~5 us staged (seven selects per 64-query search).
-__global__ void __launch_bounds__(SEL_THREADS) select_topk_kernel(const uint2* __restrict__ cand,
-                                                                 unsigned* __restrict__ gcnt, long long cap,
-                                                                 int K, long long id_base, float* out_s,
-                                                                 long long* out_i, float* thr_out,
-                                                                 const unsigned* run_if, unsigned* m_out = nullptr,
-                                                                 int keep = 0, int stage_cap = -1, float* qmeta = nullptr,
-                                                                 int qs = 64, unsigned* live_keys = nullptr,
-                                                                 float* live_edges = nullptr, int dense = 0,
-                                                                 unsigned* arm_fallback = nullptr) {
+struct SelectArgs {
+    const uint2* cand;                  // [queries][cap] candidate lists, unsorted (keep: the K best go back to their heads)
+    unsigned* gcnt;                     // entries used per query; left at 0 (keep & 1: at min(M, K)) for the call's next scan
+    long long cap;
+    int K;
+    long long id_base = 0;              // added to the row ids written to out_i
+    float* out_s = nullptr;             // [queries][K] scores and ids in rank order, padded with (-FLT_MAX, -1); null: no result
+    long long* out_i = nullptr;
+    float* thr_out = nullptr;           // [queries] the exact K-th best score (-inf with fewer than K entries), or null
+    const unsigned* run_if = nullptr;   // optional device flag: the kernel exits at once when *run_if == 0
+    unsigned* m_out = nullptr;          // [queries] list lengths, for the measurement hooks (keep & 2: added to what is there)
+    int keep = 0;                       // bit 0: the K selected entries stay at the head of the list for the next segment
+    int stage_cap = -1;                 // entries of LDS the launch reserved behind the K-entry result (-1: the most K leaves)
+    float* qmeta = nullptr;             // coarse search ([4][qs], coarse_prep_kernel): the next scan's threshold goes to [2 qs]
+    int qs = 64;                        // qmeta's stride
+    int dense = 0;                      // the list is a sample's: entry e IS row e, only the 4 score bytes are staged
+    unsigned* arm_fallback = nullptr;   // set to 1 when a query's margin in qmeta is +inf (no usable coarse bound)
+};
+
+__global__ void __launch_bounds__(SEL_THREADS) select_topk_kernel(SelectArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    if (run_if && *run_if == 0) return;
+    if (a.run_if && *a.run_if == 0) return;
     // the sample's select of a coarse search: a query without a usable coarse bound (NaN / infinite component: its margin is +inf,
     // coarse_prep_kernel) arms the exact fallback for the call - the coarse lists canonicalise NaN scores to -inf, which only the
     // exact scan tells from a true -inf (the oracle never returns a NaN-scoring row). (Set here, not by coarse_prep_kernel: that
     // launch also CLEARS the flag.)
-    if (arm_fallback && qmeta && threadIdx.x == 0 && qmeta[3 * qs + blockIdx.x] == INFINITY) *arm_fallback = 1u;
+    if (a.arm_fallback && a.qmeta && threadIdx.x == 0 && a.qmeta[3 * a.qs + blockIdx.x] == INFINITY) *a.arm_fallback = 1u;
     unsigned long long* red = reinterpret_cast<unsigned long long*>(smem);   // [16] min, [16] max
     unsigned* hist = reinterpret_cast<unsigned*>(red + 32);                  // [256]
     unsigned* wsum = hist + 256;                                             // [8]
     unsigned* ctl = wsum + 8;                                                // [8] b, above, nsel
+    const int K = a.K;
     uint2* sel = reinterpret_cast<uint2*>(ctl + 8);                          // [K]
     uint2* lent = sel + K;                                                   // [SEL_STAGE] staged copy of the list
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int q = blockIdx.x;
-    long long M = gcnt[q];
-    if (M > cap) M = cap;
-    const uint2* src = cand + (size_t)q * cap;
+    long long M = a.gcnt[q];
+    if (M > a.cap) M = a.cap;
+    const uint2* src = a.cand + (size_t)q * a.cap;
     const int need = (int)(M < K ? M : K);
     // stage_cap: entries of LDS the launch reserved behind the K-entry result buffer (-1: the most K leaves room for)
-    const bool staged = M <= (stage_cap < 0 ? sel_stage_entries(K) : stage_cap);
+    const bool staged = M <= (a.stage_cap < 0 ? sel_stage_entries(K) : a.stage_cap);
     // dense (the wide pass's sample lists: entry e IS row e - sample_scores_kernel writes cand[q][row] = (score, row)): only the
     // 4 score bytes of an entry are staged, the id is the index - 48 KiB instead of 96 for 12 288 rows, so three select blocks
     // fit on a CU instead of one (1024 of them per call of 1024 queries: 121 -> ~50 us)
     unsigned* const l32 = reinterpret_cast<unsigned*>(lent);
-    if (staged && dense) {
+    if (staged && a.dense) {
         for (long long e0 = tid; e0 < M; e0 += 4 * SEL_THREADS) {
             unsigned v[4];
 #pragma unroll
@@ -485,9 +497,9 @@ __global__ void __launch_bounds__(SEL_THREADS) select_topk_kernel(const uint2* _
             }
     #pragma unroll
             for (int o = 32; o >= 1; o >>= 1) {
-                const unsigned long long a = __shfl_xor(kmin, o), b = __shfl_xor(kmax, o);
-                kmin = a < kmin ? a : kmin;
-                kmax = b > kmax ? b : kmax;
+                const unsigned long long lo = __shfl_xor(kmin, o), hi = __shfl_xor(kmax, o);
+                kmin = lo < kmin ? lo : kmin;
+                kmax = hi > kmax ? hi : kmax;
             }
             if (lane == 0) { red[wave] = kmin; red[16 + wave] = kmax; }
             __syncthreads();
@@ -550,66 +562,41 @@ __global__ void __launch_bounds__(SEL_THREADS) select_topk_kernel(const uint2* _
             }
         }
         __syncthreads();
-        uint2* dst_keep = keep ? const_cast<uint2*>(src) : nullptr;      // every read of src is behind the barrier above
+        uint2* dst_keep = a.keep ? const_cast<uint2*>(src) : nullptr;     // every read of src is behind the barrier above
         for (int e = tid; e < need; e += SEL_THREADS) {
             const uint2 me = sel[e];
             const unsigned long long mk = ckey(me);
             int rank = 0;
             for (int j = 0; j < need; ++j) rank += ckey(sel[j]) > mk ? 1 : 0;
             if (dst_keep) dst_keep[rank] = me;
-            if (out_s) {
-                out_s[(size_t)q * K + rank] = __uint_as_float(me.x);
-                out_i[(size_t)q * K + rank] = id_base + (long long)me.y;
+            if (a.out_s) {
+                a.out_s[(size_t)q * K + rank] = __uint_as_float(me.x);
+                a.out_i[(size_t)q * K + rank] = a.id_base + (long long)me.y;
             }
-            if (thr_out && rank == K - 1) thr_out[q] = __uint_as_float(me.x);
-            if (live_keys) {                                   // the sample's best and K-th best: the live scan's ladder
-                if (rank == 0) ctl[5] = me.x;
-                if (rank == K - 1) ctl[6] = me.x;
-            }
+            if (a.thr_out && rank == K - 1) a.thr_out[q] = __uint_as_float(me.x);
             // coarse search: the next segment's scan threshold, (tau - margin) / t_q (coarse_prep_kernel's qmeta)
             // (an infinite margin - a non-finite query, coarse_prep_kernel - means "no threshold", not inf - inf)
-            if (qmeta && rank == K - 1)
-                qmeta[2 * qs + q] = qmeta[3 * qs + q] == INFINITY ? -INFINITY : (__uint_as_float(me.x) - qmeta[3 * qs + q]) * qmeta[q];
+            if (a.qmeta && rank == K - 1)
+                a.qmeta[2 * a.qs + q] = a.qmeta[3 * a.qs + q] == INFINITY ? -INFINITY : (__uint_as_float(me.x) - a.qmeta[3 * a.qs + q]) * a.qmeta[q];
         }
-        if (out_s)
+        if (a.out_s)
             for (int e = need + tid; e < K; e += SEL_THREADS) {
-                out_s[(size_t)q * K + e] = -FLT_MAX;
-                out_i[(size_t)q * K + e] = -1;
+                a.out_s[(size_t)q * K + e] = -FLT_MAX;
+                a.out_i[(size_t)q * K + e] = -1;
             }
-        if (thr_out && need < K && tid == 0) thr_out[q] = -INFINITY;
-        if (qmeta && need < K && tid == 0) qmeta[2 * qs + q] = -INFINITY;
+        if (a.thr_out && need < K && tid == 0) a.thr_out[q] = -INFINITY;
+        if (a.qmeta && need < K && tid == 0) a.qmeta[2 * a.qs + q] = -INFINITY;
     };
-    if (staged && dense) passes([&](long long e) -> uint2 { return make_uint2(l32[e], (unsigned)e); });
+    if (staged && a.dense) passes([&](long long e) -> uint2 { return make_uint2(l32[e], (unsigned)e); });
     else if (staged) passes([&](long long e) -> uint2 { return lent[e]; });
     else passes([&](long long e) -> uint2 { return src[e]; });
-    if (live_keys) {
-        // live-threshold scan (scan_coarse_live_kernel): exact threshold = the sample's K-th best, ladder of LIVE_NB edges
-        // above it in steps of an eighth of the sample top-K's spread; with fewer than K sample rows nothing is filtered
-        __syncthreads();
-        if (tid == 0) {
-            float e0 = -FLT_MAX, dl = 1.0f, tex = -INFINITY, tsc = -INFINITY;
-            const float best = need >= K ? __uint_as_float(ctl[5]) : 0.f, kth = need >= K ? __uint_as_float(ctl[6]) : 0.f;
-            if (need >= K && fabsf(best) < FLT_MAX && fabsf(kth) < FLT_MAX) {      // finite (NaN compares false)
-                e0 = kth;
-                dl = (best - kth) * 0.125f;
-                const float floor_ = fabsf(kth) * 1e-6f + 1e-12f;
-                if (!(dl > floor_)) dl = floor_;
-                tex = kth;
-                tsc = (kth - qmeta[3 * qs + q]) * qmeta[q];
-            }
-            live_keys[q] = ((__float_as_uint(tsc) & 0x80000000u) ? ~__float_as_uint(tsc) : (__float_as_uint(tsc) | 0x80000000u));
-            live_keys[64 + q] = ((__float_as_uint(tex) & 0x80000000u) ? ~__float_as_uint(tex) : (__float_as_uint(tex) | 0x80000000u));
-            live_edges[q] = e0;
-            live_edges[64 + q] = dl;
-        }
-    }
     // leave the counter zeroed for the next scan of this call (every thread read M at entry; the
     // barriers above order that read before this store) — saves a memset node per scan
     // keep = 1 (segmented coarse scan): the K selected entries stay at the head of the list and the next segment's
     // survivors are appended behind them; keep bit 1: add to the measurement counter instead of overwriting it
     if (tid == 0) {
-        gcnt[q] = keep & 1 ? (unsigned)need : 0u;
-        if (m_out) m_out[q] = (keep & 2 ? m_out[q] : 0u) + (unsigned)M;        // list length(s), for measurement hooks
+        a.gcnt[q] = a.keep & 1 ? (unsigned)need : 0u;
+        if (a.m_out) a.m_out[q] = (a.keep & 2 ? a.m_out[q] : 0u) + (unsigned)M;       // list length(s), for measurement hooks
     }
 }
 
@@ -792,10 +779,6 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
 // and the query image the scan kernels copy into LDS (entry [(qg*KS + s)*64 + lane] = 16 bytes of query 16 qg + (lane & 15):
 // bf16 k = 32 s + 8 g .. + 7, or int8 k = 64 s + 16 g .. + 15, g = lane >> 4; zero for queries >= QA). Block 0 also clears
 // the call's control words (candidate counters, overflow flag): no memset node.
-// q2 (int8, 64-query passes; round 4): the query as TWO int8 digits, y = t p1 + (t / 254) p2 + f' - the second image sits
-// COARSE_IMG2 entries behind the first and the margin is built from ||f'|| (1 / 254 of ||f||): the query's half of the
-// bound's margin is gone, the scan pays a second MFMA per fragment (it is HBM-latency bound with the matrix pipe 16 % busy).
-constexpr int COARSE_IMG2 = 4 * 8 * 64;          // entries of a full 64-query int8 image at E = 512 (32 KiB); q2 is 512-only
 // Rounding slack of the two superset bounds as a function of the row width (derivations: DESIGN.md 4.1l, summary here).
 // int8: the test compares f32 evaluations of both sides of
 //      s_r t_q D + a_r 1.001 ||y||  >=  tau_q - 1.001 (R_max + A_max) ||f_q||,
@@ -824,7 +807,7 @@ static_assert(768 * 127 * 127 < (1 << 24), "the int8 dot product must stay exact
 template <bool I8, int ET = 512>
 __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restrict__ q, int E, float rmax, float amax, int QA,
                                                           float* qmeta, uint4* qimage, unsigned* ctl, int nctl, int qs,
-                                                          int wide = 0, int q2 = 0) {
+                                                          int wide = 0) {
     constexpr int KS = ET / (I8 ? 64 : 32);         // k-steps of the 64-query image; E == ET
     constexpr int KSW = ET / 32;                    // k-steps of the wide image: 16 at 512, 24 at 768 (2 KSW <= 64 lanes write it)
     const int lane = threadIdx.x & 63;
@@ -839,10 +822,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
         if (wide) { if (lane < 2 * KSW) qimage[widx] = make_uint4(0u, 0u, 0u, 0u); }
         else
             // KS * 4 entries per query: 32 (int8) or 64 (bf16) at E = 512 - one round of the wave -, 48 or 96 at E = 768
-            for (int e = lane; e < KS * 4; e += 64) {
-                qimage[(qg * KS + (e >> 2)) * 64 + (e & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
-                if (I8 && q2) qimage[COARSE_IMG2 + (qg * KS + (e >> 2)) * 64 + (e & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
-            }
+            for (int e = lane; e < KS * 4; e += 64) qimage[(qg * KS + (e >> 2)) * 64 + (e & 3) * 16 + col] = make_uint4(0u, 0u, 0u, 0u);
         return;
     }
     const float* y = q + (size_t)qi * E;
@@ -852,20 +832,12 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
     for (int o = 32; o >= 1; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); ss += __shfl_xor(ss, o); }
     const float t = mx > 0.f ? mx / 127.0f : 1.0f;
     const float inv = I8 ? 1.0f / t : 1.0f;
-    const float t2 = t * (1.0f / 254.0f), inv2 = 1.0f / t2;             // second digit's step (q2)
-    // both digits of component v and what they leave; the query images below use the same expressions
-    auto digits = [&](float v, float& p1, float& p2) -> float {
-        p1 = fminf(fmaxf(rintf(v * inv), -127.f), 127.f);
-        const float r1 = fmaf(-t, p1, v);
-        if (!q2) { p2 = 0.f; return r1; }
-        p2 = fminf(fmaxf(rintf(r1 * inv2), -127.f), 127.f);
-        return fmaf(-t2, p2, r1);
-    };
+    // the int8 digit of component v; the query images below use the same expression
+    auto digit = [&](float v) -> float { return fminf(fmaxf(rintf(v * inv), -127.f), 127.f); };
     float ff = 0.f;
     if (I8) {
         for (int k = lane; k < E; k += 64) {
-            float p1, p2;
-            const float f = digits(y[k], p1, p2);
+            const float f = fmaf(-t, digit(y[k]), y[k]);       // what the digit leaves: f_q
             ff = fmaf(f, f, ff);
         }
 #pragma unroll
@@ -895,8 +867,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
                 unsigned pk = 0;
 #pragma unroll
                 for (int b_ = 0; b_ < 4; ++b_) {
-                    const float pq = fminf(fmaxf(rintf(p[4 * j + b_] * inv), -127.f), 127.f);
-                    pk |= ((unsigned)(int)pq & 0xffu) << (8 * b_);
+                    pk |= ((unsigned)(int)digit(p[4 * j + b_]) & 0xffu) << (8 * b_);
                 }
                 w[j] = pk;
             }
@@ -909,22 +880,15 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
         uint4 v;
         if (I8) {
             const float* p = y + 64 * s_ + 16 * g_;
-            unsigned w[4], w2[4];
+            unsigned w[4];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                unsigned pk = 0, pk2 = 0;
+                unsigned pk = 0;
 #pragma unroll
-                for (int b_ = 0; b_ < 4; ++b_) {
-                    float p1, p2;
-                    (void)digits(p[4 * j + b_], p1, p2);
-                    pk |= ((unsigned)(int)p1 & 0xffu) << (8 * b_);
-                    pk2 |= ((unsigned)(int)p2 & 0xffu) << (8 * b_);
-                }
+                for (int b_ = 0; b_ < 4; ++b_) pk |= ((unsigned)(int)digit(p[4 * j + b_]) & 0xffu) << (8 * b_);
                 w[j] = pk;
-                w2[j] = pk2;
             }
             v = make_uint4(w[0], w[1], w[2], w[3]);
-            if (q2) qimage[COARSE_IMG2 + (qg * KS + s_) * 64 + g_ * 16 + col] = make_uint4(w2[0], w2[1], w2[2], w2[3]);
         } else {
             const float* p = y + 32 * s_ + 8 * g_;
             v = make_uint4(pack2_bf16(p[0], p[1]), pack2_bf16(p[2], p[3]), pack2_bf16(p[4], p[5]), pack2_bf16(p[6], p[7]));
@@ -938,7 +902,7 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
 // the head of the list - is recognised and keeps its row id.
 // INVARIANT: every writer of cand[].x - sample_scores_kernel, rescore_pairs_kernel, rescore_pairs16_kernel and the
 // heads select_topk_kernel keeps (it copies .x unchanged) - stores either CAND_SLOT with a slot, or the RAW bits of a score that is
-// not a NaN (NaN -> -inf before the store). Never an fkey()-encoded key, never raw bits of an unchecked score: 0xffffffff is a NaN
+// not a NaN (NaN -> -inf before the store). Never an order-preserving key of one, never raw bits of an unchecked score: 0xffffffff is a NaN
 // pattern and would be read as "slot". tests/test_topk_gpu.py::test_non_finite_queries_through_the_permuted_int8_copy holds it.
 constexpr unsigned CAND_SLOT = 0xffffffffu;
 constexpr size_t RESCORE16_LDS = 512 * 4 + 4 * 16 * 68 * 4;      // rescore_pairs16_kernel (E = 512 only: the wide passes): the query + four waves' tiles of 16 row chunks
@@ -985,7 +949,6 @@ __device__ __noinline__ void coarse_flush(const uint2* list, int n, unsigned* gc
 
 // PREPASS only changes the kernel's NAME (the level-2 pre-pass over S2 rows must not dilute the profiler's
 // per-name average of the main scan).
-// Q2 (int8 only): two query digits (coarse_prep_kernel q2) - 2 QG MFMAs per fragment, D = D1 + D2 / 254.
 // 16 bytes of the streamed coarse copy (CLIPMI_NT_MASK bit 0: non-temporal)
 __device__ __forceinline__ uint4 ld_stream(const char* p) {
     typedef unsigned u4v __attribute__((ext_vector_type(4)));
@@ -996,16 +959,14 @@ __device__ __forceinline__ uint4 ld_stream(const char* p) {
         return *reinterpret_cast<const uint4*>(p);
 }
 
-template <int E, int QG, bool PREPASS, bool I8, bool Q2 = false>
+template <int E, int QG, bool PREPASS, bool I8>
 __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
-    static_assert(!Q2 || I8, "the second query digit belongs to the int8 copy");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int KS = E / (I8 ? 64 : 32);   // MFMA k-steps per 16-row tile (16 bytes per lane and step either way)
     constexpr int ROWB = I8 ? E : 2 * E;     // bytes per row of the coarse copy
     constexpr int SLOTS = 2 * KS;       // one step = two row tiles (32 rows): SLOTS 16-byte fragments per lane
-    constexpr int NIMG = QG * KS * 64;                  // 16-byte entries of one query image
-    constexpr int ND = Q2 ? 2 : 1;                      // query digits
-    constexpr int IMG_BYTES = ND * NIMG * 16;
+    constexpr int NIMG = QG * KS * 64;                  // 16-byte entries of the query image
+    constexpr int IMG_BYTES = NIMG * 16;
     static_assert(COARSE_LIST >= COARSE_FLUSH + 4 * 64, "a block's appends must fit behind a pending flush");
 
     const int tid = threadIdx.x;
@@ -1026,13 +987,6 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
 #pragma unroll
             for (int j = 0; j < 8; ++j)
                 if (base + j * 256 < NIMG) qimg[base + j * 256] = v[j];
-            if constexpr (Q2) {                                  // the second digit's image, NIMG entries behind the first in LDS
-#pragma unroll
-                for (int j = 0; j < 8; ++j) v[j] = base + j * 256 < NIMG ? a.qimage[COARSE_IMG2 + base + j * 256] : make_uint4(0u, 0u, 0u, 0u);
-#pragma unroll
-                for (int j = 0; j < 8; ++j)
-                    if (base + j * 256 < NIMG) qimg[NIMG + base + j * 256] = v[j];
-            }
         }
     }
     uint2* list = reinterpret_cast<uint2*>(smem + IMG_BYTES + (size_t)wave * COARSE_WAVE_BYTES);
@@ -1099,23 +1053,21 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
             uint4 MN[4] = {};
             load_meta(has_next ? nxt : step, MN);
 
-            AccT acc[2][ND * QG];                       // [rt][digit * QG + qg]
+            AccT acc[2][QG];                            // [rt][qg]
 #pragma unroll
             for (int rt = 0; rt < 2; ++rt)
 #pragma unroll
-                for (int qg = 0; qg < ND * QG; ++qg) acc[rt][qg] = AccT{0, 0, 0, 0};
+                for (int qg = 0; qg < QG; ++qg) acc[rt][qg] = AccT{0, 0, 0, 0};
             // One slot at a time: the LDS reads of the NEXT slot's query fragments, this slot's MFMAs, then the refill of
             // this slot's register with the next step's fragment. A load can only be issued once the MFMAs reading its
             // register have been, and its data is needed one step later, so a step lasts (HBM latency + the MFMA time
             // between two refills): refilling after every slot instead of every 8 (the first version) keeps that second
             // term at QG MFMAs - main scan 629-648 -> 619 us at 10 M rows. The sched_group_barriers state the order; no
             // fake dependency on the accumulators is needed.
-            uint4 B[2][ND * QG];
+            uint4 B[2][QG];
             auto load_b = [&](int s_, uint4* b) {
 #pragma unroll
-                for (int d = 0; d < ND; ++d)
-#pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) b[d * QG + qg] = qimg[d * NIMG + (qg * KS + s_) * 64 + lane];
+                for (int qg = 0; qg < QG; ++qg) b[qg] = qimg[(qg * KS + s_) * 64 + lane];
             };
             __builtin_amdgcn_sched_barrier(0);
             load_b(0, B[0]);
@@ -1128,7 +1080,7 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
                 if (slot + 1 < SLOTS) load_b((slot + 1) % KS, B[(slot + 1) & 1]);
                 const uint4* b = B[slot & 1];
 #pragma unroll
-                for (int qg = 0; qg < ND * QG; ++qg) {
+                for (int qg = 0; qg < QG; ++qg) {
                     if constexpr (I8)
                         acc[rt][qg] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, T[slot]),
                                                                             __builtin_bit_cast(i32x4, b[qg]), acc[rt][qg], 0, 0, 0);
@@ -1138,12 +1090,11 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
                 }
                 T[slot] = ld_stream(pn[rt] + KSTRIDE * (slot % KS));
             }
-            constexpr int NBQ = ND * QG;
-            __builtin_amdgcn_sched_group_barrier(0x100, NBQ, 0);               // slot 0's fragments
+            __builtin_amdgcn_sched_group_barrier(0x100, QG, 0);                // slot 0's fragments
 #pragma unroll
             for (int slot = 0; slot < SLOTS; ++slot) {
-                if (slot + 1 < SLOTS) __builtin_amdgcn_sched_group_barrier(0x100, NBQ, 0);   // DS reads: next slot's fragments
-                __builtin_amdgcn_sched_group_barrier(0x008, NBQ, 0);                         // MFMAs of this slot
+                if (slot + 1 < SLOTS) __builtin_amdgcn_sched_group_barrier(0x100, QG, 0);    // DS reads: next slot's fragments
+                __builtin_amdgcn_sched_group_barrier(0x008, QG, 0);                          // MFMAs of this slot
                 __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);                           // VMEM read: the refill
             }
             __builtin_amdgcn_sched_barrier(0);
@@ -1160,8 +1111,7 @@ __global__ void __launch_bounds__(256) scan_coarse_kernel(CoarseArgs a) {
                 for (int qg = 0; qg < QG; ++qg)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        float d = (float)acc[rt][qg][r];
-                        if constexpr (Q2) d = fmaf((float)acc[rt][QG + qg][r], 1.0f / 254.0f, d);
+                        const float d = (float)acc[rt][qg][r];
                         val[rt][qg][r] = I8 ? fmaf(d, sr[r], ar[r] * yt[qg]) : d;
                     }
             }
@@ -1369,522 +1319,6 @@ __global__ void __launch_bounds__(256) rescore_pairs_kernel(const float* __restr
         if (my < M) lst[my] = make_uint2(__float_as_uint(acc == acc ? acc : -INFINITY), id_my);      // NaN never ranks
     }
 }
-
-// =================================================================================================
-// Live-threshold scan (int8 copy, <= 64 queries): ONE launch over all rows, exact re-scoring INSIDE the scan.
-//
-// The segmented form above re-scores and selects between launches: 13 launches per call, ~250 us of latency-bound side
-// kernels beside 0.88 ms of scans at 10 M rows, and 5.8 k exactly re-scored rows per query because a segment's threshold
-// is frozen at its start. Here a workgroup is 4 SCANNER waves (the loop of scan_coarse_kernel) + 4 RE-SCORING waves.
-// Scanners push the pairs that pass the coarse test into a ring in LDS and never wait for anything else; re-scoring waves
-// pop them, drop what a since-risen threshold has made stale (the pair carries its coarse upper bound), gather row and
-// query from global memory, run the score-order fmaf chain (the SAME bits as rescore_pairs_kernel and the oracle), and
-// append (exact score, row) to the query's global candidate list when it reaches the query's exact threshold.
-// Thresholds rise DURING the scan through a per-query ladder in global memory: NB buckets of exact scores above the
-// sample's K-th best (edge_b = e0 + b delta, delta = an eighth of the sample top-K's spread); a re-scored row bumps its
-// bucket, and whoever bumps re-reads the query's 32 counters: the highest edge with >= K rows at or above it IS a lower
-// bound of the final K-th best (K rows score at least that), published with atomicMax as an order-preserving key - the
-// exact threshold for the re-scoring waves, (edge - margin) / t_q for the scanners, who re-read their 64 keys every step.
-// Exactness never depends on the ladder's timing: every published threshold is a valid lower bound, a true top-K row
-// passes the coarse test against any of them and its exact score reaches any of them.
-// Every spin is bounded (a wave that waits too long sets the overflow flag = the exact fallback answers, still exact).
-// =================================================================================================
-constexpr int LIVE_NB = 32;                      // ladder buckets per query
-#ifdef CLIPMI_DEV                                // (LIVE_NB also sizes the product's control block: it stays outside)
-constexpr int LIVE_QN = 4096;                    // ring entries (32 KiB)
-constexpr unsigned LIVE_EMPTY = 0xffffffffu;
-constexpr int LIVE_ROW_BITS = 26;                // ring entry .y = (query << 26) | row: shards of < 2^26 rows
-constexpr int LIVE_WB = 24;                      // 32-row steps per batch of scanner work a workgroup draws (>= its scanner waves)
-constexpr int LIVE_SPIN_LIMIT = 1 << 20;         // polls before a waiting lane gives up (~ tens of ms): overflow -> fallback
-#endif
-
-__device__ __forceinline__ unsigned fkey(float f) {             // order-preserving key of a float (-0 and +0 differ: harmless)
-    const unsigned u = __float_as_uint(f);
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(unsigned k) {
-    return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k);
-}
-
-struct LiveArgs {
-    const signed char* dbc;      // int8 copy (32-row blocks)
-    const float2* rmeta;         // per row (block scale, error norm)
-    const unsigned* slot_rows;   // the row each slot of the copy holds (quantize_rows_i8_kernel)
-    const float* db;             // f32 [N][512]
-    const float* q;              // f32 [QA][512]
-    const float* qmeta;          // [4][64]: 1/t | Y/t | (unused here) | margin
-    const uint4* qimage;         // 16x16x64 image of the queries (coarse_prep_kernel)
-    long long nrows;             // rows [0, nrows)
-    int QA, K;
-    unsigned* tau_key;           // [64] key of the scaled coarse threshold (live)
-    unsigned* tex_key;           // [64] key of the exact threshold (live)
-    const float* edge0;          // [64] ladder origin = the sample's exact K-th best
-    const float* delta;          // [64] ladder step > 0
-    unsigned* hist;              // [64][LIVE_NB]
-    uint2* cand;                 // [QA][cap] (exact score bits, row)
-    unsigned* gcnt;              // [64]
-    long long cap;
-    unsigned* overflow;
-    unsigned* chunk_ctr;         // work counter of the scanner waves (zero at launch)
-    int wb;                      // 32-row steps per work batch (>= the scanner waves of a workgroup)
-    int abl;                     // development ablation (CLIPMI_LIVE_ABL): 1 scanners push nothing, 2 re-scoring waves drop every pair
-    unsigned* stats;             // [12] pushed | push spins | popped | stale | re-scored | inserted | batches | ladder rises
-};
-
-#ifdef CLIPMI_DEV      // experimental: compiled into the development library only
-template <int QG, int NSCAN = 4>
-__global__ void __launch_bounds__(512) scan_coarse_live_kernel(LiveArgs a) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int E = 512, KS = E / 64, ROWB = E, SLOTS = 2 * KS, NIMG = QG * KS * 64, IMG_BYTES = NIMG * 16;
-    const int tid = threadIdx.x;
-    const int lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int col = lane & 15, g = lane >> 4;
-
-    const unsigned long long t_begin = a.stats ? wall_clock64() : 0ull;
-    uint4* qimg = reinterpret_cast<uint4*>(smem);
-    for (int base = tid; base < NIMG; base += 512) qimg[base] = a.qimage[base];
-    uint2* ring = reinterpret_cast<uint2*>(smem + IMG_BYTES);                      // [LIVE_QN]
-    int* ctl = reinterpret_cast<int*>(ring + LIVE_QN);                             // [0] tail, [1] head, [2] scanners done, [3] abort, [4] batches released
-    unsigned* ltau = reinterpret_cast<unsigned*>(ctl + 16);                        // [64] this workgroup's copy of the threshold keys
-    unsigned* ltex = ltau + 64;                                                    // [64] ... and of the exact thresholds' keys
-    f32x4* lcon = reinterpret_cast<f32x4*>(ltex + 64);                             // [64] ladder origin, ladder step, query scale, query slack
-    int* wqb = reinterpret_cast<int*>(lcon + 64);                                  // [8] first step of work batch b (slot b & 7); tags in ctl[8..15]
-    for (int i = tid; i < LIVE_QN; i += 512) ring[i] = make_uint2(0u, LIVE_EMPTY);
-    if (tid < 8) { ctl[tid] = 0; ctl[8 + tid] = tid == 0 ? 0 : -1; }
-    if (tid == 0) {
-        // scanner work: batches of a.wb steps. Batch 0 of a workgroup is its index in the grid, every further one comes from
-        // a counter (zeroed with the call's control words); batch 1 is drawn here, batch b + 2 by the wave that takes the first
-        // step of batch b (ctl[5] = the workgroup's step tickets)
-        wqb[0] = (int)blockIdx.x * a.wb;
-        wqb[1] = (int)(gridDim.x + atomicAdd(a.chunk_ctr, 1u)) * a.wb;
-    }
-    if (tid < 64) {
-        const bool on = tid < a.QA;
-        ltau[tid] = on ? a.tau_key[tid] : 0u;
-        ltex[tid] = on ? a.tex_key[tid] : 0u;
-        lcon[tid] = on ? f32x4{a.edge0[tid], a.delta[tid], a.qmeta[tid], a.qmeta[3 * COARSE_QS + tid]} : f32x4{0.f, 1.f, 1.f, 0.f};
-    }
-    __syncthreads();
-    if (tid == 0) ctl[9] = 1;                       // batch 1's base is in place (written before the barrier)
-
-    if (wave < NSCAN) {
-        // ------------------------------------------------------------------ scanner
-        bool active[QG];
-        float tau[QG], yt[QG];
-#pragma unroll
-        for (int qg = 0; qg < QG; ++qg) {
-            active[qg] = qg * 16 + col < a.QA;
-            tau[qg] = INFINITY;
-            yt[qg] = active[qg] ? a.qmeta[COARSE_QS + qg * 16 + col] : 0.f;
-        }
-        // work: the workgroup's waves take 32-row steps one by one from its current batch (an LDS ticket); batches come from a
-        // device-wide counter two ahead. CUs and XCDs stream at different rates: with a fixed interleave the last wave finished
-        // ~90 us (10 %) after the average one; per-wave draws from the counter queue a slow returning atomic in front of the
-        // wave's row loads (vmcnt is in order) - here a wave publishes the batch it drew at its NEXT visit.
-        const long long nsteps = (a.nrows + 31) >> 5;
-        int pend_b = -1;
-        unsigned grabbed = 0u;
-        auto take = [&]() -> long long {
-            if (pend_b >= 0) {
-                if (lane == 0) {
-                    wqb[pend_b & 7] = (int)(gridDim.x + grabbed) * a.wb;
-                    *reinterpret_cast<volatile int*>(&ctl[8 + (pend_b & 7)]) = pend_b;
-                }
-                pend_b = -1;
-            }
-            int t_ = 0;
-            if (lane == 0) t_ = atomicAdd(&ctl[5], 1);
-            t_ = __builtin_amdgcn_readfirstlane(t_);
-            const int b_ = t_ / a.wb, o_ = t_ - b_ * a.wb;
-            if (o_ == 0) {
-                if (lane == 0) grabbed = atomicAdd(a.chunk_ctr, 1u);
-                pend_b = b_ + 2;
-            }
-            int sp_ = 0;
-            while (*reinterpret_cast<volatile int*>(&ctl[8 + (b_ & 7)]) != b_) {
-                __builtin_amdgcn_s_sleep(2);
-                if (*reinterpret_cast<volatile int*>(&ctl[3]) || ++sp_ > LIVE_SPIN_LIMIT) {
-                    *a.overflow = 1u;                      // the exact fallback answers
-                    ctl[3] = 1;
-                    return -1;
-                }
-            }
-            const long long s_ = (long long)*reinterpret_cast<volatile int*>(&wqb[b_ & 7]) + o_;
-            return s_ < nsteps ? s_ : -1;
-        };
-        long long step = take();
-        unsigned st_push = 0, st_spin = 0, tm_a = 0, tm_b = 0, tm_c = 0;
-        const bool timed = a.stats != nullptr;
-        if (step >= 0) {
-            uint4 T[SLOTS];
-            auto frag_ptr = [&](long long st, int rt) {
-                return reinterpret_cast<const char*>(a.dbc) + st * (32 * ROWB) + (g >> 1) * 1024 + ((g & 1) * 32 + rt * 16 + col) * 16;
-            };
-            uint4 M[4];
-            auto load_meta = [&](long long st, uint4* m) {
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
-                    const uint4* mp = reinterpret_cast<const uint4*>(a.rmeta + st * 32 + rt * 16 + 4 * g);
-                    m[2 * rt] = mp[0];
-                    m[2 * rt + 1] = mp[1];
-                }
-            };
-            {
-                const char* p0 = frag_ptr(step, 0);
-                const char* p1 = frag_ptr(step, 1);
-#pragma unroll
-                for (int s_ = 0; s_ < KS; ++s_) {
-                    T[s_] = *reinterpret_cast<const uint4*>(p0 + 2048 * s_);
-                    T[KS + s_] = *reinterpret_cast<const uint4*>(p1 + 2048 * s_);
-                }
-                load_meta(step, M);
-            }
-            // thresholds: every step reads the WORKGROUP's copy of the keys in LDS; scanner wave 0 refreshes that copy from the
-            // published keys every 4th step (request in one step, LDS update in the next), re-scoring waves raise it when they
-            // raise a key. (All 1024 scanner waves re-reading the published keys - two cache lines, agent scope: served by the
-            // fabric, not the XCD's L2 - every step made those two lines the scan's bottleneck: 7.5 us per step, 2.3 ms per scan.)
-            unsigned tk[QG], tkn[QG];
-#pragma unroll
-            for (int qg = 0; qg < QG; ++qg) tkn[qg] = 0u;
-            int it = 0;
-            while (true) {
-#pragma unroll
-                for (int qg = 0; qg < QG; ++qg) tk[qg] = active[qg] ? *reinterpret_cast<volatile unsigned*>(ltau + qg * 16 + col) : 0u;
-                if (wave == 0) {
-                    if ((it & 3) == 0) {
-#pragma unroll
-                        for (int qg = 0; qg < QG; ++qg)
-                            tkn[qg] = active[qg] ? __hip_atomic_load(a.tau_key + qg * 16 + col, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-                    } else if ((it & 3) == 1) {
-#pragma unroll
-                        for (int qg = 0; qg < QG; ++qg)
-                            if (g == 0 && active[qg] && tkn[qg] > tk[qg]) atomicMax(ltau + qg * 16 + col, tkn[qg]);
-                    }
-                }
-                ++it;
-                const long long nxt = take();
-                const bool has_next = nxt >= 0;
-                const char* pn[2] = {frag_ptr(has_next ? nxt : step, 0), frag_ptr(has_next ? nxt : step, 1)};
-                uint4 MN[4];
-                load_meta(has_next ? nxt : step, MN);
-
-                i32x4 acc[2][QG];
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) acc[rt][qg] = i32x4{0, 0, 0, 0};
-                uint4 B[2][QG];
-                auto load_b = [&](int s_, uint4* b) {
-#pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) b[qg] = qimg[(qg * KS + s_) * 64 + lane];
-                };
-                const unsigned long long tk0 = timed ? wall_clock64() : 0ull;
-                __builtin_amdgcn_sched_barrier(0);
-                load_b(0, B[0]);
-                // one query fragment from LDS feeds BOTH 16-row tiles (the LDS pipe is the scanner's second bound: read per
-                // MFMA, 4 scanner waves keep it ~70 % busy)
-#pragma unroll
-                for (int s_ = 0; s_ < KS; ++s_) {
-                    if (s_ + 1 < KS) load_b(s_ + 1, B[(s_ + 1) & 1]);
-                    const uint4* b = B[s_ & 1];
-#pragma unroll
-                    for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                        for (int qg = 0; qg < QG; ++qg)
-                            acc[rt][qg] = __builtin_amdgcn_mfma_i32_16x16x64_i8(__builtin_bit_cast(i32x4, T[rt * KS + s_]),
-                                                                                __builtin_bit_cast(i32x4, b[qg]), acc[rt][qg], 0, 0, 0);
-                    T[s_] = *reinterpret_cast<const uint4*>(pn[0] + 2048 * s_);
-                    T[KS + s_] = *reinterpret_cast<const uint4*>(pn[1] + 2048 * s_);
-                }
-                __builtin_amdgcn_sched_group_barrier(0x100, QG, 0);
-#pragma unroll
-                for (int s_ = 0; s_ < KS; ++s_) {
-                    if (s_ + 1 < KS) __builtin_amdgcn_sched_group_barrier(0x100, QG, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2 * QG, 0);
-                    __builtin_amdgcn_sched_group_barrier(0x020, 2, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                unsigned long long tk1 = 0ull;
-                if (timed) { asm volatile("" :: "v"(acc[1][QG - 1][0])); tk1 = wall_clock64(); tm_a += (unsigned)(tk1 - tk0); }
-
-#pragma unroll
-                for (int qg = 0; qg < QG; ++qg) tau[qg] = active[qg] ? fkey_inv(tk[qg]) : INFINITY;
-                float val[2][QG][4];
-                int total = 0;
-                const int lim = (int)(a.nrows - step * 32);           // rows of this step that exist (32 except in the last block)
-#pragma unroll
-                for (int rt = 0; rt < 2; ++rt) {
-                    const float sr[4] = {__uint_as_float(M[2 * rt].x), __uint_as_float(M[2 * rt].z), __uint_as_float(M[2 * rt + 1].x),
-                                         __uint_as_float(M[2 * rt + 1].z)};
-                    const float ar[4] = {__uint_as_float(M[2 * rt].y), __uint_as_float(M[2 * rt].w), __uint_as_float(M[2 * rt + 1].y),
-                                         __uint_as_float(M[2 * rt + 1].w)};
-#pragma unroll
-                    for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            val[rt][qg][r] = fmaf((float)acc[rt][qg][r], sr[r], ar[r] * yt[qg]);
-                            if (lim < 32 && rt * 16 + 4 * g + r >= lim) val[rt][qg][r] = __uint_as_float(0x7fc00000u);   // NaN: passes no test
-                            total += __popcll(__ballot(val[rt][qg][r] >= tau[qg]));
-                        }
-                }
-                if (a.abl == 1) total = 0;
-                unsigned long long tk2 = 0ull;
-                if (timed) { asm volatile("" :: "s"(total)); tk2 = wall_clock64(); tm_b += (unsigned)(tk2 - tk1); }
-                if (total) {
-                    // ONE LDS atomic per step reserves `total` ring slots; the pairs go in by ballot prefix (scalar masks)
-                    int base = 0;
-                    if (lane == 0) base = atomicAdd(&ctl[0], total);
-                    base = __builtin_amdgcn_readfirstlane(base);
-                    // room: re-scoring waves release their 64-slot batches IN ORDER (ctl[4] = batches released), so every slot
-                    // below 64 * ctl[4] is free again. One LDS read per step instead of one read-and-wait per pushed pair.
-                    bool room = true;
-                    {
-                        int spins = 0;
-                        while (base + total > 64 * *reinterpret_cast<volatile int*>(&ctl[4]) + LIVE_QN) {
-                            __builtin_amdgcn_s_sleep(8);
-                            ++st_spin;
-                            if (*reinterpret_cast<volatile int*>(&ctl[3]) || ++spins > LIVE_SPIN_LIMIT) {
-                                *a.overflow = 1u;          // somebody gave up waiting: the exact fallback answers
-                                ctl[3] = 1;
-                                room = false;
-                                break;
-                            }
-                        }
-                    }
-                    if (room) {
-                        const unsigned row0 = (unsigned)(step * 32) + 4 * g;
-#pragma unroll
-                        for (int rt = 0; rt < 2; ++rt)
-#pragma unroll
-                            for (int qg = 0; qg < QG; ++qg)
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const unsigned long long m_ = __ballot(val[rt][qg][r] >= tau[qg]);
-                                    if (m_) {
-                                        if ((m_ >> lane) & 1ull)
-                                            ring[(base + (int)__builtin_amdgcn_mbcnt_hi((unsigned)(m_ >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m_, 0u))) &
-                                                 (LIVE_QN - 1)] = make_uint2(__float_as_uint(val[rt][qg][r]),
-                                                                             ((unsigned)(qg * 16 + col) << LIVE_ROW_BITS) | (row0 + rt * 16 + r));
-                                        base += __popcll(m_);
-                                    }
-                                }
-                        st_push += (unsigned)total;
-                    }
-                }
-                if (timed) { wave_lds_sync(); tm_c += (unsigned)(wall_clock64() - tk2); }
-                if (!has_next) break;
-                step = nxt;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) M[i] = MN[i];
-            }
-        }
-        wave_lds_sync();                                   // this wave's ring writes are done (LDS is in order per wave)
-        if (lane == 0) atomicAdd(&ctl[2], 1);
-        if (a.stats) {
-#pragma unroll
-            for (int o = 32; o >= 1; o >>= 1) st_spin += __shfl_xor(st_spin, o);
-            st_spin >>= 6;
-            if (lane == 0) {
-                atomicAdd(a.stats + 0, st_push); atomicAdd(a.stats + 1, st_spin);
-                const unsigned dt = (unsigned)(wall_clock64() - t_begin);
-                atomicMax(a.stats + 8, dt); atomicAdd(a.stats + 10, dt >> 10);
-                atomicAdd(a.stats + 15, 1u);
-                atomicAdd(a.stats + 12, tm_a >> 4); atomicAdd(a.stats + 13, tm_b >> 4); atomicAdd(a.stats + 14, tm_c >> 4);
-            }
-        }
-        return;
-    }
-
-    // ---------------------------------------------------------------------- re-scoring wave
-    // Claims 64 ring slots at a time, drops the pairs whose upper bound the threshold has passed since, and re-scores the rest
-    // EIGHT pairs per round: 8 lanes per pair request the pair's whole row and query vector (2 x 2 KB, 32 loads of 16 B per
-    // lane, ALL in flight together: one memory round trip per round), the wave transposes them through LDS in two halves and
-    // lanes 0..7 walk one pair each through the score-order fmaf chain (t, c, g). (Earlier forms: per-lane gathers kept the
-    // CU's address unit busy; 64 pairs per batch in 16 dependent 128-byte stages took ~100 us per batch - the scan waited
-    // 340 us for the re-scoring waves to drain.)
-    volatile int* vctl = ctl;
-    unsigned st_pop = 0, st_stale = 0, st_resc = 0, st_ins = 0, st_batch = 0, st_rise = 0, st_phase = 0;
-    const int pslot = lane >> 3, piece = lane & 7;
-    for (;;) {
-        int base = 0;
-        if (lane == 0) base = atomicAdd(&ctl[1], 64);
-        base = __shfl(base, 0);
-        {
-            const int dn = vctl[2];                       // read `done` BEFORE `tail`: a finished scanner's reservations are all in
-            const int tail = vctl[0];
-            if ((dn == NSCAN && base >= tail) || (vctl[3] && dn == NSCAN)) break;   // nothing at or behind this index will ever come
-        }
-        const int idx = base + lane;
-        uint2* sl = ring + (idx & (LIVE_QN - 1));
-        bool pend = true;
-        int spins = 0;
-        while (__ballot(pend)) {
-            // wait for this lane's entry - but never with filled lanes in hand for long: a scanner may be waiting for
-            // exactly those slots (phased processing; see the deadlock note in DESIGN.md 4.1e)
-            bool got = false;
-            uint2 e = make_uint2(0u, LIVE_EMPTY);
-            for (int poll = 0; poll < 64; ++poll) {
-                if (pend && !got) {
-                    e.y = *reinterpret_cast<volatile unsigned*>(&sl->y);
-                    if (e.y != LIVE_EMPTY) {
-                        e.x = *reinterpret_cast<volatile unsigned*>(&sl->x);
-                        got = true;
-                    } else {
-                        const int dn = vctl[2];
-                        const int tail = vctl[0];
-                        if (dn == NSCAN && idx >= tail) pend = false;
-                        else if (vctl[3] || ++spins > LIVE_SPIN_LIMIT) { *a.overflow = 1u; ctl[3] = 1; pend = false; }
-                    }
-                }
-                const unsigned long long waiting = __ballot(pend && !got), have = __ballot(got);
-                if (!waiting || (have && poll >= 32)) break;
-                __builtin_amdgcn_s_sleep(4);
-            }
-            if (!__ballot(got)) continue;
-            // ---- the lanes that hold a pair
-            if (got) { *sl = make_uint2(0u, LIVE_EMPTY); pend = false; ++st_pop; }
-            const unsigned qi = got ? (e.y >> LIVE_ROW_BITS) : 0u;
-            const unsigned slot_ = e.y & ((1u << LIVE_ROW_BITS) - 1u);
-            const unsigned row = (got && a.slot_rows) ? a.slot_rows[slot_] : slot_;       // the copy is a permutation of the rows
-            bool live_ = got && a.abl != 2;
-            bool scored = false;
-            float myscore = 0.f;
-            if (lane == 0) ++st_phase;
-            while (true) {
-                // (re-)check against the workgroup's threshold copy: it may have risen during the previous round
-                if (live_ && !(__uint_as_float(e.x) >= fkey_inv(*reinterpret_cast<volatile unsigned*>(ltau + qi)))) { live_ = false; ++st_stale; }
-                unsigned long long t_ = __ballot(live_);
-                if (!t_) break;
-                int mysrc = -1, mygrp = -1;
-#pragma unroll
-                for (int p_ = 0; p_ < 8; ++p_)
-                    if (t_) {
-                        const int s_ = __builtin_ctzll(t_);
-                        if (pslot == p_) mysrc = s_;
-                        if (lane == s_) { live_ = false; mygrp = p_; }          // taken by this round
-                        t_ &= t_ - 1;
-                    }
-                if (lane == 0) ++st_batch;
-                unsigned prow = __shfl(row, mysrc < 0 ? 0 : mysrc), pq = __shfl(qi, mysrc < 0 ? 0 : mysrc);
-                if (mysrc < 0) { prow = 0u; pq = 0u; }          // idle lane groups re-read row 0 / query 0 (cache hits), stored nowhere
-                f32x4 R[16], QV[16];
-                {
-                    const float* rp = a.db + (size_t)prow * E + piece * 4;
-                    const float* qp = a.q + (size_t)pq * E + piece * 4;
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) R[j] = *reinterpret_cast<const f32x4*>(rp + 32 * j);
-#pragma unroll
-                    for (int j = 0; j < 16; ++j) QV[j] = *reinterpret_cast<const f32x4*>(qp + 32 * j);
-                }
-                // the chain walks the pair's 8 lanes: a 16-float block lives in one quad (4 lanes x float4), element order
-                // (c, g) = component-major across the quad's lanes, so the running sum hops lane g-1 -> g by a quad rotation
-                // (DPP) before every fmaf; all lanes execute every step, the TRUE sum is the one travelling. Between blocks
-                // the true sum is broadcast to the group (one ds_bpermute per 16 elements). No LDS staging.
-                float acc = 0.f;
-#pragma unroll
-                for (int j = 0; j < 16; ++j)
-#pragma unroll
-                    for (int tt = 0; tt < 2; ++tt) {
-                        if (j || tt) acc = __shfl(acc, (lane & ~7) | (tt ? 3 : 7));
-#pragma unroll
-                        for (int c = 0; c < 4; ++c)
-#pragma unroll
-                            for (int g_ = 0; g_ < 4; ++g_) {
-                                const float rot = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(acc), 0x93, 0xf, 0xf, true));
-                                acc = __builtin_fmaf(R[j][c], QV[j][c], rot);
-                            }
-                    }
-                // lane 7 of every group holds its pair's exact score: back to the lane the pair came from
-                const float res = __shfl(acc, mygrp < 0 ? 0 : 8 * mygrp + 7);
-                if (mygrp >= 0) { myscore = res; scored = true; ++st_resc; }
-            }
-            // ---- the phase's scores, all lanes at once: list + ladder histogram (the constants come from LDS; the only
-            // dependent fabric round trips of a phase are the counters' returns and the ladder rows)
-            const unsigned kt = lane < a.QA ? __hip_atomic_load(a.tau_key + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-            const unsigned kx = lane < a.QA ? __hip_atomic_load(a.tex_key + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-            const bool ins = scored && myscore == myscore && myscore >= fkey_inv(*reinterpret_cast<volatile unsigned*>(ltex + qi));
-            if (ins) {
-                ++st_ins;
-                const f32x4 cn = lcon[qi];
-                float x = (myscore - cn.x) / cn.y;
-                x = x < 0.f ? 0.f : (x > (float)(LIVE_NB - 1) ? (float)(LIVE_NB - 1) : x);
-                int b = (int)x;
-                if (b > 0 && !(myscore >= fmaf((float)b, cn.y, cn.x))) --b;        // the bucket's edge must not exceed the score
-                if (myscore >= fmaf((float)b, cn.y, cn.x)) atomicAdd(&a.hist[qi * LIVE_NB + b], 1u);
-                const unsigned pos = atomicAdd(&a.gcnt[qi], 1u);
-                if ((long long)pos < a.cap) a.cand[(size_t)qi * a.cap + pos] = make_uint2(__float_as_uint(myscore), row);
-                else *a.overflow = 1u;
-            }
-            if (lane < a.QA) { atomicMax(ltau + lane, kt); atomicMax(ltex + lane, kx); }
-            // ladder: for up to four of the queries that just received a row, the highest edge with >= K rows at or above it
-            unsigned long long todo = __ballot(ins);
-            unsigned lq[4];
-            unsigned hv[4];
-            int nl = 0;
-#pragma unroll
-            for (int r_ = 0; r_ < 4; ++r_) {
-                lq[r_] = 0u;
-                hv[r_] = 0u;
-                if (todo) {
-                    const int src = __builtin_ctzll(todo);
-                    lq[r_] = __shfl(qi, src);
-                    todo &= ~__ballot(ins && qi == lq[r_]);
-                    hv[r_] = lane < LIVE_NB ? __hip_atomic_load(a.hist + lq[r_] * LIVE_NB + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0u;
-                    nl = r_ + 1;
-                }
-            }
-#pragma unroll
-            for (int r_ = 0; r_ < 4; ++r_)
-                if (r_ < nl) {
-                    unsigned v = hv[r_];
-#pragma unroll
-                    for (int o = 1; o < LIVE_NB; o <<= 1) {
-                        const unsigned t2 = __shfl_down(v, o);
-                        if (lane + o < LIVE_NB) v += t2;
-                    }
-                    const unsigned long long okm = __ballot(lane < LIVE_NB && v >= (unsigned)a.K);
-                    if (okm && lane == 0) {
-                        const int bmax = 63 - __builtin_clzll(okm);
-                        const f32x4 cn = lcon[lq[r_]];
-                        const float tnew = fmaf((float)bmax, cn.y, cn.x);
-                        const unsigned nk = fkey((tnew - cn.w) * cn.z), nx = fkey(tnew);
-                        if (nx > *reinterpret_cast<volatile unsigned*>(ltex + lq[r_])) {
-                            ++st_rise;
-                            atomicMax(a.tex_key + lq[r_], nx);
-                            atomicMax(a.tau_key + lq[r_], nk);
-                            atomicMax(ltex + lq[r_], nx);
-                            atomicMax(ltau + lq[r_], nk);
-                        }
-                    }
-                }
-        }
-        // release the batch in claim order: scanners may then reuse every slot below 64 * ctl[4]
-        if (lane == 0) {
-            int sp = 0;
-            while (vctl[4] != (base >> 6)) {
-                __builtin_amdgcn_s_sleep(2);
-                if (vctl[3] || ++sp > LIVE_SPIN_LIMIT) { *a.overflow = 1u; ctl[3] = 1; break; }
-            }
-            ctl[4] = (base >> 6) + 1;
-        }
-    }
-    if (a.stats) {
-#pragma unroll
-        for (int o = 32; o >= 1; o >>= 1) {
-            st_pop += __shfl_xor(st_pop, o); st_stale += __shfl_xor(st_stale, o); st_resc += __shfl_xor(st_resc, o);
-            st_ins += __shfl_xor(st_ins, o); st_batch += __shfl_xor(st_batch, o); st_rise += __shfl_xor(st_rise, o);
-        }
-        if (lane == 0) {
-            atomicAdd(a.stats + 2, st_pop); atomicAdd(a.stats + 3, st_stale); atomicAdd(a.stats + 4, st_resc);
-            atomicAdd(a.stats + 5, st_ins); atomicAdd(a.stats + 6, st_batch); atomicAdd(a.stats + 7, st_rise);
-            atomicMax(a.stats + 9, (unsigned)(wall_clock64() - t_begin));
-            atomicAdd(a.stats + 11, st_phase);
-        }
-    }
-}
-
-#endif  // CLIPMI_DEV
 
 // =================================================================================================
 // Wide coarse pass (int8 copy only): ONE stream of the copy for up to WIDE_MAX_Q = 1024 queries of one search call
@@ -2328,17 +1762,20 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
             a.nrows = p.sample_rows;
             int rc = launch_scan<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
             if (rc) return rc;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, cand, gcnt, p.cap, K,
-                               (long long)0, (float*)nullptr, (long long*)nullptr, thr0, (const unsigned*)nullptr);
+            SelectArgs s;
+            s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
+            s.thr_out = thr0;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(sample)");
             a.thr_in = thr0;
         }
         a.nrows = N;
         int rc = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
         if (rc) return rc;
-        hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, cand, gcnt, p.cap, K,
-                           (long long)id_base, out_score_dev + (size_t)q0 * K, (long long*)out_id_dev + (size_t)q0 * K,
-                           (float*)nullptr, (const unsigned*)nullptr);
+        SelectArgs s;
+        s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
+        s.id_base = id_base; s.out_s = out_score_dev + (size_t)q0 * K; s.out_i = (long long*)out_id_dev + (size_t)q0 * K;
+        hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
         CLIPMI_CHECK_LAUNCH("select_topk_kernel");
     }
     return 0;
@@ -2362,14 +1799,13 @@ constexpr int COARSE_Q = 64;                     // queries per coarse pass. (12
                                                  // leaves LDS for only 2 waves per CU = 2 of 4 SIMDs, and the pass turns
                                                  // MFMA-bound: 5.29 ms per 128 queries vs 2 x 2.21 ms)
 
-template <int E, int QG, bool PREPASS, bool I8, bool Q2 = false>
+template <int E, int QG, bool PREPASS, bool I8>
 int launch_coarse_t(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
     static_assert(QG <= 4, "64 queries per pass at most");
-    static_assert(E == 512 || !Q2, "the two-digit query image (COARSE_IMG2) is laid out for E = 512");
     constexpr int WAVES = 4;
     // the final publication reuses the head of the query image for 3 * 16 QG counters: keep >= 1 KiB
     // (image: 1 KiB per query group and k-step - E = 768: 48 KiB int8, 96 KiB bf16 at 64 queries; + 4 x 6 KiB of lists)
-    size_t lds = (size_t)(Q2 ? 2 : 1) * QG * (E / (I8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
+    size_t lds = (size_t)QG * (E / (I8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
     // The LAST segment's scan (3/4 of the rows) reserves COARSE_MAIN_LDS although it uses 56-88 KiB: with two batches in
     // flight on two streams, two such scans then cannot share a CU. Sharing halves each one's bandwidth, both finish
     // together and both batches run their latency-bound side kernels at the same time with HBM idle (1.06-1.08 ms per 64
@@ -2380,30 +1816,58 @@ int launch_coarse_t(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEv
     static const int wgs = [] { const int v = (int)dev_knob("CLIPMI_COARSE_WGS", 1); return v == 2 ? 2 : 1; }();
     if (!PREPASS && wgs == 1 && lds < (size_t)COARSE_MAIN_LDS) lds = COARSE_MAIN_LDS;
     if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_kernel<E, QG, PREPASS, I8, Q2>, lds)) return rc;
+    if (int rc = opt_in_lds((const void*)scan_coarse_kernel<E, QG, PREPASS, I8>, lds)) return rc;
     long long g_ = (nsteps + WAVES - 1) / WAVES;
     const int grid = (int)(g_ < (long long)NUM_CU * wgs ? g_ : (long long)NUM_CU * wgs);
     if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_kernel<E, QG, PREPASS, I8, Q2>), dim3(grid), dim3(WAVES * 64), lds, st, a);
+    hipLaunchKernelGGL((scan_coarse_kernel<E, QG, PREPASS, I8>), dim3(grid), dim3(WAVES * 64), lds, st, a);
     if (ev) (void)hipEventRecord(ev[1], st);
     CLIPMI_CHECK_LAUNCH("scan_coarse_kernel");
     return 0;
 }
 
-// E in {512, 768} (checked by the callers); the two-digit form (development library) exists at 512 only
-template <int QG, bool PREPASS, bool I8, bool Q2 = false>
-int launch_coarse(int E, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
-    if constexpr (!Q2)
-        if (E == 768) return launch_coarse_t<768, QG, PREPASS, I8, false>(a, nsteps, st, ev);
-    if (E != 512) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: E = %d", E);
-    return launch_coarse_t<512, QG, PREPASS, I8, Q2>(a, nsteps, st, ev);
+// The scan of a 64-query pass for run-time (row width, 16-query groups, pre-pass name, copy): {512, 768} x {1, 2, 4} x {pre} x
+// {int8, bf16}
+template <int E, bool I8>
+int launch_coarse_ei(int qg, bool pre, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
+    switch (qg) {
+    case 1: return pre ? launch_coarse_t<E, 1, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 1, false, I8>(a, nsteps, st, ev);
+    case 2: return pre ? launch_coarse_t<E, 2, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 2, false, I8>(a, nsteps, st, ev);
+    case 4: return pre ? launch_coarse_t<E, 4, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 4, false, I8>(a, nsteps, st, ev);
+    }
+    return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %d query groups", qg);
 }
 
-constexpr int COARSE_CTL = 2 * COARSE_Q + 32 + COARSE_Q * LIVE_NB;     // fallback counters | coarse counters | overflow flag + 28 live-scan statistics | ladder
+int launch_coarse(int E, int qg, bool pre, bool i8, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
+    if (E == 768) return i8 ? launch_coarse_ei<768, true>(qg, pre, a, nsteps, st, ev) : launch_coarse_ei<768, false>(qg, pre, a, nsteps, st, ev);
+    if (E != 512) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: E = %d", E);
+    return i8 ? launch_coarse_ei<512, true>(qg, pre, a, nsteps, st, ev) : launch_coarse_ei<512, false>(qg, pre, a, nsteps, st, ev);
+}
+
+// coarse_prep_kernel for a run-time (row width, copy); E in {512, 768} (checked by the callers)
+void launch_coarse_prep(int E, bool i8, unsigned blocks, hipStream_t st, const float* q, float rmax, float amax, int QA, float* qmeta,
+                        uint4* qimage, unsigned* ctl, int nctl, int qs, int wide) {
+    const auto kern = E == 768 ? (i8 ? coarse_prep_kernel<true, 768> : coarse_prep_kernel<false, 768>)
+                               : (i8 ? coarse_prep_kernel<true, 512> : coarse_prep_kernel<false, 512>);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(256), 0, st, q, E, rmax, amax, QA, qmeta, qimage, ctl, nctl, qs, wide);
+}
+
+// sample_scores_kernel for a run-time (row width, QG): 16 QG queries per workgroup, their f32 image in LDS (32 KiB per 16 queries,
+// 48 KiB at E = 768)
+int launch_sample_scores(int E, int QG, dim3 grid, hipStream_t st, const float* db, long long nrows, const float* q, int QA,
+                         uint2* cand, long long cap, unsigned* gcnt) {
+    const size_t lds = (size_t)QG * (E / 16) * 1024;
+    const auto kern = E == 768 ? (QG == 2 ? sample_scores_kernel<768, 2> : sample_scores_kernel<768, 1>)
+                               : (QG == 2 ? sample_scores_kernel<512, 2> : sample_scores_kernel<512, 1>);
+    if (int rc = opt_in_lds((const void*)kern, lds)) return rc;
+    hipLaunchKernelGGL(kern, grid, dim3(256), lds, st, db, nrows, q, QA, cand, cap, gcnt);
+    return 0;
+}
+
+constexpr int COARSE_CTL = 2 * COARSE_Q + 32;     // fallback counters | coarse counters | flag block (word 0: the overflow flag)
 struct CoarseWs {
     uint2* cand_e; uint2* cand_c; unsigned* gcnt_e; unsigned* gcnt_c; float* thr0; float* tauc; unsigned* flag;
     unsigned* last_m; float* qmeta; uint4* qimage;
-    unsigned* hist; unsigned* live_keys; float* live_edges;       // live-threshold scan (scan_coarse_live_kernel)
 };
 
 // the plan of the coarse path's side kernels (sample select, fallback scan + select): within COARSE_SIDE_LDS when K allows
@@ -2420,9 +1884,6 @@ size_t carve_coarse(const Plan& p, void* base, size_t cap, CoarseWs* w) {
     x.gcnt_e = ar.take<unsigned>(COARSE_CTL);          // one control block, cleared by coarse_prep_kernel
     x.gcnt_c = x.gcnt_e + COARSE_Q;
     x.flag = x.gcnt_e + 2 * COARSE_Q;
-    x.hist = x.flag + 32;
-    x.live_keys = ar.take<unsigned>(2 * COARSE_Q);
-    x.live_edges = ar.take<float>(2 * COARSE_Q);
     x.thr0 = ar.take<float>(COARSE_Q);
     x.tauc = ar.take<float>(COARSE_Q);
     x.last_m = ar.take<unsigned>(COARSE_Q);
@@ -2478,46 +1939,14 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
     if (int rc = opt_in_rescore(E)) return rc;
     // int8: the rows the copy's slots hold, behind the block meta (quantize_rows_i8_kernel); bf16 copy: rows in order
     const unsigned* slot_rows = i8 ? i8_slot_rows(rmeta, N) : nullptr;
-    // int8 copy, shards below 2^26 rows: the live-threshold scan - EXPERIMENTAL, off unless CLIPMI_LIVE=1. Bit-exact, ONE scan
-    // launch, half the re-scored pairs, but 2.3 ms per 10 M-row scan against 0.9 ms for the three segmented scans (r03): its
-    // 138 KB of LDS leave one workgroup = FOUR scanner waves per CU with one 16 KB step in flight each, a quarter of the bytes
-    // in flight the segmented kernel's 16 waves per CU keep, and the scan is HBM-latency bound.
-#ifdef CLIPMI_DEV
-    static const bool live_on = dev_knob("CLIPMI_LIVE", 0) == 1;
-    const bool live = i8 && live_on && N < (1ll << LIVE_ROW_BITS);
-    // CLIPMI_COARSE_Q2=1: the query as TWO int8 digits (coarse_prep_kernel q2): -42 % coarse survivors, but the scan's second
-    // MFMA per fragment costs more than the re-scoring it saves - measured, development library only
-    static const bool q2_on = dev_knob("CLIPMI_COARSE_Q2", 0) != 0;
-    const bool q2 = i8 && q2_on && !live;
-    // both laboratory forms are built for E = 512 (LiveArgs rows of 512, COARSE_IMG2): asked for at 768 they refuse
-    if (E != 512 && i8 && (live_on || q2_on))
-        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse_i8: CLIPMI_LIVE / CLIPMI_COARSE_Q2 need E = 512 (E = %d)", E);
-#else
-    constexpr bool live = false;
-    constexpr bool q2 = false;
-#endif
 
     for (int q0 = 0; q0 < Q; q0 += COARSE_Q) {
         const int qa = (Q - q0) < COARSE_Q ? (Q - q0) : COARSE_Q;
         const float* qg = q_dev + (size_t)q0 * E;
         // per-query constants, the query image the scans copy, and the cleared counters + overflow flag (selects re-zero
         // what they consume): one launch per 64-query group
-        {
-            const int nq = (qa + 15) / 16 * 16;
-            if (i8 && E == 768)
-                hipLaunchKernelGGL((coarse_prep_kernel<true, 768>), dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
-                                   w.gcnt_e, COARSE_CTL, COARSE_QS, 0, 0);
-            else if (i8)
-                hipLaunchKernelGGL(coarse_prep_kernel<true>, dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
-                                   w.gcnt_e, COARSE_CTL, COARSE_QS, 0, q2 ? 1 : 0);
-            else if (E == 768)
-                hipLaunchKernelGGL((coarse_prep_kernel<false, 768>), dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
-                                   w.gcnt_e, COARSE_CTL, COARSE_QS, 0, 0);
-            else
-                hipLaunchKernelGGL(coarse_prep_kernel<false>, dim3(nq / 4), dim3(256), 0, st, qg, E, rmax, amax, qa, w.qmeta, w.qimage,
-                                   w.gcnt_e, COARSE_CTL, COARSE_QS);
-            CLIPMI_CHECK_LAUNCH("coarse_prep_kernel");
-        }
+        launch_coarse_prep(E, i8, (unsigned)((qa + 15) / 16 * 4), st, qg, rmax, amax, qa, w.qmeta, w.qimage, w.gcnt_e, COARSE_CTL, COARSE_QS, 0);
+        CLIPMI_CHECK_LAUNCH("coarse_prep_kernel");
         ScanArgs a;
         a.db = static_cast<const float*>(db_dev);
         a.K = K; a.C = p.C; a.wave_bytes = p.wave_bytes;
@@ -2551,56 +1980,37 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
             c.row0 = r0;
             c.nrows = r1 - r0;
             const long long nsteps = (c.nrows + 31) / 32;
-            int rc_;
-#ifdef CLIPMI_DEV
-            if (i8 && q2)
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<1, false, true, true>(E, c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<2, false, true, true>(E, c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, true, true>(E, c, nsteps, st, ev) : launch_coarse<4, false, true, true>(E, c, nsteps, st, ev));
-            else
-#endif
-            if (i8)
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, true>(E, c, nsteps, st, ev) : launch_coarse<1, false, true>(E, c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, true>(E, c, nsteps, st, ev) : launch_coarse<2, false, true>(E, c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, true>(E, c, nsteps, st, ev) : launch_coarse<4, false, true>(E, c, nsteps, st, ev));
-            else
-                rc_ = qa <= 16 ? (pre ? launch_coarse<1, true, false>(E, c, nsteps, st, ev) : launch_coarse<1, false, false>(E, c, nsteps, st, ev))
-                    : qa <= 32 ? (pre ? launch_coarse<2, true, false>(E, c, nsteps, st, ev) : launch_coarse<2, false, false>(E, c, nsteps, st, ev))
-                               : (pre ? launch_coarse<4, true, false>(E, c, nsteps, st, ev) : launch_coarse<4, false, false>(E, c, nsteps, st, ev));
-            if (rc_) return rc_;
+            if (int rc_ = launch_coarse(E, qa <= 16 ? 1 : qa <= 32 ? 2 : 4, pre, i8, c, nsteps, st, ev)) return rc_;
             // ~1-3 k survivors per query = ~11 blocks of 256 pairs; a larger grid only queues idle blocks
             launch_rescore(false, dim3(12, qa), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, COARSE_CAP, slot_rows, E);
             CLIPMI_CHECK_LAUNCH("rescore_pairs_kernel");
             // 4096 staged entries (32 KiB of LDS) cover these lists; a select block then fits on a CU even beside the
             // last segment's scan of ANOTHER batch in flight (104 KiB), which the 96-KiB staging of the sample select does not
             const int scap = p.stage < 4096 ? p.stage : 4096;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st,
-                               w.cand_c, w.gcnt_c, COARSE_CAP, K, idb, os, oi, thr_out, (const unsigned*)nullptr, m_out, keep, scap,
-                               thr_out ? w.qmeta : (float*)nullptr);
+            SelectArgs s;
+            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = COARSE_CAP; s.K = K;
+            s.id_base = idb; s.out_s = os; s.out_i = oi;
+            s.thr_out = thr_out; s.qmeta = thr_out ? w.qmeta : nullptr;
+            s.m_out = m_out; s.keep = keep; s.stage_cap = scap;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(coarse)");
             return 0;
         };
         // level 1 (exact, unfiltered, all <= 64 queries in one launch): scores of the first rows -> K-th best per query
         {
             const long long rows1 = two_level ? S1 : S2;
-            const size_t lds1 = (size_t)(E / 16) * 1024;           // the f32 image of 16 queries: 32 KiB, 48 KiB at E = 768
-            if (int rc = opt_in_lds(E == 768 ? (const void*)sample_scores_kernel<768> : (const void*)sample_scores_kernel<512>, lds1)) return rc;
             long long gs = ((rows1 + 15) / 16 + 3) / 4;
             if (gs > NUM_CU) gs = NUM_CU;
-            if (E == 768)
-                hipLaunchKernelGGL(sample_scores_kernel<768>, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), dim3(256), lds1, st, static_cast<const float*>(db_dev),
-                                   rows1, qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c);
-            else
-            hipLaunchKernelGGL(sample_scores_kernel<512>, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), dim3(256), lds1, st, static_cast<const float*>(db_dev),
-                               rows1, qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c);
+            if (int rc = launch_sample_scores(E, 1, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), st, static_cast<const float*>(db_dev), rows1,
+                                              qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c)) return rc;
             CLIPMI_CHECK_LAUNCH("sample_scores_kernel");
             // the sample's lists are dense (entry e IS row e): only the 4 score bytes are staged, as the wide pass's sample
             // select does (48 KiB instead of 96 per block; round 5)
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)rows1 * 4 + 16, st,
-                               w.cand_c, w.gcnt_c, COARSE_CAP, K,
-                               (long long)0, (float*)nullptr, (long long*)nullptr, w.thr0, (const unsigned*)nullptr,
-                               (unsigned*)nullptr, 0, (int)rows1, w.qmeta, COARSE_QS, live ? w.live_keys : (unsigned*)nullptr,
-                               live ? w.live_edges : (float*)nullptr, 1, w.flag);
+            SelectArgs s;
+            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = COARSE_CAP; s.K = K;
+            s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = COARSE_QS;
+            s.stage_cap = (int)rows1; s.dense = 1; s.arm_fallback = w.flag;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)rows1 * 4 + 16, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(sample 1)");
         }
         // Segments of the copy, each scanned ONCE: [0, S2) (level 2 of the pre-pass, threshold from level 1), then
@@ -2612,54 +2022,9 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
         float* os_final = out_score_dev + (size_t)q0 * K;
         long long* oi_final = (long long*)out_id_dev + (size_t)q0 * K;
         long long r_done = 0;
-#ifdef CLIPMI_DEV
-        if (live) {
-            // ONE launch over all rows: scanners + re-scoring waves, thresholds rising through the ladder (scan_coarse_live_kernel)
-            LiveArgs la;
-            la.dbc = static_cast<const signed char*>(dbh_dev); la.rmeta = rmeta; la.db = static_cast<const float*>(db_dev);
-            la.slot_rows = slot_rows;
-            la.q = qg; la.qmeta = w.qmeta; la.qimage = w.qimage; la.nrows = N; la.QA = qa; la.K = K;
-            la.tau_key = w.live_keys; la.tex_key = w.live_keys + COARSE_Q; la.edge0 = w.live_edges; la.delta = w.live_edges + COARSE_Q;
-            la.hist = w.hist; la.cand = w.cand_c; la.gcnt = w.gcnt_c; la.cap = COARSE_CAP; la.overflow = w.flag; la.chunk_ctr = w.flag + 1;
-            static const int live_wb = [] { const int v = (int)dev_knob("CLIPMI_LIVE_WB", LIVE_WB); return v < 8 ? 8 : v; }();
-            la.wb = live_wb;
-            static const bool live_stats = dev_knob_set("CLIPMI_LIVE_STATS");
-            la.stats = live_stats ? w.flag + 4 : nullptr;
-            static const int live_abl = (int)dev_knob("CLIPMI_LIVE_ABL", 0);
-            la.abl = live_abl;
-            const int QGl = qa <= 16 ? 1 : qa <= 32 ? 2 : 4;
-            size_t lds = (size_t)QGl * 8 * 1024 + (size_t)LIVE_QN * 8 + 64 + 512 + 1024 + 64;
-            if (lds < (size_t)COARSE_MAIN_LDS) lds = COARSE_MAIN_LDS;           // as the segmented form's last segment
-            const void* fn = QGl == 1 ? (const void*)scan_coarse_live_kernel<1> : QGl == 2 ? (const void*)scan_coarse_live_kernel<2>
-                                                                                           : (const void*)scan_coarse_live_kernel<4>;
-            if (int rc = opt_in_lds(fn, lds)) return rc;
-            long long g_ = ((N + 31) / 32 + 3) / 4;
-            const int grid = (int)(g_ < NUM_CU ? g_ : NUM_CU);
-            static const int live_nscan = (int)dev_knob("CLIPMI_LIVE_NSCAN", 6);
-            if (scan_ev) (void)hipEventRecord(scan_ev[0], st);
-            if (QGl == 4 && live_nscan == 5) {
-                if (int rc = opt_in_lds((const void*)scan_coarse_live_kernel<4, 5>, lds)) return rc;
-                hipLaunchKernelGGL((scan_coarse_live_kernel<4, 5>), dim3(grid), dim3(512), lds, st, la);
-            } else if (QGl == 4 && live_nscan == 6) {
-                if (int rc = opt_in_lds((const void*)scan_coarse_live_kernel<4, 6>, lds)) return rc;
-                hipLaunchKernelGGL((scan_coarse_live_kernel<4, 6>), dim3(grid), dim3(512), lds, st, la);
-            } else
-            if (QGl == 1) hipLaunchKernelGGL(scan_coarse_live_kernel<1>, dim3(grid), dim3(512), lds, st, la);
-            else if (QGl == 2) hipLaunchKernelGGL(scan_coarse_live_kernel<2>, dim3(grid), dim3(512), lds, st, la);
-            else hipLaunchKernelGGL(scan_coarse_live_kernel<4>, dim3(grid), dim3(512), lds, st, la);
-            if (scan_ev) (void)hipEventRecord(scan_ev[1], st);
-            CLIPMI_CHECK_LAUNCH("scan_coarse_live_kernel");
-            const int scap = p.stage < 4096 ? p.stage : 4096;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st,
-                               w.cand_c, w.gcnt_c, COARSE_CAP, K, (long long)id_base, os_final, oi_final, (float*)nullptr,
-                               (const unsigned*)nullptr, w.last_m, 0, scap, (float*)nullptr);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(live)");
-        }
-#endif
         // development knob: CLIPMI_COARSE_SEGS=n (>= 4): n geometric segments from 64 k rows, as the wide pass plans them
         static const int nseg_env = (int)dev_knob("CLIPMI_COARSE_SEGS", 0);
-        if (live) {
-        } else if (two_level && nseg_env >= 4 && N >= (1 << 20)) {
+        if (two_level && nseg_env >= 4 && N >= (1 << 20)) {
             long long b = 65536;
             const double ratio = pow((double)N / 65536.0, 1.0 / (nseg_env - 1));
             for (int sgi = 0; sgi + 1 < nseg_env; ++sgi) {
@@ -2668,8 +2033,7 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
                 r_done = r1;
                 b = (long long)(b * ratio);
             }
-        } else
-        if (two_level) {
+        } else if (two_level) {
             if (int rc = coarse_pass(0, S2, true, w.thr0, nullptr, nullptr, 0, scan_ev ? scan_ev + 2 : nullptr, w.last_m, 1)) return rc;
             r_done = S2;
             long long N1 = (N / 4) & ~31ll;
@@ -2680,18 +2044,19 @@ int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const 
             }
         }
         // last segment (its threshold was written by the previous select): scan, exact re-scoring, select into the result
-        if (!live)
-            if (int rc = coarse_pass(r_done, N, false, nullptr, os_final, oi_final, (long long)id_base, scan_ev, w.last_m, two_level ? 2 : 0))
-                return rc;
+        if (int rc = coarse_pass(r_done, N, false, nullptr, os_final, oi_final, (long long)id_base, scan_ev, w.last_m, two_level ? 2 : 0))
+            return rc;
         // 6. fallback: exact scan + select, exiting at once unless a coarse list overflowed
         //    (two launches: the exact scan takes its groups of p.QA queries as blockIdx.y, each with its own lists)
         {
             const int ny = (qa + p.QA - 1) / p.QA;
             a.q = qg; a.QA = qa < p.QA ? qa : p.QA; a.q_total = qa; a.nrows = N; a.thr_in = w.thr0; a.run_if = w.flag;
             if (int rc2 = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, nullptr, ny)) return rc2;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, w.cand_e, w.gcnt_e, p.cap, K,
-                               (long long)id_base, os_final, oi_final, (float*)nullptr, (const unsigned*)w.flag,
-                               (unsigned*)nullptr, 0, p.stage, (float*)nullptr);
+            SelectArgs s;
+            s.cand = w.cand_e; s.gcnt = w.gcnt_e; s.cap = p.cap; s.K = K;
+            s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final;
+            s.run_if = w.flag; s.stage_cap = p.stage;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(fallback)");
         }
     }
@@ -3072,20 +2437,13 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
     const unsigned* slot_rows = i8_slot_rows(rmeta, N);
     if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
     if (int rc = opt_in_rescore(E)) return rc;
-    const size_t lds1 = (size_t)(E / 16) * 1024;               // the f32 image of 16 queries: 32 KiB, 48 KiB at E = 768
-    if (int rc = opt_in_lds(E == 768 ? (const void*)sample_scores_kernel<768> : (const void*)sample_scores_kernel<512>, lds1)) return rc;
     int ev_used = 0;
 
     for (int q0 = 0; q0 < Q; q0 += chunk) {
         const int qc = (Q - q0) < chunk ? (Q - q0) : chunk;
         const float* qg = q_dev + (size_t)q0 * E;
         const int nsets = (qc + 63) / 64;
-        if (E == 768)
-            hipLaunchKernelGGL((coarse_prep_kernel<true, 768>), dim3(nsets * 16), dim3(256), 0, st, qg, E, rmax, amax, qc, w.qmeta,
-                               w.qimage, w.gcnt_e, 2 * qs + 4, qs, 1, 0);
-        else
-        hipLaunchKernelGGL(coarse_prep_kernel<true>, dim3(nsets * 16), dim3(256), 0, st, qg, E, rmax, amax, qc, w.qmeta, w.qimage,
-                           w.gcnt_e, 2 * qs + 4, qs, 1);
+        launch_coarse_prep(E, true, (unsigned)(nsets * 16), st, qg, rmax, amax, qc, w.qmeta, w.qimage, w.gcnt_e, 2 * qs + 4, qs, 1);
         CLIPMI_CHECK_LAUNCH("coarse_prep_kernel(wide)");
         long long S1 = p.stage < 4096 ? 4096 : (p.stage / 16) * 16;
         if (S1 > 12288) S1 = 12288;
@@ -3098,30 +2456,18 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
             static const int sqg = (int)dev_knob("CLIPMI_WIDE_SAMPLE_QG", 2);
             const int ngroups = (qc + 16 * sqg - 1) / (16 * sqg);
             if (ngroups >= 8 / sqg && gs > sdiv) gs = (gs + sdiv - 1) / sdiv;
-            if (E == 768) {
-                // QG = 2 at 768 as well: 48 row registers more than at 512, inside the 512 of a 256-thread workgroup (resource
-                // table, DESIGN 4.1l: no scratch)
-                if (sqg == 2) {
-                    if (int rc = opt_in_lds((const void*)sample_scores_kernel<768, 2>, 2 * lds1)) return rc;
-                    hipLaunchKernelGGL((sample_scores_kernel<768, 2>), dim3((unsigned)gs, (unsigned)ngroups), dim3(256), 2 * lds1, st,
-                                       static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
-                } else
-                hipLaunchKernelGGL(sample_scores_kernel<768>, dim3((unsigned)gs, (unsigned)ngroups), dim3(256), lds1, st,
-                                   static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
-            } else
-            if (sqg == 2) {
-                if (int rc = opt_in_lds((const void*)sample_scores_kernel<512, 2>, 2 * lds1)) return rc;
-                hipLaunchKernelGGL((sample_scores_kernel<512, 2>), dim3((unsigned)gs, (unsigned)ngroups), dim3(256), 2 * lds1, st,
-                                   static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
-            } else
-            hipLaunchKernelGGL(sample_scores_kernel<512>, dim3((unsigned)gs, (unsigned)ngroups), dim3(256), lds1, st,
-                               static_cast<const float*>(db_dev), S1, qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c);
+            // QG = 2 at 768 as well: 48 row registers more than at 512, inside the 512 of a 256-thread workgroup (resource table,
+            // no scratch)
+            if (int rc = launch_sample_scores(E, sqg == 2 ? 2 : 1, dim3((unsigned)gs, (unsigned)ngroups), st, static_cast<const float*>(db_dev), S1,
+                                              qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c)) return rc;
             CLIPMI_CHECK_LAUNCH("sample_scores_kernel(wide)");
             // dense staging (4 bytes per row): S1 <= 12 288 rows always fit; LDS sized for them, not for the generic 8-byte stage
             const size_t lds_dense = SEL_FIXED + (size_t)K * 8 + (size_t)S1 * 4 + 16;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), lds_dense, st, w.cand_c, w.gcnt_c, WIDE_CAP, K,
-                               (long long)0, (float*)nullptr, (long long*)nullptr, w.thr0, (const unsigned*)nullptr,
-                               (unsigned*)nullptr, 0, (int)S1, w.qmeta, qs, (unsigned*)nullptr, (float*)nullptr, 1, w.flag);
+            SelectArgs s;
+            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = WIDE_CAP; s.K = K;
+            s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = qs;
+            s.stage_cap = (int)S1; s.dense = 1; s.arm_fallback = w.flag;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), lds_dense, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide sample)");
         }
         WideArgs c;
@@ -3170,10 +2516,12 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
             CLIPMI_CHECK_LAUNCH("rescore_pairs16_kernel(wide)");
             // keep: bit 0 = the K best stay at the head of the list for the next segment; bit 1 = add to the survivor count
             const int keep = (last ? 0 : 1) | (sgi > 0 ? 2 : 0);
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st,
-                               w.cand_c, w.gcnt_c, WIDE_CAP, K, last ? (long long)id_base : 0ll, last ? os_final : (float*)nullptr,
-                               last ? oi_final : (long long*)nullptr, last ? (float*)nullptr : w.thr0, (const unsigned*)nullptr,
-                               w.last_m, keep, scap, last ? (float*)nullptr : w.qmeta, qs);
+            SelectArgs s;
+            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = WIDE_CAP; s.K = K;
+            if (last) { s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final; }
+            else { s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = qs; }
+            s.m_out = w.last_m; s.keep = keep; s.stage_cap = scap;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide)");
             r0 = bnd[sgi];
         }
@@ -3186,9 +2534,11 @@ int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta,
             const int ny = (qc + p.QA - 1) / p.QA;
             a.q = qg; a.QA = qc < p.QA ? qc : p.QA; a.q_total = qc; a.nrows = N; a.thr_in = w.thr0; a.run_if = w.flag;
             if (int rc2 = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, nullptr, ny)) return rc2;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), p.lds_sel, st, w.cand_e, w.gcnt_e, p.cap, K,
-                               (long long)id_base, os_final, oi_final, (float*)nullptr, (const unsigned*)w.flag,
-                               (unsigned*)nullptr, 0, p.stage, (float*)nullptr, qs);
+            SelectArgs s;
+            s.cand = w.cand_e; s.gcnt = w.gcnt_e; s.cap = p.cap; s.K = K;
+            s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final;
+            s.run_if = w.flag; s.stage_cap = p.stage;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), p.lds_sel, st, s);
             CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide fallback)");
         }
     }
@@ -3565,27 +2915,6 @@ extern "C" int clipmi_dbg_topk_wide_i8_scan_ms(const void* db_dev, const void* d
 static int dbg_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, bool i8, const float2* rmeta, float amax, int64_t N,
                               int E, float rmax, const float* q_dev, int Q, int K, float* out_score_dev,
                               int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
-                              long long* survivors);
-
-extern "C" int clipmi_dbg_topk_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
-                                              const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
-                                              void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
-                                              long long* survivors) {
-    return dbg_coarse_scan_ms(db_dev, db_bf16_dev, false, nullptr, 0.f, N, E, rmax, q_dev, Q, K, out_score_dev, out_id_dev,
-                              ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
-}
-
-extern "C" int clipmi_dbg_topk_coarse_i8_scan_ms(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax,
-                                                 int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
-                                                 float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
-                                                 void* stream, int reps, float* scan_ms, long long* survivors) {
-    return dbg_coarse_scan_ms(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K,
-                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
-}
-
-static int dbg_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, bool i8, const float2* rmeta, float amax, int64_t N,
-                              int E, float rmax, const float* q_dev, int Q, int K, float* out_score_dev,
-                              int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
                               long long* survivors) {
     if (!scan_ms || reps < 1 || Q > COARSE_Q) return set_err(CLIPMI_EINVAL, "dbg_topk_coarse_scan_ms: bad arguments");
     // three event pairs: [0,1] the last segment, [2,3] rows [0, S2), [4,5] rows [S2, N1) of the coarse copy (see
@@ -3609,16 +2938,6 @@ static int dbg_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, bool 
     }
     for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]);
     if (rc == 0) *scan_ms = (float)(total / reps);
-    if (rc == 0 && dev_knob_set("CLIPMI_LIVE_STATS")) {
-        Plan p; CoarseWs w; coarse_plan(N, E, Q, K, p); carve_coarse(p, ws_dev, ws_bytes, &w);
-        unsigned h[28];
-        if (hipMemcpy(h, w.flag + 4, sizeof(h), hipMemcpyDeviceToHost) == hipSuccess) {
-            fprintf(stderr, "scanner wave time, mean us: matrix loop (incl. waiting for rows) %.1f | bounds + compare %.1f | push %.1f\n",
-                    h[12] * 16 * 0.01 / (h[15] ? h[15] : 1), h[13] * 16 * 0.01 / (h[15] ? h[15] : 1), h[14] * 16 * 0.01 / (h[15] ? h[15] : 1));
-            fprintf(stderr, "live scan (last call): pushed %u (push spins %u) popped %u stale %u re-scored %u inserted %u rounds %u (phases %u) ladder rises %u | last scanner wave done at %.1f us (mean %.1f), last re-scoring wave at %.1f us\n",
-                    h[0], h[1], h[2], h[3], h[4], h[5], h[6], h[11], h[7], h[8] * 0.01, h[10] * 1024.0 * 0.01 / (h[15] ? h[15] : 1), h[9] * 0.01);
-        }
-    }
     if (rc == 0 && survivors) {       // rows that survived the coarse pass, summed over the Q queries of the last call
         Plan p;
         CoarseWs w;
@@ -3633,6 +2952,22 @@ static int dbg_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, bool 
         *survivors = tot;
     }
     return rc;
+}
+
+extern "C" int clipmi_dbg_topk_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
+                                              const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
+                                              void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
+                                              long long* survivors) {
+    return dbg_coarse_scan_ms(db_dev, db_bf16_dev, false, nullptr, 0.f, N, E, rmax, q_dev, Q, K, out_score_dev, out_id_dev,
+                              ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
+}
+
+extern "C" int clipmi_dbg_topk_coarse_i8_scan_ms(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax,
+                                                 int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
+                                                 float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
+                                                 void* stream, int reps, float* scan_ms, long long* survivors) {
+    return dbg_coarse_scan_ms(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K,
+                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
 }
 
 // Measurement hook (bench.py roofline): the same call sequence as clipmi_topk_ip, `reps` times,

@@ -29,8 +29,9 @@ def test_library_exports_every_declared_symbol(clipmi):
 
 def test_product_library_reads_no_environment_and_ships_no_lab_kernels(clipmi):
     """The product library imports no getenv (the CLIPMI_* A/B knobs exist in the -DCLIPMI_DEV build only) and does not
-    contain the laboratory kernels that no product path selects (live-threshold scan, gemm2w); the development library,
-    which tools/ and two child-process tests load with CLIPMI_DEV_LIB=1, has both."""
+    contain the laboratory kernels that no product path selects (the wide scan's ablations; the live-threshold scan, the two-digit
+    query scan and gemm2w have left the tree); the development library, which tools/ and the child-process tests load with
+    CLIPMI_DEV_LIB=1, has both."""
     lib = os.path.join(ROOT, "cli-p_amd", "libclipmi.so")
     dev = os.path.join(ROOT, "cli-p_amd", "libclipmi_dev.so")
     assert clipmi._lib.LIB_PATH == lib
@@ -38,12 +39,12 @@ def test_product_library_reads_no_environment_and_ships_no_lab_kernels(clipmi):
     assert "getenv" not in undefined
     blob = open(lib, "rb").read()
     assert b"scan_coarse_live_kernel" not in blob and b"gemm2w_resid_ln_kernel" not in blob
-    two_digit_scan = b"scan_coarse_kernelILi512ELi4ELb0ELb1ELb1E"        # <512, 4, false, int8, two query digits>: DESIGN 4.1h
-    assert two_digit_scan not in blob
+    wide_ablation = b"scan_coarse_wide_kernelILi8ELi1ELi16E"            # <8 waves, ABL = 1 (no compare), 16 k-steps>: CLIPMI_WIDE_ABL
+    assert wide_ablation not in blob
     assert os.path.exists(dev), "build() also builds libclipmi_dev.so"
     assert "getenv" in subprocess.check_output(["nm", "-D", "--undefined-only", dev], text=True)
     dblob = open(dev, "rb").read()
-    assert b"scan_coarse_live_kernel" in dblob and two_digit_scan in dblob
+    assert wide_ablation in dblob
 
 
 def test_tower_struct_matches_header(clipmi, tmp_path):

@@ -1,9 +1,12 @@
-"""Live-threshold scan (development aid): bit-exactness vs the exact f32 scan + timing at several N / Q."""
+"""Child process of tests/test_topk_gpu.py: the int8 coarse search under whatever CLIPMI_* knobs the environment sets (they are
+read once per process; development library), bit for bit against the exact f32 scan, + timing at several N / Q.
+
+    python tests/topk_knobs_child.py [N] [Q,Q,...]      one "... exact: True|False" line per Q
+"""
 import sys, os, time
 os.environ.setdefault("CLIPMI_DEV_LIB", "1")   # A/B knobs: development library only
-os.environ.setdefault("CLIPMI_LIVE", "1")      # the live scan is off by default (topk.hip)
 import torch
-sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import clipmi
 dev = torch.device("cuda:0")
 N = int(sys.argv[1]) if len(sys.argv) > 1 else 10_000_000

@@ -10,7 +10,7 @@ if sys.argv[1] == "run":
         import importlib
         _b = importlib.import_module("cli-p_amd.build")
         clipmi._lib.LIB_PATH = os.environ["AB_LIB"]
-        _b.is_current = lambda: True
+        _b.is_current = lambda *variant: True
     dev = torch.device("cuda:0")
     N, Q, K = int(sys.argv[2]), int(sys.argv[3]), int(sys.argv[4])
     g = torch.Generator(device=dev); g.manual_seed(1)
