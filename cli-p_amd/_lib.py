@@ -217,6 +217,31 @@ def stream_ptr(device=None):
     return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
+def pack16(arrays, tail=0, pin=False):
+    """Arrays -> (one uint8 host tensor that holds their bytes at 16-byte-aligned offsets, the offsets). tail: that many more bytes behind
+    them for the caller to fill, aligned too - the last offset is theirs. pin: page-locked, at least 16 bytes, the gaps not zeroed."""
+    import numpy as np
+    import torch
+    offs, end = [], 0
+    for nbytes in [a.nbytes for a in arrays] + ([tail] if tail else []):
+        offs.append((end + 15) // 16 * 16)
+        end = offs[-1] + nbytes
+    # (numpy's zeros, not torch's: a torch fill of this size wakes the OpenMP team, which then spins beside the decode workers)
+    host = torch.empty(max(end, 16), dtype=torch.uint8).pin_memory() if pin else torch.from_numpy(np.zeros(end, np.uint8))
+    hv = host.numpy()
+    for a, o in zip(arrays, offs):
+        hv[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
+    return host, offs
+
+
+def to_device16(arrays, device, tail=0, fill=None):
+    """pack16 into pinned memory, fill(view of the tail), ONE asynchronous copy on torch's current stream -> (device tensor, offsets, host tensor)"""
+    host, offs = pack16(arrays, tail, pin=True)
+    if tail:
+        fill(host.numpy()[offs[-1]:offs[-1] + tail])
+    return host.to(device, non_blocking=True), offs, host
+
+
 _SIDE_STREAMS = {}
 
 

@@ -168,7 +168,7 @@ JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then w
 
 
 class HDR:
-    """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, pipeline.py reads them
+    """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, device_stage.py reads them
     through these names); [24..31] are zero. Offsets count bytes from the region's start."""
     KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA or KIND_PNG_INDEX
     NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
@@ -356,7 +356,7 @@ def _stage_png_kind(kind):
 # out, "decoded" those of them the device did not report.
 Kind = namedtuple("Kind", "kind bit magic stager stat counts")
 FULL_SIZE = Kind(2, 1, None, decode_full, None, None)         # decoded pixels at full size, for the resize on the device
-# the parsed files, in the order serve() tries them and the device's statuses are laid out (pipeline.device_stage)
+# the parsed files, in the order serve() tries them and the device's statuses are laid out (device_stage.DeviceStage.run)
 PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
           Kind(KIND_PROGRESSIVE, 4, "jpeg", stage_jpeg_progressive, "jpeg_progressive_files", "staged"),
           Kind(KIND_PNG, 8, "png", stage_png, "png_files", "decoded"),

@@ -70,14 +70,7 @@ def decode_device(items, device, stream=None):
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
     if n == 0:
         return out, recs, status
-    o_tab = (recs.nbytes + 15) // 16 * 16
-    o_str = (o_tab + tables.nbytes + 15) // 16 * 16
-    host = torch.empty(o_str + streams.nbytes, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-    hv[o_tab:o_tab + tables.nbytes] = tables.reshape(-1)
-    hv[o_str:] = streams
-    dev = host.to(device, non_blocking=True)
+    dev, (_, o_tab, o_str), _ = _lib.to_device16([recs, tables, streams], device)
     ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, len(tables)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
@@ -90,21 +83,19 @@ def decode_device(items, device, stream=None):
     return out, recs, status
 
 
-def decode_files(blobs, device, keep_stuffing=False):
-    """JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
-    device reported it corrupt). Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM.
-    keep_stuffing: hand the segments over as they are in the file and let the device remove the byte stuffing (the pipeline's form)."""
+def _decode_files(blobs, device, parser, decode):
+    """decode_files' and decode_progressive_files' body: parser(file) -> a record or Unsupported; decode: the records' decode_*_device"""
     items, where = [], []
     for k, b in enumerate(blobs):
         try:
-            items.append(parse(b, keep_stuffing=keep_stuffing))
+            items.append(parser(b))
             where.append(k)
         except Unsupported:
             pass
     res = [None] * len(blobs)
     if not items:
         return res
-    out, recs, status = decode_device(items, device)
+    out, recs, status = decode(items, device)
     st = status.cpu().numpy()
     host = out.cpu().numpy()
     for t, k in enumerate(where):
@@ -113,6 +104,13 @@ def decode_files(blobs, device, keep_stuffing=False):
             h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
             res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
     return res
+
+
+def decode_files(blobs, device, keep_stuffing=False):
+    """JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
+    device reported it corrupt). Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM.
+    keep_stuffing: hand the segments over as they are in the file and let the device remove the byte stuffing (the pipeline's form)."""
+    return _decode_files(blobs, device, lambda b: parse(b, keep_stuffing=keep_stuffing), decode_device)
 
 
 # ---- progressive files (jpeg_parse.parse_progressive; csrc/jpeg.hip jpeg_progressive_kernel). Opt-in in the pipeline.
@@ -172,16 +170,7 @@ def decode_progressive_device(items, device, stream=None):
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
     if n == 0:
         return out, recs, status
-    o_scan = (recs.nbytes + 15) // 16 * 16
-    o_tab = (o_scan + scans.nbytes + 15) // 16 * 16
-    o_str = (o_tab + tables.nbytes + 15) // 16 * 16
-    host = torch.empty(o_str + streams.nbytes, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-    hv[o_scan:o_scan + scans.nbytes] = scans.view(np.uint8).reshape(-1)
-    hv[o_tab:o_tab + tables.nbytes] = tables.reshape(-1)
-    hv[o_str:] = streams
-    dev = host.to(device, non_blocking=True)
+    dev, (_, o_scan, o_tab, o_str), _ = _lib.to_device16([recs, scans, tables, streams], device)
     ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, len(tables)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
@@ -198,25 +187,7 @@ def decode_progressive_device(items, device, stream=None):
 def decode_progressive_files(blobs, device):
     """Progressive JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder
     or the device reported it). Synchronises; a convenience for tests and tools."""
-    items, where = [], []
-    for k, b in enumerate(blobs):
-        try:
-            items.append(parse_progressive(b))
-            where.append(k)
-        except Unsupported:
-            pass
-    res = [None] * len(blobs)
-    if not items:
-        return res
-    out, recs, status = decode_progressive_device(items, device)
-    st = status.cpu().numpy()
-    host = out.cpu().numpy()
-    for t, k in enumerate(where):
-        if st[t] == 0:
-            r = recs[t]
-            h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
-            res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
-    return res
+    return _decode_files(blobs, device, parse_progressive, decode_progressive_device)
 
 
 # ---- decode + the transform in one call (csrc/jpeg.hip jpeg_color_resize_h_kernel): baseline and progressive files straight to
@@ -261,15 +232,7 @@ def stage_transform(blobs, n_px, device, keep_stuffing=False):
         jobs["out_index"] = [k for k, _ in members]
         jobs["src_off"] = recs["out_off"]                 # (the decoder's rows: what the unfused form's resize reads)
         arrays += [jobs, coef, streams]
-        offs, end = [], 0
-        for a in arrays:
-            offs.append((end + 15) // 16 * 16)
-            end = offs[-1] + a.nbytes
-        host = torch.empty(max(end, 16), dtype=torch.uint8).pin_memory()
-        hv = host.numpy()
-        for a, o in zip(arrays, offs):
-            hv[o:o + a.nbytes] = a.view(np.uint8).reshape(-1)
-        dev = host.to(device, non_blocking=True)
+        dev, offs, host = _lib.to_device16(arrays, device)
         st.keep.append(host)
         st.groups.append(dict(progressive=bool(progressive), n=len(items), dev=dev, offs=offs, nscans=len(scans) if progressive else 0,
                               ntables=len(tables), total_blocks=total_blocks, max_blocks=max_blocks, max_pixels=max_pixels,

@@ -67,12 +67,7 @@ def decode_device(items, device, stream=None):
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
     if n == 0:
         return out, recs, status
-    o_str = (recs.nbytes + 15) // 16 * 16
-    host = torch.empty(o_str + streams.nbytes, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:recs.nbytes] = recs.view(np.uint8).reshape(-1)
-    hv[o_str:] = streams
-    dev = host.to(device, non_blocking=True)
+    dev, (_, o_str), _ = _lib.to_device16([recs, streams], device)
     ws_bytes = int(size_of(n, total_raw))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
@@ -123,8 +118,8 @@ def transform_device(items, out_rows, n_px, out, decoded, recs, device):
     """The transform of decoded files on the device: the rows of `decoded` (decode_device's buffer, records `recs`) of the Parsed
     `items`, all of one kind -> out[out_rows[k]] uint8 [3,n_px,n_px], through the entry of that kind: clipmi_resize_crop_rgb8,
     clipmi_resize_crop_rgba8 or clipmi_nearest_crop_p8."""
-    from .decode_worker import nearest_plan, resize_plan
-    from .resize import JOB, NEAREST_JOB
+    from .decode_worker import nearest_plan
+    from .resize import NEAREST_JOB, pack_jobs
     L = _lib.lib()
     kind = items[0].kind
     px = PX_BYTES[kind]
@@ -146,22 +141,11 @@ def transform_device(items, out_rows, n_px, out, decoded, recs, device):
                                       _lib.stream_ptr(device))
         _lib.check(rc, "clipmi_nearest_crop_p8")
         return
-    jobs = np.zeros(n, dtype=JOB)
-    coefs, coff, toff, max_rows = [], 0, 0, 1
-    for k, it in enumerate(items):
-        p = resize_plan(it.width, it.height, n_px)
-        j = jobs[k]
-        j["src_off"], j["w"], j["h"], j["r0"], j["nrows"], j["out_index"] = int(recs[k]["out_off"]), it.width, it.height, p["r0"], p["nrows"], out_rows[k]
-        j["need_h"], j["need_v"], j["left"], j["top"], j["hk"], j["vk"] = p["need_h"], p["need_v"], p["left"], p["top"], p["hk"], p["vk"]
-        j["hcoef_off"], j["vcoef_off"], j["tmp_off"] = coff, coff + p["hcoef"].size, toff
-        coefs += [p["hcoef"], p["vcoef"]]
-        coff += p["hcoef"].size + p["vcoef"].size
-        toff += p["nrows"] * n_px * px
-        max_rows = max(max_rows, p["nrows"])
-    coef = np.concatenate(coefs + [np.zeros(1, np.int32)]).astype(np.int32)
+    jobs, coef, _, scratch_bytes, max_rows = pack_jobs([(it.height, it.width) for it in items], n_px, px=px)
+    jobs["src_off"], jobs["out_index"] = recs["out_off"][:n], out_rows      # (the decoder's rows; the caller's rows of `out`)
     small = np.concatenate([jobs.view(np.uint8).reshape(-1), coef.view(np.uint8)])
     dsmall = torch.from_numpy(small).to(device)
-    scratch = torch.empty(max(toff, 1), dtype=torch.uint8, device=device)
+    scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
     name = "clipmi_resize_crop_rgba8" if kind == "alpha" else "clipmi_resize_crop_rgb8"
     rc = getattr(L, name)(decoded.data_ptr(), dsmall.data_ptr(), n, max_rows, dsmall.data_ptr() + jobs.nbytes, n_px, out.data_ptr(),
                           scratch.data_ptr(), _lib.stream_ptr(device))

@@ -22,8 +22,9 @@ NEAREST_JOB = np.dtype([("src_off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("out_in
 assert NEAREST_JOB.itemsize == 48
 
 
-def pack_jobs(shapes, n_px, plans=None):
-    """Job records + one coefficient array for images of the given (h, w) shapes laid out back to back (HWC bytes).
+def pack_jobs(shapes, n_px, plans=None, px=3):
+    """Job records + one coefficient array for images of the given (h, w) shapes laid out back to back (HWC bytes, px a pixel:
+    the source layout and the rows between the two passes).
     -> (jobs structured array, coef int32 array, raw bytes total, scratch bytes, max_rows)"""
     jobs = np.zeros(len(shapes), dtype=JOB)
     coefs, coff, soff, toff, max_rows = [], 0, 0, 0, 1
@@ -37,8 +38,8 @@ def pack_jobs(shapes, n_px, plans=None):
         j["vcoef_off"] = coff
         coefs.append(p["vcoef"]); coff += p["vcoef"].size
         j["tmp_off"] = toff
-        toff += p["nrows"] * n_px * 3
-        soff += h * w * 3
+        toff += p["nrows"] * n_px * px
+        soff += h * w * px
         max_rows = max(max_rows, p["nrows"])
     coef = np.concatenate(coefs).astype(np.int32) if coff else np.zeros(1, np.int32)
     return jobs, coef, soff, max(toff, 1), max_rows
@@ -59,18 +60,14 @@ def resize_crop_device(images, n_px, device, out=None):
         if a.dtype != np.uint8 or a.ndim != 3 or a.shape[2] != 3:
             raise ValueError("resize_crop_device: expected uint8 [H,W,3] arrays")
     jobs, coef, raw_bytes, scratch_bytes, max_rows = pack_jobs([a.shape[:2] for a in images], n_px)
-    o_coef = (jobs.nbytes + 15) // 16 * 16
-    o_raw = (o_coef + coef.nbytes + 15) // 16 * 16
-    host = torch.empty(o_raw + raw_bytes, dtype=torch.uint8).pin_memory()
-    hv = host.numpy()
-    hv[:jobs.nbytes] = jobs.view(np.uint8).reshape(-1)
-    hv[o_coef:o_coef + coef.nbytes] = coef.view(np.uint8)
-    off = o_raw
-    for a in images:
-        n = a.size
-        hv[off:off + n] = np.ascontiguousarray(a).reshape(-1)
-        off += n
-    dev = host.to(device, non_blocking=True)
+
+    def pixels(tail):
+        off = 0
+        for a in images:
+            tail[off:off + a.size] = np.ascontiguousarray(a).reshape(-1)
+            off += a.size
+
+    dev, (_, o_coef, o_raw), _ = _lib.to_device16([jobs, coef], device, tail=raw_bytes, fill=pixels)
     scratch = torch.empty(scratch_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
     rc = L.clipmi_resize_crop_rgb8(base + o_raw, base, B, max_rows, base + o_coef, n_px, out.data_ptr(), scratch.data_ptr(),

@@ -124,9 +124,9 @@ def test_pack_lays_out_aligned_streams_and_shares_tables():
 
 def test_worker_regions_and_the_records_built_from_them(tmp_path):
     """What a decode worker lays out for a JPEG file (decode_worker.stage_jpeg) and what the parent builds out of a batch's
-    regions (pipeline.jpeg_records) is, field for field, what jpeg.pack builds from the parsed files: sizes, sampling,
+    regions (device_stage.jpeg_records) is, field for field, what jpeg.pack builds from the parsed files: sizes, sampling,
     quantisation steps, table indices into the distinct tables, the segment's bytes, restart intervals, the resize plan."""
-    from clipmi import jpeg, pipeline
+    from clipmi import device_stage, jpeg
     from clipmi import decode_worker as dw
     rng = np.random.default_rng(12)
     specs = [(224, 224, dict(quality=95, subsampling=2)), (300, 500, dict(quality=85, subsampling=1)),
@@ -149,7 +149,7 @@ def test_worker_regions_and_the_records_built_from_them(tmp_path):
         Image.fromarray(smooth(rng, 50, 50)).save(str(tmp_path / "p.jpg"), format="JPEG", progressive=True)
         dw.stage_jpeg(str(tmp_path / "p.jpg"), n_px, big[6 * cap:7 * cap])
     comp = np.arange(n)
-    recs, tables, jobs, out_sz, blocks, nt = pipeline.jpeg_records(big, n, cap, slots, comp, n_px)
+    recs, tables, jobs, out_sz, blocks, nt = device_stage.jpeg_records(big, n, cap, slots, comp, n_px)
     ref, rtab, rstreams, _, total_blocks, _, _ = jpeg.pack(items)
     assert nt == len(rtab) and int(blocks.sum()) == total_blocks
     tables = tables.reshape(nt, jpeg_parse.TABLE_BYTES)

@@ -9,7 +9,7 @@ import numpy as np
 from PIL import Image
 
 from clipmi import decode_worker as dw
-from clipmi import pipeline
+from clipmi import device_stage, pipeline
 
 vp, i32, i64 = C.c_void_p, C.c_int, C.c_int64
 TRANSFORM = [vp, i32, vp, i32, vp, vp]                      # jobs, max_rows, coef, n_px, out, scratch
@@ -37,16 +37,16 @@ def test_encode_files_has_the_keyword_and_the_switch_is_off_when_unset(monkeypat
     p = inspect.signature(pipeline.encode_files).parameters
     assert "jpeg_fused" in p and p["jpeg_fused"].default is None
     monkeypatch.delenv("CLIPMI_DEVICE_JPEG_FUSED", raising=False)
-    assert pipeline.jpeg_fused_default() is False
+    assert device_stage.jpeg_fused_default() is False
     for value, on in (("", False), ("0", False), ("1", True)):
         monkeypatch.setenv("CLIPMI_DEVICE_JPEG_FUSED", value)
-        assert pipeline.jpeg_fused_default() is on
-    assert pipeline.formats(False) is pipeline._FORMATS
-    fused = pipeline.formats(True)
-    assert set(fused) == set(pipeline._FORMATS)
-    for kind in pipeline._FORMATS:
+        assert device_stage.jpeg_fused_default() is on
+    assert device_stage.formats(False) is device_stage._FORMATS
+    fused = device_stage.formats(True)
+    assert set(fused) == set(device_stage._FORMATS)
+    for kind in device_stage._FORMATS:
         changed = kind in (dw.KIND_BASELINE, dw.KIND_PROGRESSIVE)
-        assert (fused[kind] != pipeline._FORMATS[kind]) == changed
+        assert (fused[kind] != device_stage._FORMATS[kind]) == changed
         assert (fused[kind][4] is None) == changed            # no transform entry of its own: the decode entry transforms
 
 
@@ -64,9 +64,9 @@ def test_a_fused_file_needs_its_full_size_rows_less(tmp_path):
         assert stage(None, n_px, region, data=buf.getvalue())[2] > 0
         hd = region[:4 * dw.JPEG_HDR_INTS].view(np.int32).astype(np.int64)[None, :]
         assert (hd[0, dw.HDR.W], hd[0, dw.HDR.H], hd[0, dw.HDR.HS], hd[0, dw.HDR.VS]) == (w, h, 2, 2)
-        off = pipeline.file_need(hd, pipeline.formats(False)[kind], n_px)
-        on = pipeline.file_need(hd, pipeline.formats(True)[kind], n_px)
+        off = device_stage.file_need(hd, device_stage.formats(False)[kind], n_px)
+        on = device_stage.file_need(hd, device_stage.formats(True)[kind], n_px)
         assert off.shape == (1,) and int(on[0]) == int(off[0]) - rows
         assert int(on[0]) == int(hd[0, dw.HDR.BLOCKS]) * 192 + int(hd[0, dw.HDR.NROWS]) * n_px * 3
     for kind in (dw.KIND_PNG, dw.KIND_PNG_ALPHA, dw.KIND_PNG_INDEX):
-        assert pipeline.formats(True)[kind] is pipeline._FORMATS[kind]
+        assert device_stage.formats(True)[kind] is device_stage._FORMATS[kind]

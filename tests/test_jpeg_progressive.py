@@ -132,9 +132,9 @@ def test_parser_refuses_more_than_max_scans_and_too_much_work(monkeypatch):
 
 
 def test_worker_regions_give_the_records_pack_progressive_gives(tmp_path):
-    """decode_worker.stage_jpeg_progressive's region, read back by pipeline.progressive_records, holds the records, scans,
+    """decode_worker.stage_jpeg_progressive's region, read back by device_stage.progressive_records, holds the records, scans,
     tables and segments jpeg.pack_progressive builds from the same files (the pipeline's form of the same input)."""
-    from clipmi import decode_worker, jpeg, pipeline
+    from clipmi import decode_worker, device_stage, jpeg
     rng = np.random.default_rng(12)
     blobs = [encode(smooth(rng, 40 + 9 * k, 60 - 5 * k), quality=75 + k, subsampling=k % 3, progressive=True) for k in range(4)]
     blobs.append(jpeg_progressive.writer_cases(rng, big=False)[1][0])
@@ -148,7 +148,7 @@ def test_worker_regions_give_the_records_pack_progressive_gives(tmp_path):
         decode_worker.stage_jpeg_progressive(_baseline(tmp_path), 224, big[:cap])
     assert decode_worker.stage_jpeg_progressive(str(tmp_path / "0.jpg"), 224, big[:256])[2] < 0          # does not fit: bytes wanted
     decode_worker.stage_jpeg_progressive(str(tmp_path / "0.jpg"), 224, big[:cap])
-    recs, scans, tables, jobs, out_sz, blocks, nt = pipeline.progressive_records(big, len(blobs), cap, np.arange(len(blobs)),
+    recs, scans, tables, jobs, out_sz, blocks, nt = device_stage.progressive_records(big, len(blobs), cap, np.arange(len(blobs)),
                                                                                 np.arange(len(blobs)), 224)
     items = [jpeg_parse.parse_progressive(b) for b in blobs]
     prec, pscans, ptables = jpeg.pack_progressive(items)[:3]

@@ -215,9 +215,9 @@ def test_stage_png_round_trips_a_file_through_a_region(tmp_path):
 
 def test_worker_regions_and_the_png_records_built_from_them(tmp_path):
     """What a decode worker lays out for PNG files (decode_worker.stage_png) and what the parent builds out of a batch's regions
-    (pipeline.png_records) is, field for field, what png.pack builds from the parsed files, with the streams in place in the
+    (device_stage.png_records) is, field for field, what png.pack builds from the parsed files, with the streams in place in the
     segment; the resize jobs are resize_plan's, with the coefficient blocks where the jobs point."""
-    from clipmi import decode_worker as dw, pipeline
+    from clipmi import decode_worker as dw, device_stage
     rng = np.random.default_rng(7)
     specs = [(64, 96, 3), (260, 300, 1), (224, 224, 3), (300, 260, 1)]          # (h, w, channels)
     n, cap, n_px = len(specs) + 2, 256 << 10, 224
@@ -233,7 +233,7 @@ def test_worker_regions_and_the_png_records_built_from_them(tmp_path):
         slots.append(slot)
         items.append(png_parse.parse(blob))
     comp = np.arange(n)
-    recs, jobs, out_sz, raw_sz = pipeline.png_records(big, n, cap, slots, comp, n_px)
+    recs, jobs, out_sz, raw_sz = device_stage.png_records(big, n, cap, slots, comp, n_px)
     ref = png.pack(items)[0]
     for f in ("stream_bytes", "width", "height", "channels", "raw_off", "out_off"):
         assert np.array_equal(recs[f], ref[f]), f

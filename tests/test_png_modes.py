@@ -303,9 +303,9 @@ def test_stage_png_region_layout_with_the_bit_on_and_off(tmp_path):
 
 
 def test_records_the_parent_builds_from_the_regions(tmp_path):
-    """pipeline._FORMATS' records for the two new kinds, out of a batch's regions: field for field png.pack's, the jobs resize_plan's
+    """device_stage._FORMATS' records for the two new kinds, out of a batch's regions: field for field png.pack's, the jobs resize_plan's
     or the nearest tables' where the regions hold them"""
-    from clipmi import pipeline
+    from clipmi import device_stage
     dw = decode_worker
     rng = np.random.default_rng(16)
     n_px, cap = 224, 256 << 10
@@ -322,13 +322,13 @@ def test_records_the_parent_builds_from_the_regions(tmp_path):
             assert 0 < dw.stage_png(str(path), n_px, big[slot * cap:(slot + 1) * cap], modes=True)[2] <= cap
             slots.append(slot)
             items.append(png_parse.parse(blob, modes=True))
-        records, decoder_bytes, group, fpx, entry = pipeline._FORMATS[kind]
+        records, decoder_bytes, group, fpx, entry = device_stage._FORMATS[kind]
         assert fpx == px and entry == ("clipmi_nearest_crop_p8" if px == 1 else "clipmi_resize_crop_rgba8")
         recs, jobs, out_sz, raw_sz = records(big, n, cap, slots, np.arange(n), n_px)
         ref = png.pack(items)[0]
         for f in ("stream_bytes", "width", "height", "channels", "raw_off", "out_off", "reserved"):
             assert np.array_equal(recs[f], ref[f]), f
-        hd = pipeline._headers(big, n, cap, np.asarray(slots))
+        hd = device_stage._headers(big, n, cap, np.asarray(slots))
         assert list(decoder_bytes(hd)) == [it.raw_bytes() for it in items]
         assert list(out_sz) == [(it.width * it.height * px + 15) // 16 * 16 for it in items]
         assert list(raw_sz) == [(it.raw_bytes() + 15) // 16 * 16 for it in items]

@@ -353,9 +353,9 @@ def test_lmdb_file_reader_deep_tree_small_pages(clipmi, tmp_path):
 
 
 def test_pipeline_groups_files_under_a_budget(clipmi):
-    """pipeline._groups, the rule by which device_stage splits a batch's parsed files into launches: a group closes when the next
+    """device_stage._groups, the rule by which DeviceStage splits a batch's parsed files into launches: a group closes when the next
     file would exceed the budget, a file above the budget is a group of its own; _pack16 lays a group's records out 16-aligned."""
-    groups = clipmi.pipeline._groups
+    groups = clipmi.device_stage._groups
     assert groups(np.zeros(0, np.int64), 100) == []                              # device_stage skips a kind without files
     assert groups(np.array([7]), 100) == [(0, 1)] and groups(np.array([700]), 100) == [(0, 1)]
     assert groups(np.array([101, 200, 150, 1000]), 100) == [(0, 1), (1, 2), (2, 3), (3, 4)]       # every file above the budget
@@ -363,6 +363,6 @@ def test_pipeline_groups_files_under_a_budget(clipmi):
     assert groups(np.array([30, 30, 30, 30, 500, 10, 20, 90, 10, 91]), 100) == [(0, 3), (3, 4), (4, 5), (5, 7), (7, 9), (9, 10)]
     assert groups(np.array([1, 2, 3]), 1 << 40) == [(0, 3)]
     a, b, c = np.arange(5, dtype=np.int32), np.zeros(0, np.uint8), np.arange(3, dtype=np.int64)
-    buf, offs = clipmi.pipeline._pack16([a, b, c])
+    buf, offs = clipmi.device_stage._pack16([a, b, c])
     assert offs == [0, 32, 32] and buf.dtype == np.uint8 and buf.size == 32 + 24
     assert buf[:20].tobytes() == a.tobytes() and not buf[20:32].any() and buf[32:].tobytes() == c.tobytes()
