@@ -1675,26 +1675,30 @@ int opt_in_lds(const void* fn, size_t bytes) {
     return 0;
 }
 
-template <int E, bool PREPASS, int QG>
-int launch_scan_t(const ScanArgs& a, int grid, int waves, size_t lds, hipStream_t st, hipEvent_t* ev, int ny) {
-    const void* fn = (const void*)scan_topk_f32_kernel<E, PREPASS, QG>;
-    if (int rc = opt_in_lds(fn, lds)) return rc;
+// One kernel launch of the search paths: the LDS limit, the opt-in above 64 KiB, an optional event pair around the launch,
+// and the launch check under `name`.
+template <typename Args>
+int launch_kernel(void (*kern)(Args), const char* name, dim3 grid, dim3 block, size_t lds, hipStream_t st, hipEvent_t* ev,
+                  const Args& a) {
+    if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "%s: %zu B of LDS", name, lds);
+    if (int rc = opt_in_lds((const void*)kern, lds)) return rc;
     // measurement: plain event records around the launch (for a millisecond-scale kernel they agree
     // with rocprofv3's dispatch time to <1 %; hipExtLaunchKernel's start/stop events read ~7 % long here)
     if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_topk_f32_kernel<E, PREPASS, QG>), dim3(grid, ny), dim3(waves * 64), lds, st, a);
+    hipLaunchKernelGGL(kern, grid, block, lds, st, a);
     if (ev) (void)hipEventRecord(ev[1], st);
-    CLIPMI_CHECK_LAUNCH("scan_topk_f32_kernel");
+    CLIPMI_CHECK_LAUNCH(name);
     return 0;
 }
 
 template <bool PREPASS>
 int launch_scan(int E, int QG, const ScanArgs& a, int grid, int waves, size_t lds, hipStream_t st, hipEvent_t* ev = nullptr,
                 int ny = 1) {
-    if (E == 512) return QG == 2 ? launch_scan_t<512, PREPASS, 2>(a, grid, waves, lds, st, ev, ny)
-                                 : launch_scan_t<512, PREPASS, 1>(a, grid, waves, lds, st, ev, ny);
-    return QG == 2 ? launch_scan_t<768, PREPASS, 2>(a, grid, waves, lds, st, ev, ny)
-                   : launch_scan_t<768, PREPASS, 1>(a, grid, waves, lds, st, ev, ny);
+    auto go = [&](void (*kern)(ScanArgs)) {
+        return launch_kernel(kern, "scan_topk_f32_kernel", dim3(grid, ny), dim3(waves * 64), lds, st, ev, a);
+    };
+    if (E == 512) return QG == 2 ? go(scan_topk_f32_kernel<512, PREPASS, 2>) : go(scan_topk_f32_kernel<512, PREPASS, 1>);
+    return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2>) : go(scan_topk_f32_kernel<768, PREPASS, 1>);
 }
 
 }  // namespace
@@ -1799,13 +1803,24 @@ constexpr int COARSE_Q = 64;                     // queries per coarse pass. (12
                                                  // leaves LDS for only 2 waves per CU = 2 of 4 SIMDs, and the pass turns
                                                  // MFMA-bound: 5.29 ms per 128 queries vs 2 x 2.21 ms)
 
-template <int E, int QG, bool PREPASS, bool I8>
-int launch_coarse_t(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
-    static_assert(QG <= 4, "64 queries per pass at most");
+// The scan of a 64-query pass for run-time (row width, 16-query groups, pre-pass name, copy): {512, 768} x {1, 2, 4} x {pre} x
+// {int8, bf16}
+template <int E, bool I8, class Go>
+int launch_coarse_ei(int qg, bool pre, const Go& go) {
+    switch (qg) {
+    case 1: return pre ? go(scan_coarse_kernel<E, 1, true, I8>) : go(scan_coarse_kernel<E, 1, false, I8>);
+    case 2: return pre ? go(scan_coarse_kernel<E, 2, true, I8>) : go(scan_coarse_kernel<E, 2, false, I8>);
+    case 4: return pre ? go(scan_coarse_kernel<E, 4, true, I8>) : go(scan_coarse_kernel<E, 4, false, I8>);
+    }
+    return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %d query groups", qg);
+}
+
+int launch_coarse(int E, int qg, bool pre, bool i8, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
+    if (E != 512 && E != 768) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: E = %d", E);
     constexpr int WAVES = 4;
     // the final publication reuses the head of the query image for 3 * 16 QG counters: keep >= 1 KiB
     // (image: 1 KiB per query group and k-step - E = 768: 48 KiB int8, 96 KiB bf16 at 64 queries; + 4 x 6 KiB of lists)
-    size_t lds = (size_t)QG * (E / (I8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
+    size_t lds = (size_t)qg * (E / (i8 ? 64 : 32)) * 1024 + WAVES * COARSE_WAVE_BYTES;
     // The LAST segment's scan (3/4 of the rows) reserves COARSE_MAIN_LDS although it uses 56-88 KiB: with two batches in
     // flight on two streams, two such scans then cannot share a CU. Sharing halves each one's bandwidth, both finish
     // together and both batches run their latency-bound side kernels at the same time with HBM idle (1.06-1.08 ms per 64
@@ -1814,34 +1829,14 @@ int launch_coarse_t(const CoarseArgs& a, long long nsteps, hipStream_t st, hipEv
     // batch takes 0.97-1.00 ms. (Padding every scan, i.e. the 114 KiB all of them used to need: 1.02-1.04 ms.)
     // development: CLIPMI_COARSE_WGS=2 - two workgroups (8 waves, 128 KB of rows in flight) per CU, no LDS padding
     static const int wgs = [] { const int v = (int)dev_knob("CLIPMI_COARSE_WGS", 1); return v == 2 ? 2 : 1; }();
-    if (!PREPASS && wgs == 1 && lds < (size_t)COARSE_MAIN_LDS) lds = COARSE_MAIN_LDS;
-    if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_kernel<E, QG, PREPASS, I8>, lds)) return rc;
+    if (!pre && wgs == 1 && lds < (size_t)COARSE_MAIN_LDS) lds = COARSE_MAIN_LDS;
     long long g_ = (nsteps + WAVES - 1) / WAVES;
     const int grid = (int)(g_ < (long long)NUM_CU * wgs ? g_ : (long long)NUM_CU * wgs);
-    if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_kernel<E, QG, PREPASS, I8>), dim3(grid), dim3(WAVES * 64), lds, st, a);
-    if (ev) (void)hipEventRecord(ev[1], st);
-    CLIPMI_CHECK_LAUNCH("scan_coarse_kernel");
-    return 0;
-}
-
-// The scan of a 64-query pass for run-time (row width, 16-query groups, pre-pass name, copy): {512, 768} x {1, 2, 4} x {pre} x
-// {int8, bf16}
-template <int E, bool I8>
-int launch_coarse_ei(int qg, bool pre, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
-    switch (qg) {
-    case 1: return pre ? launch_coarse_t<E, 1, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 1, false, I8>(a, nsteps, st, ev);
-    case 2: return pre ? launch_coarse_t<E, 2, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 2, false, I8>(a, nsteps, st, ev);
-    case 4: return pre ? launch_coarse_t<E, 4, true, I8>(a, nsteps, st, ev) : launch_coarse_t<E, 4, false, I8>(a, nsteps, st, ev);
-    }
-    return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: %d query groups", qg);
-}
-
-int launch_coarse(int E, int qg, bool pre, bool i8, const CoarseArgs& a, long long nsteps, hipStream_t st, hipEvent_t* ev) {
-    if (E == 768) return i8 ? launch_coarse_ei<768, true>(qg, pre, a, nsteps, st, ev) : launch_coarse_ei<768, false>(qg, pre, a, nsteps, st, ev);
-    if (E != 512) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse: E = %d", E);
-    return i8 ? launch_coarse_ei<512, true>(qg, pre, a, nsteps, st, ev) : launch_coarse_ei<512, false>(qg, pre, a, nsteps, st, ev);
+    auto go = [&](void (*kern)(CoarseArgs)) {
+        return launch_kernel(kern, "scan_coarse_kernel", dim3(grid), dim3(WAVES * 64), lds, st, ev, a);
+    };
+    if (E == 768) return i8 ? launch_coarse_ei<768, true>(qg, pre, go) : launch_coarse_ei<768, false>(qg, pre, go);
+    return i8 ? launch_coarse_ei<512, true>(qg, pre, go) : launch_coarse_ei<512, false>(qg, pre, go);
 }
 
 // coarse_prep_kernel for a run-time (row width, copy); E in {512, 768} (checked by the callers)
@@ -1865,10 +1860,23 @@ int launch_sample_scores(int E, int QG, dim3 grid, hipStream_t st, const float* 
 }
 
 constexpr int COARSE_CTL = 2 * COARSE_Q + 32;     // fallback counters | coarse counters | flag block (word 0: the overflow flag)
+inline int wide_qs(int Q) { return (Q + 63) / 64 * 64; }
+
+// The workspace of one chunk of a coarse search and what sizes it: query stride, candidate slots per query, control words,
+// uint4 entries of the query image, and whether the (unused) tauc slot of the 64-query passes exists.
+struct WsShape { int qs; long long cap; int nctl; size_t image; bool tauc; };
 struct CoarseWs {
-    uint2* cand_e; uint2* cand_c; unsigned* gcnt_e; unsigned* gcnt_c; float* thr0; float* tauc; unsigned* flag;
+    uint2* cand_e; uint2* cand_c; unsigned* gcnt_e; unsigned* gcnt_c; unsigned* flag; float* thr0; float* tauc;
     unsigned* last_m; float* qmeta; uint4* qimage;
 };
+
+// 64-query passes: the bf16 image of 64 queries, 64 KiB at E = 512, 96 KiB at 768 (int8: half of it)
+inline WsShape pass64_shape(int E) { return {COARSE_Q, COARSE_CAP, COARSE_CTL, (size_t)4 * (E / 32) * 64, true}; }
+// wide passes of Qc queries: 2 (E / 32) 64 entries per 64-query set: 32 KiB, 48 KiB at E = 768
+inline WsShape wide_shape(int E, int Qc) {
+    const int qs = wide_qs(Qc);
+    return {qs, WIDE_CAP, 2 * qs + 4, qs / 64 * (size_t)(4 * E), false};
+}
 
 // the plan of the coarse path's side kernels (sample select, fallback scan + select): within COARSE_SIDE_LDS when K allows
 bool coarse_plan(long long N, int E, int Q, int K, Plan& p) {
@@ -1876,19 +1884,20 @@ bool coarse_plan(long long N, int E, int Q, int K, Plan& p) {
     return make_plan(N, E, q, K, p, COARSE_SIDE_LDS) || make_plan(N, E, q, K, p);
 }
 
-size_t carve_coarse(const Plan& p, void* base, size_t cap, CoarseWs* w) {
+size_t carve(const Plan& p, const WsShape& s, void* base, size_t cap, CoarseWs* w) {
+    const size_t qs = (size_t)s.qs;
     Arena ar(base ? base : reinterpret_cast<void*>(256), cap);
     CoarseWs x;
-    x.cand_e = ar.take<uint2>((size_t)COARSE_Q * p.cap);   // the fallback's lists, all query groups side by side
-    x.cand_c = ar.take<uint2>((size_t)COARSE_Q * COARSE_CAP);
-    x.gcnt_e = ar.take<unsigned>(COARSE_CTL);          // one control block, cleared by coarse_prep_kernel
-    x.gcnt_c = x.gcnt_e + COARSE_Q;
-    x.flag = x.gcnt_e + 2 * COARSE_Q;
-    x.thr0 = ar.take<float>(COARSE_Q);
-    x.tauc = ar.take<float>(COARSE_Q);
-    x.last_m = ar.take<unsigned>(COARSE_Q);
-    x.qmeta = ar.take<float>(4 * 64);
-    x.qimage = ar.take<uint4>((size_t)4 * (p.E / 32) * 64);      // the bf16 image of 64 queries, 64 KiB at E = 512, 96 KiB at 768 (int8: half of it)
+    x.cand_e = ar.take<uint2>(qs * p.cap);             // the exact fallback's lists, all query groups side by side
+    x.cand_c = ar.take<uint2>(qs * s.cap);
+    x.gcnt_e = ar.take<unsigned>(s.nctl);              // one control block, cleared by coarse_prep_kernel
+    x.gcnt_c = x.gcnt_e + qs;
+    x.flag = x.gcnt_e + 2 * qs;
+    x.thr0 = ar.take<float>(qs);
+    x.tauc = s.tauc ? ar.take<float>(qs) : nullptr;
+    x.last_m = ar.take<unsigned>(qs);
+    x.qmeta = ar.take<float>(4 * qs);
+    x.qimage = ar.take<uint4>(s.image);
     if (w) *w = x;
     return ar.off + 256;
 }
@@ -1916,177 +1925,7 @@ inline void launch_rescore(bool wide, dim3 grid, hipStream_t st, const float* db
     else hipLaunchKernelGGL(rescore_pairs_kernel<512>, grid, dim3(256), RESCORE_LDS, st, db, q, cand, gcnt, cap, slot_rows);
 }
 
-// i8 = false: dbh_dev is the bf16 copy (rmeta, amax unused); i8 = true: dbh_dev is the int8 copy, rmeta its per-row
-// (scale, error norm) pairs padded to a multiple of 32 rows, amax >= every error norm
-int topk_ip_coarse_impl(const void* db_dev, const void* dbh_dev, bool i8, const float2* rmeta, float amax, int64_t N, int E,
-                        float rmax, const float* q_dev, int Q,
-                        int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
-                        void* stream, hipEvent_t* scan_ev) {
-    if (!db_dev || !dbh_dev || !q_dev || !out_score_dev || !out_id_dev || !ws_dev || (i8 && !rmeta))
-        return set_err(CLIPMI_EINVAL, "topk_ip_coarse: NULL pointer");
-    if (i8 && !(amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", amax);
-    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N)
-        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
-    if (!(rmax > 0.f) || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", rmax, (long long)N);
-    Plan p;
-    if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
-    if (ws_bytes < carve_coarse(p, nullptr, ~(size_t)0, nullptr))
-        return set_err(CLIPMI_EWORKSPACE, "topk_ip_coarse: workspace %zu too small", ws_bytes);
-    CoarseWs w;
-    carve_coarse(p, ws_dev, ws_bytes, &w);
-    hipStream_t st = as_stream(stream);
-    if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
-    if (int rc = opt_in_rescore(E)) return rc;
-    // int8: the rows the copy's slots hold, behind the block meta (quantize_rows_i8_kernel); bf16 copy: rows in order
-    const unsigned* slot_rows = i8 ? i8_slot_rows(rmeta, N) : nullptr;
-
-    for (int q0 = 0; q0 < Q; q0 += COARSE_Q) {
-        const int qa = (Q - q0) < COARSE_Q ? (Q - q0) : COARSE_Q;
-        const float* qg = q_dev + (size_t)q0 * E;
-        // per-query constants, the query image the scans copy, and the cleared counters + overflow flag (selects re-zero
-        // what they consume): one launch per 64-query group
-        launch_coarse_prep(E, i8, (unsigned)((qa + 15) / 16 * 4), st, qg, rmax, amax, qa, w.qmeta, w.qimage, w.gcnt_e, COARSE_CTL, COARSE_QS, 0);
-        CLIPMI_CHECK_LAUNCH("coarse_prep_kernel");
-        ScanArgs a;
-        a.db = static_cast<const float*>(db_dev);
-        a.K = K; a.C = p.C; a.wave_bytes = p.wave_bytes;
-        a.cand = w.cand_e; a.gcnt = w.gcnt_e; a.cap = p.cap;
-        // 1. exact two-level pre-pass: thr0[q] = exact K-th best score of the first S2 rows (S2 ~ N*K/2048,
-        //    so that only ~2-3 k rows per query survive the coarse pass; every survivor costs a 2-KB row
-        //    read in the re-scoring pass). Level 1 (S1 rows, no threshold) only feeds level 2's filter.
-        // (not rounded up to a power of two: at 12.5 M rows that made the first segment 524 k rows instead of 311 k and its
-        //  re-scoring, filtered only by level 1's weak bound, the largest of the three)
-        long long S2 = (N * (long long)K / 2048 + 31) & ~31ll;
-        if (S2 > ((N / 8) & ~31ll)) S2 = (N / 8) & ~31ll;
-        if (S2 < 32768) S2 = 32768;
-        // level 1 only has to thin level 2's candidates (S2*K/S1 per query): 8 k rows are enough, and its
-        // select then ranks 8 k entries per query instead of 32 k
-        // (12288 = what the select keeps in LDS; N >= 65536 here)
-        long long S1 = p.stage < 4096 ? 4096 : (p.stage / 16) * 16;
-        if (S1 > 12288) S1 = 12288;
-        if (S2 < S1) S2 = S1;
-        // (one unfiltered scan of S2 rows was tried for small shards: its 32 k-entry selects cost more
-        //  than the level-1 scan + select they replace)
-        const bool two_level = S2 > S1;
-        CoarseArgs c;
-        c.dbc = dbh_dev; c.rmeta = rmeta; c.qmeta = w.qmeta; c.qimage = w.qimage; c.q = qg; c.QA = qa; c.tauc = w.tauc; c.row0 = 0;
-        c.cand = w.cand_c; c.gcnt = w.gcnt_c; c.cap = COARSE_CAP; c.overflow = w.flag;
-        c.abl = (int)dev_knob("CLIPMI_COARSE_ABL", 0);
-        // rows [r0, r1) of the copy through the coarse machinery: scan -> exact re-scoring of the survivors -> select.
-        // keep & 1: the K best so far stay at the head of the candidate lists (gcnt = K) and the next segment appends behind
-        // them, so no row is scanned twice; `pre` only picks the kernel NAME profilers average under.
-        auto coarse_pass = [&](long long r0, long long r1, bool pre, float* thr_out, float* os, long long* oi, long long idb,
-                               hipEvent_t* ev, unsigned* m_out, int keep) -> int {
-            c.row0 = r0;
-            c.nrows = r1 - r0;
-            const long long nsteps = (c.nrows + 31) / 32;
-            if (int rc_ = launch_coarse(E, qa <= 16 ? 1 : qa <= 32 ? 2 : 4, pre, i8, c, nsteps, st, ev)) return rc_;
-            // ~1-3 k survivors per query = ~11 blocks of 256 pairs; a larger grid only queues idle blocks
-            launch_rescore(false, dim3(12, qa), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, COARSE_CAP, slot_rows, E);
-            CLIPMI_CHECK_LAUNCH("rescore_pairs_kernel");
-            // 4096 staged entries (32 KiB of LDS) cover these lists; a select block then fits on a CU even beside the
-            // last segment's scan of ANOTHER batch in flight (104 KiB), which the 96-KiB staging of the sample select does not
-            const int scap = p.stage < 4096 ? p.stage : 4096;
-            SelectArgs s;
-            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = COARSE_CAP; s.K = K;
-            s.id_base = idb; s.out_s = os; s.out_i = oi;
-            s.thr_out = thr_out; s.qmeta = thr_out ? w.qmeta : nullptr;
-            s.m_out = m_out; s.keep = keep; s.stage_cap = scap;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(coarse)");
-            return 0;
-        };
-        // level 1 (exact, unfiltered, all <= 64 queries in one launch): scores of the first rows -> K-th best per query
-        {
-            const long long rows1 = two_level ? S1 : S2;
-            long long gs = ((rows1 + 15) / 16 + 3) / 4;
-            if (gs > NUM_CU) gs = NUM_CU;
-            if (int rc = launch_sample_scores(E, 1, dim3((unsigned)gs, (unsigned)((qa + 15) / 16)), st, static_cast<const float*>(db_dev), rows1,
-                                              qg, qa, w.cand_c, (long long)COARSE_CAP, w.gcnt_c)) return rc;
-            CLIPMI_CHECK_LAUNCH("sample_scores_kernel");
-            // the sample's lists are dense (entry e IS row e): only the 4 score bytes are staged, as the wide pass's sample
-            // select does (48 KiB instead of 96 per block; round 5)
-            SelectArgs s;
-            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = COARSE_CAP; s.K = K;
-            s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = COARSE_QS;
-            s.stage_cap = (int)rows1; s.dense = 1; s.arm_fallback = w.flag;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)rows1 * 4 + 16, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(sample 1)");
-        }
-        // Segments of the copy, each scanned ONCE: [0, S2) (level 2 of the pre-pass, threshold from level 1), then
-        // [S2, N1) and [N1, N) with N1 ~ N/4. After every segment the exact K-th best of all rows seen so far is the
-        // next segment's threshold: the last 75 % of the rows are filtered by the K-th best of the first 25 % (about 100
-        // survivors per query at 10 M rows instead of 6 k with the level-2 threshold), which is what the exact re-scoring
-        // pass - a 2-KB row read per survivor - is paid for. One more segment would save ~25 us of re-scoring and cost
-        // ~55 us of launches.
-        float* os_final = out_score_dev + (size_t)q0 * K;
-        long long* oi_final = (long long*)out_id_dev + (size_t)q0 * K;
-        long long r_done = 0;
-        // development knob: CLIPMI_COARSE_SEGS=n (>= 4): n geometric segments from 64 k rows, as the wide pass plans them
-        static const int nseg_env = (int)dev_knob("CLIPMI_COARSE_SEGS", 0);
-        if (two_level && nseg_env >= 4 && N >= (1 << 20)) {
-            long long b = 65536;
-            const double ratio = pow((double)N / 65536.0, 1.0 / (nseg_env - 1));
-            for (int sgi = 0; sgi + 1 < nseg_env; ++sgi) {
-                const long long r1 = b & ~31ll;
-                if (int rc = coarse_pass(r_done, r1, true, w.thr0, nullptr, nullptr, 0, nullptr, w.last_m, sgi ? 3 : 1)) return rc;
-                r_done = r1;
-                b = (long long)(b * ratio);
-            }
-        } else if (two_level) {
-            if (int rc = coarse_pass(0, S2, true, w.thr0, nullptr, nullptr, 0, scan_ev ? scan_ev + 2 : nullptr, w.last_m, 1)) return rc;
-            r_done = S2;
-            long long N1 = (N / 4) & ~31ll;
-            if (N1 < 4 * S2) N1 = 4 * S2;
-            if (N1 + 65536 <= N) {
-                if (int rc = coarse_pass(r_done, N1, true, w.thr0, nullptr, nullptr, 0, scan_ev ? scan_ev + 4 : nullptr, w.last_m, 3)) return rc;
-                r_done = N1;
-            }
-        }
-        // last segment (its threshold was written by the previous select): scan, exact re-scoring, select into the result
-        if (int rc = coarse_pass(r_done, N, false, nullptr, os_final, oi_final, (long long)id_base, scan_ev, w.last_m, two_level ? 2 : 0))
-            return rc;
-        // 6. fallback: exact scan + select, exiting at once unless a coarse list overflowed
-        //    (two launches: the exact scan takes its groups of p.QA queries as blockIdx.y, each with its own lists)
-        {
-            const int ny = (qa + p.QA - 1) / p.QA;
-            a.q = qg; a.QA = qa < p.QA ? qa : p.QA; a.q_total = qa; a.nrows = N; a.thr_in = w.thr0; a.run_if = w.flag;
-            if (int rc2 = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, nullptr, ny)) return rc2;
-            SelectArgs s;
-            s.cand = w.cand_e; s.gcnt = w.gcnt_e; s.cap = p.cap; s.K = K;
-            s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final;
-            s.run_if = w.flag; s.stage_cap = p.stage;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(fallback)");
-        }
-    }
-    return 0;
-}
-
 // ---- wide pass: host side -----------------------------------------------------------------------------------------
-struct WideWs {
-    uint2* cand_e; uint2* cand_c; unsigned* gcnt_e; unsigned* gcnt_c; unsigned* flag; float* thr0; unsigned* last_m;
-    float* qmeta; uint4* qimage;
-};
-
-inline int wide_qs(int Q) { return (Q + 63) / 64 * 64; }
-
-size_t carve_wide(const Plan& p, int Qc, void* base, size_t cap, WideWs* w) {
-    const size_t qs = (size_t)wide_qs(Qc);
-    Arena ar(base ? base : reinterpret_cast<void*>(256), cap);
-    WideWs x;
-    x.cand_e = ar.take<uint2>(qs * p.cap);            // the exact fallback's lists
-    x.cand_c = ar.take<uint2>(qs * WIDE_CAP);
-    x.gcnt_e = ar.take<unsigned>(2 * qs + 4);         // one control block, cleared by coarse_prep_kernel
-    x.gcnt_c = x.gcnt_e + qs;
-    x.flag = x.gcnt_e + 2 * qs;
-    x.thr0 = ar.take<float>(qs);
-    x.last_m = ar.take<unsigned>(qs);
-    x.qmeta = ar.take<float>(4 * qs);
-    x.qimage = ar.take<uint4>(qs / 64 * (size_t)(4 * p.E));     // 2 (E / 32) 64 entries per 64-query set: 32 KiB, 48 KiB at E = 768
-    if (w) *w = x;
-    return ar.off + 256;
-}
 
 bool wide_disabled() {          // CLIPMI_WIDE=0: searches of more than 64 queries as 64-query passes (A/B aid)
     static const bool off = dev_knob("CLIPMI_WIDE", 1) == 0;
@@ -2357,35 +2196,21 @@ __global__ void __launch_bounds__(512) scan_coarse_wide2_kernel(WideArgs a) {
 // not have, so a part-filled tile no longer costs a full one (round 4 picked tiles of 256 queries for 513-768 queries)
 inline int wide2_groups(int Q) { (void)Q; return 2; }
 
-template <int NB, int NG>
-int launch_wide2_t(const WideArgs& a, hipStream_t st, hipEvent_t* ev) {
-    const size_t lds = (size_t)NB * W2_SLOT + 8 * WIDE_WAVE_BYTES + 8 * 64 * 96;        // ring | pair lists | hit queues
-    if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse_wide2: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_wide2_kernel<NB, NG>, lds)) return rc;
-    if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_wide2_kernel<NB, NG>), dim3(NUM_CU), dim3(512), lds, st, a);
-    if (ev) (void)hipEventRecord(ev[1], st);
-    CLIPMI_CHECK_LAUNCH("scan_coarse_wide2_kernel");
-    return 0;
-}
-
 template <int NB>
 int launch_wide2(const WideArgs& a, hipStream_t st, hipEvent_t* ev, int ng) {
-    return ng == 2 ? launch_wide2_t<NB, 2>(a, st, ev) : launch_wide2_t<NB, 1>(a, st, ev);
+    const size_t lds = (size_t)NB * W2_SLOT + 8 * WIDE_WAVE_BYTES + 8 * 64 * 96;        // ring | pair lists | hit queues
+    auto go = [&](void (*kern)(WideArgs)) {
+        return launch_kernel(kern, "scan_coarse_wide2_kernel", dim3(NUM_CU), dim3(512), lds, st, ev, a);
+    };
+    return ng == 2 ? go(scan_coarse_wide2_kernel<NB, 2>) : go(scan_coarse_wide2_kernel<NB, 1>);
 }
 
 template <int WAVES, int ABL = 0, int KS = 16>
-int launch_wide_t(const WideArgs& a, hipStream_t st, hipEvent_t* ev) {
+int launch_wide(const WideArgs& a, hipStream_t st, hipEvent_t* ev) {
     // image (2 KiB per k-step and 64-query set) | thresholds | lists: 8 waves 154 KiB at E = 512, 4 waves 110 KiB at E = 768
     if (a.spt > (KS == 24 ? WIDE768_TILE_SETS : WIDE_TILE_SETS)) return set_err(CLIPMI_EINVAL, "scan_coarse_wide: %d sets per tile", a.spt);
     const size_t lds = (size_t)a.spt * (KS * 2048) + 2048 + WAVES * WIDE_WAVE_BYTES;
-    if (lds > (size_t)LDS_LIMIT) return set_err(CLIPMI_EUNSUPPORTED, "scan_coarse_wide: %zu B of LDS", lds);
-    if (int rc = opt_in_lds((const void*)scan_coarse_wide_kernel<WAVES, ABL, KS>, lds)) return rc;
-    if (ev) (void)hipEventRecord(ev[0], st);
-    hipLaunchKernelGGL((scan_coarse_wide_kernel<WAVES, ABL, KS>), dim3(NUM_CU), dim3(WAVES * 64), lds, st, a);
-    if (ev) (void)hipEventRecord(ev[1], st);
-    CLIPMI_CHECK_LAUNCH("scan_coarse_wide_kernel");
-    return 0;
+    return launch_kernel(scan_coarse_wide_kernel<WAVES, ABL, KS>, "scan_coarse_wide_kernel", dim3(NUM_CU), dim3(WAVES * 64), lds, st, ev, a);
 }
 
 // segment boundaries of a wide search: rows [0, b[0]), [b[0], b[1]), ... [b[n-2], N); b[n-1] = N. After every segment the
@@ -2411,139 +2236,257 @@ int wide_segments(long long N, int K, long long S1, long long* b) {
     return n;
 }
 
-// int8 coarse-then-exact search of 64 < Q queries: chunks of <= WIDE_MAX_Q queries, each ONE pass of the copy in segments.
+// segment boundaries of a 64-query search, in wide_segments' form: [0, S2) (the pre-pass, its threshold from the sample),
+// then [S2, N1) and [N1, N) with N1 ~ N/4, each scanned ONCE. After every segment the exact K-th best of all rows seen so far
+// is the next segment's threshold: the last 75 % of the rows are filtered by the K-th best of the first 25 % (about 100
+// survivors per query at 10 M rows instead of 6 k with the pre-pass threshold), which is what the exact re-scoring
+// pass - a 2-KB row read per survivor - is paid for. One more segment would save ~25 us of re-scoring and cost
+// ~55 us of launches.
+int coarse_segments(long long N, int K, long long S1, long long* b) {
+    // S2 ~ N*K/2048, so that only ~2-3 k rows per query survive the coarse pass; every survivor costs a 2-KB row read in the
+    // re-scoring pass. The sample (S1 rows, no threshold) only feeds this segment's filter.
+    // (not rounded up to a power of two: at 12.5 M rows that made the first segment 524 k rows instead of 311 k and its
+    //  re-scoring, filtered only by the sample's weak bound, the largest of the three)
+    // (one unfiltered scan of S2 rows was tried for small shards: its 32 k-entry selects cost more
+    //  than the sample scan + select they replace)
+    long long S2 = (N * (long long)K / 2048 + 31) & ~31ll;
+    if (S2 > ((N / 8) & ~31ll)) S2 = (N / 8) & ~31ll;
+    if (S2 < 32768) S2 = 32768;                     // > S1 (<= 12 288) always, and <= N / 2 (N >= 65536 here)
+    long long N1 = (N / 4) & ~31ll;
+    if (N1 < 4 * S2) N1 = 4 * S2;
+    int n = 0;
+    b[n++] = S2;
+    if (N1 + 65536 <= N) b[n++] = N1;
+    b[n++] = N;
+    (void)S1;
+    return n;
+}
+
+// ---- the coarse search: one set of stages, driven for 64-query and for wide passes ------------------------------------------
+// The copy a search scans. i8 = false: dbc is the bf16 copy (rmeta, amax unused); i8 = true: dbc is the int8 copy, rmeta its
+// per-row (scale, error norm) pairs padded to a multiple of 32 rows, amax >= every error norm
+struct CoarseCopy { const void* dbc; const float2* rmeta; bool i8; float rmax, amax; };
+
+// One chunk of a search (<= 64 or <= 1 024 queries): what every stage reads.
+struct Chunk {
+    int E, K, Q, qs;                 // Q: queries of this chunk; qs: the stride of qmeta and of the workspace's per-query arrays
+    bool i8, wide;                   // wide: launch_rescore's form
+    long long N, cap;                // cap: candidate slots per query
+    const float* db; const float* q; const unsigned* slot_rows;
+    Plan p; CoarseWs w;
+    long long id_base; float* out_s; long long* out_i;
+    hipStream_t st;
+};
+
+int coarse_check(const void* db, const CoarseCopy& cp, int64_t N, int E, const float* q, int Q, int K, const float* out_s,
+                 const int64_t* out_i, const void* ws, Plan& p) {
+    if (!db || !cp.dbc || !q || !out_s || !out_i || !ws || (cp.i8 && !cp.rmeta))
+        return set_err(CLIPMI_EINVAL, "topk_ip_coarse: NULL pointer");
+    if (cp.i8 && !(cp.amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", cp.amax);
+    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N)
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
+    if (!(cp.rmax > 0.f) || N >= (1ll << 32) - 1)
+        return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", cp.rmax, (long long)N);
+    if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
+    return 0;
+}
+
+// rows of the sample: it only has to thin the first segment's candidates (S2*K/S1 per query): 8 k rows are enough, and its
+// select then ranks 8 k entries per query instead of 32 k (12288 = what the select keeps in LDS; N >= 65536 here)
+inline long long sample_rows(const Plan& p) {
+    const long long S1 = p.stage < 4096 ? 4096 : (p.stage / 16) * 16;
+    return S1 > 12288 ? 12288 : S1;
+}
+
+// the sample (exact, unfiltered, every query of the chunk in one launch): scores of the first S1 rows -> K-th best per query
+// = the first segment's threshold
+int sample_threshold(const Chunk& c, long long S1, int QG, dim3 grid) {
+    if (int rc = launch_sample_scores(c.E, QG, grid, c.st, c.db, S1, c.q, c.Q, c.w.cand_c, c.cap, c.w.gcnt_c)) return rc;
+    CLIPMI_CHECK_LAUNCH("sample_scores_kernel");
+    // the sample's lists are dense (entry e IS row e): only the 4 score bytes are staged (48 KiB instead of 96 per block;
+    // round 5). S1 <= 12 288 rows always fit; LDS sized for them, not for the generic 8-byte stage
+    SelectArgs s;
+    s.cand = c.w.cand_c; s.gcnt = c.w.gcnt_c; s.cap = c.cap; s.K = c.K;
+    s.thr_out = c.w.thr0; s.qmeta = c.w.qmeta; s.qs = c.qs;
+    s.stage_cap = (int)S1; s.dense = 1; s.arm_fallback = c.w.flag;
+    hipLaunchKernelGGL(select_topk_kernel, dim3(c.Q), dim3(SEL_THREADS), SEL_FIXED + (size_t)c.K * 8 + (size_t)S1 * 4 + 16, c.st, s);
+    CLIPMI_CHECK_LAUNCH("select_topk_kernel(sample)");
+    return 0;
+}
+
+// segment `seg` of the copy behind its scan: exact re-scoring of the survivors -> select. Every segment but the last leaves
+// the exact K-th best of all rows seen so far as the next one's threshold; the last writes the result.
+int rescore_select(const Chunk& c, int seg, bool last) {
+    // ~1-3 k survivors per query = ~11 blocks of 256 pairs; a larger grid only queues idle blocks
+    launch_rescore(c.wide, dim3(12, c.Q), c.st, c.db, c.q, c.w.cand_c, c.w.gcnt_c, c.cap, c.slot_rows, c.E);
+    CLIPMI_CHECK_LAUNCH("rescore_pairs_kernel");
+    // 4096 staged entries (32 KiB of LDS) cover these lists; a select block then fits on a CU even beside the
+    // last segment's scan of ANOTHER batch in flight (104 KiB), which the 96-KiB staging of the sample select does not
+    const int scap = c.p.stage < 4096 ? c.p.stage : 4096;
+    SelectArgs s;
+    s.cand = c.w.cand_c; s.gcnt = c.w.gcnt_c; s.cap = c.cap; s.K = c.K;
+    if (last) { s.id_base = c.id_base; s.out_s = c.out_s; s.out_i = c.out_i; }
+    else { s.thr_out = c.w.thr0; s.qmeta = c.w.qmeta; s.qs = c.qs; }
+    // keep: bit 0 = the K best stay at the head of the list (gcnt = K) and the next segment appends behind them, so no row is
+    // scanned twice; bit 1 = add to the survivor count
+    s.m_out = c.w.last_m; s.keep = (last ? 0 : 1) | (seg > 0 ? 2 : 0); s.stage_cap = scap;
+    hipLaunchKernelGGL(select_topk_kernel, dim3(c.Q), dim3(SEL_THREADS), SEL_FIXED + (size_t)c.K * 8 + (size_t)scap * 8, c.st, s);
+    CLIPMI_CHECK_LAUNCH("select_topk_kernel(coarse)");
+    return 0;
+}
+
+// fallback: exact scan + select, exiting at once unless a coarse list overflowed
+// (two launches: the exact scan takes its groups of p.QA queries as blockIdx.y, each with its own lists)
+int exact_fallback(const Chunk& c) {
+    const Plan& p = c.p;
+    ScanArgs a;
+    a.db = c.db;
+    a.K = c.K; a.C = p.C; a.wave_bytes = p.wave_bytes;
+    a.cand = c.w.cand_e; a.gcnt = c.w.gcnt_e; a.cap = p.cap;
+    a.q = c.q; a.QA = c.Q < p.QA ? c.Q : p.QA; a.q_total = c.Q; a.nrows = c.N; a.thr_in = c.w.thr0; a.run_if = c.w.flag;
+    if (int rc = launch_scan<false>(c.E, p.QG, a, p.grid, p.waves, p.lds_scan, c.st, nullptr, (c.Q + p.QA - 1) / p.QA)) return rc;
+    SelectArgs s;
+    s.cand = c.w.cand_e; s.gcnt = c.w.gcnt_e; s.cap = p.cap; s.K = c.K;
+    s.id_base = c.id_base; s.out_s = c.out_s; s.out_i = c.out_i;
+    s.run_if = c.w.flag; s.stage_cap = p.stage;
+    hipLaunchKernelGGL(select_topk_kernel, dim3(c.Q), dim3(SEL_THREADS), p.lds_sel, c.st, s);
+    CLIPMI_CHECK_LAUNCH("select_topk_kernel(fallback)");
+    return 0;
+}
+
+struct SampleGeom { int QG; dim3 grid; };
+
+// The 64-query passes of the bf16 or the int8 copy: what they do their own way.
+struct Pass64 {
+    CoarseCopy copy;
+    static constexpr bool wide = false;
+    int chunk(int) const { return COARSE_Q; }
+    WsShape shape(int E, int) const { return pass64_shape(E); }
+    // per-query constants, the query image the scans copy, and the cleared counters + overflow flag (selects re-zero
+    // what they consume): one launch per 64-query group
+    unsigned prep_blocks(int Q) const { return (unsigned)((Q + 15) / 16 * 4); }
+    SampleGeom sample(int Q, long long S1) const {
+        long long gs = ((S1 + 15) / 16 + 3) / 4;
+        if (gs > NUM_CU) gs = NUM_CU;
+        return {1, dim3((unsigned)gs, (unsigned)((Q + 15) / 16))};
+    }
+    int segments(long long N, int K, long long S1, long long* b) const { return coarse_segments(N, K, S1, b); }
+    // `pre` (every segment but the last) only picks the kernel NAME profilers average under
+    int scan(const Chunk& c, long long r0, long long r1, bool last, hipEvent_t* ev) const {
+        CoarseArgs a;
+        a.dbc = copy.dbc; a.rmeta = copy.rmeta; a.qmeta = c.w.qmeta; a.qimage = c.w.qimage; a.q = c.q; a.QA = c.Q; a.tauc = c.w.tauc;
+        a.row0 = r0; a.nrows = r1 - r0;
+        a.cand = c.w.cand_c; a.gcnt = c.w.gcnt_c; a.cap = c.cap; a.overflow = c.w.flag;
+        a.abl = (int)dev_knob("CLIPMI_COARSE_ABL", 0);
+        return launch_coarse(c.E, c.Q <= 16 ? 1 : c.Q <= 32 ? 2 : 4, !last, copy.i8, a, (a.nrows + 31) / 32, c.st, ev);
+    }
+};
+
+// The wide passes of the int8 copy (64 < Q): chunks of <= WIDE_MAX_Q queries, each ONE pass of the copy in segments.
 // E = 768 (clipmi_topk_ip_wide_i8 only): the same sequence with the four-wave scan (tiles of 128 queries), the sample and the
 // 64-pair re-scoring at 768; chunks of WIDE768_MAX_Q.
-int topk_wide_impl(const void* db_dev, const void* db8_dev, const float2* rmeta, float amax, int64_t N, int E, float rmax,
-                   const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev, void* ws_dev,
-                   size_t ws_bytes, void* stream, hipEvent_t* scan_ev, int max_ev, int* n_ev) {
-    if (!db_dev || !db8_dev || !q_dev || !out_score_dev || !out_id_dev || !ws_dev || !rmeta)
-        return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: NULL pointer");
-    if (!(amax >= 0.f)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse_i8: amax=%g", amax);
-    // clipmi_topk_ip_coarse_i8 sends E = 768 through the 64-query passes; clipmi_topk_ip_wide_i8 here
-    if ((E != 512 && E != 768) || N < SAMPLE_MIN_N)
-        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse (wide pass): needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
-    if (!(rmax > 0.f) || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", rmax, (long long)N);
-    Plan p;
-    if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
-    const int chunk = wide_max_q(E), tile_sets = E == 768 ? WIDE768_TILE_SETS : WIDE_TILE_SETS;
-    const int qc_max = Q < chunk ? Q : chunk;
-    if (ws_bytes < carve_wide(p, qc_max, nullptr, ~(size_t)0, nullptr))
-        return set_err(CLIPMI_EWORKSPACE, "topk_ip_coarse_i8: workspace %zu too small", ws_bytes);
-    WideWs w;
-    carve_wide(p, qc_max, ws_dev, ws_bytes, &w);
-    const int qs = wide_qs(qc_max);
-    hipStream_t st = as_stream(stream);
-    const unsigned* slot_rows = i8_slot_rows(rmeta, N);
-    if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
-    if (int rc = opt_in_rescore(E)) return rc;
-    int ev_used = 0;
-
-    for (int q0 = 0; q0 < Q; q0 += chunk) {
-        const int qc = (Q - q0) < chunk ? (Q - q0) : chunk;
-        const float* qg = q_dev + (size_t)q0 * E;
-        const int nsets = (qc + 63) / 64;
-        launch_coarse_prep(E, true, (unsigned)(nsets * 16), st, qg, rmax, amax, qc, w.qmeta, w.qimage, w.gcnt_e, 2 * qs + 4, qs, 1);
-        CLIPMI_CHECK_LAUNCH("coarse_prep_kernel(wide)");
-        long long S1 = p.stage < 4096 ? 4096 : (p.stage / 16) * 16;
-        if (S1 > 12288) S1 = 12288;
-        {
-            // grid.y = 16-query groups (up to 64): blocks of the same x read the same rows, and every block first copies a
-            // 32-KiB query image - so few, fat blocks per group (each wave 4+ row tiles) once the groups alone fill the chip
-            long long gs = ((S1 + 15) / 16 + 3) / 4;
-            if (gs > NUM_CU) gs = NUM_CU;
-            static const int sdiv = [] { const int d = (int)dev_knob("CLIPMI_WIDE_SAMPLE_DIV", 8); return d > 0 ? d : 8; }();
-            static const int sqg = (int)dev_knob("CLIPMI_WIDE_SAMPLE_QG", 2);
-            const int ngroups = (qc + 16 * sqg - 1) / (16 * sqg);
-            if (ngroups >= 8 / sqg && gs > sdiv) gs = (gs + sdiv - 1) / sdiv;
-            // QG = 2 at 768 as well: 48 row registers more than at 512, inside the 512 of a 256-thread workgroup (resource table,
-            // no scratch)
-            if (int rc = launch_sample_scores(E, sqg == 2 ? 2 : 1, dim3((unsigned)gs, (unsigned)ngroups), st, static_cast<const float*>(db_dev), S1,
-                                              qg, qc, w.cand_c, (long long)WIDE_CAP, w.gcnt_c)) return rc;
-            CLIPMI_CHECK_LAUNCH("sample_scores_kernel(wide)");
-            // dense staging (4 bytes per row): S1 <= 12 288 rows always fit; LDS sized for them, not for the generic 8-byte stage
-            const size_t lds_dense = SEL_FIXED + (size_t)K * 8 + (size_t)S1 * 4 + 16;
-            SelectArgs s;
-            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = WIDE_CAP; s.K = K;
-            s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = qs;
-            s.stage_cap = (int)S1; s.dense = 1; s.arm_fallback = w.flag;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), lds_dense, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide sample)");
-        }
-        WideArgs c;
-        c.dbc = static_cast<const signed char*>(db8_dev); c.rmeta = rmeta; c.qmeta = w.qmeta; c.qimage = w.qimage;
-        c.bmeta = rmeta + i8_row_meta_entries(N);
-        c.Q = qc; c.qs = qs;
-        c.nqt = (nsets + tile_sets - 1) / tile_sets;
-        c.spt = (nsets + c.nqt - 1) / c.nqt;
-        c.cand = w.cand_c; c.gcnt = w.gcnt_c; c.cap = WIDE_CAP; c.overflow = w.flag;
+struct WidePass {
+    CoarseCopy copy;
+    static constexpr bool wide = true;
+    int chunk(int E) const { return wide_max_q(E); }
+    WsShape shape(int E, int Qc) const { return wide_shape(E, Qc); }
+    unsigned prep_blocks(int Q) const { return (unsigned)((Q + 63) / 64 * 16); }
+    SampleGeom sample(int Q, long long S1) const {
+        // grid.y = 16-query groups (up to 64): blocks of the same x read the same rows, and every block first copies a
+        // 32-KiB query image - so few, fat blocks per group (each wave 4+ row tiles) once the groups alone fill the chip
+        long long gs = ((S1 + 15) / 16 + 3) / 4;
+        if (gs > NUM_CU) gs = NUM_CU;
+        static const int sdiv = [] { const int d = (int)dev_knob("CLIPMI_WIDE_SAMPLE_DIV", 8); return d > 0 ? d : 8; }();
+        static const int sqg = (int)dev_knob("CLIPMI_WIDE_SAMPLE_QG", 2);
+        const int ngroups = (Q + 16 * sqg - 1) / (16 * sqg);
+        if (ngroups >= 8 / sqg && gs > sdiv) gs = (gs + sdiv - 1) / sdiv;
+        // QG = 2 at 768 as well: 48 row registers more than at 512, inside the 512 of a 256-thread workgroup (resource table,
+        // no scratch)
+        return {sqg == 2 ? 2 : 1, dim3((unsigned)gs, (unsigned)ngroups)};
+    }
+    int segments(long long N, int K, long long S1, long long* b) const { return wide_segments(N, K, S1, b); }
+    int scan(const Chunk& c, long long r0, long long r1, bool, hipEvent_t* ev) const {
+        const int qc = c.Q, nsets = (qc + 63) / 64, tile_sets = c.E == 768 ? WIDE768_TILE_SETS : WIDE_TILE_SETS;
+        WideArgs a;
+        a.dbc = static_cast<const signed char*>(copy.dbc); a.rmeta = copy.rmeta; a.qmeta = c.w.qmeta; a.qimage = c.w.qimage;
+        a.bmeta = copy.rmeta + i8_row_meta_entries(c.N);
+        a.row0 = r0; a.nrows = r1 - r0;
+        a.Q = qc; a.qs = c.qs;
+        a.nqt = (nsets + tile_sets - 1) / tile_sets;
+        a.spt = (nsets + a.nqt - 1) / a.nqt;
+        a.cand = c.w.cand_c; a.gcnt = c.w.gcnt_c; a.cap = c.cap; a.overflow = c.w.flag;
         {
             static const int map_env = (int)dev_knob("CLIPMI_WIDE_MAP", 0), pf_env = (int)dev_knob("CLIPMI_WIDE_PF", 0);
-            c.map_mode = map_env; c.pf_mode = pf_env;
+            a.map_mode = map_env; a.pf_mode = pf_env;
         }
-        long long bnd[WIDE_MAX_SEGS];
-        const int nseg = wide_segments(N, K, S1, bnd);
-        float* os_final = out_score_dev + (size_t)q0 * K;
-        long long* oi_final = (long long*)out_id_dev + (size_t)q0 * K;
-        const int scap = p.stage < 4096 ? p.stage : 4096;
-        long long r0 = 0;
-        for (int sgi = 0; sgi < nseg; ++sgi) {
-            const bool last = sgi + 1 == nseg;
-            c.row0 = r0;
-            c.nrows = bnd[sgi] - r0;
-            hipEvent_t* ev = (scan_ev && ev_used + 2 <= max_ev) ? scan_ev + ev_used : nullptr;
-            if (E == 768) {
-                if (int rc = (launch_wide_t<4, 0, 24>(c, st, ev))) return rc;
-            } else {
+        if (c.E == 768) return launch_wide<4, 0, 24>(a, c.st, ev);
 #ifdef CLIPMI_DEV
-            static const int abl = (int)dev_knob("CLIPMI_WIDE_ABL", 0);        // ablations + the 4-wave form: development build only
-            // CLIPMI_WIDE2=0: never the second form (A/B); CLIPMI_WIDE2_MINQ: smallest query count that takes it
-            static const int w2 = (int)dev_knob("CLIPMI_WIDE2", 1);
-            static const int w2_minq = (int)dev_knob("CLIPMI_WIDE2_MINQ", W2_MIN_Q);
-            static const int w2_ng = (int)dev_knob("CLIPMI_WIDE2_NG", 0);              // 1 / 2: force the groups per wave (A/B)
-            if (w2 && qc >= w2_minq) {
-                if (int rc = launch_wide2<4>(c, st, ev, w2_ng == 1 || w2_ng == 2 ? w2_ng : wide2_groups(qc))) return rc;
-            } else
-            if (int rc = abl == 1 ? launch_wide_t<8, 1>(c, st, ev) : abl == 2 ? launch_wide_t<8, 2>(c, st, ev)
-                       : abl == 3 ? launch_wide_t<8, 3>(c, st, ev)
-                       : wide_waves() == 4 ? launch_wide_t<4>(c, st, ev) : launch_wide_t<8>(c, st, ev)) return rc;
+        static const int abl = (int)dev_knob("CLIPMI_WIDE_ABL", 0);        // ablations + the 4-wave form: development build only
+        // CLIPMI_WIDE2=0: never the second form (A/B); CLIPMI_WIDE2_MINQ: smallest query count that takes it
+        static const int w2 = (int)dev_knob("CLIPMI_WIDE2", 1);
+        static const int w2_minq = (int)dev_knob("CLIPMI_WIDE2_MINQ", W2_MIN_Q);
+        static const int w2_ng = (int)dev_knob("CLIPMI_WIDE2_NG", 0);              // 1 / 2: force the groups per wave (A/B)
+        if (w2 && qc >= w2_minq) return launch_wide2<4>(a, c.st, ev, w2_ng == 1 || w2_ng == 2 ? w2_ng : wide2_groups(qc));
+        return abl == 1 ? launch_wide<8, 1>(a, c.st, ev) : abl == 2 ? launch_wide<8, 2>(a, c.st, ev)
+             : abl == 3 ? launch_wide<8, 3>(a, c.st, ev)
+             : wide_waves() == 4 ? launch_wide<4>(a, c.st, ev) : launch_wide<8>(a, c.st, ev);
 #else
-            if (int rc = qc >= W2_MIN_Q ? launch_wide2<4>(c, st, ev, wide2_groups(qc)) : launch_wide_t<8>(c, st, ev)) return rc;
+        return qc >= W2_MIN_Q ? launch_wide2<4>(a, c.st, ev, wide2_groups(qc)) : launch_wide<8>(a, c.st, ev);
 #endif
-            }
-            if (ev) ev_used += 2;
-            launch_rescore(true, dim3(12, qc), st, static_cast<const float*>(db_dev), qg, w.cand_c, w.gcnt_c, WIDE_CAP, slot_rows, E);
-            CLIPMI_CHECK_LAUNCH("rescore_pairs16_kernel(wide)");
-            // keep: bit 0 = the K best stay at the head of the list for the next segment; bit 1 = add to the survivor count
-            const int keep = (last ? 0 : 1) | (sgi > 0 ? 2 : 0);
-            SelectArgs s;
-            s.cand = w.cand_c; s.gcnt = w.gcnt_c; s.cap = WIDE_CAP; s.K = K;
-            if (last) { s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final; }
-            else { s.thr_out = w.thr0; s.qmeta = w.qmeta; s.qs = qs; }
-            s.m_out = w.last_m; s.keep = keep; s.stage_cap = scap;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), SEL_FIXED + (size_t)K * 8 + (size_t)scap * 8, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide)");
-            r0 = bnd[sgi];
-        }
-        // fallback: exact scan + select, exiting at once unless a list overflowed
-        {
-            ScanArgs a;
-            a.db = static_cast<const float*>(db_dev);
-            a.K = K; a.C = p.C; a.wave_bytes = p.wave_bytes;
-            a.cand = w.cand_e; a.gcnt = w.gcnt_e; a.cap = p.cap;
-            const int ny = (qc + p.QA - 1) / p.QA;
-            a.q = qg; a.QA = qc < p.QA ? qc : p.QA; a.q_total = qc; a.nrows = N; a.thr_in = w.thr0; a.run_if = w.flag;
-            if (int rc2 = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, nullptr, ny)) return rc2;
-            SelectArgs s;
-            s.cand = w.cand_e; s.gcnt = w.gcnt_e; s.cap = p.cap; s.K = K;
-            s.id_base = id_base; s.out_s = os_final; s.out_i = oi_final;
-            s.run_if = w.flag; s.stage_cap = p.stage;
-            hipLaunchKernelGGL(select_topk_kernel, dim3(qc), dim3(SEL_THREADS), p.lds_sel, st, s);
-            CLIPMI_CHECK_LAUNCH("select_topk_kernel(wide fallback)");
-        }
     }
-    if (n_ev) *n_ev = ev_used;
+};
+
+// The coarse-then-exact search, chunk by chunk: prep -> sample threshold -> per segment of the copy (scan -> exact re-scoring
+// -> select) -> exact fallback. `events` (measurement hooks): pairs handed out in order to the launches that stream the copy,
+// as far as max_events reaches; *used = how many were recorded.
+template <class Driver>
+int coarse_search(const Driver& d, const void* db_dev, int64_t N, int E, const float* q_dev, int Q, int K, int64_t id_base,
+                  float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream,
+                  hipEvent_t* events = nullptr, int max_events = 0, int* used = nullptr) {
+    Chunk c;
+    if (int rc = coarse_check(db_dev, d.copy, N, E, q_dev, Q, K, out_score_dev, out_id_dev, ws_dev, c.p)) return rc;
+    const int chunk = d.chunk(E);
+    const WsShape shape = d.shape(E, Q < chunk ? Q : chunk);
+    if (ws_bytes < carve(c.p, shape, nullptr, ~(size_t)0, nullptr))
+        return set_err(CLIPMI_EWORKSPACE, "topk_ip_coarse: workspace %zu too small", ws_bytes);
+    carve(c.p, shape, ws_dev, ws_bytes, &c.w);
+    c.E = E; c.K = K; c.qs = shape.qs; c.i8 = d.copy.i8; c.wide = Driver::wide; c.N = N; c.cap = shape.cap;
+    c.db = static_cast<const float*>(db_dev);
+    // int8: the rows the copy's slots hold, behind the block meta (quantize_rows_i8_kernel); bf16 copy: rows in order
+    c.slot_rows = c.i8 ? i8_slot_rows(d.copy.rmeta, N) : nullptr;
+    c.id_base = id_base; c.st = as_stream(stream);
+    if (int rc = opt_in_lds((const void*)select_topk_kernel, c.p.lds_sel)) return rc;
+    if (int rc = opt_in_rescore(E)) return rc;
+    const long long S1 = sample_rows(c.p);
+    long long bnd[WIDE_MAX_SEGS];
+    const int nseg = d.segments(N, K, S1, bnd);
+    int ev_used = 0;
+    for (int q0 = 0; q0 < Q; q0 += chunk) {
+        c.Q = (Q - q0) < chunk ? (Q - q0) : chunk;
+        c.q = q_dev + (size_t)q0 * E;
+        c.out_s = out_score_dev + (size_t)q0 * K;
+        c.out_i = (long long*)out_id_dev + (size_t)q0 * K;
+        launch_coarse_prep(E, c.i8, d.prep_blocks(c.Q), c.st, c.q, d.copy.rmax, d.copy.amax, c.Q, c.w.qmeta, c.w.qimage, c.w.gcnt_e,
+                           shape.nctl, c.qs, Driver::wide);
+        CLIPMI_CHECK_LAUNCH("coarse_prep_kernel");
+        const SampleGeom sg = d.sample(c.Q, S1);
+        if (int rc = sample_threshold(c, S1, sg.QG, sg.grid)) return rc;
+        long long r0 = 0;
+        for (int seg = 0; seg < nseg; r0 = bnd[seg++]) {
+            const bool last = seg + 1 == nseg;
+            hipEvent_t* ev = (events && ev_used + 2 <= max_events) ? events + ev_used : nullptr;
+            if (int rc = d.scan(c, r0, bnd[seg], last, ev)) return rc;
+            if (ev) ev_used += 2;
+            if (int rc = rescore_select(c, seg, last)) return rc;
+        }
+        if (int rc = exact_fallback(c)) return rc;
+    }
+    if (used) *used = ev_used;
     return 0;
+}
+
+inline CoarseCopy i8_copy(const void* db_i8_dev, const float* meta_dev, float rmax, float amax) {
+    return {db_i8_dev, reinterpret_cast<const float2*>(meta_dev), true, rmax, amax};
 }
 }  // namespace
 }  // namespace clipmi
@@ -2554,10 +2497,10 @@ extern "C" size_t clipmi_topk_ip_coarse_workspace_bytes(int64_t N, int E, int Q,
         set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: unsupported: needs E = 512 or 768, N >= %d and a supported K", SAMPLE_MIN_N);
         return 0;
     }
-    size_t need = carve_coarse(p, nullptr, ~(size_t)0, nullptr);
+    size_t need = carve(p, pass64_shape(E), nullptr, ~(size_t)0, nullptr);
     // E = 768 has no wide pass: more than 64 queries run as 64-query passes inside the call, on the one 64-query workspace
     if (Q > COARSE_Q && E == 512) {           // the int8 path takes a search of more than 64 queries as wide passes
-        const size_t wide = carve_wide(p, Q < WIDE_MAX_Q ? Q : WIDE_MAX_Q, nullptr, ~(size_t)0, nullptr);
+        const size_t wide = carve(p, wide_shape(E, Q < WIDE_MAX_Q ? Q : WIDE_MAX_Q), nullptr, ~(size_t)0, nullptr);
         need = wide > need ? wide : need;
     }
     return need;
@@ -2566,8 +2509,8 @@ extern "C" size_t clipmi_topk_ip_coarse_workspace_bytes(int64_t N, int E, int Q,
 extern "C" int clipmi_topk_ip_coarse(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
                                      const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev,
                                      int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream) {
-    return topk_ip_coarse_impl(db_dev, db_bf16_dev, false, nullptr, 0.f, N, E, rmax, q_dev, Q, K, id_base, out_score_dev,
-                               out_id_dev, ws_dev, ws_bytes, stream, nullptr);
+    return coarse_search(Pass64{{db_bf16_dev, nullptr, false, rmax, 0.f}}, db_dev, N, E, q_dev, Q, K, id_base, out_score_dev,
+                         out_id_dev, ws_dev, ws_bytes, stream);
 }
 
 extern "C" size_t clipmi_i8_copy_bytes(int64_t N, int E) {
@@ -2823,11 +2766,10 @@ extern "C" int clipmi_rows_to_bf16(const float* db_dev, int64_t N, int E, void* 
 extern "C" int clipmi_topk_ip_coarse_i8(const void* db_dev, const void* db_i8_dev, const float* meta_dev, float amax, int64_t N,
                                         int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
                                         float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream) {
+    const CoarseCopy copy = i8_copy(db_i8_dev, meta_dev, rmax, amax);
     if (Q > COARSE_Q && E == 512 && !wide_disabled())
-        return topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K, id_base,
-                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr, 0, nullptr);
-    return topk_ip_coarse_impl(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q,
-                               K, id_base, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr);
+        return coarse_search(WidePass{copy}, db_dev, N, E, q_dev, Q, K, id_base, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream);
+    return coarse_search(Pass64{copy}, db_dev, N, E, q_dev, Q, K, id_base, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream);
 }
 
 // The opt-in pair (ABI 8): clipmi_topk_ip_coarse_i8 with a wide pass at E = 768 as well. E = 512 and Q <= 64 ARE that function
@@ -2837,7 +2779,7 @@ extern "C" size_t clipmi_topk_ip_wide_workspace_bytes(int64_t N, int E, int Q, i
     if (need == 0 || E != 768 || Q <= COARSE_Q) return need;
     Plan p;
     if (!coarse_plan(N, E, Q, K, p)) return need;
-    const size_t wide = carve_wide(p, Q < WIDE768_MAX_Q ? Q : WIDE768_MAX_Q, nullptr, ~(size_t)0, nullptr);
+    const size_t wide = carve(p, wide_shape(E, Q < WIDE768_MAX_Q ? Q : WIDE768_MAX_Q), nullptr, ~(size_t)0, nullptr);
     return wide > need ? wide : need;
 }
 
@@ -2845,11 +2787,34 @@ extern "C" int clipmi_topk_ip_wide_i8(const void* db_dev, const void* db_i8_dev,
                                       int E, float rmax, const float* q_dev, int Q, int K, int64_t id_base,
                                       float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream) {
     if (Q > COARSE_Q && E == 768)
-        return topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K, id_base,
-                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, nullptr, 0, nullptr);
+        return coarse_search(WidePass{i8_copy(db_i8_dev, meta_dev, rmax, amax)}, db_dev, N, E, q_dev, Q, K, id_base, out_score_dev,
+                             out_id_dev, ws_dev, ws_bytes, stream);
     return clipmi_topk_ip_coarse_i8(db_dev, db_i8_dev, meta_dev, amax, N, E, rmax, q_dev, Q, K, id_base, out_score_dev, out_id_dev,
                                     ws_dev, ws_bytes, stream);
 }
+
+// The event pairs of a measurement hook: created together, destroyed together (also when creation fails part-way).
+namespace {
+struct ScanEvents {
+    static constexpr int MAX = 2 * WIDE_MAX_SEGS;
+    hipEvent_t ev[MAX];
+    int n = 0;
+    bool create() {
+        while (n < MAX && hipEventCreate(&ev[n]) == hipSuccess) ++n;
+        return n == MAX;
+    }
+    ~ScanEvents() { for (int i = 0; i < n; ++i) (void)hipEventDestroy(ev[i]); }
+    double sum_ms(int used) const {          // the summed duration of the first `used` / 2 pairs
+        double total = 0.0;
+        for (int j = 0; j + 1 < used; j += 2) {
+            float ms = 0.f;
+            (void)hipEventElapsedTime(&ms, ev[j], ev[j + 1]);
+            total += ms;
+        }
+        return total;
+    }
+};
+}  // namespace
 
 // Measurement hook of the wide passes (64 < Q, E = 512 or 768): the call `reps` times, chunk by chunk, with events around every
 // wide scan launch; synchronises after each chunk to read its survivor counts and overflow flag (both are per-chunk state of the
@@ -2864,46 +2829,36 @@ extern "C" int clipmi_dbg_topk_wide_i8_scan_ms(const void* db_dev, const void* d
     Plan p;
     if (N < SAMPLE_MIN_N || !coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EUNSUPPORTED, "dbg_topk_wide_i8_scan_ms: unsupported N=%lld K=%d", (long long)N, K);
     const int chunk = wide_max_q(E);
-    constexpr int NEV = 2 * WIDE_MAX_SEGS;
-    hipEvent_t ev[NEV];
-    for (int i = 0; i < NEV; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) return set_err(CLIPMI_EHIP, "hipEventCreate");
+    ScanEvents ev;
+    if (!ev.create()) return set_err(CLIPMI_EHIP, "hipEventCreate");
     unsigned host[WIDE_MAX_Q > WIDE768_MAX_Q ? WIDE_MAX_Q : WIDE768_MAX_Q];
     hipStream_t st = as_stream(stream);
-    int rc = 0, launches = 0, armed = 0;
+    const WidePass wide{i8_copy(db_i8_dev, meta_dev, rmax, amax)};
+    int launches = 0, armed = 0;
     long long tot = 0;
     double total = 0.0;
-    for (int r = 0; r < reps && rc == 0; ++r) {
+    for (int r = 0; r < reps; ++r) {
         launches = 0; armed = 0; tot = 0; total = 0.0;
-        for (int q0 = 0; q0 < Q && rc == 0; q0 += chunk) {
+        for (int q0 = 0; q0 < Q; q0 += chunk) {
             const int qc = (Q - q0) < chunk ? (Q - q0) : chunk;
             int n_ev = 0;
             // a chunk of <= 64 queries (the tail of Q = k chunk + 1 ...) is still a wide pass inside a whole call: keep it one here
-            rc = topk_wide_impl(db_dev, db_i8_dev, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev + (size_t)q0 * E,
-                                qc, K, 0, out_score_dev + (size_t)q0 * K, out_id_dev + (size_t)q0 * K, ws_dev, ws_bytes, stream, ev,
-                                NEV, &n_ev);
-            if (rc) break;
-            if (hipStreamSynchronize(st) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipStreamSynchronize"); break; }
-            for (int j = 0; j + 1 < n_ev; j += 2) {
-                float ms = 0.f;
-                (void)hipEventElapsedTime(&ms, ev[j], ev[j + 1]);
-                total += ms;
-            }
+            if (int rc = coarse_search(wide, db_dev, N, E, q_dev + (size_t)q0 * E, qc, K, 0, out_score_dev + (size_t)q0 * K,
+                                       out_id_dev + (size_t)q0 * K, ws_dev, ws_bytes, stream, ev.ev, ScanEvents::MAX, &n_ev))
+                return rc;
+            if (hipStreamSynchronize(st) != hipSuccess) return set_err(CLIPMI_EHIP, "hipStreamSynchronize");
+            total += ev.sum_ms(n_ev);
             launches += n_ev / 2;
-            WideWs w;
-            carve_wide(p, qc, ws_dev, ws_bytes, &w);
+            CoarseWs w;
+            carve(p, wide_shape(E, qc), ws_dev, ws_bytes, &w);
             unsigned flag = 0;
             if (hipMemcpy(host, w.last_m, sizeof(unsigned) * qc, hipMemcpyDeviceToHost) != hipSuccess ||
-                hipMemcpy(&flag, w.flag, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess) {
-                rc = set_err(CLIPMI_EHIP, "hipMemcpy(wide counters)");
-                break;
-            }
+                hipMemcpy(&flag, w.flag, sizeof(unsigned), hipMemcpyDeviceToHost) != hipSuccess)
+                return set_err(CLIPMI_EHIP, "hipMemcpy(wide counters)");
             for (int i = 0; i < qc; ++i) tot += host[i] < WIDE_CAP ? host[i] : WIDE_CAP;
             armed |= flag != 0;
         }
     }
-    for (int i = 0; i < NEV; ++i) (void)hipEventDestroy(ev[i]);
-    if (rc) return rc;
     *scan_ms = (float)total;
     if (survivors) *survivors = tot;
     if (scan_launches) *scan_launches = launches;
@@ -2911,54 +2866,44 @@ extern "C" int clipmi_dbg_topk_wide_i8_scan_ms(const void* db_dev, const void* d
     return 0;
 }
 
-// Measurement hook: clipmi_topk_ip_coarse `reps` times with events around the bf16 scan kernel (Q <= 64).
-static int dbg_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, bool i8, const float2* rmeta, float amax, int64_t N,
-                              int E, float rmax, const float* q_dev, int Q, int K, float* out_score_dev,
-                              int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
-                              long long* survivors) {
+// Measurement hook: a 64-query search (Q <= 64) `reps` times with events around the launches that stream the coarse copy ONCE -
+// one scan per segment; *scan_ms = their summed duration, averaged over the repetitions
+static int dbg_coarse_scan_ms(const void* db_dev, const CoarseCopy& copy, int64_t N, int E, const float* q_dev, int Q, int K,
+                              float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes, void* stream, int reps,
+                              float* scan_ms, long long* survivors) {
     if (!scan_ms || reps < 1 || Q > COARSE_Q) return set_err(CLIPMI_EINVAL, "dbg_topk_coarse_scan_ms: bad arguments");
-    // three event pairs: [0,1] the last segment, [2,3] rows [0, S2), [4,5] rows [S2, N1) of the coarse copy (see
-    // topk_ip_coarse_impl): together the launches that stream the copy ONCE; *scan_ms = their summed duration
-    hipEvent_t ev[6];
-    for (int i = 0; i < 6; ++i)
-        if (hipEventCreate(&ev[i]) != hipSuccess) return set_err(CLIPMI_EHIP, "hipEventCreate");
+    ScanEvents ev;
+    if (!ev.create()) return set_err(CLIPMI_EHIP, "hipEventCreate");
     double total = 0.0;
-    int rc = 0;
-    for (int i = 0; i < reps && rc == 0; ++i) {
-        for (int j = 0; j < 6; ++j) (void)hipEventRecord(ev[j], as_stream(stream));     // a skipped segment reads ~0
-        rc = topk_ip_coarse_impl(db_dev, db_bf16_dev, i8, rmeta, amax, N, E, rmax, q_dev, Q, K, 0, out_score_dev, out_id_dev,
-                                 ws_dev, ws_bytes, stream, ev);
-        if (rc) break;
-        if (hipStreamSynchronize(as_stream(stream)) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipStreamSynchronize"); break; }
-        for (int j = 0; j < 3; ++j) {
-            float ms = 0.f;
-            (void)hipEventElapsedTime(&ms, ev[2 * j], ev[2 * j + 1]);
-            total += ms;
-        }
+    for (int i = 0; i < reps; ++i) {
+        int n_ev = 0;
+        if (int rc = coarse_search(Pass64{copy}, db_dev, N, E, q_dev, Q, K, 0, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream,
+                                   ev.ev, ScanEvents::MAX, &n_ev))
+            return rc;
+        if (hipStreamSynchronize(as_stream(stream)) != hipSuccess) return set_err(CLIPMI_EHIP, "hipStreamSynchronize");
+        total += ev.sum_ms(n_ev);
     }
-    for (int i = 0; i < 6; ++i) (void)hipEventDestroy(ev[i]);
-    if (rc == 0) *scan_ms = (float)(total / reps);
-    if (rc == 0 && survivors) {       // rows that survived the coarse pass, summed over the Q queries of the last call
+    *scan_ms = (float)(total / reps);
+    if (survivors) {       // rows that survived the coarse pass, summed over the Q queries of the last call
         Plan p;
         CoarseWs w;
         coarse_plan(N, E, Q, K, p);
-        carve_coarse(p, ws_dev, ws_bytes, &w);
+        carve(p, pass64_shape(E), ws_dev, ws_bytes, &w);
         unsigned host[COARSE_Q];
-        if (hipStreamSynchronize(as_stream(stream)) != hipSuccess ||
-            hipMemcpy(host, w.last_m, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
+        if (hipMemcpy(host, w.last_m, sizeof(host), hipMemcpyDeviceToHost) != hipSuccess)
             return set_err(CLIPMI_EHIP, "hipMemcpy(gcnt)");
         long long tot = 0;
         for (int i = 0; i < Q; ++i) tot += host[i] < COARSE_CAP ? host[i] : COARSE_CAP;
         *survivors = tot;
     }
-    return rc;
+    return 0;
 }
 
 extern "C" int clipmi_dbg_topk_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
                                               const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
                                               void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms,
                                               long long* survivors) {
-    return dbg_coarse_scan_ms(db_dev, db_bf16_dev, false, nullptr, 0.f, N, E, rmax, q_dev, Q, K, out_score_dev, out_id_dev,
+    return dbg_coarse_scan_ms(db_dev, {db_bf16_dev, nullptr, false, rmax, 0.f}, N, E, q_dev, Q, K, out_score_dev, out_id_dev,
                               ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
 }
 
@@ -2966,8 +2911,8 @@ extern "C" int clipmi_dbg_topk_coarse_i8_scan_ms(const void* db_dev, const void*
                                                  int64_t N, int E, float rmax, const float* q_dev, int Q, int K,
                                                  float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
                                                  void* stream, int reps, float* scan_ms, long long* survivors) {
-    return dbg_coarse_scan_ms(db_dev, db_i8_dev, true, reinterpret_cast<const float2*>(meta_dev), amax, N, E, rmax, q_dev, Q, K,
-                              out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
+    return dbg_coarse_scan_ms(db_dev, i8_copy(db_i8_dev, meta_dev, rmax, amax), N, E, q_dev, Q, K, out_score_dev, out_id_dev,
+                              ws_dev, ws_bytes, stream, reps, scan_ms, survivors);
 }
 
 // Measurement hook (bench.py roofline): the same call sequence as clipmi_topk_ip, `reps` times,

@@ -13,9 +13,9 @@ calls clipmi_topk_ip through the C ABI. Multi-GPU: one process per GPU, rows spl
 by rank, per-rank top-K, ONE all-gather (RCCL when the tensors are on the GPU), then the same
 K-way merge on every rank (clipmi_merge_topk) — SURVEY.md §8e.
 """
-import struct
-
+import collections
 import os
+import struct
 
 import numpy as np
 import torch
@@ -59,6 +59,40 @@ def coarse_eligible(coarse, d, ntotal):
     """THE predicate of the coarse path: a coarse copy was asked for, the width has coarse kernels, the shard is large enough.
     IndexFlatIP.uses_coarse(), repl.open_sharded and repl.main all decide with it."""
     return coarse in ("bf16", "int8") and d in COARSE_DIMS and ntotal >= COARSE_MIN_ROWS
+
+
+Route = collections.namedtuple("Route", "entry workspace chunk")
+
+
+def search_route(coarse, d, wide_768, Q):
+    """(library entry, its workspace function, queries per call of a pipelined search) for one search of Q queries.
+    coarse: "bf16", "int8", or None when the coarse path is not usable (not eligible, or a non-finite or zero rmax / amax);
+    wide_768: IndexFlatIP._wide_768_on(). Pure: touches no device and no library. A search of more than `chunk` queries
+    alternates chunk-sized calls between two streams (IndexFlatIP._search_pipelined); chunk None: one call, whatever Q."""
+    if coarse is None:
+        return Route("clipmi_topk_ip", "clipmi_topk_ip_workspace_bytes", None)
+    if coarse == "bf16":
+        return Route("clipmi_topk_ip_coarse", "clipmi_topk_ip_coarse_workspace_bytes", IndexFlatIP.PASS_Q)
+    # more than 64 queries: the int8 path takes the whole search as wide passes inside the library (one stream of the
+    # copy per <= 1024 queries, csrc/topk.hip "Wide coarse pass"); the bf16 path pipelines its 64-query passes here, and so
+    # does the int8 path at d = 768 by default: clipmi_topk_ip_coarse_i8 has no wide pass there (a 256-query tile of 768
+    # bytes does not fit in LDS) and would run the 64-query passes one after the other on one stream
+    if d == 512:
+        # int8, more than one wide chunk (1024 queries): the chunks alternate between two streams the same way - one chunk's
+        # re-scoring and selects run beside the other's matrix-bound scan (10 M rows, 2 x 1024 queries: 6.37 -> 6.07 ms per
+        # chunk, 160.9 -> 168.8 k q/s; a single chunk cut in two halves gains nothing: 162.4 k)
+        return Route("clipmi_topk_ip_coarse_i8", "clipmi_topk_ip_coarse_workspace_bytes", IndexFlatIP.WIDE_Q)
+    # (opt-in at d = 768, `wide_768`: the library's wide pass there - clipmi_topk_ip_wide_i8 -, chunks of WIDE_Q_768 queries)
+    if wide_768 and Q > IndexFlatIP.PASS_Q:
+        return Route("clipmi_topk_ip_wide_i8", "clipmi_topk_ip_wide_workspace_bytes", IndexFlatIP.WIDE_Q_768)
+    return Route("clipmi_topk_ip_coarse_i8", "clipmi_topk_ip_coarse_workspace_bytes", IndexFlatIP.PASS_Q)
+
+
+def _alloc_out(out, Q, K, device):
+    """The caller's (scores, ids) views, or fresh f32 / i64 [Q,K] tensors."""
+    if out is not None:
+        return out
+    return (torch.empty((Q, K), dtype=torch.float32, device=device), torch.empty((Q, K), dtype=torch.int64, device=device))
 
 
 class IndexFlatIP:
@@ -209,31 +243,20 @@ class IndexFlatIP:
         q = q.to(device=self.device, dtype=torch.float32).contiguous()
         Q = q.shape[0]
         N = db.shape[0]
-        coarse = self.uses_coarse()
-        if coarse and self.coarse == "int8":
+        # build the copy; a non-finite or zero bound leaves the search on the exact path
+        coarse = self.coarse if self.uses_coarse() else None
+        if coarse == "int8":
             db8, meta, amax, rmax = self.matrix_i8()
-            coarse = rmax > 0.0 and np.isfinite(rmax) and np.isfinite(amax)
+            if not (rmax > 0.0 and np.isfinite(rmax) and np.isfinite(amax)):
+                coarse = None
         elif coarse:
             dbh, rmax = self.matrix_bf16()
-            coarse = rmax > 0.0 and np.isfinite(rmax)
-        # more than 64 queries: the int8 path takes the whole search as wide passes inside the library (one stream of the
-        # copy per <= 1024 queries, csrc/topk.hip "Wide coarse pass"); the bf16 path pipelines its 64-query passes here, and so
-        # does the int8 path at d = 768 by default: clipmi_topk_ip_coarse_i8 has no wide pass there (a 256-query tile of 768
-        # bytes does not fit in LDS) and would run the 64-query passes one after the other on one stream
-        # (opt-in at d = 768, `wide_768`: the library's wide pass there - clipmi_topk_ip_wide_i8 -, chunks of WIDE_Q_768 queries)
-        wide768 = bool(coarse) and self._wide_768_on() and Q > self.PASS_Q
-        if coarse and (self.coarse != "int8" or self.d != 512) and not wide768 and Q > self.PASS_Q and self.batches_in_flight > 1 \
-                and not _one_pass:
-            return self._search_pipelined(q, K, out, self.PASS_Q)
-        # int8, more than one wide chunk (1024 queries): the chunks alternate between two streams the same way - one chunk's
-        # re-scoring and selects run beside the other's matrix-bound scan (10 M rows, 2 x 1024 queries: 6.37 -> 6.07 ms per chunk,
-        # 160.9 -> 168.8 k q/s; a single chunk cut in two halves gains nothing: 162.4 k)
-        if coarse and self.coarse == "int8" and self.d == 512 and Q > self.WIDE_Q and self.batches_in_flight > 1 and not _one_pass:
-            return self._search_pipelined(q, K, out, self.WIDE_Q)
-        if wide768 and Q > self.WIDE_Q_768 and self.batches_in_flight > 1 and not _one_pass:
-            return self._search_pipelined(q, K, out, self.WIDE_Q_768)
-        need = (L.clipmi_topk_ip_wide_workspace_bytes if wide768 else L.clipmi_topk_ip_coarse_workspace_bytes if coarse
-                else L.clipmi_topk_ip_workspace_bytes)(N, self.d, Q, K)
+            if not (rmax > 0.0 and np.isfinite(rmax)):
+                coarse = None
+        route = search_route(coarse, self.d, self._wide_768_on(), Q)
+        if route.chunk and Q > route.chunk and self.batches_in_flight > 1 and not _one_pass:
+            return self._search_pipelined(q, K, out, route.chunk)
+        need = getattr(L, route.workspace)(N, self.d, Q, K)
         if need == 0:
             raise _lib.ClipmiError("topk_ip: " + _lib.last_error())
         # the workspace belongs to the stream the call is enqueued on (torch's current stream): two batches in flight on
@@ -242,33 +265,17 @@ class IndexFlatIP:
         ws = self._ws.get(skey)
         if ws is None or ws.numel() < need:
             ws = self._ws[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
-        if out is None:
-            out_s = torch.empty((Q, K), dtype=torch.float32, device=self.device)
-            out_i = torch.empty((Q, K), dtype=torch.int64, device=self.device)
+        out_s, out_i = _alloc_out(out, Q, K, self.device)
+        # one library call; only its leading arguments depend on the copy
+        if coarse == "int8":
+            lead = (db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, self.d, rmax)
+        elif coarse:
+            lead = (db.data_ptr(), dbh.data_ptr(), N, self.d, rmax)
         else:
-            out_s, out_i = out
-        if wide768:
-            rc = L.clipmi_topk_ip_wide_i8(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, self.d, rmax, q.data_ptr(),
-                                          Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
-                                          ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "clipmi_topk_ip_wide_i8")
-            return out_s, out_i
-        if coarse and self.coarse == "int8":
-            rc = L.clipmi_topk_ip_coarse_i8(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, self.d, rmax, q.data_ptr(),
-                                            Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
-                                            ws.numel(), _lib.stream_ptr(self.device))
-            _lib.check(rc, "clipmi_topk_ip_coarse_i8")
-            return out_s, out_i
-        if coarse:
-            rc = L.clipmi_topk_ip_coarse(db.data_ptr(), dbh.data_ptr(), N, self.d, rmax, q.data_ptr(), Q, K, self.id_base,
-                                         out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(),
-                                         _lib.stream_ptr(self.device))
-            _lib.check(rc, "clipmi_topk_ip_coarse")
-            return out_s, out_i
-        rc = L.clipmi_topk_ip(db.data_ptr(), _lib.F32, N, self.d, q.data_ptr(), Q, K, self.id_base,
-                              out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(), ws.numel(),
-                              _lib.stream_ptr(self.device))
-        _lib.check(rc, "clipmi_topk_ip")
+            lead = (db.data_ptr(), _lib.F32, N, self.d)
+        rc = getattr(L, route.entry)(*lead, q.data_ptr(), Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
+                                     ws.numel(), _lib.stream_ptr(self.device))
+        _lib.check(rc, route.entry)
         return out_s, out_i
 
     PASS_Q = 64                   # queries of one coarse pass (csrc/topk.hip COARSE_Q)
@@ -288,11 +295,7 @@ class IndexFlatIP:
         what bench.py measures as "two batches in flight" (0.97-1.03 vs 1.09-1.10 ms per pass at 10 M rows). Same calls,
         same results; the caller's stream waits for the side stream before anything after the search runs."""
         Q = q.shape[0]
-        if out is None:
-            out_s = torch.empty((Q, K), dtype=torch.float32, device=self.device)
-            out_i = torch.empty((Q, K), dtype=torch.int64, device=self.device)
-        else:
-            out_s, out_i = out
+        out_s, out_i = _alloc_out(out, Q, K, self.device)
         # lanes = the caller's stream + ONE side stream, the process-wide one that CLIP.encode_image's second kernel sequence uses
         # too (_lib.side_stream: this ROCm gives only the first three streams of a process their own hardware queue and every
         # later one shares the fourth - two side streams created after a caller's own two ran on ONE queue, back to back:
@@ -380,11 +383,7 @@ class ShardedFlatIP:
             self.local.search_device(q, K, out=(rec_s, rec_i))
             dist.all_gather_into_tensor(gath, rec, group=self.group)
             L = _lib.lib()
-            if out is None:
-                out_s = torch.empty((Q, K), dtype=torch.float32, device=dev)
-                out_i = torch.empty((Q, K), dtype=torch.int64, device=dev)
-            else:
-                out_s, out_i = out
+            out_s, out_i = _alloc_out(out, Q, K, dev)
             rc = L.clipmi_merge_topk_packed(gath.data_ptr(), rec.numel(), self.world, Q, K, out_s.data_ptr(),
                                             out_i.data_ptr(), _lib.stream_ptr(dev))
             _lib.check(rc, "clipmi_merge_topk_packed")
