@@ -87,7 +87,8 @@ struct ScanArgs {
     int C;                  // candidate capacity per (wave, query): multiple of 16, >= K + 16
     int wave_bytes;         // LDS bytes per wave
     const float* thr_in;    // [QA] initial thresholds (valid lower bounds) or nullptr
-    uint2* cand;            // [QA][cap] dense candidate lists (unsorted), cap >= NL * C
+    uint2* cand;            // [QA][cap] dense candidate lists (unsorted); entries per query <= rows of the launch <= cap
+                            // (every (query, row) pair is published at most once: make_plan's cap = min(NL * C, rows))
     unsigned* gcnt;         // [32] entries used per query; zeroed on the stream before the launch
     long long cap;
     const unsigned* run_if; // optional device flag: the kernel exits at once when *run_if == 0
@@ -1664,7 +1665,25 @@ bool make_plan(long long N, int E, int Q, int K, Plan& p, int lds_limit = LDS_LI
     p.NL_sample = (long long)p.grid_sample * p.waves;
     const long long nl = p.NL > p.NL_sample ? p.NL : p.NL_sample;
     p.cap = nl * p.C;
+    // a scan appends every (query, row) pair at most once and compaction only drops entries: the waves of one launch never
+    // publish more than `rows` entries per query, and the lists are dense (one running counter per query). Without this bound a
+    // large K on a small index sized the lists by the pre-pass's many one-tile waves: 2048 x 8144 entries = 133 MB per query
+    // at K = 8128 for 70 k rows, 8.5 GB for the 64 lists of a coarse search's fallback.
+    // (the pre-pass only runs with N >= SAMPLE_MIN_N >= S rows, so N bounds both launches)
+    const long long rows = (long long)align_up((size_t)(N > 0 ? N : 1), 16);
+    if (p.cap > rows) p.cap = rows;
     return true;
+}
+
+// the largest K make_plan accepts at row width E (it depends on nothing else: the last plan tried is one wave, one query)
+int max_k(int E) {
+    Plan p;
+    int lo = 0, hi = 1 << 20;                    // make_plan(lo) holds or lo = 0; make_plan(hi) fails
+    while (hi - lo > 1) {
+        const int mid = lo + (hi - lo) / 2;
+        (make_plan(1, E, 1, mid, p) ? lo : hi) = mid;
+    }
+    return lo;
 }
 
 int opt_in_lds(const void* fn, size_t bytes) {
@@ -1709,8 +1728,8 @@ using namespace clipmi;
 extern "C" size_t clipmi_topk_ip_workspace_bytes(int64_t N, int E, int Q, int K) {
     Plan p;
     if (!make_plan(N, E, Q, K, p)) {
-        set_err(CLIPMI_EINVAL, "topk_ip: unsupported N=%lld E=%d Q=%d K=%d (E in {512,768}, 1 <= K <= ~8000)",
-                (long long)N, E, Q, K);
+        set_err(CLIPMI_EINVAL, "topk_ip: unsupported N=%lld E=%d Q=%d K=%d (E in {512,768}; 1 <= K <= %d at E = 512, <= %d at E = 768)",
+                (long long)N, E, Q, K, max_k(512), max_k(768));
         return 0;
     }
     return align_up((size_t)p.QA * p.cap * sizeof(uint2), 256) + 256 /*gcnt*/ + 256 /*thr*/ + 256;
@@ -1724,7 +1743,8 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
     if (N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip: N=%lld exceeds 2^32-2 rows per shard", (long long)N);
     Plan p;
     if (!make_plan(N, E, Q, K, p))
-        return set_err(CLIPMI_EINVAL, "topk_ip: unsupported N=%lld E=%d Q=%d K=%d", (long long)N, E, Q, K);
+        return set_err(CLIPMI_EINVAL, "topk_ip: unsupported N=%lld E=%d Q=%d K=%d (E in {512,768}; 1 <= K <= %d at E = 512, <= %d at E = 768)",
+                       (long long)N, E, Q, K, max_k(512), max_k(768));
     hipStream_t st = as_stream(stream);
     if (N == 0) {
         const long long n = (long long)Q * K;
@@ -2287,7 +2307,7 @@ int coarse_check(const void* db, const CoarseCopy& cp, int64_t N, int E, const f
         return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: needs E = 512 or 768 and N >= %d", SAMPLE_MIN_N);
     if (!(cp.rmax > 0.f) || N >= (1ll << 32) - 1)
         return set_err(CLIPMI_EINVAL, "topk_ip_coarse: rmax=%g N=%lld", cp.rmax, (long long)N);
-    if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d", Q, K);
+    if (!coarse_plan(N, E, Q, K, p)) return set_err(CLIPMI_EINVAL, "topk_ip_coarse: unsupported Q=%d K=%d (1 <= K <= %d at E = %d)", Q, K, max_k(E), E);
     return 0;
 }
 
@@ -2494,7 +2514,8 @@ inline CoarseCopy i8_copy(const void* db_i8_dev, const float* meta_dev, float rm
 extern "C" size_t clipmi_topk_ip_coarse_workspace_bytes(int64_t N, int E, int Q, int K) {
     Plan p;
     if ((E != 512 && E != 768) || N < SAMPLE_MIN_N || !coarse_plan(N, E, Q, K, p)) {
-        set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: unsupported: needs E = 512 or 768, N >= %d and a supported K", SAMPLE_MIN_N);
+        set_err(CLIPMI_EUNSUPPORTED, "topk_ip_coarse: unsupported: needs E = 512 or 768, N >= %d and 1 <= K <= %d at E = 512, <= %d at E = 768",
+                SAMPLE_MIN_N, max_k(512), max_k(768));
         return 0;
     }
     size_t need = carve(p, pass64_shape(E), nullptr, ~(size_t)0, nullptr);

@@ -146,6 +146,10 @@ int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev,
  *                ascending id; slots beyond min(K, N) hold score -FLT_MAX and id -1
  *   Scores are bit-exact f32: for each (row, query) one fmaf chain in the fixed order
  *   documented in DESIGN.md ("score order") and restated in oracle/topk_oracle.c.
+ *   K range: 1 <= K <= 8128 at E = 512, 1 <= K <= 7104 at E = 768, whatever N and Q (one query's K + 16 candidate
+ *   slots and as many of scratch must fit in LDS beside the query image, which is wider at 768). A larger K is
+ *   CLIPMI_EINVAL and a workspace size of 0; the coarse and wide entry points below accept the same range.
+ *   clipmi_merge_topk takes R * K <= 13609 (one LDS pass): eight shards merge on the device up to K = 1701.
  */
 size_t clipmi_topk_ip_workspace_bytes(int64_t N, int E, int Q, int K);
 int clipmi_topk_ip(const void* db_dev, int db_dtype, int64_t N, int E,

@@ -22,9 +22,11 @@ def test_coarse_workspace_accepts_768_and_keeps_512(clipmi):
     assert "unsupported" in clipmi._lib.last_error()
     # E = 512: byte for byte what the library returned before 768 was accepted - less, in the 64-query workspaces, the 9 216 bytes
     # of the live-threshold scan's ladder (64 x 32 words of the control block), keys and edges (512 bytes each), which left with
-    # that scan; the wide workspaces (Q = 200, 1024) never held them
+    # that scan; the wide workspaces (Q = 200, 1024) never held them. (70 001 rows at K = 300: the exact
+    # fallback's 64 lists are capped at one entry per row, 70 016 slots instead of 1024 waves x 320 - make_plan's row bound,
+    # tests/test_topk_krange.py - which takes 64 x 257 664 x 8 bytes off this one)
     for (N, Q, K), want in (((100000, 64, 51), 176238336 - 9216), ((100000, 200, 51), 235020800),
-                            ((10000000, 64, 51), 218181376 - 9216), ((70001, 5, 300), 302067456 - 9216),
+                            ((10000000, 64, 51), 218181376 - 9216), ((70001, 5, 300), 302067456 - 9216 - 64 * 257664 * 8),
                             ((200003, 1024, 101), 1342734848)):
         assert L.clipmi_topk_ip_coarse_workspace_bytes(N, 512, Q, K) == want, (N, Q, K)
     # the 768 workspace is the 512 one + the larger query image (bf16: four 16-query groups x 24 k-steps x 1 KiB instead of x 16)
