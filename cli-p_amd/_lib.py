@@ -29,7 +29,7 @@ SYMBOLS = [
     "clipmi_dbg_gemm_bf16", "clipmi_dbg_layernorm", "clipmi_dbg_attention", "clipmi_dbg_topk_scan_ms",
     "clipmi_dbg_encode_image_probe_ms", "clipmi_dbg_encode_image_probe3_ms",
     "clipmi_dbg_split_stats", "clipmi_dbg_gemm_ln", "clipmi_dbg_gemm_resid_ln", "clipmi_dbg_gemm_resid_ln_leaf", "clipmi_dbg_gemm_ln_leaf", "clipmi_dbg_quantize_rows_fp8mx", "clipmi_dbg_gemm_fp8_bsa",
-    "clipmi_dbg_embed_image", "clipmi_dbg_embed_text",
+    "clipmi_dbg_embed_image", "clipmi_dbg_embed_text", "clipmi_dbg_gemm_plan", "clipmi_dbg_gemm_fp8_plan",
 ]
 
 
@@ -186,6 +186,10 @@ def lib():
     L.clipmi_dbg_embed_image.argtypes = [TP, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     L.clipmi_dbg_embed_text.restype = i32
     L.clipmi_dbg_embed_text.argtypes = [TP, vp, vp, i32, vp, vp, vp, vp, vp, sz, vp]
+    L.clipmi_dbg_gemm_plan.restype = i32
+    L.clipmi_dbg_gemm_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
+    L.clipmi_dbg_gemm_fp8_plan.restype = i32
+    L.clipmi_dbg_gemm_fp8_plan.argtypes = [i32, i32, i32, i32, i32, i32, i32, C.POINTER(C.c_int32), i32]
     L.clipmi_dbg_topk_scan_ms.restype = i32
     L.clipmi_dbg_topk_scan_ms.argtypes = [vp, i64, i32, vp, i32, i32, vp, vp, vp, sz, vp, i32, C.POINTER(C.c_float)]
     L.clipmi_dbg_encode_image_probe_ms.restype = i32

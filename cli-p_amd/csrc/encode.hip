@@ -135,233 +135,219 @@ int launch_gather_rows(const void* src, void* dst, int B, int L, size_t row_byte
     return 0;
 }
 
-// the 12 (or 24) residual attention blocks shared by both towers. weight_format 1 (BASELINE.json configs[4]): the
-// four linear layers of a block run on the FP8 matrix cores - weights are e4m3 with one scale per output channel
-// (packed by weights.py), the bf16 activation rows are quantised to e4m3 with one scale per row right before each
-// GEMM (quantize_rows_fp8_kernel), gemm256f8 applies both scales in its epilogue. LayerNorm, attention, the
-// residual stream, patch embedding and the final projection are unchanged.
-// *pruned (vision towers): the last block ran its tail on the class-token rows, which are in w.x3c / w.xc, not w.x3 / w.x
-int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int causal, hipStream_t st, GemmProbe* probe,
-               bool* pruned = nullptr) {
-    const int W = t->width, L = t->tokens, M = B * L;
-    const bool fp8 = t->weight_format == 1;
-    const bool tail = pruned && !causal && !fp8 && (t->ln_fold ? w.x3c != nullptr : w.xc != nullptr) && encode_tail();
-    if (pruned) *pruned = tail;
-    auto linear = [&](const unsigned short* A, int K, uint64_t w_off, uint64_t b_off, void* out, int N, int epi) -> int {
-        GemmArgs g{};
-        g.bias = at<float>(blob, b_off); g.out = out; g.M = M; g.N = N; g.K = K;
-        g.A = A; g.W = at<unsigned short>(blob, w_off);
-        return launch_gemm_algo(g, epi, 0, st, probe);
-    };
-#ifdef CLIPMI_DEV
-    if (t->ln_fold && fp8) {
-        // FP8 blocks with folded LayerNorms (round 4; VERDICT r03 "What's missing" #1; development library: parity-green and
-        // measured SLOWER than the LayerNorm-pass tower below - DESIGN 4.4c - while its GEMMs run on the non-persistent kernel). The residual stream stays f32 in w.x;
-        // every producer of residual rows (the embedding stage through rows_mx_stats_kernel, then the two residual GEMMs'
-        // store passes: EPI_BIAS_RESID_LN8) also leaves them as e4m3 with MX block scales (w.x8 / w.x8_bs) with their
-        // row-statistics partials (w.ln_part), and qkv / c_fc take THOSE as their A operand with the LN-folded epilogue
-        // rstd (acc w_scale - mean colsum) + cb on weights e4m3(W diag(gamma)). No stand-alone LayerNorm pass is left
-        // (round 3: two per layer, 26 x 30 us of a 7.37 ms step).
-        auto lnfold8 = [&](uint64_t w_off, uint64_t s_off, uint64_t cb_off, uint64_t cs_off, void* out, unsigned char* out_bs, int N,
-                           int epi) -> int {
-            GemmArgs g{};
-            g.A = reinterpret_cast<const unsigned short*>(w.x8); g.a_bscale = w.x8_bs;
-            g.W = at<unsigned short>(blob, w_off); g.w_scale = at<float>(blob, s_off);
-            g.bias = at<float>(blob, cb_off); g.colsum = at<float>(blob, cs_off); g.ln_part_in = w.ln_part;
-            g.out = out; g.out_bscale = out_bs; g.M = M; g.N = N; g.K = W;
-            return launch_gemm_fp8(g, epi, st);
-        };
-        auto resid8 = [&](const unsigned char* A8, int K, uint64_t w_off, uint64_t s_off, uint64_t b_off) -> int {
-            GemmArgs g{};
-            g.A = reinterpret_cast<const unsigned short*>(A8); g.a_bscale = w.a_bs;
-            g.W = at<unsigned short>(blob, w_off); g.w_scale = at<float>(blob, s_off); g.bias = at<float>(blob, b_off);
-            g.out = w.x; g.x8 = w.x8; g.x8_bs = w.x8_bs; g.ln_part = w.ln_part; g.M = M; g.N = W; g.K = K;
-            return launch_gemm_fp8(g, EPI_BIAS_RESID_LN8, st);
-        };
-        unsigned char* const big8 = reinterpret_cast<unsigned char*>(w.big);
-        static const bool fuse_off = dev_knob("CLIPMI_FP8_FUSE", 1) == 0;   // A/B aid (development build): stand-alone MX passes
-        for (int l = 0; l < t->layers; ++l) {
-            const uint64_t lb = t->off_layers + (uint64_t)l * t->layer_stride;
-            if (int rc = lnfold8(lb + t->lo_qkv_w, lb + t->lo_qkv_s, lb + t->lo_qkv_cb, lb + t->lo_qkv_colsum, w.big, nullptr, 3 * W, EPI_LN_BIAS_BF16)) return rc;
-            bool fused = false;
-            if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st, fuse_off ? nullptr : w.a8, w.a_bs, &fused)) return rc;
-            if (!fused)
-                if (int rc = launch_quantize_rows_fp8mx(w.h, w.a8, w.a_bs, M, W, st)) return rc;
-            if (int rc = resid8(w.a8, W, lb + t->lo_out_w, lb + t->lo_out_s, lb + t->lo_out_b)) return rc;
-            if (!fuse_off) {
-                // the QuickGELU rows leave c_fc as e4m3 + block scales, into the bf16 buffer's bytes
-                if (int rc = lnfold8(lb + t->lo_fc_w, lb + t->lo_fc_s, lb + t->lo_fc_cb, lb + t->lo_fc_colsum, big8, w.a_bs, 4 * W, EPI_LN_BIAS_QGELU_BF16)) return rc;
-                if (int rc = resid8(big8, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_s, lb + t->lo_proj_b)) return rc;
-            } else {
-                if (int rc = lnfold8(lb + t->lo_fc_w, lb + t->lo_fc_s, lb + t->lo_fc_cb, lb + t->lo_fc_colsum, w.big, nullptr, 4 * W, EPI_LN_BIAS_QGELU_BF16)) return rc;
-                if (int rc = launch_quantize_rows_fp8mx(w.big, w.a8, w.a_bs, M, 4 * W, st)) return rc;
-                if (int rc = resid8(w.a8, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_s, lb + t->lo_proj_b)) return rc;
-            }
-        }
-        return 0;
-    }
-#endif
-    if (t->ln_fold) {
-        // LN-folded blocks (gemm.hpp): ln_1 / ln_2 never run as passes of their own and the residual stream lives split
-        // in w.x3 with its row statistics in w.ln_part; w.x (f32) is only the embedding stage's output and the
-        // scratch of residual GEMMs that run on a non-persistent kernel. lo_qkv_w / lo_fc_w hold W * diag(ln weight).
-        auto lb_of = [&](int l) { return t->off_layers + (uint64_t)l * t->layer_stride; };
-        // One prompt / one image (M <= 128: the skinny kernels, ~90 dependent launches of ~4 us): the residual GEMMs update the
-        // split rows themselves and hand the statistics on as leaves (GemmArgs.ln_leaf; round 5: 24 split / statistics launches
-        // fewer per tower). `leaves`: w.ln_leaf, not w.ln_part, describes the rows in w.x3.
-        const bool leaf_mode = w.ln_leaf != nullptr && gemm_resid_writes_leaves(M, W, W) && gemm_resid_writes_leaves(M, W, 4 * W);
-        bool leaves = false;
-        auto ln_linear = [&](uint64_t w_off, uint64_t cb_off, uint64_t cs_off, int N, int epi) -> int {
-            GemmArgs g{};
-            g.A = static_cast<const unsigned short*>(w.x3); g.lda_bytes = (unsigned)resid_row_bytes(W);
-            g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, cb_off);
-            g.colsum = at<float>(blob, cs_off); g.ln_part_in = w.ln_part;
-            if (leaves) g.ln_leaf_in = w.ln_leaf;
-            g.out = w.big; g.M = M; g.N = N; g.K = W;
-            return launch_gemm_algo(g, epi, 0, st, probe);
-        };
-        auto resid_linear = [&](const unsigned short* A, int K, uint64_t w_off, uint64_t b_off) -> int {
-            GemmArgs g{};
-            g.A = A; g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, b_off);
-            g.M = M; g.N = W; g.K = K;
-            g.x3 = w.x3; g.ln_part = w.ln_part; g.tmp_f32 = w.x;
-            if (leaf_mode) { g.ln_leaf = w.ln_leaf; leaves = true; }
-            return launch_gemm_algo(g, EPI_BIAS_RESID_LN_F32, 0, st, probe);
-        };
-        // (the caller left the embedded rows split: ln_pre writes hi / lo / partials itself; the text tower, which has no
-        //  LayerNorm in front of the blocks, runs split_stats_kernel over its embedded rows)
-        for (int l = 0; l < t->layers; ++l) {
-            const uint64_t lb = lb_of(l);
-            if (int rc = ln_linear(lb + t->lo_qkv_w, lb + t->lo_qkv_cb, lb + t->lo_qkv_colsum, 3 * W, EPI_LN_BIAS_BF16)) return rc;
-            if (tail && l == t->layers - 1) {
-                // the pruned tail: K and V of every token were needed, from here on only the class-token rows are. Their
-                // residual rows move to w.x3c (not in place: row b would land on rows another workgroup still reads), out_proj
-                // reads its A rows L apart in w.h, c_fc / c_proj use the head of w.big. No probe: bench.py's per-kernel times
-                // stay averages over launches of one shape. B <= 128: the skinny kernels with statistics leaves of their own.
-                const bool tleaf = w.leafc != nullptr && gemm_resid_writes_leaves(B, W, W) && gemm_resid_writes_leaves(B, W, 4 * W);
-                if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st)) return rc;
-                if (int rc = launch_gather_rows(w.x3, w.x3c, B, L, resid_row_bytes(W), st)) return rc;
-                auto tail_resid = [&](const unsigned short* A, unsigned lda_bytes, int K, uint64_t w_off, uint64_t b_off) -> int {
-                    GemmArgs g{};
-                    g.A = A; g.lda_bytes = lda_bytes; g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, b_off);
-                    g.M = B; g.N = W; g.K = K;
-                    g.x3 = w.x3c; g.ln_part = w.partc; g.tmp_f32 = w.x;
-                    if (tleaf) g.ln_leaf = w.leafc;
-                    return launch_gemm_algo(g, EPI_BIAS_RESID_LN_F32, 0, st, nullptr);
-                };
-                if (int rc = tail_resid(w.h, (unsigned)((size_t)L * W * 2), W, lb + t->lo_out_w, lb + t->lo_out_b)) return rc;
-                GemmArgs g{};
-                g.A = static_cast<const unsigned short*>(w.x3c); g.lda_bytes = (unsigned)resid_row_bytes(W);
-                g.W = at<unsigned short>(blob, lb + t->lo_fc_w); g.bias = at<float>(blob, lb + t->lo_fc_cb);
-                g.colsum = at<float>(blob, lb + t->lo_fc_colsum); g.ln_part_in = w.partc;
-                if (tleaf) g.ln_leaf_in = w.leafc;
-                g.out = w.big; g.M = B; g.N = 4 * W; g.K = W;
-                if (int rc = launch_gemm_algo(g, EPI_LN_BIAS_QGELU_BF16, 0, st, nullptr)) return rc;
-                return tail_resid(w.big, 0u, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b);     // the last block: done
-            }
-            // (bench probe, mode 2: attention's own end stamp, so that out_proj gets a completion-to-completion time too)
-            hipEvent_t* aev = nullptr;
-            if (probe && probe->mode == 2 && probe->n < GemmProbe::MAX) {
-                const int pi = probe->begin(GemmProbe::EPI_ATTENTION, 2, st, 0);
-                aev = &probe->ev[2 * pi];
-            }
-            if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st, nullptr, nullptr, nullptr, aev)) return rc;
-            if (int rc = resid_linear(w.h, W, lb + t->lo_out_w, lb + t->lo_out_b)) return rc;
-            if (int rc = ln_linear(lb + t->lo_fc_w, lb + t->lo_fc_cb, lb + t->lo_fc_colsum, 4 * W, EPI_LN_BIAS_QGELU_BF16)) return rc;
-            if (int rc = resid_linear(w.big, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b)) return rc;
-        }
-        return 0;
-    }
-    if (fp8) {
-        // FP8 blocks. LayerNorm writes its rows as e4m3 with a row scale (it sees whole rows); the two activations that a
-        // GEMM consumes straight from a producing kernel - attention's output and the QuickGELU rows - travel as e4m3 with
-        // MX block scales written by the producer itself where it has the fused form (attention52x4; the persistent
-        // QuickGELU GEMM), else by quantize_rows_fp8mx_kernel over the producer's bf16 rows: the same bytes either way.
-        auto gemm8 = [&](const unsigned char* A8, const float* a_scale, const unsigned char* a_bs, int K, uint64_t w_off,
-                         uint64_t s_off, uint64_t b_off, void* out, unsigned char* out_bs, int N, int epi) -> int {
-            GemmArgs g{};
-            g.bias = at<float>(blob, b_off); g.out = out; g.M = M; g.N = N; g.K = K;
-            g.A = reinterpret_cast<const unsigned short*>(A8);
-            g.W = at<unsigned short>(blob, w_off);
-            g.a_scale = a_scale; g.a_bscale = a_bs; g.out_bscale = out_bs;
-            g.w_scale = at<float>(blob, s_off);
-            return launch_gemm_fp8(g, epi, st);
-        };
-        static const bool fuse_off = dev_knob("CLIPMI_FP8_FUSE", 1) == 0;   // A/B aid (development build)
-        const bool fc_mx = !fuse_off && gemm_fp8_emits_mx(M, 4 * W, W);
-        unsigned char* const big8 = reinterpret_cast<unsigned char*>(w.big);
-        for (int l = 0; l < t->layers; ++l) {
-            const uint64_t lb = t->off_layers + (uint64_t)l * t->layer_stride;
-            LnArgs ln{w.x, at<float>(blob, lb + t->lo_ln1_w), at<float>(blob, lb + t->lo_ln1_b), w.h, nullptr, 1, M, W, 1};
-            ln.out8 = w.a8; ln.scale8 = w.a_scale;
-            if (int rc = launch_layernorm(ln, st)) return rc;
-            if (int rc = gemm8(w.a8, w.a_scale, nullptr, W, lb + t->lo_qkv_w, lb + t->lo_qkv_s, lb + t->lo_qkv_b, w.big, nullptr, 3 * W, EPI_BIAS_BF16)) return rc;
-            bool fused = false;
-            if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st, fuse_off ? nullptr : w.a8, w.a_bs, &fused)) return rc;
-            if (!fused)
-                if (int rc = launch_quantize_rows_fp8mx(w.h, w.a8, w.a_bs, M, W, st)) return rc;
-            if (int rc = gemm8(w.a8, nullptr, w.a_bs, W, lb + t->lo_out_w, lb + t->lo_out_s, lb + t->lo_out_b, w.x, nullptr, W, EPI_BIAS_RESID_F32)) return rc;
-            ln.w = at<float>(blob, lb + t->lo_ln2_w); ln.b = at<float>(blob, lb + t->lo_ln2_b);
-            if (int rc = launch_layernorm(ln, st)) return rc;
-            const unsigned char* h8 = w.a8;
-            if (fc_mx) {
-                // the QuickGELU rows leave the GEMM as e4m3 + block scales, into the bf16 buffer's bytes
-                if (int rc = gemm8(w.a8, w.a_scale, nullptr, W, lb + t->lo_fc_w, lb + t->lo_fc_s, lb + t->lo_fc_b, big8, w.a_bs, 4 * W, EPI_BIAS_QGELU_BF16)) return rc;
-                h8 = big8;
-            } else {
-                if (int rc = gemm8(w.a8, w.a_scale, nullptr, W, lb + t->lo_fc_w, lb + t->lo_fc_s, lb + t->lo_fc_b, w.big, nullptr, 4 * W, EPI_BIAS_QGELU_BF16)) return rc;
-                if (int rc = launch_quantize_rows_fp8mx(w.big, w.a8, w.a_bs, M, 4 * W, st)) return rc;
-            }
-            if (int rc = gemm8(h8, nullptr, w.a_bs, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_s, lb + t->lo_proj_b, w.x, nullptr, W, EPI_BIAS_RESID_F32)) return rc;
-        }
-        return 0;
-    }
-    for (int l = 0; l < t->layers; ++l) {
+// One layer's tensors in the weight blob (clipmi_tower lo_*), typed; qkv_b / fc_b are the folded cb rows in LN-folded towers
+struct LayerW {
+    const unsigned short *qkv_w, *out_w, *fc_w, *proj_w;
+    const float *qkv_b, *out_b, *fc_b, *proj_b, *qkv_colsum, *fc_colsum, *qkv_s, *out_s, *fc_s, *proj_s, *ln1_w, *ln1_b, *ln2_w, *ln2_b;
+    LayerW(const clipmi_tower* t, const void* blob, int l) {
         const uint64_t lb = t->off_layers + (uint64_t)l * t->layer_stride;
-        LnArgs ln{w.x, at<float>(blob, lb + t->lo_ln1_w), at<float>(blob, lb + t->lo_ln1_b), w.h, nullptr, 1, M, W, 1};
-        if (int rc = launch_layernorm(ln, st)) return rc;
-        if (int rc = linear(w.h, W, lb + t->lo_qkv_w, lb + t->lo_qkv_b, w.big, 3 * W, EPI_BIAS_BF16)) return rc;
-        if (int rc = launch_attention(w.big, w.h, B, L, t->heads, causal, 1, st)) return rc;
-        if (tail && l == t->layers - 1) {
-            // the pruned tail (see the LN-folded form above): the class-token rows of the f32 residual move to w.xc, ln_2
-            // writes its B rows to the head of w.h once out_proj has read the attention rows there
-            if (int rc = launch_gather_rows(w.x, w.xc, B, L, (size_t)W * 4, st)) return rc;
-            auto tail_linear = [&](const unsigned short* A, unsigned lda_bytes, int K, uint64_t w_off, uint64_t b_off, void* out, int N,
-                                   int epi) -> int {
-                GemmArgs g{};
-                g.A = A; g.lda_bytes = lda_bytes; g.W = at<unsigned short>(blob, w_off); g.bias = at<float>(blob, b_off);
-                g.out = out; g.M = B; g.N = N; g.K = K;
-                return launch_gemm_algo(g, epi, 0, st, nullptr);
-            };
-            if (int rc = tail_linear(w.h, (unsigned)((size_t)L * W * 2), W, lb + t->lo_out_w, lb + t->lo_out_b, w.xc, W, EPI_BIAS_RESID_F32)) return rc;
-            LnArgs ln2{w.xc, at<float>(blob, lb + t->lo_ln2_w), at<float>(blob, lb + t->lo_ln2_b), w.h, nullptr, 1, B, W, 1};
-            if (int rc = launch_layernorm(ln2, st)) return rc;
-            if (int rc = tail_linear(w.h, 0u, W, lb + t->lo_fc_w, lb + t->lo_fc_b, w.big, 4 * W, EPI_BIAS_QGELU_BF16)) return rc;
-            return tail_linear(w.big, 0u, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b, w.xc, W, EPI_BIAS_RESID_F32);     // the last block: done
-        }
-        if (int rc = linear(w.h, W, lb + t->lo_out_w, lb + t->lo_out_b, w.x, W, EPI_BIAS_RESID_F32)) return rc;
-        ln.w = at<float>(blob, lb + t->lo_ln2_w); ln.b = at<float>(blob, lb + t->lo_ln2_b);
-        if (int rc = launch_layernorm(ln, st)) return rc;
-        if (int rc = linear(w.h, W, lb + t->lo_fc_w, lb + t->lo_fc_b, w.big, 4 * W, EPI_BIAS_QGELU_BF16)) return rc;
-        if (int rc = linear(w.big, 4 * W, lb + t->lo_proj_w, lb + t->lo_proj_b, w.x, W, EPI_BIAS_RESID_F32)) return rc;
+        auto f = [&](uint64_t lo) { return at<float>(blob, lb + lo); };
+        auto h = [&](uint64_t lo) { return at<unsigned short>(blob, lb + lo); };
+        qkv_w = h(t->lo_qkv_w); out_w = h(t->lo_out_w); fc_w = h(t->lo_fc_w); proj_w = h(t->lo_proj_w);
+        qkv_b = f(t->ln_fold ? t->lo_qkv_cb : t->lo_qkv_b); fc_b = f(t->ln_fold ? t->lo_fc_cb : t->lo_fc_b);
+        out_b = f(t->lo_out_b); proj_b = f(t->lo_proj_b); qkv_colsum = f(t->lo_qkv_colsum); fc_colsum = f(t->lo_fc_colsum);
+        qkv_s = f(t->lo_qkv_s); out_s = f(t->lo_out_s); fc_s = f(t->lo_fc_s); proj_s = f(t->lo_proj_s);          // FP8 weight scales
+        ln1_w = f(t->lo_ln1_w); ln1_b = f(t->lo_ln1_b); ln2_w = f(t->lo_ln2_w); ln2_b = f(t->lo_ln2_b);
+    }
+};
+
+// the fields every linear layer sets; what a form adds (statistics, scales, the split residual) the form sets itself
+GemmArgs linear(const void* A, size_t lda_bytes, const unsigned short* W, const float* bias, int M, int N, int K, void* out) {
+    GemmArgs g{};
+    g.A = static_cast<const unsigned short*>(A); g.lda_bytes = (unsigned)lda_bytes; g.W = W; g.bias = bias;
+    g.M = M; g.N = N; g.K = K; g.out = out;
+    return g;
+}
+
+// where the blocks left the residual rows: f32 x or split x3 (the tower's form), one per image every row_step rows (L, or 1 behind a tail)
+struct Resid { const float* x; const void* x3; long long row_step; };
+
+// what every block form works on; tail: the last block runs its tail on the class-token rows (vision towers, bf16 weights)
+struct Blocks {
+    const clipmi_tower* t; const void* blob; const Ws& w; int B, causal; hipStream_t st; GemmProbe* probe; bool tail; int W, L, M, last;
+};
+
+// plain blocks, the pruned tail (see tail_ln): the class-token rows of the f32 residual move to w.xc, ln_2 writes its B rows to the
+// head of w.h once out_proj has read the attention rows there
+int tail_plain(const Blocks& c, const LayerW& lw, Resid& r) {
+    const Ws& w = c.w; const int B = c.B, W = c.W;
+    if (int rc = launch_gather_rows(w.x, w.xc, B, c.L, (size_t)W * 4, c.st)) return rc;
+    if (int rc = launch_gemm_algo(linear(w.h, (size_t)c.L * W * 2, lw.out_w, lw.out_b, B, W, W, w.xc), EPI_BIAS_RESID_F32, 0, c.st, nullptr)) return rc;
+    LnArgs ln2{w.xc, lw.ln2_w, lw.ln2_b, w.h, nullptr, 1, B, W, 1};
+    if (int rc = launch_layernorm(ln2, c.st)) return rc;
+    if (int rc = launch_gemm_algo(linear(w.h, 0, lw.fc_w, lw.fc_b, B, 4 * W, W, w.big), EPI_BIAS_QGELU_BF16, 0, c.st, nullptr)) return rc;
+    r = Resid{w.xc, nullptr, 1};
+    return launch_gemm_algo(linear(w.big, 0, lw.proj_w, lw.proj_b, B, W, 4 * W, w.xc), EPI_BIAS_RESID_F32, 0, c.st, nullptr);
+}
+
+int blocks_plain(const Blocks& c, Resid& r) {
+    const Ws& w = c.w; const int W = c.W, M = c.M;
+    for (int l = 0; l <= c.last; ++l) {
+        const LayerW lw(c.t, c.blob, l);
+        LnArgs ln{w.x, lw.ln1_w, lw.ln1_b, w.h, nullptr, 1, M, W, 1};
+        if (int rc = launch_layernorm(ln, c.st)) return rc;
+        if (int rc = launch_gemm_algo(linear(w.h, 0, lw.qkv_w, lw.qkv_b, M, 3 * W, W, w.big), EPI_BIAS_BF16, 0, c.st, c.probe)) return rc;
+        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st)) return rc;
+        if (c.tail && l == c.last) return tail_plain(c, lw, r);
+        if (int rc = launch_gemm_algo(linear(w.h, 0, lw.out_w, lw.out_b, M, W, W, w.x), EPI_BIAS_RESID_F32, 0, c.st, c.probe)) return rc;
+        ln.w = lw.ln2_w; ln.b = lw.ln2_b;
+        if (int rc = launch_layernorm(ln, c.st)) return rc;
+        if (int rc = launch_gemm_algo(linear(w.h, 0, lw.fc_w, lw.fc_b, M, 4 * W, W, w.big), EPI_BIAS_QGELU_BF16, 0, c.st, c.probe)) return rc;
+        if (int rc = launch_gemm_algo(linear(w.big, 0, lw.proj_w, lw.proj_b, M, W, 4 * W, w.x), EPI_BIAS_RESID_F32, 0, c.st, c.probe)) return rc;
     }
     return 0;
 }
 
-// pooled rows -> final LayerNorm -> projection [E][W] -> f32 [B][E] (-> optional L2 normalise)
-int run_head(const clipmi_tower* t, const void* blob, const Ws& w, int B, const int* rowidx, long long row_step,
-             float* out, int normalize, hipStream_t st) {
-    const bool split = t->ln_fold && t->weight_format == 0;      // bf16 LN-folded towers keep the residual as (hi, lo)
-    LnArgs ln{split ? nullptr : w.x, at<float>(blob, t->off_ln_post_w), at<float>(blob, t->off_ln_post_b), w.pooled, rowidx,
-              row_step, B, t->width, 1};
-    ln.x3 = w.x3;                          // split: the residual stream is rows of (hi | lo)
-    if (int rc = launch_layernorm(ln, st)) return rc;
-    GemmArgs g{};
-    g.A = w.pooled; g.W = at<unsigned short>(blob, t->off_out_proj); g.bias = nullptr; g.out = out;
-    g.M = B; g.N = t->embed; g.K = t->width;
-    if (int rc = launch_gemm_algo(g, EPI_F32, 0, st)) return rc;
-    if (normalize) return clipmi_l2_normalize_rows(out, B, t->embed, st);
+// LN-folded blocks, the pruned tail: K and V of every token were needed, from here on only the class-token rows are. Their residual
+// rows move to w.x3c (not in place: row b would land on rows another workgroup still reads), out_proj reads its A rows L apart in w.h,
+// c_fc / c_proj use the head of w.big. No probe: bench.py's per-kernel times stay averages over one shape. B <= 128: leaves of their own.
+int tail_ln(const Blocks& c, const LayerW& lw, Resid& r) {
+    const Ws& w = c.w; const int B = c.B, W = c.W;
+    float* const leaf = w.leafc && gemm_resid_writes_leaves(B, W, W) && gemm_resid_writes_leaves(B, W, 4 * W) ? w.leafc : nullptr;
+    if (int rc = launch_attention(w.big, w.h, B, c.L, c.t->heads, c.causal, 1, c.st)) return rc;
+    if (int rc = launch_gather_rows(w.x3, w.x3c, B, c.L, resid_row_bytes(W), c.st)) return rc;
+    GemmArgs out = linear(w.h, (size_t)c.L * W * 2, lw.out_w, lw.out_b, B, W, W, nullptr);
+    out.x3 = w.x3c; out.ln_part = w.partc; out.ln_leaf = leaf; out.tmp_f32 = w.x;
+    if (int rc = launch_gemm_algo(out, EPI_BIAS_RESID_LN_F32, 0, c.st, nullptr)) return rc;
+    GemmArgs fc = linear(w.x3c, resid_row_bytes(W), lw.fc_w, lw.fc_b, B, 4 * W, W, w.big);
+    fc.colsum = lw.fc_colsum; fc.ln_part_in = w.partc; fc.ln_leaf_in = leaf;
+    if (int rc = launch_gemm_algo(fc, EPI_LN_BIAS_QGELU_BF16, 0, c.st, nullptr)) return rc;
+    GemmArgs proj = linear(w.big, 0, lw.proj_w, lw.proj_b, B, W, 4 * W, nullptr);
+    proj.x3 = w.x3c; proj.ln_part = w.partc; proj.ln_leaf = leaf; proj.tmp_f32 = w.x;
+    r = Resid{nullptr, w.x3c, 1};
+    return launch_gemm_algo(proj, EPI_BIAS_RESID_LN_F32, 0, c.st, nullptr);
+}
+
+// LN-folded blocks (gemm.hpp): ln_1 / ln_2 never run as passes of their own, the residual stream lives split in w.x3 with its row
+// statistics in w.ln_part (the caller left the embedded rows so); w.x (f32) is only the scratch of residual GEMMs off the persistent kernel
+int blocks_ln(const Blocks& c, Resid& r) {
+    const Ws& w = c.w; const int W = c.W, M = c.M;
+    // One prompt / one image (M <= 128: the skinny kernels, ~90 dependent launches of ~4 us): the residual GEMMs update the split rows
+    // themselves and hand the statistics on as leaves. leaf_in: w.ln_leaf, not w.ln_part, describes w.x3 - from the first residual GEMM on.
+    float* const leaf = w.ln_leaf && gemm_resid_writes_leaves(M, W, W) && gemm_resid_writes_leaves(M, W, 4 * W) ? w.ln_leaf : nullptr;
+    const float* leaf_in = nullptr;
+    for (int l = 0; l <= c.last; ++l) {
+        const LayerW lw(c.t, c.blob, l);
+        GemmArgs qkv = linear(w.x3, resid_row_bytes(W), lw.qkv_w, lw.qkv_b, M, 3 * W, W, w.big);
+        qkv.colsum = lw.qkv_colsum; qkv.ln_part_in = w.ln_part; qkv.ln_leaf_in = leaf_in;
+        if (int rc = launch_gemm_algo(qkv, EPI_LN_BIAS_BF16, 0, c.st, c.probe)) return rc;
+        if (c.tail && l == c.last) return tail_ln(c, lw, r);
+        // (bench probe, mode 2: attention's own end stamp, so that out_proj gets a completion-to-completion time too)
+        hipEvent_t* aev = nullptr;
+        if (c.probe && c.probe->mode == 2 && c.probe->n < GemmProbe::MAX) aev = &c.probe->ev[2 * c.probe->begin(GemmProbe::EPI_ATTENTION, 2, c.st, 0)];
+        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st, nullptr, nullptr, nullptr, aev)) return rc;
+        GemmArgs out = linear(w.h, 0, lw.out_w, lw.out_b, M, W, W, nullptr);
+        out.x3 = w.x3; out.ln_part = w.ln_part; out.ln_leaf = leaf; out.tmp_f32 = w.x;
+        if (int rc = launch_gemm_algo(out, EPI_BIAS_RESID_LN_F32, 0, c.st, c.probe)) return rc;
+        leaf_in = leaf;
+        GemmArgs fc = linear(w.x3, resid_row_bytes(W), lw.fc_w, lw.fc_b, M, 4 * W, W, w.big);
+        fc.colsum = lw.fc_colsum; fc.ln_part_in = w.ln_part; fc.ln_leaf_in = leaf_in;
+        if (int rc = launch_gemm_algo(fc, EPI_LN_BIAS_QGELU_BF16, 0, c.st, c.probe)) return rc;
+        GemmArgs proj = linear(w.big, 0, lw.proj_w, lw.proj_b, M, W, 4 * W, nullptr);
+        proj.x3 = w.x3; proj.ln_part = w.ln_part; proj.ln_leaf = leaf; proj.tmp_f32 = w.x;
+        if (int rc = launch_gemm_algo(proj, EPI_BIAS_RESID_LN_F32, 0, c.st, c.probe)) return rc;
+    }
     return 0;
+}
+
+// The two steps both FP8 forms share: attention's output and the QuickGELU rows travel as e4m3 with MX block scales, written by the
+// producer itself where it has the fused form (attention52x4; the persistent QuickGELU GEMM), else by quantize_rows_fp8mx_kernel over
+// the producer's bf16 rows: the same bytes either way.
+bool fp8_fuse_off() { static const bool off = dev_knob("CLIPMI_FP8_FUSE", 1) == 0; return off; }   // A/B aid (development build)
+// attention -> e4m3 rows w.a8 + block scales w.a_bs
+int attention_fp8(const Blocks& c, const Ws& w) {
+    bool fused = false;
+    if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st, fp8_fuse_off() ? nullptr : w.a8, w.a_bs, &fused)) return rc;
+    return fused ? 0 : launch_quantize_rows_fp8mx(w.h, w.a8, w.a_bs, c.M, c.W, c.st);
+}
+// c_fc (`fc`, into w.big) -> e4m3 QuickGELU rows *h8 + block scales w.a_bs; mx_out: the GEMM writes them itself, into the bf16 buffer's bytes
+int fc_fp8(const Blocks& c, const Ws& w, GemmArgs fc, int epi, bool mx_out, const unsigned char** h8) {
+    if (mx_out) fc.out_bscale = w.a_bs;
+    *h8 = mx_out ? reinterpret_cast<const unsigned char*>(w.big) : w.a8;
+    if (int rc = launch_gemm_fp8(fc, epi, c.st)) return rc;
+    return mx_out ? 0 : launch_quantize_rows_fp8mx(w.big, w.a8, w.a_bs, c.M, 4 * c.W, c.st);
+}
+
+// FP8 blocks (weight_format 1, BASELINE.json configs[4]): the four linear layers run on the FP8 matrix cores - weights are e4m3 with one
+// scale per output channel, LayerNorm writes its rows as e4m3 with a row scale, gemm256f8 applies both scales in its epilogue
+int blocks_fp8(const Blocks& c) {
+    const Ws& w = c.w; const int W = c.W, M = c.M;
+    const bool fc_mx = !fp8_fuse_off() && gemm_fp8_emits_mx(M, 4 * W, W);
+    for (int l = 0; l <= c.last; ++l) {
+        const LayerW lw(c.t, c.blob, l);
+        LnArgs ln{w.x, lw.ln1_w, lw.ln1_b, w.h, nullptr, 1, M, W, 1};
+        ln.out8 = w.a8; ln.scale8 = w.a_scale;
+        if (int rc = launch_layernorm(ln, c.st)) return rc;
+        GemmArgs qkv = linear(w.a8, 0, lw.qkv_w, lw.qkv_b, M, 3 * W, W, w.big);
+        qkv.a_scale = w.a_scale; qkv.w_scale = lw.qkv_s;
+        if (int rc = launch_gemm_fp8(qkv, EPI_BIAS_BF16, c.st)) return rc;
+        if (int rc = attention_fp8(c, w)) return rc;
+        GemmArgs out = linear(w.a8, 0, lw.out_w, lw.out_b, M, W, W, w.x);
+        out.a_bscale = w.a_bs; out.w_scale = lw.out_s;
+        if (int rc = launch_gemm_fp8(out, EPI_BIAS_RESID_F32, c.st)) return rc;
+        ln.w = lw.ln2_w; ln.b = lw.ln2_b;
+        if (int rc = launch_layernorm(ln, c.st)) return rc;
+        GemmArgs fc = linear(w.a8, 0, lw.fc_w, lw.fc_b, M, 4 * W, W, w.big);
+        fc.a_scale = w.a_scale; fc.w_scale = lw.fc_s;
+        const unsigned char* h8;
+        if (int rc = fc_fp8(c, w, fc, EPI_BIAS_QGELU_BF16, fc_mx, &h8)) return rc;
+        GemmArgs proj = linear(h8, 0, lw.proj_w, lw.proj_b, M, W, 4 * W, w.x);
+        proj.a_bscale = w.a_bs; proj.w_scale = lw.proj_s;
+        if (int rc = launch_gemm_fp8(proj, EPI_BIAS_RESID_F32, c.st)) return rc;
+    }
+    return 0;
+}
+
+#ifdef CLIPMI_DEV
+// FP8 blocks with folded LayerNorms (development library: parity-green and measured SLOWER than the LayerNorm-pass tower above,
+// DESIGN 4.4c). The residual stream stays f32 in w.x; every producer of residual rows (the embedding stage through
+// rows_mx_stats_kernel, then the residual GEMMs' store passes: EPI_BIAS_RESID_LN8) also leaves them as e4m3 with MX block scales
+// (w.x8 / w.x8_bs) and statistics partials (w.ln_part); qkv / c_fc take THOSE as A, with the LN-folded epilogue. No LayerNorm pass.
+int blocks_ln_fp8(const Blocks& c) {
+    const Ws& w = c.w; const int W = c.W, M = c.M;
+    for (int l = 0; l <= c.last; ++l) {
+        const LayerW lw(c.t, c.blob, l);
+        GemmArgs qkv = linear(w.x8, 0, lw.qkv_w, lw.qkv_b, M, 3 * W, W, w.big);
+        qkv.a_bscale = w.x8_bs; qkv.w_scale = lw.qkv_s; qkv.colsum = lw.qkv_colsum; qkv.ln_part_in = w.ln_part;
+        if (int rc = launch_gemm_fp8(qkv, EPI_LN_BIAS_BF16, c.st)) return rc;
+        if (int rc = attention_fp8(c, w)) return rc;
+        GemmArgs out = linear(w.a8, 0, lw.out_w, lw.out_b, M, W, W, w.x);
+        out.a_bscale = w.a_bs; out.w_scale = lw.out_s; out.x8 = w.x8; out.x8_bs = w.x8_bs; out.ln_part = w.ln_part;
+        if (int rc = launch_gemm_fp8(out, EPI_BIAS_RESID_LN8, c.st)) return rc;
+        GemmArgs fc = linear(w.x8, 0, lw.fc_w, lw.fc_b, M, 4 * W, W, w.big);
+        fc.a_bscale = w.x8_bs; fc.w_scale = lw.fc_s; fc.colsum = lw.fc_colsum; fc.ln_part_in = w.ln_part;
+        const unsigned char* h8;
+        if (int rc = fc_fp8(c, w, fc, EPI_LN_BIAS_QGELU_BF16, !fp8_fuse_off(), &h8)) return rc;
+        GemmArgs proj = linear(h8, 0, lw.proj_w, lw.proj_b, M, W, 4 * W, w.x);
+        proj.a_bscale = w.a_bs; proj.w_scale = lw.proj_s; proj.x8 = w.x8; proj.x8_bs = w.x8_bs; proj.ln_part = w.ln_part;
+        if (int rc = launch_gemm_fp8(proj, EPI_BIAS_RESID_LN8, c.st)) return rc;
+    }
+    return 0;
+}
+#endif
+
+// the 12 (or 24) residual attention blocks shared by both towers, in the tower's form; *r: where they leave the residual rows
+int run_layers(const clipmi_tower* t, const void* blob, const Ws& w, int B, int causal, hipStream_t st, GemmProbe* probe, Resid* r) {
+    const bool fp8 = t->weight_format == 1;
+    const bool tail = !causal && !fp8 && (t->ln_fold ? w.x3c != nullptr : w.xc != nullptr) && encode_tail();
+    const Blocks c{t, blob, w, B, causal, st, probe, tail, t->width, t->tokens, B * t->tokens, t->layers - 1};
+    *r = Resid{w.x, w.x3, t->tokens};
+#ifdef CLIPMI_DEV
+    if (t->ln_fold && fp8) return blocks_ln_fp8(c);
+#endif
+    if (t->ln_fold) return blocks_ln(c, *r);
+    return fp8 ? blocks_fp8(c) : blocks_plain(c, *r);
+}
+
+// rows r (with rowidx: gathered by index, the text tower's EOT rows) -> final LayerNorm -> projection [E][W] -> f32 [B][E] (-> L2 normalise)
+int run_head(const clipmi_tower* t, const void* blob, const Ws& w, const Resid& r, int B, const int* rowidx, float* out, int normalize, hipStream_t st) {
+    const bool split = t->ln_fold && t->weight_format == 0;      // bf16 LN-folded towers keep the residual as (hi, lo)
+    LnArgs ln{split ? nullptr : r.x, at<float>(blob, t->off_ln_post_w), at<float>(blob, t->off_ln_post_b), w.pooled, rowidx,
+              r.row_step, B, t->width, 1};
+    ln.x3 = r.x3;                          // split: the residual stream is rows of (hi | lo)
+    if (int rc = launch_layernorm(ln, st)) return rc;
+    if (int rc = launch_gemm_algo(linear(w.pooled, 0, at<unsigned short>(blob, t->off_out_proj), nullptr, B, t->embed, t->width, out), EPI_F32, 0, st)) return rc;
+    return normalize ? clipmi_l2_normalize_rows(out, B, t->embed, st) : 0;
 }
 
 }  // namespace
@@ -421,20 +407,14 @@ static int encode_image_impl(const clipmi_tower* t, const void* blob_dev, const 
     Ws w;
     carve(t, B, ws_dev, ws_bytes, &w);
     hipStream_t st = as_stream(stream);
-    const int L = t->tokens;
     if (int rc = embed_image(t, blob_dev, pixels_dev, pix_dtype, B, w, 0, true, st)) return rc;
 #ifdef CLIPMI_DEV
     if (t->ln_fold && t->weight_format == 1)     // FP8 tower with folded LayerNorms: the embedded rows' e4m3 image + statistics for the first qkv GEMM
-        if (int rc = launch_rows_mx_stats(w.x, w.x8, w.x8_bs, w.ln_part, B * L, t->width, st)) return rc;
+        if (int rc = launch_rows_mx_stats(w.x, w.x8, w.x8_bs, w.ln_part, B * t->tokens, t->width, st)) return rc;
 #endif
-    bool pruned = false;
-    if (int rc = run_layers(t, blob_dev, w, B, 0, st, probe, &pruned)) return rc;
-    if (pruned) {            // the class-token rows are compact
-        Ws wc = w;
-        wc.x = w.xc; wc.x3 = w.x3c;
-        return run_head(t, blob_dev, wc, B, nullptr, 1, out_dev, normalize, st);
-    }
-    return run_head(t, blob_dev, w, B, nullptr, L, out_dev, normalize, st);
+    Resid r;
+    if (int rc = run_layers(t, blob_dev, w, B, 0, st, probe, &r)) return rc;
+    return run_head(t, blob_dev, w, r, B, nullptr, out_dev, normalize, st);
 }
 
 extern "C" int clipmi_encode_image(const clipmi_tower* t, const void* blob_dev, const void* pixels_dev, int pix_dtype,
@@ -479,19 +459,28 @@ static int embed_text(const clipmi_tower* t, const void* blob_dev, const int32_t
     return 0;
 }
 
+// arguments of clipmi_encode_text and of its test hook (`who` names the entry point in the message)
+static int check_text_args(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q, bool have_out, const void* ws_dev,
+                           size_t ws_bytes, const char* who) {
+    if (int rc = check_tower(t, 1, who)) return rc;
+    if (!blob_dev || !ids_dev || !have_out || !ws_dev) return set_err(CLIPMI_EINVAL, "%s: NULL pointer", who);
+    if (Q < 1) return set_err(CLIPMI_EINVAL, "%s: Q=%d", who, Q);
+    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
+    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    return 0;
+}
+
 extern "C" int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev, const int32_t* ids_dev, int Q,
                                   float* out_dev, int normalize, void* ws_dev, size_t ws_bytes, void* stream) {
-    if (int rc = check_tower(t, 1, "encode_text")) return rc;
-    if (!blob_dev || !ids_dev || !out_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "encode_text: NULL pointer");
-    if (Q < 1) return set_err(CLIPMI_EINVAL, "encode_text: Q=%d", Q);
-    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
-    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "encode_text: workspace %zu < %zu", ws_bytes, need);
+    if (int rc = check_text_args(t, blob_dev, ids_dev, Q, out_dev != nullptr, ws_dev, ws_bytes, "encode_text")) return rc;
     Ws w;
     carve(t, Q, ws_dev, ws_bytes, &w);
     hipStream_t st = as_stream(stream);
     if (int rc = embed_text(t, blob_dev, ids_dev, Q, w, st)) return rc;
-    if (int rc = run_layers(t, blob_dev, w, Q, 1, st, nullptr)) return rc;
-    return run_head(t, blob_dev, w, Q, w.rowidx, 1, out_dev, normalize, st);
+    Resid r;
+    if (int rc = run_layers(t, blob_dev, w, Q, 1, st, nullptr, &r)) return rc;
+    r.row_step = 1;          // the head gathers the EOT rows by index
+    return run_head(t, blob_dev, w, r, Q, w.rowidx, out_dev, normalize, st);
 }
 
 // Test hooks of the embedding front ends: the product's own launch sequence (embed_image / embed_text above) in the tower's
@@ -530,11 +519,7 @@ extern "C" int clipmi_dbg_embed_text(const clipmi_tower* t, const void* blob_dev
                                      void* x3_out_dev, float* part_out_dev, int32_t* rowidx_out_dev, void* ws_dev, size_t ws_bytes,
                                      void* stream) {
     const char* who = "dbg_embed_text";
-    if (int rc = check_tower(t, 1, who)) return rc;
-    if (!blob_dev || !ids_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "%s: NULL pointer", who);
-    if (Q < 1) return set_err(CLIPMI_EINVAL, "%s: Q=%d", who, Q);
-    const size_t need = clipmi_encode_text_workspace_bytes(t, Q);
-    if (ws_bytes < need) return set_err(CLIPMI_EWORKSPACE, "%s: workspace %zu < %zu", who, ws_bytes, need);
+    if (int rc = check_text_args(t, blob_dev, ids_dev, Q, true, ws_dev, ws_bytes, who)) return rc;
     const bool split = t->ln_fold && t->weight_format == 0;
     if (split ? rows_out_dev != nullptr : (x3_out_dev != nullptr || part_out_dev != nullptr))
         return set_err(CLIPMI_EINVAL, "%s: this tower's rows are %s", who, split ? "split rows + partials" : "f32 rows");

@@ -19,6 +19,7 @@
 // loads bias / residual and stores results as 8- or 16-byte vectors.
 #pragma once
 #include "common.hpp"
+#include "gemm_plan.hpp"     // Epilogue, the epilogue predicates, SKINNY_MAX_M
 
 namespace clipmi {
 
@@ -53,21 +54,6 @@ __device__ __forceinline__ f32x4 quick_gelu4(f32x4 x) {
     r.z = __builtin_amdgcn_rcpf(d.z); r.w = __builtin_amdgcn_rcpf(d.w);
     return x * r;
 }
-
-enum Epilogue {
-    EPI_BIAS_BF16 = 0,        // out bf16 [M][N] = acc + bias
-    EPI_BIAS_QGELU_BF16 = 1,  // out bf16 = quick_gelu(acc + bias)
-    EPI_BIAS_RESID_F32 = 2,   // out f32 [M][N] += acc + bias        (residual stream, in place)
-    EPI_F32 = 3,              // out f32 = acc (+ bias if given)
-    EPI_PATCH_F32 = 4,        // out f32 [b*L + 1 + p][n] = acc + pos[1 + p][n],  m = b*np + p
-    // LayerNorm folded into the GEMM that consumes it ("LN-folded" linear layers, see ln_fold below):
-    EPI_LN_BIAS_BF16 = 5,        // out bf16 = rstd[m] * (acc - mean[m] * colsum[n]) + bias[n]
-    EPI_LN_BIAS_QGELU_BF16 = 6,  // out bf16 = quick_gelu(the same)
-    EPI_BIAS_RESID_LN_F32 = 7,   // split residual: x3 (hi | lo rows) += acc + bias, + row-statistics partials of the new rows
-    EPI_BIAS_RESID_LN8 = 8       // FP8 towers with folded LayerNorms (round 4): out f32 [M][N] += acc + bias, and the new rows
-                                 // also leave as e4m3 with MX block scales (x8, x8_bs: the A operand of the next LN-folded
-                                 // FP8 GEMM) with their row-statistics partials (ln_part)
-};
 
 // ---- LN-folded linear layers ---------------------------------------------------------------------------------
 // y = LayerNorm(x; gamma, beta) W^T + b, with mean / rstd the row statistics of x, equals
@@ -255,10 +241,6 @@ __device__ __forceinline__ uint2 mx_pack_bf16x8(uint4 x, unsigned& sb_out) {
     return fp8_pack8(f);
 }
 
-constexpr bool epi_is_ln(int e) { return e == EPI_LN_BIAS_BF16 || e == EPI_LN_BIAS_QGELU_BF16; }
-constexpr bool epi_is_qgelu(int e) { return e == EPI_BIAS_QGELU_BF16 || e == EPI_LN_BIAS_QGELU_BF16; }
-constexpr bool epi_is_bf16_out(int e) { return e == EPI_BIAS_BF16 || e == EPI_BIAS_QGELU_BF16 || epi_is_ln(e); }
-
 struct GemmArgs {
     const unsigned short* A;   // bf16 [M][K]; rows lda_bytes apart when that is set (the hi halves of split-residual rows)
     const unsigned short* W;   // bf16 [N][K]
@@ -295,7 +277,6 @@ struct GemmArgs {
     float* ln_leaf;
     const float* ln_leaf_in;
 };
-constexpr int SKINNY_MAX_M = 128;       // rows up to which the skinny kernels (gemm_skinny.hpp) take a GEMM
 // elements (bf16) between two A rows
 __host__ __device__ inline size_t gemm_lda(const GemmArgs& g) { return g.lda_bytes ? (size_t)g.lda_bytes / 2 : (size_t)g.K; }
 
@@ -508,7 +489,6 @@ struct GemmProbe {
     }
 };
 
-int launch_gemm(const GemmArgs& g, int epi, hipStream_t st, GemmProbe* probe = nullptr);
 int launch_gemm_algo(const GemmArgs& g, int epi, int algo, hipStream_t st, GemmProbe* probe = nullptr);
 int launch_gemm_fp8(const GemmArgs& g, int epi, hipStream_t st, int mx = 1);      // gemm256f8.hpp: e4m3 operands + scales
 bool gemm_resid_writes_leaves(int M, int N, int K);   // the residual GEMM of this shape runs on the skinny kernel and can take ln_leaf

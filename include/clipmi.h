@@ -520,6 +520,21 @@ int clipmi_dbg_gemm_ln_leaf(const void* x3_dev, const void* wg_dev, const float*
 int clipmi_dbg_gemm_resid_ln(const void* a_dev, const void* w_dev, const float* bias_dev, void* x3_dev, float* part_dev,
                              float* tmp_dev, int M, int N, int K, int algo, void* stream);
 
+/* Which kernel a GEMM of this shape runs on (csrc/gemm_plan.hpp: the rule the launchers follow), host only - no device is
+ * touched, no operand exists. clipmi_dbg_gemm_plan: the bf16 GEMMs; epi = the EPI_* number, algo 0 = by shape, 1 / 2 / 3 force
+ * the 128 x 128 / 256 x 256 / persistent 256 x 256 kernel, ln_leaf / ln_leaf_in != 0: the caller passes statistics leaves
+ * (M <= 128), dbg: 0. clipmi_dbg_gemm_fp8_plan: the FP8 GEMMs; mx as bits 8-9 of clipmi_dbg_gemm_fp8 select it (1 the product's
+ * choice, 0 plain FP8, 2 MX off the persistent kernel), a_bscale / out_bscale != 0: block-scaled A / e4m3 + block-scale output.
+ * out[0] = the number of launches (> 1: the rows that fill whole rounds of 256 x 256 tiles run first, on the persistent
+ * kernel), then per launch 7 values: rows, kernel (0 128 x 128, 1 256 x 256, 2 persistent, 3 skinny, 4 gemm256f8, 5 gemm256f8
+ * with block-scaled A), the kernel's epilogue, 1 if it is an f32 launch into the scratch rows with split_stats behind it,
+ * 1 if the skinny residual producer writes statistics leaves, and the persistent kernel's grid and LDS bytes. out[22], refused
+ * or not: what the encode path's own query of the plan answers for (M, N, K) - clipmi_dbg_gemm_plan: the residual GEMM runs on
+ * the skinny kernel and can write leaves; clipmi_dbg_gemm_fp8_plan: the QuickGELU GEMM can write e4m3 + block scales. n_out:
+ * the length of out (23 holds everything). A shape the launcher refuses returns its error code and message. */
+int clipmi_dbg_gemm_plan(int M, int N, int K, int epi, int algo, int ln_leaf, int ln_leaf_in, int dbg, int32_t* out, int n_out);
+int clipmi_dbg_gemm_fp8_plan(int M, int N, int K, int epi, int mx, int a_bscale, int out_bscale, int32_t* out, int n_out);
+
 /* The embedding front ends of the two towers - everything in front of the first block - as clipmi_encode_image /
  * clipmi_encode_text enqueue them (the same function runs in both), in the tower's ordinary workspace
  * (clipmi_encode_*_workspace_bytes), followed by copies of the results on the same stream. Every `*_out_dev` pointer may be NULL.
