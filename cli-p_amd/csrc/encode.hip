@@ -187,7 +187,7 @@ int blocks_plain(const Blocks& c, Resid& r) {
         LnArgs ln{w.x, lw.ln1_w, lw.ln1_b, w.h, nullptr, 1, M, W, 1};
         if (int rc = launch_layernorm(ln, c.st)) return rc;
         if (int rc = launch_gemm_algo(linear(w.h, 0, lw.qkv_w, lw.qkv_b, M, 3 * W, W, w.big), EPI_BIAS_BF16, 0, c.st, c.probe)) return rc;
-        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st)) return rc;
+        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, ATTN_DEFAULT, c.st)) return rc;
         if (c.tail && l == c.last) return tail_plain(c, lw, r);
         if (int rc = launch_gemm_algo(linear(w.h, 0, lw.out_w, lw.out_b, M, W, W, w.x), EPI_BIAS_RESID_F32, 0, c.st, c.probe)) return rc;
         ln.w = lw.ln2_w; ln.b = lw.ln2_b;
@@ -204,7 +204,7 @@ int blocks_plain(const Blocks& c, Resid& r) {
 int tail_ln(const Blocks& c, const LayerW& lw, Resid& r) {
     const Ws& w = c.w; const int B = c.B, W = c.W;
     float* const leaf = w.leafc && gemm_resid_writes_leaves(B, W, W) && gemm_resid_writes_leaves(B, W, 4 * W) ? w.leafc : nullptr;
-    if (int rc = launch_attention(w.big, w.h, B, c.L, c.t->heads, c.causal, 1, c.st)) return rc;
+    if (int rc = launch_attention(w.big, w.h, B, c.L, c.t->heads, c.causal, ATTN_DEFAULT, c.st)) return rc;
     if (int rc = launch_gather_rows(w.x3, w.x3c, B, c.L, resid_row_bytes(W), c.st)) return rc;
     GemmArgs out = linear(w.h, (size_t)c.L * W * 2, lw.out_w, lw.out_b, B, W, W, nullptr);
     out.x3 = w.x3c; out.ln_part = w.partc; out.ln_leaf = leaf; out.tmp_f32 = w.x;
@@ -235,7 +235,7 @@ int blocks_ln(const Blocks& c, Resid& r) {
         // (bench probe, mode 2: attention's own end stamp, so that out_proj gets a completion-to-completion time too)
         hipEvent_t* aev = nullptr;
         if (c.probe && c.probe->mode == 2 && c.probe->n < GemmProbe::MAX) aev = &c.probe->ev[2 * c.probe->begin(GemmProbe::EPI_ATTENTION, 2, c.st, 0)];
-        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st, nullptr, nullptr, nullptr, aev)) return rc;
+        if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, ATTN_DEFAULT, c.st, nullptr, nullptr, nullptr, aev)) return rc;
         GemmArgs out = linear(w.h, 0, lw.out_w, lw.out_b, M, W, W, nullptr);
         out.x3 = w.x3; out.ln_part = w.ln_part; out.ln_leaf = leaf; out.tmp_f32 = w.x;
         if (int rc = launch_gemm_algo(out, EPI_BIAS_RESID_LN_F32, 0, c.st, c.probe)) return rc;
@@ -257,7 +257,7 @@ bool fp8_fuse_off() { static const bool off = dev_knob("CLIPMI_FP8_FUSE", 1) == 
 // attention -> e4m3 rows w.a8 + block scales w.a_bs
 int attention_fp8(const Blocks& c, const Ws& w) {
     bool fused = false;
-    if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, 1, c.st, fp8_fuse_off() ? nullptr : w.a8, w.a_bs, &fused)) return rc;
+    if (int rc = launch_attention(w.big, w.h, c.B, c.L, c.t->heads, c.causal, ATTN_DEFAULT, c.st, fp8_fuse_off() ? nullptr : w.a8, w.a_bs, &fused)) return rc;
     return fused ? 0 : launch_quantize_rows_fp8mx(w.h, w.a8, w.a_bs, c.M, c.W, c.st);
 }
 // c_fc (`fc`, into w.big) -> e4m3 QuickGELU rows *h8 + block scales w.a_bs; mx_out: the GEMM writes them itself, into the bf16 buffer's bytes

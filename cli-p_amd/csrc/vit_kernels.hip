@@ -1,5 +1,6 @@
 // vit_kernels.hip — launchers for the non-GEMM tower kernels and their debug entry points.
 #include "vit_kernels.hpp"
+#include "attention.hpp"
 #include <hip/hip_ext.h>
 #include <cstdlib>
 
@@ -35,7 +36,7 @@ static int launch_attn_t(const unsigned short* qkv, unsigned short* out, int B, 
     return 0;
 }
 
-int launch_attention(const unsigned short* qkv, unsigned short* out, int B, int L, int heads, int causal, int tr,
+int launch_attention(const unsigned short* qkv, unsigned short* out, int B, int L, int heads, int causal, AttnForm form,
                      hipStream_t st, unsigned char* out8, unsigned char* out_bs, bool* fused, hipEvent_t* probe_ev) {
     if (fused) *fused = false;
     if (B < 1) return 0;
@@ -52,37 +53,35 @@ int launch_attention(const unsigned short* qkv, unsigned short* out, int B, int 
         CLIPMI_CHECK_LAUNCH("attention_flash_kernel");
         return 0;
     }
-    const int nt = (L + 15) / 16;
-    // development switch for A/B runs on one box: CLIPMI_ATTN52=0 keeps ViT-B/32 on attention_kernel<4>
-    // (CLIPMI_ATTN52: 0 = attention_kernel<4>, 1 = attention52_kernel, default 2 = attention52x4_kernel)
-    static const int use52 = (int)dev_knob("CLIPMI_ATTN52", 2);
-    if (L >= 49 && L <= 52 && !causal && tr == 1 && use52 == 2) {
+    const long long items = (long long)B * heads;
+    const bool vitb32 = L >= 49 && L <= 52 && !causal;
+    if (vitb32 && form == ATTN_DEFAULT) {
         // one workgroup per (image, head), one query tile per wave
-        const long long items = (long long)B * heads;
         const long long resident = (long long)NUM_CU * 5;               // 5 workgroups (20 waves, <= 96 VGPRs) per CU
+        const dim3 grid((unsigned)(items < resident ? items : resident));
+        const size_t lds = 64 * 128 + 52 * 128;
+        unsigned char* const none = nullptr;
         if (out8 && out_bs && fused) {
-            hipLaunchKernelGGL(attention52x4_kernel<true>, dim3((unsigned)(items < resident ? items : resident)), dim3(256),
-                               64 * 128 + 52 * 128, st, qkv, out, B, L, heads, out8, out_bs);
+            hipLaunchKernelGGL(attention52x4_kernel<true>, grid, dim3(256), lds, st, qkv, out, B, L, heads, out8, out_bs);
             *fused = true;
         } else if (probe_ev) {
-            hipExtLaunchKernelGGL(attention52x4_kernel<false>, dim3((unsigned)(items < resident ? items : resident)), dim3(256),
-                                  64 * 128 + 52 * 128, st, probe_ev[0], probe_ev[1], 0, qkv, out, B, L, heads, (unsigned char*)nullptr,
-                                  (unsigned char*)nullptr);
+            hipExtLaunchKernelGGL(attention52x4_kernel<false>, grid, dim3(256), lds, st, probe_ev[0], probe_ev[1], 0, qkv, out, B, L,
+                                  heads, none, none);
         } else {
-            hipLaunchKernelGGL(attention52x4_kernel<false>, dim3((unsigned)(items < resident ? items : resident)), dim3(256),
-                               64 * 128 + 52 * 128, st, qkv, out, B, L, heads, (unsigned char*)nullptr, (unsigned char*)nullptr);
+            hipLaunchKernelGGL(attention52x4_kernel<false>, grid, dim3(256), lds, st, qkv, out, B, L, heads, none, none);
         }
         CLIPMI_CHECK_LAUNCH("attention52x4_kernel");
         return 0;
     }
-    if (L >= 49 && L <= 52 && !causal && tr && use52) {
-        // ViT-B/32: the low-register form (24 waves per CU); tr = 0 keeps the plain-read reference kernel for tests
-        const long long items = (long long)B * heads;
+    if (vitb32 && form == ATTN_ONE_WAVE) {
+        // the low-register one-wave form (24 waves per CU)
         const size_t lds = 4 * 52 * 128;
         hipLaunchKernelGGL(attention52_kernel, dim3((unsigned)((items + 3) / 4)), dim3(256), lds, st, qkv, out, B, L, heads);
         CLIPMI_CHECK_LAUNCH("attention52_kernel");
         return 0;
     }
+    const int nt = (L + 15) / 16;
+    const bool tr = form != ATTN_PLAIN_READS;
 #define ATT(NT_)                                                                                         \
     if (nt <= NT_) {                                                                                     \
         if (causal) return tr ? launch_attn_t<NT_, true, true>(qkv, out, B, L, heads, st)                \
@@ -150,7 +149,8 @@ extern "C" int clipmi_dbg_attention(const void* qkv_dev, void* out_dev, int B, i
                                     void* stream) {
     if (!qkv_dev || !out_dev) return set_err(CLIPMI_EINVAL, "dbg_attention: NULL pointer");
     return launch_attention(static_cast<const unsigned short*>(qkv_dev), static_cast<unsigned short*>(out_dev), B, L,
-                            heads, causal & 1, (causal & 2) ? 0 : ((causal & 4) ? 2 : 1), as_stream(stream));
+                            heads, causal & 1, (causal & 2) ? ATTN_PLAIN_READS : ((causal & 4) ? ATTN_ONE_WAVE : ATTN_DEFAULT),
+                            as_stream(stream));
 }
 
 extern "C" int clipmi_dbg_quantize_rows_fp8(const void* in_bf16_dev, void* out_fp8_dev, float* scale_dev, int M, int K,

@@ -3,6 +3,11 @@ against plain torch fp32 references of the same op computed on the SAME bf16-rou
 the only differences are accumulation order and the kernel's own output rounding.
 Tolerances: f32 outputs 2e-4 relative to the output scale (f32 accumulation over K <= 3072);
 bf16 outputs one bf16 ulp (2^-8 relative) on top of that."""
+import hashlib
+import json
+import os
+import re
+
 import pytest
 import torch
 
@@ -152,15 +157,52 @@ def test_attention52_forms_are_bit_identical(clipmi, gpu, B, L, heads):
     W = heads * 64
     qd = _bf16(torch.randn(B * L, 3 * W, generator=g) * 1.5).to(gpu)
     outs = []
-    for flags in (0, 4):
+    for flags in (0, 4, 2):           # flags 2: attention_kernel<4, false, false> (the generic kernel, 2-byte V reads)
         out = torch.full((B * L, W), float("nan"), dtype=torch.bfloat16, device=gpu)
         clipmi._lib.check(Lb.clipmi_dbg_attention(qd.data_ptr(), out.data_ptr(), B, L, heads, flags, None), "attn")
         torch.cuda.synchronize()
         outs.append(out)
     assert torch.isfinite(outs[0].float()).all() and torch.equal(outs[0], outs[1])
+    assert torch.equal(outs[0], outs[2])
     if B <= 257:
         ref = _attn_ref(qd.cpu(), B, L, heads, 0)
         assert (outs[0].float().cpu() - ref).abs().max().item() <= 3 * (2.0 ** -8) * ref.abs().max().item()
+
+
+def attention_digest_cases():
+    """(B, L, heads, flags) of tests/golden/attention_parent.json: the smallest shapes that reach every attention instantiation
+    (NT = 1, 2, 4, 5 with and without the causal mask, transposed and 2-byte V reads; the three ViT-B/32 forms; the flash
+    kernel) and every edge (L below, at and one past a tile; one key block, one past it, a masked last block; more items than
+    the ViT-B/32 grid: 3 084 against 1 280, so that the item loop, its prefetch and its last-item exit run)."""
+    short = [(3, 5, 2, 0), (4, 16, 2, 1), (2, 17, 2, 0), (2, 32, 3, 1), (7, 33, 3, 0), (1, 64, 12, 0), (2, 77, 8, 1), (2, 80, 8, 1)]
+    cases = short + [(B, L, h, f | 2) for B, L, h, f in short]
+    cases += [(B, L, h, f) for B, L, h in ((5, 49, 2), (3, 50, 12), (2, 52, 3)) for f in (0, 2, 4)]
+    cases += [(257, 50, 12, 0), (257, 50, 12, 4)]
+    cases += [(3, 81, 2, 0), (1, 128, 1, 0), (1, 129, 3, 0), (2, 197, 12, 0), (1, 257, 16, 0)]
+    return cases
+
+
+def attention_digest(clipmi, gpu, B, L, heads, flags):
+    """SHA-256 of clipmi_dbg_attention's output bytes for test_attention's inputs (seed B * 100 + L)."""
+    g = torch.Generator(device="cpu"); g.manual_seed(B * 100 + L)
+    W = heads * 64
+    qd = _bf16(torch.randn(B * L, 3 * W, generator=g) * 1.5).to(gpu)
+    out = torch.full((B * L, W), float("nan"), dtype=torch.bfloat16, device=gpu)
+    clipmi._lib.check(clipmi._lib.lib().clipmi_dbg_attention(qd.data_ptr(), out.data_ptr(), B, L, heads, flags, None), "attn")
+    torch.cuda.synchronize()
+    return hashlib.sha256(out.view(torch.int16).cpu().numpy().tobytes()).hexdigest()
+
+
+def test_attention_bits_of_the_parent_commit(clipmi, gpu):
+    """tests/golden/attention_parent.json: digests of the attention kernels' output, recorded on an MI355X from a build of the
+    commit BEFORE the kernels were put together from shared pieces (csrc/attention.hpp). Every one reproduces: the kernels
+    compute the bits they computed then. A digest that differs is a change of behaviour, not a reason to record again."""
+    gold = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "attention_parent.json")))
+    assert re.fullmatch(r"[0-9a-f]{40}", gold["commit"]), "the file names the commit it was recorded at"
+    want = {tuple(c[:4]): c[4] for c in gold["cases"]}
+    assert sorted(want) == sorted(attention_digest_cases())
+    bad = [(c, d) for c in attention_digest_cases() if (d := attention_digest(clipmi, gpu, *c)) != want[c]]
+    assert not bad, f"digests differ from commit {gold['commit'][:7]}: {bad}"
 
 
 @pytest.mark.parametrize("B,L,heads", [(2, 197, 12), (1, 257, 16), (2, 577, 16), (3, 81, 2), (1, 128, 1), (1, 129, 3)])
