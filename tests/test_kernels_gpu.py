@@ -504,6 +504,13 @@ def test_gemm_resid_ln_producer(clipmi, gpu, M, N, K):
     assert torch.equal(hi3, new.to(torch.bfloat16)) or (hi3.float() - new).abs().max().item() <= 2.0 ** -8 * new.abs().max().item()
     xs = new.double().reshape(M, N // 256, 256)
     assert (part3[..., 0].double() - xs.sum(-1)).abs().max().item() <= 1e-4 * xs.abs().sum(-1).max().item()
+    # the sums of squares are taken of the f32 rows BEFORE they are split (as split_stats takes them: _check_split's rule), so
+    # their reference is the float64 value of those rows, not the 15-bit rows read back
+    x64 = (a.double() @ w.double().t() + bias.double() + xold.double()).reshape(M, N // 256, 256)
+    q64 = (x64 * x64).sum(-1)
+    qerr = ((part3[..., 1].double() - q64) / q64).abs().max().item()
+    print(f"M={M} N={N} K={K}: sums of squares, worst relative error {qerr}")
+    assert qerr <= 3e-6
     for algo in (0, 1, 2):
         for got, want, what in zip(res[algo], res[3], ("split rows", "part")):
             assert torch.equal(got, want), f"algo {algo} vs the fused store pass: {what} differs"
