@@ -30,6 +30,7 @@ SYMBOLS = [
     "clipmi_dbg_encode_image_probe_ms", "clipmi_dbg_encode_image_probe3_ms",
     "clipmi_dbg_split_stats", "clipmi_dbg_gemm_ln", "clipmi_dbg_gemm_resid_ln", "clipmi_dbg_gemm_resid_ln_leaf", "clipmi_dbg_gemm_ln_leaf", "clipmi_dbg_quantize_rows_fp8mx", "clipmi_dbg_gemm_fp8_bsa",
     "clipmi_dbg_embed_image", "clipmi_dbg_embed_text", "clipmi_dbg_gemm_plan", "clipmi_dbg_gemm_fp8_plan",
+    "clipmi_dbg_attention_fp8mx",
 ]
 
 
@@ -182,6 +183,8 @@ def lib():
     L.clipmi_dbg_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
     L.clipmi_dbg_attention.restype = i32
     L.clipmi_dbg_attention.argtypes = [vp, vp, i32, i32, i32, i32, vp]
+    L.clipmi_dbg_attention_fp8mx.restype = i32
+    L.clipmi_dbg_attention_fp8mx.argtypes = [vp, vp, vp, vp, i32, i32, i32, C.POINTER(C.c_int), vp]
     L.clipmi_dbg_embed_image.restype = i32
     L.clipmi_dbg_embed_image.argtypes = [TP, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz, vp]
     L.clipmi_dbg_embed_text.restype = i32

@@ -153,6 +153,20 @@ extern "C" int clipmi_dbg_attention(const void* qkv_dev, void* out_dev, int B, i
                             as_stream(stream));
 }
 
+// launch_attention as the FP8 towers call it (ATTN_DEFAULT, no mask, with out8 / out_bs): *fused reports whether the shape's
+// kernel wrote e4m3 rows + MX block scales (then out_bf16_dev is not written) or bf16 rows as always
+extern "C" int clipmi_dbg_attention_fp8mx(const void* qkv_dev, void* out_bf16_dev, void* out_fp8_dev, void* bscale_dev, int B,
+                                          int L, int heads, int* fused, void* stream) {
+    if (!qkv_dev || !out_bf16_dev || !out_fp8_dev || !bscale_dev || !fused)
+        return set_err(CLIPMI_EINVAL, "dbg_attention_fp8mx: NULL pointer");
+    bool f = false;
+    const int rc = launch_attention(static_cast<const unsigned short*>(qkv_dev), static_cast<unsigned short*>(out_bf16_dev), B, L,
+                                    heads, 0, ATTN_DEFAULT, as_stream(stream), static_cast<unsigned char*>(out_fp8_dev),
+                                    static_cast<unsigned char*>(bscale_dev), &f);
+    *fused = f ? 1 : 0;
+    return rc;
+}
+
 extern "C" int clipmi_dbg_quantize_rows_fp8(const void* in_bf16_dev, void* out_fp8_dev, float* scale_dev, int M, int K,
                                             void* stream) {
     return launch_quantize_rows_fp8(static_cast<const unsigned short*>(in_bf16_dev), static_cast<unsigned char*>(out_fp8_dev),

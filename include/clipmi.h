@@ -454,6 +454,13 @@ int clipmi_dbg_layernorm(const float* x_dev, const float* w_dev, const float* b_
 /* qkv bf16 [B*L][3W] -> softmax(q k^T / 8 (+causal)) v -> bf16 [B*L][W], head dim 64 */
 int clipmi_dbg_attention(const void* qkv_dev, void* out_dev, int B, int L, int heads,
                          int causal, void* stream);
+/* The same attention (no mask) as the FP8 towers launch it, with the fused output stage where the shape's kernel has one
+ * (49 <= L <= 52): *fused = 1 and the rows leave as e4m3 [B*L][W] + MX scale bytes [B*L][W / 32] - the bytes
+ * clipmi_dbg_quantize_rows_fp8mx makes of clipmi_dbg_attention's rows - and out_bf16_dev is not written; otherwise *fused = 0,
+ * bf16 rows in out_bf16_dev and the other two untouched. (An addition to ABI 8 in the sense of the note above: nothing
+ * existing changes, CLIPMI_ABI_VERSION stays 8.) */
+int clipmi_dbg_attention_fp8mx(const void* qkv_dev, void* out_bf16_dev, void* out_fp8_dev, void* bscale_dev, int B, int L,
+                               int heads, int* fused, void* stream);
 
 /* clipmi_topk_ip's launch sequence `reps` times with HIP events around the MAIN scan kernel on
  * `stream`; synchronises; *scan_ms = average duration of that kernel (bench.py roofline). Q <= 16 */
