@@ -52,6 +52,15 @@ constexpr long long dev_knob(const char*, long long dflt) { return dflt; }
 int launch_resize_v_rgb8(const void* jobs_dev, int njobs, const int32_t* coef_dev, int n_px, const void* scratch_dev, void* out_dev,
                          hipStream_t st);
 
+// Pillow's fixed point for resampling (Resample.c PRECISION_BITS = 32 - 8 - 2): a sum starts at 1 << (RZ_PREC - 1) and is clipped
+// to 8 bits here. For resize.hip's passes and for jpeg.hip's fused horizontal pass, which runs in front of launch_resize_v_rgb8.
+constexpr int RZ_PREC = 22;
+
+__device__ __forceinline__ unsigned char rz_clip8(int v) {
+    v >>= RZ_PREC;
+    return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
+}
+
 constexpr int NUM_CU = 256;           // MI355X
 constexpr int LDS_BYTES = 160 * 1024; // per CU
 

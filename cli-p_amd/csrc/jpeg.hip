@@ -6,8 +6,10 @@
 // Pillow itself; oracle/jpeg_oracle.py is the CPU restatement, pinned against Pillow in tests/test_jpeg.py).
 // Everything else (CMYK, ...) stays with Pillow in the decode workers; PNG files have png.hip.
 //
-// Kernels, one batch of images per call:
+// Kernels, one batch of images per call (every kernel takes an image's block and plane layout from jpeg_geom):
+//   jpeg_unstuff_kernel      the 0x00 behind every 0xFF removed in place, for segments the host hands over as they are in the file
 //   jpeg_build_luts_kernel   canonical Huffman codes of the batch's distinct DHT tables -> 10-bit look-up + slow-path arrays
+//                            (jpeg_build_pluts_kernel: the progressive form of the entries; one builder, jp_build_lut)
 //   jpeg_huffman_kernel      the entropy-coded segment -> int16 coefficients (DC still differential). Huffman decoding is a
 //                            serial chain (a symbol's first bit is known only when the previous symbol has been decoded);
 //                            a workgroup owns an image and decodes it in 1024-bit SUBSEQUENCES, one per thread: every thread
@@ -25,10 +27,14 @@
 //   jpeg_idct_kernel         jidctint.c's jpeg_idct_islow with the dequantisation folded in, one block per thread; a block
 //                            outside the range where libjpeg-turbo's IDCT provably equals it is reported (status 4)
 //   jpeg_color_kernel        jdsample.c's fancy (triangle) upsampling with jdmainct.c's edge rows + jdcolor.c's
-//                            16-bit fixed-point YCbCr -> RGB; rows of width*3 bytes, as Pillow's array
+//                            16-bit fixed-point YCbCr -> RGB (jp_pixel); rows of width*3 bytes, as Pillow's array
 //   jpeg_color_resize_h_kernel   the transform entries' form of the last step: the same upsampling and colour conversion fused with
 //                            Pillow's horizontal resampling pass (resize.hip's resize_h_kernel), over the rows and columns the
 //                            transform's window needs only - the full-size RGB rows are never written
+//   jpeg_progressive_kernel  progressive files: every scan of an image applied to its coefficients, in place of
+//                            jpeg_huffman_kernel and jpeg_dc_kernel; jpeg_idct_kernel and the colour kernels follow as above
+#include <type_traits>
+
 #include "common.hpp"
 
 namespace clipmi {
@@ -45,6 +51,50 @@ struct JpegImage {             // mirrors clipmi_jpeg_image (include/clipmi.h)
     int stuffed, reserved;
     unsigned char quant[3][64];
 };
+
+// An image's blocks and planes. Coefficients (int16 [64] per block, from coef_all + coef_off * 64) come in scan order: MCU
+// after MCU, each the hv luma blocks, then Cb, Cr. Planes of an image (bytes from planes + coef_off * 64):
+// Y [my vs 8][mx hs 8], then Cb, Cr [my 8][mx 8]
+struct JpegGeom {
+    int W, H;
+    int hs, vs;                    // luma sampling factors (grey: 1, whatever the file says); chroma is 1 x 1
+    int hv, bpm;                   // luma blocks, all blocks per MCU
+    int mx, my;                    // MCUs per row, per column
+    long long nmcu;                // mx my
+    int yw, cw;                    // bytes per row of the luma plane, of a chroma plane
+    int dw, dh;                    // chroma columns, rows under the image at 2 x sampling (fancy upsampling's edges)
+    int mode;                      // chroma upsampling: 0 1x1 (copy), 1 h2v1, 2 h2v2
+    bool color;
+    const unsigned char* py;       // the planes: luma, Cb and Cr (only from jpeg_geom with the planes' base)
+    const unsigned char* pc[2];
+    // bytes from the luma plane to the plane of component c = 1 (Cb), 2 (Cr)
+    __device__ __forceinline__ long long plane_off(int c) const { return (long long)mx * my * hv * 64 + (long long)(c - 1) * mx * my * 64; }
+};
+
+// (The record by pointer, and the sampling factors read behind the test for grey, as the kernels did before they shared this: a
+// reference parameter lets the compiler load every field up front, which cost jpeg_huffman_kernel a VGPR and two spilled SGPRs.)
+__device__ __forceinline__ JpegGeom jpeg_geom(const JpegImage* im, const unsigned char* planes = nullptr) {
+    JpegGeom g;
+    g.color = im->ncomp != 1;
+    g.hs = im->ncomp == 1 ? 1 : im->hs;
+    g.vs = im->ncomp == 1 ? 1 : im->vs;
+    g.hv = g.hs * g.vs;
+    g.bpm = im->ncomp == 1 ? 1 : g.hv + 2;
+    g.W = im->width;
+    g.H = im->height;
+    g.mx = (g.W + 8 * g.hs - 1) / (8 * g.hs);
+    g.my = (g.H + 8 * g.vs - 1) / (8 * g.vs);
+    g.nmcu = (long long)g.mx * g.my;
+    g.yw = g.mx * g.hs * 8;
+    g.cw = g.mx * 8;
+    g.dw = (g.W + 1) >> 1;
+    g.dh = (g.H + 1) >> 1;
+    g.mode = g.hs == 1 ? 0 : (g.vs == 1 ? 1 : 2);
+    g.py = planes + im->coef_off * 64;
+    g.pc[0] = g.py + g.plane_off(1);
+    g.pc[1] = g.py + g.plane_off(2);
+    return g;
+}
 
 constexpr int JP_T = 128;          // threads per workgroup = subsequences per chunk: ONE wave (waves that walk serial chains
                                    // must not share a SIMD: 870 two-wave workgroups ran 3.2 x slower than one)
@@ -152,13 +202,21 @@ __global__ void __launch_bounds__(256) jpeg_unstuff_kernel(unsigned char* __rest
     }
 }
 
-__global__ void __launch_bounds__(256) jpeg_build_luts_kernel(const unsigned char* __restrict__ raw, JpLut* __restrict__ luts) {
+// The canonical codes of one raw DHT table (jdhuff.c jpeg_make_d_derived_tbl) into a look-up table, by one workgroup of 256:
+// thread 0 walks the code lengths, then a thread per symbol fills the entries its code is a prefix of. The table types share
+// `fast`, maxcode, valoff and vals; per type: the entry's encoding (jp_lut_entry) and JpLut's second level with its `covered`.
+__device__ __forceinline__ unsigned short jp_lut_entry(const JpLut&, unsigned sym, unsigned len, bool ac) {
+    return (unsigned short)jp_entry(sym, len, ac);
+}
+
+template <class Lut>
+__device__ __forceinline__ void jp_build_lut(const unsigned char* __restrict__ t, Lut& L) {
+    constexpr bool LONG = std::is_same<Lut, JpLut>::value;
     __shared__ int first_code[18], first_idx[18];
-    const unsigned char* t = raw + (size_t)blockIdx.x * JP_RAW;
-    JpLut& L = luts[blockIdx.x];
     const int tid = threadIdx.x;
     for (int i = tid; i < (1 << JP_FAST); i += 256) L.fast[i] = 0;
-    for (int i = tid; i < (JP_LONG << (16 - JP_FAST)); i += 256) L.second[i] = 0;
+    if constexpr (LONG)
+        for (int i = tid; i < (JP_LONG << (16 - JP_FAST)); i += 256) L.second[i] = 0;
     if (tid == 0) {
         int code = 0, k = 0, covered = 1;
         for (int l = 1; l <= 16; ++l) {
@@ -174,7 +232,7 @@ __global__ void __launch_bounds__(256) jpeg_build_luts_kernel(const unsigned cha
         first_idx[17] = k > 256 ? 256 : k;
         L.maxcode[0] = L.maxcode[17] = -1;
         L.valoff[0] = L.valoff[17] = 0;
-        L.covered = covered;
+        if constexpr (LONG) L.covered = covered;
     }
     L.vals[tid] = t[16 + tid];
     __syncthreads();
@@ -182,19 +240,25 @@ __global__ void __launch_bounds__(256) jpeg_build_luts_kernel(const unsigned cha
         int l = 1;
         while (l < 16 && tid >= first_idx[l + 1]) ++l;
         const int code = first_code[l] + (tid - first_idx[l]);
-        const unsigned short e = (unsigned short)jp_entry(t[16 + tid], (unsigned)l, t[272] != 0);
+        const unsigned short e = jp_lut_entry(L, t[16 + tid], (unsigned)l, t[272] != 0);
         if (l <= JP_FAST && code < (1 << l)) {
             const int base = code << (JP_FAST - l);
             for (int j = 0; j < (1 << (JP_FAST - l)); ++j) L.fast[base + j] = e;
-        } else if (l > JP_FAST && code < (1 << l)) {
-            const int v16 = code << (16 - l);
-            const int pre = (v16 >> (16 - JP_FAST)) - ((1 << JP_FAST) - JP_LONG);
-            if (pre >= 0) {
-                const int base = (pre << (16 - JP_FAST)) + (v16 & ((1 << (16 - JP_FAST)) - 1));
-                for (int j = 0; j < (1 << (16 - l)); ++j) L.second[base + j] = e;
+        } else if constexpr (LONG) {
+            if (l > JP_FAST && code < (1 << l)) {
+                const int v16 = code << (16 - l);
+                const int pre = (v16 >> (16 - JP_FAST)) - ((1 << JP_FAST) - JP_LONG);
+                if (pre >= 0) {
+                    const int base = (pre << (16 - JP_FAST)) + (v16 & ((1 << (16 - JP_FAST)) - 1));
+                    for (int j = 0; j < (1 << (16 - l)); ++j) L.second[base + j] = e;
+                }
             }
         }
     }
+}
+
+__global__ void __launch_bounds__(256) jpeg_build_luts_kernel(const unsigned char* __restrict__ raw, JpLut* __restrict__ luts) {
+    jp_build_lut(raw + (size_t)blockIdx.x * JP_RAW, luts[blockIdx.x]);
 }
 
 struct JpState {
@@ -376,11 +440,9 @@ __global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char*
     __shared__ JpShared sh;
     const JpegImage& im = images[blockIdx.x];
     const int tid = threadIdx.x;
-    const int hv = im.ncomp == 1 ? 1 : im.hs * im.vs;
-    const int bpm = im.ncomp == 1 ? 1 : hv + 2;
-    const long long mx = (im.width + 8 * (im.ncomp == 1 ? 1 : im.hs) - 1) / (8 * (im.ncomp == 1 ? 1 : im.hs));
-    const long long my = (im.height + 8 * (im.ncomp == 1 ? 1 : im.vs) - 1) / (8 * (im.ncomp == 1 ? 1 : im.vs));
-    const long long total = mx * my * bpm;
+    const JpegGeom g = jpeg_geom(&im);
+    const int hv = g.hv, bpm = g.bpm;
+    const long long nmcu = g.nmcu, total = nmcu * bpm;
     const unsigned nbits = (unsigned)im.stream_bytes * 8u;
     short* coef = coef_all + im.coef_off * 64;
     const unsigned* src = reinterpret_cast<const unsigned*>(streams + im.stream_off);
@@ -411,7 +473,7 @@ __global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char*
         if (tid == 0) sh.first[0] = 0;
         __syncthreads();
         const unsigned* offs = reinterpret_cast<const unsigned*>(streams + im.intervals_off);
-        const long long nmcu = mx * my, ri = im.restart_interval;
+        const long long ri = im.restart_interval;
         for (int k = tid; k < im.n_intervals; k += JP_T) {
             unsigned p = offs[k] * 8u, bz = 0;
             const unsigned end = (k + 1 < im.n_intervals ? offs[k + 1] : (unsigned)im.stream_bytes) * 8u;
@@ -544,9 +606,9 @@ __global__ void __launch_bounds__(256) jpeg_dc_kernel(const JpegImage* __restric
     __shared__ int part[3][256];
     const JpegImage& im = images[blockIdx.x];
     const int tid = threadIdx.x;
-    const int hs = im.ncomp == 1 ? 1 : im.hs, vs = im.ncomp == 1 ? 1 : im.vs;
-    const int hv = hs * vs, bpm = im.ncomp == 1 ? 1 : hv + 2;
-    const long long nmcu = (long long)((im.width + 8 * hs - 1) / (8 * hs)) * ((im.height + 8 * vs - 1) / (8 * vs));
+    const JpegGeom g = jpeg_geom(&im);
+    const int hv = g.hv, bpm = g.bpm;
+    const long long nmcu = g.nmcu;
     const long long per = (nmcu + 255) / 256;
     const long long m0 = per * tid, m1 = m0 + per < nmcu ? m0 + per : nmcu;
     short* coef = coef_all + im.coef_off * 64;
@@ -623,8 +685,6 @@ __device__ __forceinline__ void jp_idct8(const int* v, int stride, int* o, int o
     o[4 * ostride] = (t13 - o0 + R) >> SHIFT;
 }
 
-// planes of an image (bytes from planes + coef_off * 64): Y [my vs 8][mx hs 8], then Cb, Cr [my 8][mx 8]
-//
 // Status 4: a block outside the range where Pillow's IDCT provably equals this one. libjpeg-turbo runs jpeg_idct_islow in one of
 // two forms, chosen by the CPU it runs on, and both equal int32 arithmetic + a clamp to [0, 255] only on a bounded range:
 //   * SIMD (jidctint-sse2 / -avx2): the dequantisation is a 16-bit multiply (pmullw: the low 16 bits), the pass-1 outputs are
@@ -643,27 +703,25 @@ __device__ __forceinline__ void jp_idct8(const int* v, int stride, int* o, int o
 __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restrict__ images, const short* __restrict__ coef_all,
                                                         unsigned char* __restrict__ planes, int* __restrict__ status) {
     const JpegImage& im = images[blockIdx.y];
-    const int hs = im.ncomp == 1 ? 1 : im.hs, vs = im.ncomp == 1 ? 1 : im.vs;
-    const int hv = hs * vs, bpm = im.ncomp == 1 ? 1 : hv + 2;
-    const int mx = (im.width + 8 * hs - 1) / (8 * hs), my = (im.height + 8 * vs - 1) / (8 * vs);
+    const JpegGeom g = jpeg_geom(&im, planes);
+    const int hs = g.hs, vs = g.vs, hv = g.hv, bpm = g.bpm, mx = g.mx;
     const long long b = (long long)blockIdx.x * 128 + threadIdx.x;
-    if (b >= (long long)mx * my * bpm) return;
+    if (b >= g.nmcu * bpm) return;
     const long long mcu = b / bpm;
     const int k = (int)(b - mcu * bpm);
     const int comp = k < hv ? 0 : k - hv + 1;
     const int mcx = (int)(mcu % mx), mcy = (int)(mcu / mx);
     int bx, by, pw;
-    unsigned char* plane = planes + im.coef_off * 64;
-    const long long ysize = (long long)mx * my * hv * 64;
+    unsigned char* plane = const_cast<unsigned char*>(g.py);    // (this kernel writes the planes the others read)
     if (comp == 0) {
         bx = mcx * hs + k % hs;
         by = mcy * vs + k / hs;
-        pw = mx * hs * 8;
+        pw = g.yw;
     } else {
         bx = mcx;
         by = mcy;
-        pw = mx * 8;
-        plane += ysize + (long long)(comp - 1) * mx * my * 64;
+        pw = g.cw;
+        plane += g.plane_off(comp);
     }
     const uint4* cp = reinterpret_cast<const uint4*>(coef_all + (im.coef_off + b) * 64);
     int x[64], ws[64];
@@ -702,60 +760,72 @@ __global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restr
     if (((out16 >> 16) | (out10 >> 10)) && status[blockIdx.y] == 0) status[blockIdx.y] = 4;     // (the first error found stands)
 }
 
-__global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __restrict__ images, const unsigned char* __restrict__ planes,
-                                                         unsigned char* __restrict__ out) {
-    const JpegImage& im = images[blockIdx.y];
-    const int W = im.width, H = im.height;
-    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (idx >= (long long)W * H) return;
-    const int y = (int)(idx / W), x = (int)(idx - (long long)y * W);
-    const int hs = im.ncomp == 1 ? 1 : im.hs, vs = im.ncomp == 1 ? 1 : im.vs;
-    const int mx = (W + 8 * hs - 1) / (8 * hs), my = (H + 8 * vs - 1) / (8 * vs);
-    const unsigned char* py = planes + im.coef_off * 64;
-    const int yw = mx * hs * 8;
-    const int Y = py[(size_t)y * yw + x];
-    unsigned char* o = out + im.out_off + ((size_t)y * W + x) * 3;
-    if (im.ncomp == 1) {
-        o[0] = o[1] = o[2] = (unsigned char)Y;
-        return;
-    }
-    const int cw = mx * 8;
-    const unsigned char* pc[2];
-    pc[0] = py + (size_t)mx * my * hs * vs * 64;
-    pc[1] = pc[0] + (size_t)mx * my * 64;
-    int cc[2];
-    if (hs == 1) {
-        for (int c = 0; c < 2; ++c) cc[c] = pc[c][(size_t)y * cw + x];
-    } else {
-        const int dw = (W + 1) >> 1;
-        const int cx = x >> 1;
-        if (vs == 1) {                          // h2v1_fancy_upsample
-            for (int c = 0; c < 2; ++c) {
-                const unsigned char* r = pc[c] + (size_t)y * cw;
-                const int p = r[cx];
-                if (x & 1) cc[c] = cx == dw - 1 ? p : (3 * p + r[cx + 1] + 2) >> 2;
-                else cc[c] = cx == 0 ? p : (3 * p + r[cx - 1] + 1) >> 2;
-            }
-        } else {                                // h2v2_fancy_upsample, context rows duplicated at the image's edges
-            const int dh = (H + 1) >> 1;
-            const int cy = y >> 1;
-            const int oy = (y & 1) ? (cy + 1 < dh ? cy + 1 : dh - 1) : (cy > 0 ? cy - 1 : 0);
-            for (int c = 0; c < 2; ++c) {
-                const unsigned char* r0 = pc[c] + (size_t)cy * cw;
-                const unsigned char* r1 = pc[c] + (size_t)oy * cw;
-                const int s = 3 * r0[cx] + r1[cx];
-                if (x & 1) cc[c] = cx == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * r0[cx + 1] + r1[cx + 1] + 7) >> 4;
-                else cc[c] = cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * r0[cx - 1] + r1[cx - 1] + 8) >> 4;
-            }
-        }
-    }
-    const int cb = cc[0] - 128, cr = cc[1] - 128;             // jdcolor.c build_ycc_rgb_table: FIX(1.402), FIX(0.34414), ...
+// ---- A pixel from the planes: the file's one statement of jdsample.c's fancy (triangle) upsampling, with jdmainct.c's context
+// rows duplicated at the image's edges, and of jdcolor.c's 16-bit fixed-point YCbCr -> RGB. jpeg_color_kernel and the transform
+// entries' jpeg_color_resize_h_kernel both compute their pixels here, so the two paths cannot drift apart.
+__device__ __forceinline__ unsigned jp_rgb(int Y, int cbs, int crs) {          // -> R | G << 8 | B << 16
+    const int cb = cbs - 128, cr = crs - 128;             // jdcolor.c build_ycc_rgb_table: FIX(1.402), FIX(0.34414), ...
     int r = Y + ((91881 * cr + 32768) >> 16);
     int g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
     int b = Y + ((116130 * cb + 32768) >> 16);
-    o[0] = (unsigned char)(r < 0 ? 0 : (r > 255 ? 255 : r));
-    o[1] = (unsigned char)(g < 0 ? 0 : (g > 255 ? 255 : g));
-    o[2] = (unsigned char)(b < 0 ? 0 : (b > 255 ? 255 : b));
+    r = r < 0 ? 0 : (r > 255 ? 255 : r);
+    g = g < 0 ? 0 : (g > 255 ? 255 : g);
+    b = b < 0 ? 0 : (b > 255 ? 255 : b);
+    return (unsigned)r | ((unsigned)g << 8) | ((unsigned)b << 16);
+}
+
+// The chroma sample of source column x: r0 = the chroma row of the pixel's own row, r1 = the context row (2x2 only), both indexed
+// by chroma column - `off`. mode (JpegGeom): 0 copy, 1 h2v1_fancy_upsample, 2 h2v2_fancy_upsample
+__device__ __forceinline__ int jp_chroma(const unsigned char* r0, const unsigned char* r1, int off, int x, int dw, int mode) {
+    if (mode == 0) return r0[x - off];
+    const int cx = x >> 1, i = cx - off;
+    if (mode == 1) {
+        const int p = r0[i];
+        if (x & 1) return cx == dw - 1 ? p : (3 * p + r0[i + 1] + 2) >> 2;
+        return cx == 0 ? p : (3 * p + r0[i - 1] + 1) >> 2;
+    }
+    const int s = 3 * r0[i] + r1[i];
+    if (x & 1) return cx == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * r0[i + 1] + r1[i + 1] + 7) >> 4;
+    return cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * r0[i - 1] + r1[i - 1] + 8) >> 4;
+}
+
+__device__ __forceinline__ int jp_context_row(const JpegGeom& g, int y) {      // h2v2: the other chroma row of source row y
+    const int cy = y >> 1;
+    return (y & 1) ? (cy + 1 < g.dh ? cy + 1 : g.dh - 1) : (cy > 0 ? cy - 1 : 0);
+}
+
+// One pixel (x, y) of the image straight from the planes in memory
+__device__ __forceinline__ unsigned jp_pixel(const JpegGeom& g, int x, int y) {
+    const int Y = g.py[(size_t)y * g.yw + x];
+    if (!g.color) return (unsigned)Y * 0x010101u;
+    int cc[2];
+    // (the sampling decided once for both chroma planes, a constant for jp_chroma in each branch: with jp_chroma left to decide per
+    // plane, jpeg_color_kernel took 8.5 instead of 8.1 ms over 435 photos of 2 000 x 1 500)
+    if (g.mode == 0) {
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, 0);
+    } else if (g.mode == 1) {
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, 1);
+    } else {
+        const int cy = y >> 1, oy = jp_context_row(g, y);
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, 2);
+    }
+    return jp_rgb(Y, cc[0], cc[1]);
+}
+
+__device__ __forceinline__ unsigned jp_pixel_clamped(const JpegGeom& g, int x, int y) {       // coordinates clamped into the image
+    return jp_pixel(g, x < 0 ? 0 : (x >= g.W ? g.W - 1 : x), y < 0 ? 0 : (y >= g.H ? g.H - 1 : y));
+}
+
+__global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __restrict__ images, const unsigned char* __restrict__ planes,
+                                                         unsigned char* __restrict__ out) {
+    const JpegImage& im = images[blockIdx.y];
+    const JpegGeom g = jpeg_geom(&im, planes);
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)g.W * g.H) return;
+    const int y = (int)(idx / g.W), x = (int)(idx - (long long)y * g.W);
+    const unsigned v = jp_pixel(g, x, y);
+    unsigned char* o = out + im.out_off + ((size_t)y * g.W + x) * 3;
+    o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16);
 }
 
 // ---- jpeg_color_kernel + resize_h_kernel (resize.hip) in one pass, for the transform entries: the full-size RGB image is never
@@ -772,62 +842,16 @@ __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __rest
 //   resample  one thread per (row, output): the dot product over LDS pixels and LDS coefficients, three byte stores
 // LDS use does not depend on the image's width. An output whose taps do not fit a chunk by themselves (more than JF_SPAN source
 // columns or JF_COEF coefficients under ONE output: a shorter side beyond 100 x n_px) is computed tap by tap from the planes in
-// memory (jf_pixel_global), as is any output whose first tap and count do not lie inside the staged span.
+// memory (jp_pixel), as is any output whose first tap and count do not lie inside the staged span.
 constexpr int JF_T = 256;
 constexpr int JF_ROWS = 8;                 // source rows per workgroup; 2x2 chroma needs JF_ROWS / 2 + 3 <= JF_ROWS rows
 constexpr int JF_SPAN = 512;               // source columns per chunk
 constexpr int JF_COEF = 3072;              // coefficients per chunk
 constexpr int JF_TILE_W = JF_SPAN + 16;    // staged bytes per row: the span, widened to multiples of 8 at both ends
 
-__device__ __forceinline__ unsigned jf_rgb(int Y, int cbs, int crs) {          // jdcolor.c, as jpeg_color_kernel
-    const int cb = cbs - 128, cr = crs - 128;
-    int r = Y + ((91881 * cr + 32768) >> 16);
-    int g = Y + ((-22554 * cb + 32768 - 46802 * cr) >> 16);
-    int b = Y + ((116130 * cb + 32768) >> 16);
-    r = r < 0 ? 0 : (r > 255 ? 255 : r);
-    g = g < 0 ? 0 : (g > 255 ? 255 : g);
-    b = b < 0 ? 0 : (b > 255 ? 255 : b);
-    return (unsigned)r | ((unsigned)g << 8) | ((unsigned)b << 16);
-}
-
-// The chroma sample of source column x (jdsample.c's fancy upsampling, as jpeg_color_kernel): r0 = the chroma row of the pixel's
-// own row, r1 = the context row (2x2 only), both indexed by chroma column - `off`. mode 0: 1x1 (copy), 1: h2v1, 2: h2v2
-__device__ __forceinline__ int jf_chroma(const unsigned char* r0, const unsigned char* r1, int off, int x, int dw, int mode) {
-    if (mode == 0) return r0[x - off];
-    const int cx = x >> 1, i = cx - off;
-    if (mode == 1) {
-        const int p = r0[i];
-        if (x & 1) return cx == dw - 1 ? p : (3 * p + r0[i + 1] + 2) >> 2;
-        return cx == 0 ? p : (3 * p + r0[i - 1] + 1) >> 2;
-    }
-    const int s = 3 * r0[i] + r1[i];
-    if (x & 1) return cx == dw - 1 ? (4 * s + 7) >> 4 : (3 * s + 3 * r0[i + 1] + r1[i + 1] + 7) >> 4;
-    return cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * r0[i - 1] + r1[i - 1] + 8) >> 4;
-}
-
-struct JfGeom {                // an image's planes, as jpeg_idct_kernel lays them out
-    const unsigned char* py;
-    const unsigned char* pc[2];
-    int W, H, yw, cw, dw, dh, mode;
-    bool color;
-};
-
-__device__ __forceinline__ int jf_context_row(const JfGeom& g, int y) {        // h2v2: the other chroma row of source row y
-    const int cy = y >> 1;
-    return (y & 1) ? (cy + 1 < g.dh ? cy + 1 : g.dh - 1) : (cy > 0 ? cy - 1 : 0);
-}
-
-// One pixel straight from the planes in memory, coordinates clamped into the image
-__device__ __forceinline__ unsigned jf_pixel_global(const JfGeom& g, int x, int y) {
-    x = x < 0 ? 0 : (x >= g.W ? g.W - 1 : x);
-    y = y < 0 ? 0 : (y >= g.H ? g.H - 1 : y);
-    const int Y = g.py[(size_t)y * g.yw + x];
-    if (!g.color) return (unsigned)Y * 0x010101u;
-    int cc[2];
-    const int cy = g.mode == 2 ? y >> 1 : y, oy = g.mode == 2 ? jf_context_row(g, y) : y;
-#pragma unroll
-    for (int c = 0; c < 2; ++c) cc[c] = jf_chroma(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, g.mode);
-    return jf_rgb(Y, cc[0], cc[1]);
+// One tap of the horizontal pass: a pixel R | G << 8 | B << 16 times its coefficient, into the three sums
+__device__ __forceinline__ void jf_tap(int (&a)[3], unsigned v, int c) {
+    a[0] += (int)(v & 255u) * c; a[1] += (int)((v >> 8) & 255u) * c; a[2] += (int)(v >> 16) * c;
 }
 
 __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegImage* __restrict__ images,
@@ -845,22 +869,9 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
     const clipmi_resize_job j = jobs[blockIdx.y];
     const int tid = threadIdx.x;
     const int row0 = blockIdx.x * JF_ROWS;
-    JfGeom g;
-    g.W = im.width;
-    g.H = im.height;
+    const JpegGeom g = jpeg_geom(&im, planes);
     if (row0 >= j.nrows || g.W < 1 || g.H < 1) return;                      // (the whole workgroup)
     const int nr = j.nrows - row0 < JF_ROWS ? j.nrows - row0 : JF_ROWS;
-    g.color = im.ncomp != 1;
-    const int hs = g.color ? im.hs : 1, vs = g.color ? im.vs : 1;
-    const int mx = (g.W + 8 * hs - 1) / (8 * hs), my = (g.H + 8 * vs - 1) / (8 * vs);
-    g.mode = hs == 1 ? 0 : (vs == 1 ? 1 : 2);
-    g.yw = mx * hs * 8;
-    g.cw = mx * 8;
-    g.dw = (g.W + 1) >> 1;
-    g.dh = (g.H + 1) >> 1;
-    g.py = planes + im.coef_off * 64;
-    g.pc[0] = g.py + (size_t)mx * my * hs * vs * 64;
-    g.pc[1] = g.pc[0] + (size_t)mx * my * 64;
     const int hk = j.hk > 0 ? j.hk : 0;
     const int* cf = coef + j.hcoef_off;
     unsigned char* dst = scratch + j.tmp_off + (size_t)row0 * n_px * 3;
@@ -882,7 +893,7 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
                 fits = cf[c] >= sx0 && end - sx0 <= JF_SPAN && (long long)(tid + 1) * hk <= JF_COEF;
             }
             // (first taps and ends do not decrease along an axis, so `fits` holds for a prefix of the threads; a table that breaks
-            // this only sends outputs to jf_pixel_global below)
+            // this only sends outputs to jp_pixel below)
             const int n = __syncthreads_count(fits);
             if (fits && tid == n - 1) s_end = end;
             __syncthreads();
@@ -930,12 +941,12 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
         // ---- convert
         for (int r = 0; r < nr; ++r) {
             const int y = min(ylo + r, g.H - 1);
-            const int t0 = g.mode == 2 ? (y >> 1) - cylo : r, t1 = g.mode == 2 ? jf_context_row(g, y) - cylo : r;
+            const int t0 = g.mode == 2 ? (y >> 1) - cylo : r, t1 = g.mode == 2 ? jp_context_row(g, y) - cylo : r;
             for (int p = tid; p < span; p += JF_T) {
                 const int x = sx0 + p;
                 const int Y = s_y[r][x - yb];
                 unsigned v = (unsigned)Y * 0x010101u;
-                if (g.color) v = jf_rgb(Y, jf_chroma(s_c[0][t0], s_c[0][t1], cb, x, g.dw, g.mode), jf_chroma(s_c[1][t0], s_c[1][t1], cb, x, g.dw, g.mode));
+                if (g.color) v = jp_rgb(Y, jp_chroma(s_c[0][t0], s_c[0][t1], cb, x, g.dw, g.mode), jp_chroma(s_c[1][t0], s_c[1][t1], cb, x, g.dw, g.mode));
                 s_rgb[r][p] = v;
             }
         }
@@ -946,40 +957,28 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
             unsigned char* o = dst + ((size_t)r * n_px + x0 + xo) * 3;
             if (!j.need_h) {
                 const int x = j.left + x0 + xo;
-                const unsigned v = x >= sx0 && x < sx1 ? s_rgb[r][x - sx0] : jf_pixel_global(g, x, ylo + r);
+                const unsigned v = x >= sx0 && x < sx1 ? s_rgb[r][x - sx0] : jp_pixel_clamped(g, x, ylo + r);
                 o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16);
                 continue;
             }
-            int a0 = 1 << 21, a1 = a0, a2 = a0;                  // Pillow: from 2^(PRECISION_BITS - 1), as resize_h_kernel
+            int a[3] = {1 << (RZ_PREC - 1), 1 << (RZ_PREC - 1), 1 << (RZ_PREC - 1)};     // as resize_h_kernel
             if (span > 0 && s_xmin[xo] >= sx0 && s_cnt[xo] >= 0 && s_cnt[xo] <= hk && s_xmin[xo] + s_cnt[xo] <= sx1) {
                 const unsigned* px = &s_rgb[r][s_xmin[xo] - sx0];
                 const int* kk = &s_coef[xo * hk];
                 const int cnt = s_cnt[xo];
-                for (int k = 0; k < cnt; ++k) {
-                    const unsigned v = px[k];
-                    const int c = kk[k];
-                    a0 += (int)(v & 255u) * c; a1 += (int)((v >> 8) & 255u) * c; a2 += (int)(v >> 16) * c;
-                }
+                for (int k = 0; k < cnt; ++k) jf_tap(a, px[k], kk[k]);
             } else {
                 const int xmin = cf[x0 + xo], cnt = min(max(cf[n_px + x0 + xo], 0), hk);
                 const int* kk = cf + 2 * (size_t)n_px + (size_t)(x0 + xo) * hk;
-                for (int k = 0; k < cnt; ++k) {
-                    const unsigned v = jf_pixel_global(g, xmin + k, ylo + r);
-                    const int c = kk[k];
-                    a0 += (int)(v & 255u) * c; a1 += (int)((v >> 8) & 255u) * c; a2 += (int)(v >> 16) * c;
-                }
+                for (int k = 0; k < cnt; ++k) jf_tap(a, jp_pixel_clamped(g, xmin + k, ylo + r), kk[k]);
             }
-            a0 >>= 22; a1 >>= 22; a2 >>= 22;
             // three byte stores, as resize_h_kernel: the packed form has been miscompiled (resize_h_rgba_kernel's comment)
-            o[0] = (unsigned char)(a0 < 0 ? 0 : (a0 > 255 ? 255 : a0));
-            o[1] = (unsigned char)(a1 < 0 ? 0 : (a1 > 255 ? 255 : a1));
-            o[2] = (unsigned char)(a2 < 0 ? 0 : (a2 > 255 ? 255 : a2));
+            o[0] = rz_clip8(a[0]); o[1] = rz_clip8(a[1]); o[2] = rz_clip8(a[2]);
         }
         __syncthreads();                                         // the next chunk rewrites every LDS piece
         x0 = x1;
     }
 }
-
 
 // ---- Progressive files (SOF2, Huffman; ITU T.81 Annex G as libjpeg's jdphuff.c decodes it). The host (jpeg_parse.parse_progressive)
 // hands over only files whose scan script is complete - every coefficient of every component at Al = 0 by EOI - so that
@@ -1017,38 +1016,12 @@ struct JpegProgImage {         // mirrors clipmi_jpeg_progressive_image
     unsigned char quant[3][64];
 };
 
+__device__ __forceinline__ unsigned short jp_lut_entry(const JppLut&, unsigned sym, unsigned len, bool) {
+    return (unsigned short)((len << 8) | sym);
+}
+
 __global__ void __launch_bounds__(256) jpeg_build_pluts_kernel(const unsigned char* __restrict__ raw, JppLut* __restrict__ luts) {
-    __shared__ int first_code[18], first_idx[18];
-    const unsigned char* t = raw + (size_t)blockIdx.x * JP_RAW;
-    JppLut& L = luts[blockIdx.x];
-    const int tid = threadIdx.x;
-    for (int i = tid; i < (1 << JP_FAST); i += 256) L.fast[i] = 0;
-    if (tid == 0) {
-        int code = 0, k = 0;
-        for (int l = 1; l <= 16; ++l) {
-            const int n = t[l - 1];
-            first_code[l] = code;
-            first_idx[l] = k;
-            L.maxcode[l] = n ? code + n - 1 : -1;
-            L.valoff[l] = k - code;
-            code = (code + n) << 1;
-            k += n;
-        }
-        first_idx[17] = k > 256 ? 256 : k;
-        L.maxcode[0] = L.maxcode[17] = -1;
-        L.valoff[0] = L.valoff[17] = 0;
-    }
-    L.vals[tid] = t[16 + tid];
-    __syncthreads();
-    if (tid < first_idx[17]) {
-        int l = 1;
-        while (l < 16 && tid >= first_idx[l + 1]) ++l;
-        const int code = first_code[l] + (tid - first_idx[l]);
-        if (l <= JP_FAST && code < (1 << l)) {
-            const int base = code << (JP_FAST - l);
-            for (int j = 0; j < (1 << (JP_FAST - l)); ++j) L.fast[base + j] = (unsigned short)((l << 8) | t[16 + tid]);
-        }
-    }
+    jp_build_lut(raw + (size_t)blockIdx.x * JP_RAW, luts[blockIdx.x]);
 }
 
 // A lane's bit reader over one scan's segment: 64 bits buffered, MSB first (bits behind the segment read as zeros).
@@ -1123,28 +1096,28 @@ __global__ void __launch_bounds__(JPP_T) jpeg_progressive_kernel(const unsigned 
     const JpegProgImage& pim = pimages[blockIdx.x];
     const int tid = threadIdx.x;
     const int ncomp = pim.ncomp;
-    const int hs = ncomp == 1 ? 1 : pim.hs, vs = ncomp == 1 ? 1 : pim.vs;
-    const int hv = hs * vs, bpm = ncomp == 1 ? 1 : hv + 2;
-    const int mx = hs > 0 ? (pim.width + 8 * hs - 1) / (8 * hs) : 0, my = vs > 0 ? (pim.height + 8 * vs - 1) / (8 * vs) : 0;
     const int nsc = pim.n_scans, s0 = pim.first_scan;
     short* coef = coef_all + pim.coef_off * 64;
     const bool valid = nsc >= 1 && nsc <= JPP_MAX_SCANS && s0 >= 0 && s0 <= nscans_all - nsc && (ncomp == 1 || ncomp == 3) &&
-                       pim.width >= 1 && pim.height >= 1 && hs >= 1 && hs <= 2 && vs >= 1 && vs <= hs;
-    if (tid == 0) {                                     // the record jpeg_idct_kernel / jpeg_color_kernel read
-        JpegImage r{};
-        r.coef_off = pim.coef_off;
-        r.out_off = pim.out_off;
-        r.ncomp = 1;                                    // a record outside the limits: an empty grey image, nothing to do
-        r.hs = r.vs = 1;
-        if (valid) {
-            r.width = pim.width;
-            r.height = pim.height;
-            r.ncomp = ncomp;
-            r.hs = pim.hs;
-            r.vs = pim.vs;
+                       pim.width >= 1 && pim.height >= 1 && (ncomp == 1 || (pim.hs >= 1 && pim.hs <= 2 && pim.vs >= 1 && pim.vs <= pim.hs));
+    JpegImage r{};                                      // the record jpeg_idct_kernel / jpeg_color_kernel read
+    r.coef_off = pim.coef_off;
+    r.out_off = pim.out_off;
+    r.ncomp = 1;                                        // a record outside the limits: an empty grey image, nothing to do
+    r.hs = r.vs = 1;
+    if (valid) {
+        r.width = pim.width;
+        r.height = pim.height;
+        r.ncomp = ncomp;
+        r.hs = pim.hs;
+        r.vs = pim.vs;
+    }
+    const JpegGeom g = jpeg_geom(&r);                    // (of the record written: no division by a sampling factor not checked)
+    const int hs = g.hs, vs = g.vs, hv = g.hv, bpm = g.bpm, mx = g.mx, my = g.my;
+    if (tid == 0) {
+        if (valid)
             for (int c = 0; c < 3; ++c)
                 for (int k = 0; k < 64; ++k) r.quant[c][k] = pim.quant[c][k];
-        }
         images[blockIdx.x] = r;
         bad = ran_out = 0;
         nroots = 0;
@@ -1336,6 +1309,13 @@ extern "C" int64_t clipmi_jpeg_workspace_bytes(int64_t total_blocks, int ntables
            (int64_t)align_up((size_t)total_blocks * 64, 256);
 }
 
+// What all four decode entries ask of the arguments they share
+static bool jpeg_args_ok(const void* streams_dev, const void* images_dev, int n, const void* tables_dev, int ntables, int64_t total_blocks,
+                         int64_t max_blocks, const int32_t* status_dev, const void* ws_dev) {
+    return streams_dev && images_dev && tables_dev && status_dev && ws_dev && n >= 0 && ntables >= 1 && total_blocks >= 1 &&
+           max_blocks >= 1 && max_blocks <= total_blocks;
+}
+
 // The baseline decode up to the sample planes (shared by the decode and the transform entry) -> 0 and the planes, or an error
 static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
                                 int64_t total_blocks, int64_t max_blocks, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
@@ -1367,23 +1347,29 @@ static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images
     return 0;
 }
 
+// The plain decode entries' tail: jpeg_color_kernel over the planes, a thread per pixel of the largest image
+static int jpeg_color_tail(const char* who, const JpegImage* images, const unsigned char* planes, int n, int64_t max_pixels, void* out_dev,
+                           hipStream_t st) {
+    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "%s: batch too large for one launch", who);
+    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
+                       static_cast<unsigned char*>(out_dev));
+    CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
+    return 0;
+}
+
 extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
                                        int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
                                        void* ws_dev, int64_t ws_bytes, void* stream) {
     if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || ntables < 1 || total_blocks < 1 ||
-        max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
+    if (!jpeg_args_ok(streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks, status_dev, ws_dev) || !out_dev ||
+        max_pixels < 1)
         return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: bad arguments");
-    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "jpeg_decode_rgb8: batch too large for one launch");
     hipStream_t st = as_stream(stream);
     unsigned char* planes = nullptr;
     if (int rc = jpeg_baseline_planes("jpeg_decode_rgb8", streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks,
                                       status_dev, ws_dev, ws_bytes, st, &planes))
         return rc;
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st,
-                       static_cast<const JpegImage*>(images_dev), planes, static_cast<unsigned char*>(out_dev));
-    CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
-    return 0;
+    return jpeg_color_tail("jpeg_decode_rgb8", static_cast<const JpegImage*>(images_dev), planes, n, max_pixels, out_dev, st);
 }
 
 // The transform entries' tail: the fused colour conversion + horizontal pass over the planes, then resize.hip's vertical pass
@@ -1406,8 +1392,8 @@ extern "C" int clipmi_jpeg_decode_transform_rgb8(void* streams_dev, void* images
                                                  const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev, int32_t* status_dev,
                                                  void* ws_dev, int64_t ws_bytes, void* stream) {
     if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !tables_dev || !status_dev || !ws_dev || n < 0 || ntables < 1 || total_blocks < 1 ||
-        max_blocks < 1 || max_blocks > total_blocks || !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
+    if (!jpeg_args_ok(streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks, status_dev, ws_dev) ||
+        !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
         return set_err(CLIPMI_EINVAL, "jpeg_decode_transform_rgb8: bad arguments");
     hipStream_t st = as_stream(stream);
     unsigned char* planes = nullptr;
@@ -1461,20 +1447,16 @@ extern "C" int clipmi_jpeg_decode_progressive_rgb8(const void* streams_dev, cons
                                                    int64_t max_pixels, void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
                                                    void* stream) {
     if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !out_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 ||
-        ntables < 1 || total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks || max_pixels < 1)
+    if (!jpeg_args_ok(streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks, status_dev, ws_dev) || !scans_dev ||
+        nscans < 1 || !out_dev || max_pixels < 1)
         return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: bad arguments");
-    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_rgb8: batch too large for one launch");
     hipStream_t st = as_stream(stream);
     unsigned char* planes = nullptr;
     JpegImage* images = nullptr;
     if (int rc = jpeg_progressive_planes("jpeg_decode_progressive_rgb8", streams_dev, images_dev, n, scans_dev, nscans, tables_dev, ntables,
                                          total_blocks, max_blocks, status_dev, ws_dev, ws_bytes, st, &planes, &images))
         return rc;
-    hipLaunchKernelGGL(jpeg_color_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st, images, planes,
-                       static_cast<unsigned char*>(out_dev));
-    CLIPMI_CHECK_LAUNCH("jpeg_color_kernel");
-    return 0;
+    return jpeg_color_tail("jpeg_decode_progressive_rgb8", images, planes, n, max_pixels, out_dev, st);
 }
 
 extern "C" int clipmi_jpeg_decode_progressive_transform_rgb8(const void* streams_dev, const void* images_dev, int n, const void* scans_dev,
@@ -1483,9 +1465,8 @@ extern "C" int clipmi_jpeg_decode_progressive_transform_rgb8(const void* streams
                                                              const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev,
                                                              int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream) {
     if (n == 0) return 0;
-    if (!streams_dev || !images_dev || !scans_dev || !tables_dev || !status_dev || !ws_dev || n < 0 || nscans < 1 || ntables < 1 ||
-        total_blocks < 1 || max_blocks < 1 || max_blocks > total_blocks ||
-        !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
+    if (!jpeg_args_ok(streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks, status_dev, ws_dev) || !scans_dev ||
+        nscans < 1 || !jpeg_transform_args_ok(jobs_dev, max_rows, coef_dev, n_px, out_dev, scratch_dev))
         return set_err(CLIPMI_EINVAL, "jpeg_decode_progressive_transform_rgb8: bad arguments");
     hipStream_t st = as_stream(stream);
     unsigned char* planes = nullptr;

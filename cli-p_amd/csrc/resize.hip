@@ -24,13 +24,6 @@ struct ResizeJob {             // mirrors clipmi_resize_job (include/clipmi.h)
     long long tmp_off;
 };
 
-constexpr int RZ_PREC = 22;
-
-__device__ __forceinline__ unsigned char rz_clip8(int v) {
-    v >>= RZ_PREC;
-    return (unsigned char)(v < 0 ? 0 : (v > 255 ? 255 : v));
-}
-
 // horizontal pass: tmp[row][x][c] for the job's needed source rows and the n_px window columns.
 // grid (row blocks, jobs); one thread per (row, x); per-axis coefficient block = [n_px] xmin | [n_px] cnt | [n_px][k] kk
 __global__ void __launch_bounds__(256) resize_h_kernel(const unsigned char* __restrict__ raw, const ResizeJob* __restrict__ jobs,

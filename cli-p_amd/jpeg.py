@@ -57,30 +57,40 @@ def pack(items):
     return recs, tables, np.frombuffer(b"".join(pieces), np.uint8), ooff, coff, max_blocks, max_pixels
 
 
-def decode_device(items, device, stream=None):
-    """Parsed records -> (out uint8 device tensor, records, status int32 device tensor): the RGB rows of image k start at
-    records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is."""
+def _decode_device(items, device, packer, workspace, entry):
+    """decode_device's and decode_progressive_device's body. packer: pack or pack_progressive (the arrays in front of the
+    streams are the entry's records and tables, in its order); workspace(L, n, total_blocks, ntables) -> bytes; entry: the library call"""
     device = torch.device(device)
     if device.type != "cuda":
-        raise _lib.ClipmiError("jpeg.decode_device needs the HIP path (no CPU fallback)")
+        raise _lib.ClipmiError(f"jpeg: {entry} needs the HIP path (no CPU fallback)")
     L = _lib.lib()
-    recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items)
+    *arrays, streams, out_bytes, total_blocks, max_blocks, max_pixels = packer(items)
+    recs, tables = arrays[0], arrays[-1]
     n = len(items)
     out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=device)
     status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
     if n == 0:
         return out, recs, status
-    dev, (_, o_tab, o_str), _ = _lib.to_device16([recs, tables, streams], device)
-    ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, len(tables)))
+    dev, offs, _ = _lib.to_device16(arrays + [streams], device)
+    ws_bytes = int(workspace(L, n, total_blocks, len(tables)))
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
     base = dev.data_ptr()
-    rc = L.clipmi_jpeg_decode_rgb8(base + o_str, base, n, base + o_tab, len(tables), total_blocks, max_blocks, max_pixels,
-                                   out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(device))
-    _lib.check(rc, "clipmi_jpeg_decode_rgb8")
+    head = [base + offs[-1], base + offs[0], n]                    # streams, records, then (scans, their count,) tables, their count
+    for a, o in zip(arrays[1:], offs[1:-1]):
+        head += [base + o, len(a)]
+    rc = getattr(L, entry)(*head, total_blocks, max_blocks, max_pixels, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
+                           _lib.stream_ptr(device))
+    _lib.check(rc, entry)
     cur = torch.cuda.current_stream(device)
     dev.record_stream(cur)
     ws.record_stream(cur)
     return out, recs, status
+
+
+def decode_device(items, device, stream=None):
+    """Parsed records -> (out uint8 device tensor, records, status int32 device tensor): the RGB rows of image k start at
+    records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is."""
+    return _decode_device(items, device, pack, lambda L, n, blocks, nt: L.clipmi_jpeg_workspace_bytes(blocks, nt), "clipmi_jpeg_decode_rgb8")
 
 
 def _decode_files(blobs, device, parser, decode):
@@ -160,28 +170,8 @@ def pack_progressive(items):
 def decode_progressive_device(items, device, stream=None):
     """Progressive records -> (out uint8 device tensor, records, status int32 device tensor), as decode_device: the RGB rows of
     image k start at records[k]["out_off"]. Asynchronous on torch's current stream of `device`."""
-    device = torch.device(device)
-    if device.type != "cuda":
-        raise _lib.ClipmiError("jpeg.decode_progressive_device needs the HIP path (no CPU fallback)")
-    L = _lib.lib()
-    recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items)
-    n = len(items)
-    out = torch.empty(max(out_bytes, 16), dtype=torch.uint8, device=device)
-    status = torch.zeros(max(n, 1), dtype=torch.int32, device=device)
-    if n == 0:
-        return out, recs, status
-    dev, (_, o_scan, o_tab, o_str), _ = _lib.to_device16([recs, scans, tables, streams], device)
-    ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(n, total_blocks, len(tables)))
-    ws = torch.empty(ws_bytes, dtype=torch.uint8, device=device)
-    base = dev.data_ptr()
-    rc = L.clipmi_jpeg_decode_progressive_rgb8(base + o_str, base, n, base + o_scan, len(scans), base + o_tab, len(tables), total_blocks,
-                                               max_blocks, max_pixels, out.data_ptr(), status.data_ptr(), ws.data_ptr(), ws_bytes,
-                                               _lib.stream_ptr(device))
-    _lib.check(rc, "clipmi_jpeg_decode_progressive_rgb8")
-    cur = torch.cuda.current_stream(device)
-    dev.record_stream(cur)
-    ws.record_stream(cur)
-    return out, recs, status
+    return _decode_device(items, device, pack_progressive, lambda L, n, blocks, nt: L.clipmi_jpeg_progressive_workspace_bytes(n, blocks, nt),
+                          "clipmi_jpeg_decode_progressive_rgb8")
 
 
 def decode_progressive_files(blobs, device):

@@ -138,6 +138,33 @@ def test_vit_l_size(tmp_path):
     assert np.array_equal(plain, ref) and np.array_equal(out, plain)
 
 
+def test_outputs_whose_taps_exceed_a_chunk_are_computed_tap_by_tap(tmp_path):
+    """n_px = 8 over sides of 1100 and more: an output has 553 - 603 taps (resize.pack_jobs' hk), more source columns than a chunk
+    of jpeg_color_resize_h_kernel stages (JF_SPAN = 512), so every output is summed tap by tap from the planes in memory - the
+    pixel function jpeg_color_kernel runs, called by the fused kernel. The odd sizes put the dw-1 / dh-1 edges of fancy upsampling
+    under those taps; the 600 x 4000 panorama has 303 taps, few outputs per chunk under the coefficient limit (JF_COEF)."""
+    rng = np.random.default_rng(45)
+    files = []
+    for (h, w) in [(1100, 1200), (1101, 1203), (1203, 1101)]:
+        a = smooth(rng, h, w)
+        for sub in (0, 1, 2):
+            files.append((f"{h}x{w} sub{sub}", encode(a, quality=90, subsampling=sub)))
+            files.append((f"{h}x{w} sub{sub} progressive", encode(a, quality=90, subsampling=sub, progressive=True)))
+    files.append(("600x4000 sub2", encode(smooth(rng, 600, 4000), quality=90, subsampling=2)))
+    kinds = [device_kind(b) for _, b in files]
+    assert kinds == ["baseline", "progressive"] * 9 + ["baseline"]
+    blobs = [b for _, b in files]
+    ref = pillow_transform(tmp_path, blobs, 8)
+    out, status = jpeg.transform_files(blobs, 8, DEV, fused=True)
+    plain, plain_status = jpeg.transform_files(blobs, 8, DEV, fused=False)
+    assert not status.cpu().numpy().any() and not plain_status.cpu().numpy().any()
+    out, plain = out.cpu().numpy(), plain.cpu().numpy()
+    for k, (label, _) in enumerate(files):
+        assert np.array_equal(plain[k], ref[k]), f"unfused != Pillow: {label}"
+        assert np.array_equal(out[k], plain[k]), f"fused != unfused: {label}"
+        assert np.array_equal(out[k], ref[k]), f"fused != Pillow: {label}"
+
+
 def _fused_pipeline_worker(tmp):
     """Own process, the product's start order (decode workers first, GPU second): a directory of baseline and progressive files of
     the sizes above beside a PNG and a CMYK JPEG (Pillow's), a file whose data ends early and a broken one."""
