@@ -1,6 +1,6 @@
 #!/bin/bash
 # gfx950 ISA + kernel metadata of one translation unit of the built library (development aid).
-# usage: tools/isa_dump.sh topk [obj-dir]   ->  /tmp/clipmi_isa/topk.s, /tmp/clipmi_isa/topk.notes
+# usage: tools/isa_dump.sh topk [obj-dir]   ->  /tmp/clipmi_isa/topk.s, /tmp/clipmi_isa/topk.notes   (topk includes coarse_scan.hpp; rowcopy: the index build side)
 set -e
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
 TU=${1:-topk}
