@@ -31,6 +31,7 @@ SYMBOLS = [
     "clipmi_dbg_split_stats", "clipmi_dbg_gemm_ln", "clipmi_dbg_gemm_resid_ln", "clipmi_dbg_gemm_resid_ln_leaf", "clipmi_dbg_gemm_ln_leaf", "clipmi_dbg_quantize_rows_fp8mx", "clipmi_dbg_gemm_fp8_bsa",
     "clipmi_dbg_embed_image", "clipmi_dbg_embed_text", "clipmi_dbg_gemm_plan", "clipmi_dbg_gemm_fp8_plan",
     "clipmi_dbg_attention_fp8mx",
+    "clipmi_dbg_layernorm_forms", "clipmi_dbg_gather_rows", "clipmi_dbg_gemm_fp8_mxout",
 ]
 
 
@@ -181,6 +182,12 @@ def lib():
     L.clipmi_dbg_gemm_resid_ln.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.clipmi_dbg_layernorm.restype = i32
     L.clipmi_dbg_layernorm.argtypes = [vp, vp, vp, vp, i32, i32, i32, vp]
+    L.clipmi_dbg_layernorm_forms.restype = i32
+    L.clipmi_dbg_layernorm_forms.argtypes = [vp, vp, vp, i64, vp, vp, vp, i32, vp, vp, vp, vp, i32, i32, vp]
+    L.clipmi_dbg_gather_rows.restype = i32
+    L.clipmi_dbg_gather_rows.argtypes = [vp, vp, i32, i32, sz, vp]
+    L.clipmi_dbg_gemm_fp8_mxout.restype = i32
+    L.clipmi_dbg_gemm_fp8_mxout.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.clipmi_dbg_attention.restype = i32
     L.clipmi_dbg_attention.argtypes = [vp, vp, i32, i32, i32, i32, vp]
     L.clipmi_dbg_attention_fp8mx.restype = i32

@@ -535,6 +535,12 @@ extern "C" int clipmi_dbg_embed_text(const clipmi_tower* t, const void* blob_dev
     return copy_out(rowidx_out_dev, w.rowidx, (size_t)Q * 4, st, who);
 }
 
+// launch_gather_rows as the pruned tail calls it: dst[b][:] = src[b * L][:], rows of row_bytes bytes
+extern "C" int clipmi_dbg_gather_rows(const void* src_dev, void* dst_dev, int B, int L, size_t row_bytes, void* stream) {
+    if (!src_dev || !dst_dev || B < 1 || L < 1 || row_bytes < 16) return set_err(CLIPMI_EINVAL, "dbg_gather_rows: bad arguments");
+    return launch_gather_rows(src_dev, dst_dev, B, L, row_bytes, as_stream(stream));
+}
+
 // Measurement hook (bench.py roofline): clipmi_encode_image `reps` times per estimator with HIP events around the launches
 // of the GEMM whose epilogue is `probe_epi` (1 = MLP c_fc + QuickGELU) on `stream`; synchronises. Three estimators of that
 // kernel's in-situ duration, each from its own `reps` forward passes (ms[0..2], averages over the timed launches):

@@ -269,6 +269,17 @@ extern "C" int clipmi_dbg_gemm_fp8(const void* a8_dev, const void* w8_dev, const
     return launch_gemm_fp8(g, epi, as_stream(stream), mx);
 }
 
+// clipmi_dbg_gemm_fp8's default form (mx = 1) with GemmArgs::out_bscale: where the plan runs the persistent QuickGELU kernel the rows
+// leave as e4m3, N bytes apart in out_dev, + MX scale bytes; every other shape or epilogue with out_bscale_dev set is refused
+extern "C" int clipmi_dbg_gemm_fp8_mxout(const void* a8_dev, const void* w8_dev, const float* a_scale_dev, const float* w_scale_dev,
+                                         const float* bias_dev, void* out_dev, void* out_bscale_dev, int M, int N, int K, int epi,
+                                         void* stream) {
+    if (epi < 0 || epi > 3) return set_err(CLIPMI_EINVAL, "dbg_gemm_fp8_mxout: epi %d", epi);
+    GemmArgs g = hook_args(a8_dev, w8_dev, bias_dev, out_dev, M, N, K);
+    g.a_scale = a_scale_dev; g.w_scale = w_scale_dev; g.out_bscale = static_cast<unsigned char*>(out_bscale_dev);
+    return launch_gemm_fp8(g, epi, as_stream(stream), 1);
+}
+
 // The plans alone, host only. out[0] = nparts, then (rows, kernel, epi, scratch, leaves, grid, lds) per part, out[22] = `query`: what
 // gemm_resid_writes_leaves / gemm_fp8_emits_mx answer for the shape; unused entries 0. A refusal: the return value + clipmi_last_error().
 static int plan_out(const GemmPlan& p, bool query, int32_t* out, int n_out) {

@@ -143,6 +143,20 @@ extern "C" int clipmi_dbg_layernorm(const float* x_dev, const float* w_dev, cons
     return launch_layernorm(a, as_stream(stream));
 }
 
+// every field of LnArgs, one to one (clipmi.h): the forms the towers launch that clipmi_dbg_layernorm does not reach
+extern "C" int clipmi_dbg_layernorm_forms(const float* x_dev, const void* x3_dev, const int32_t* rowidx_dev, int64_t row_step,
+                                          const float* w_dev, const float* b_dev, void* out_dev, int out_bf16, void* out8_dev,
+                                          float* scale8_dev, void* out_x3_dev, float* out_part_dev, int M, int W, void* stream) {
+    if ((x_dev == nullptr) == (x3_dev == nullptr)) return set_err(CLIPMI_EINVAL, "dbg_layernorm_forms: one of x, x3");
+    if (!w_dev || !b_dev || (!out_dev && !out8_dev && !out_x3_dev) || (out8_dev && !scale8_dev) || (out8_dev && out_x3_dev) ||
+        row_step < 0)
+        return set_err(CLIPMI_EINVAL, "dbg_layernorm_forms: NULL pointer");
+    LnArgs a{x_dev, w_dev, b_dev, out_dev, rowidx_dev, row_step, M, W, out_bf16};
+    a.out8 = static_cast<unsigned char*>(out8_dev); a.scale8 = scale8_dev;
+    a.x3 = x3_dev; a.out_x3 = out_x3_dev; a.out_part = out_part_dev;
+    return launch_layernorm(a, as_stream(stream));
+}
+
 // `causal` bit 0 = causal mask; bit 1 = use the 2-byte LDS reads instead of ds_read_b64_tr_b16; bit 2 = the one-wave-
 // per-(image, head) form attention52_kernel where the default is attention52x4_kernel (49 <= L <= 52)
 extern "C" int clipmi_dbg_attention(const void* qkv_dev, void* out_dev, int B, int L, int heads, int causal,

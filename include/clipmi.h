@@ -527,6 +527,32 @@ int clipmi_dbg_gemm_ln_leaf(const void* x3_dev, const void* wg_dev, const float*
 int clipmi_dbg_gemm_resid_ln(const void* a_dev, const void* w_dev, const float* bias_dev, void* x3_dev, float* part_dev,
                              float* tmp_dev, int M, int N, int K, int algo, void* stream);
 
+/* The row kernels in every form the towers launch them (tests/test_rows_exact_gpu.py; additions to ABI 8 in the sense of the
+ * note above: nothing existing changes, CLIPMI_ABI_VERSION stays 8).
+ * clipmi_dbg_layernorm_forms sets every field of the LayerNorm launcher's arguments one to one. Output row r is made of source
+ * row rowidx_dev[r] (int32 [M]) or, without rowidx_dev, r * row_step (1 = dense); the source is f32 rows x_dev [..][W] or split
+ * rows x3_dev [..][3 W bytes], exactly one of the two. One output form:
+ *   out8_dev + scale8_dev       : e4m3 [M][W] + f32 row scales [M], the bytes clipmi_dbg_quantize_rows_fp8 makes of the bf16 rows
+ *                                 (out_dev is not written);
+ *   out_x3_dev + out_part_dev   : split rows [M][3 W bytes] + statistics partials [M][W/256][2] (W % 256 == 0), the bytes
+ *                                 clipmi_dbg_split_stats makes of the f32 rows (out_dev is not written);
+ *   out_dev                     : bf16 (out_bf16 != 0) or f32 [M][W]; out_dev == x_dev (f32, dense) normalises in place.
+ * W % 4 == 0, W <= 1024.
+ * clipmi_dbg_gather_rows: dst[b][:] = src[b * L][:], b < B, rows of row_bytes bytes (a multiple of 16): the class-token rows of the
+ * pruned last block.
+ * clipmi_dbg_gemm_fp8_mxout: clipmi_dbg_gemm_fp8 in its default form with one more output: with out_bscale_dev set, a QuickGELU
+ * GEMM (epi 1) that runs on the persistent kernel writes its rows as e4m3, N bytes apart, into out_dev and their MX scale bytes
+ * [M][N / 32] into out_bscale_dev - the bytes clipmi_dbg_quantize_rows_fp8mx makes of the bf16 rows; any other epilogue or a shape
+ * off the persistent kernel is refused (clipmi_dbg_gemm_fp8_plan with out_bscale = 1 says which). out_bscale_dev == NULL: bf16 /
+ * f32 rows as clipmi_dbg_gemm_fp8 writes them. */
+int clipmi_dbg_layernorm_forms(const float* x_dev, const void* x3_dev, const int32_t* rowidx_dev, int64_t row_step,
+                               const float* w_dev, const float* b_dev, void* out_dev, int out_bf16, void* out8_dev,
+                               float* scale8_dev, void* out_x3_dev, float* out_part_dev, int M, int W, void* stream);
+int clipmi_dbg_gather_rows(const void* src_dev, void* dst_dev, int B, int L, size_t row_bytes, void* stream);
+int clipmi_dbg_gemm_fp8_mxout(const void* a8_dev, const void* w8_dev, const float* a_scale_dev, const float* w_scale_dev,
+                              const float* bias_dev, void* out_dev, void* out_bscale_dev, int M, int N, int K, int epi,
+                              void* stream);
+
 /* Which kernel a GEMM of this shape runs on (csrc/gemm_plan.hpp: the rule the launchers follow), host only - no device is
  * touched, no operand exists. clipmi_dbg_gemm_plan: the bf16 GEMMs; epi = the EPI_* number, algo 0 = by shape, 1 / 2 / 3 force
  * the 128 x 128 / 256 x 256 / persistent 256 x 256 kernel, ln_leaf / ln_leaf_in != 0: the caller passes statistics leaves
