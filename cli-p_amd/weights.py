@@ -31,6 +31,9 @@ ARCHS = {
     # width 256 (the smallest the FP8 path accepts), 101 tokens (flash attention), 3 layers
     "toy-256": dict(v_width=256, v_layers=3, patch=14, res=140,
                     t_width=128, t_layers=2, ctx=16, vocab=512, embed=128),
+    # toy's vision tower beside a 256-wide, 3-layer text tower: the smallest LN-folded text tower (tests/wiring_cases.py)
+    "toy-t256": dict(v_width=128, v_layers=2, patch=32, res=64,
+                     t_width=256, t_layers=3, ctx=16, vocab=512, embed=128),
     # 2-layer toy used by kernel-level tests (SURVEY.md §8c fixture (i))
     "toy": dict(v_width=128, v_layers=2, patch=32, res=64,
                 t_width=128, t_layers=2, ctx=16, vocab=512, embed=128),
