@@ -15,11 +15,13 @@ namespace {
 // same radix select, so results stay bit-exact against the oracle.
 //
 // Superset argument. Let s(r) be the exact (fmaf-chain) score of row r and c(r) the bf16-MFMA score of
-// the bf16-rounded operands. bf16 RNE has relative error u = 2^-9 per operand, so the exact products
-// differ by at most (2u + u^2)|a_k b_k|; both accumulations (f32, E terms, any order) add at most
+// the bf16-rounded operands. bf16 keeps 8 significant bits, so RNE has relative error u8 = 2^-8 per operand and the
+// exact products differ by at most (2 u8 + u8^2)|a_k b_k| = 0.0078278 |a_k b_k| (reached: both mantissas just under a
+// rounding tie, 1 + (1 - d) 2^-8, in every component); both accumulations (f32, E terms, any order) add at most
 // ~2 * E * 2^-24 * sum|a_k b_k|. With sum|a_k b_k| <= ||row|| ||q||, at E = 512:
-//        |c(r) - s(r)| <= 0.004 * ||row|| * ||q||  <=  margin_q := 0.0041 * R_max * ||q||
-// (R_max = largest row norm, kept with the bf16 copy). E = 768: 0.0040017 and 0.0041305, bf16_margin_coef<E> below. tau0_q = exact K-th best of the first S rows is
+//        |c(r) - s(r)| <= 0.0078888 * ||row|| * ||q||  <=  margin_q := 0.0080 * R_max * ||q||
+// (R_max = largest row norm, kept with the bf16 copy). E = 768: 0.0079193 and 0.0080305, bf16_margin_coef<E> below;
+// tests/coarse_tight.py family B presses this bound. tau0_q = exact K-th best of the first S rows is
 // a lower bound of the final K-th best score; every row of the true top-K has s >= tau0_q, hence
 // c >= tau0_q - margin_q =: the coarse threshold. If a candidate list overflows its capacity a device
 // flag makes the (otherwise early-exiting) exact-scan fallback launches run and overwrite the result.
@@ -48,7 +50,7 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 //   [qs]   1.001 ||y|| / t_q (int8)                       or 0
 //   [2 qs] the value the scan compares against, (tau - margin) * [0] - written by select_topk_kernel each time a new exact
 //          K-th best tau is known (-inf until then)
-//   [3 qs] margin: 1.001 (R_max + A_max) ||f_q|| + 1e-4 R_max ||y|| (int8, f_q = y - t_q p_q) or 1.001 * 0.0041 R_max ||q||
+//   [3 qs] margin: 1.001 (R_max + A_max) ||f_q|| + 1e-4 R_max ||y|| (int8, f_q = y - t_q p_q) or 1.001 * bf16_margin_coef<E> R_max ||q||
 //         (bf16); +inf when it is not a number (the threshold then stays -inf: everything survives, the result stays exact)
 // and the query image the scan kernels copy into LDS (entry [(qg*KS + s)*64 + lane] = 16 bytes of query 16 qg + (lane & 15):
 // bf16 k = 32 s + 8 g .. + 7, or int8 k = 64 s + 16 g .. + 15, g = lane >> 4; zero for queries >= QA). Block 0 also clears
@@ -68,14 +70,17 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 // Needed: (2 E + 16) u = 6.2e-5 at E = 512, 9.3e-5 at E = 768. The constant is 1e-4 * E / 512: 1e-4 at 512 (unchanged, bit for
 // bit), 1.5e-4 at 768 - the same 1.6 x head room at both widths instead of 1.08 x; it is < 1 % of the query half of the margin
 // (1.001 (R + A) ||f_q|| ~ 7.6e-3 R ||y|| on unit data), so the survivor count does not notice.
-// bf16: |c - s| <= (2 u9 + u9^2 + 2 E u) ||x|| ||y||, u9 = 2^-9: 0.0039712 at 512, 0.0040017 at 768 (no longer below the
-// 0.004 the header's argument rounds to). The constant is 0.0041 + 2 (E - 512) u: 0.0041 at 512 (unchanged), 0.0041305 at 768 -
-// the same 1.3e-4 of head room at both widths.
+// bf16: |c - s| <= (2 u8 + u8^2 + 2 E u) ||x|| ||y||, u8 = 2^-8 (8 significant bits: half an ulp of a mantissa in [1, 2) is
+// 2^-8): 0.0078888 at 512, 0.0079193 at 768. The constant is 0.0080 + 2 (E - 512) u: 0.0080 at 512, 0.0080305 at 768 - the same
+// 1.1e-4 of head room at both widths (the kernel multiplies by 1.001 once more for the f32 norms).
 template <int E>
 constexpr float i8_round_slack() { return 1e-4f * ((float)E / 512.0f); }
 template <int E>
-constexpr float bf16_margin_coef() { return 0.0041f + 2.0f * (float)(E - 512) * 5.9604644775390625e-8f; }
-static_assert(i8_round_slack<512>() == 1e-4f && bf16_margin_coef<512>() == 0.0041f, "E = 512 keeps its constants bit for bit");
+constexpr float bf16_margin_coef() { return 0.0080f + 2.0f * (float)(E - 512) * 5.9604644775390625e-8f; }
+static_assert(i8_round_slack<512>() == 1e-4f && bf16_margin_coef<512>() == 0.0080f, "the constants at E = 512: 1e-4 (int8 slack), 0.0080 (bf16 margin)");
+template <int E>
+constexpr bool bf16_coef_covers() { return (double)bf16_margin_coef<E>() > 2.0 / 256 + 1.0 / 65536 + 2.0 * E / 16777216; }
+static_assert(bf16_coef_covers<512>() && bf16_coef_covers<768>(), "the bf16 margin must cover 2 u8 + u8^2 + 2 E 2^-24, u8 = 2^-8");
 static_assert(768 * 127 * 127 < (1 << 24), "the int8 dot product must stay exact in f32");
 
 template <bool I8, int ET = 512>

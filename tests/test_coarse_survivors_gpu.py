@@ -1,19 +1,21 @@
 """-m gpu: how many (query, row) pairs each coarse scan hands to the exact re-scoring pass, against the counts recorded from
-the parent commit of csrc/coarse_scan.hpp (tests/golden/coarse_survivors_parent.json, never written from here).
+the parent commit of csrc/coarse_scan.hpp (tests/golden/coarse_survivors_parent.json, never written from here; its bf16
+entries were recorded again, under `commit_bf16`, when the bf16 margin coefficient was corrected - a change of the counts by
+design), and - the 64-query `unit` cases - against the band of the numpy restatement of the scan's test
+(tests/coarse_tight.py::count_band), so that a recorded count is not merely the code's own word.
 
 The bit-exact suites cannot see a scan that keeps too many or too few pairs outside the top K: the lists are supersets. The
 measurement hooks return the number of exactly re-scored pairs, a deterministic function of the data (the thresholds are exact
 K-th bests; atomics only change the order inside a list), so every case reproduces its count EXACTLY - a count that differs is
 a change of behaviour, not a reason to record again. Each case also compares the hook's ids with the oracle (all queries up to
 200; beyond that with the exact scan on the GPU, and 64 evenly spaced queries with the oracle)."""
-import ctypes as C
 import json
 import os
 
 import numpy as np
 import pytest
-import torch
 
+import coarse_tight as ct
 from conftest import unit_rows
 
 pytestmark = pytest.mark.gpu
@@ -76,30 +78,8 @@ def index(clipmi, gpu, kind, E, copy):
 def measure(clipmi, gpu, c):
     """The measurement hook of the case's path, one repetition -> (ids, re-scored pairs, fallback armed or None)."""
     _, kind, E, copy, Q = c
-    idx = index(clipmi, gpu, kind, E, copy)
-    L = clipmi._lib.lib()
-    qd = torch.from_numpy(rows(kind, E)[1][:Q].copy()).to(gpu)
-    need = max(L.clipmi_topk_ip_coarse_workspace_bytes(N, E, Q, K), L.clipmi_topk_ip_wide_workspace_bytes(N, E, Q, K))
-    assert need > 0, clipmi._lib.last_error()
-    ws = torch.empty(need, dtype=torch.uint8, device=gpu)
-    os_ = torch.empty((Q, K), dtype=torch.float32, device=gpu)
-    oi_ = torch.full((Q, K), -7, dtype=torch.int64, device=gpu)
-    ms, surv, nl, armed = C.c_float(0), C.c_longlong(-1), C.c_int(-1), C.c_int(-1)
-    db = idx.matrix()
-    tail = (qd.data_ptr(), Q, K, os_.data_ptr(), oi_.data_ptr(), ws.data_ptr(), ws.numel(), None, 1, C.byref(ms), C.byref(surv))
-    if copy == "bf16":
-        dbh, rmax = idx.matrix_bf16()
-        rc = L.clipmi_dbg_topk_coarse_scan_ms(db.data_ptr(), dbh.data_ptr(), N, E, rmax, *tail)
-    else:
-        db8, meta, amax, rmax = idx.matrix_i8()
-        if Q <= 64:
-            rc = L.clipmi_dbg_topk_coarse_i8_scan_ms(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, E, rmax, *tail)
-        else:
-            rc = L.clipmi_dbg_topk_wide_i8_scan_ms(db.data_ptr(), db8.data_ptr(), meta.data_ptr(), amax, N, E, rmax, *tail,
-                                                   C.byref(nl), C.byref(armed))
-    clipmi._lib.check(rc, case_id(c))
-    torch.cuda.synchronize()
-    return oi_.cpu().numpy(), surv.value, (armed.value if Q > 64 else None)
+    _, ids, surv, armed = ct.scan_hook(clipmi, gpu, index(clipmi, gpu, kind, E, copy), rows(kind, E)[1][:Q], K, copy, case_id(c))
+    return ids, surv, armed
 
 
 def reference(clipmi, gpu, topk_oracle, kind, E):
@@ -121,6 +101,8 @@ def reference(clipmi, gpu, topk_oracle, kind, E):
 def test_the_recorded_cases_are_these():
     g = json.load(open(GOLDEN))
     assert len(g["commit"]) == 40 and int(g["commit"], 16) >= 0
+    assert len(g["commit_bf16"]) == 40 and int(g["commit_bf16"], 16) >= 0 and g["commit_bf16"] != g["commit"] and g["reason_bf16"]
+    assert [e["id"] for e in g["cases"] if e.get("recorded") == "commit_bf16"] == [case_id(c) for c in CASES if c[3] == "bf16"]
     assert [e["id"] for e in g["cases"]] == [case_id(c) for c in CASES]
 
 
@@ -141,3 +123,30 @@ def test_survivor_count_equals_the_parents(clipmi, gpu, topk_oracle, c):
         assert np.array_equal(ids, Ie[:Q])
         sub = pick < Q
         assert np.array_equal(ids[pick[sub]], Io[sub])
+
+
+BAND_CASES = [c for c in CASES if c[1] == "unit" and c[4] <= 64]
+_exact, _copy = {}, {}
+
+
+@pytest.mark.parametrize("c", BAND_CASES, ids=[case_id(c) for c in BAND_CASES])
+def test_survivor_count_lies_in_the_restatements_band(clipmi, gpu, topk_oracle, c):
+    """What the 64-query hooks count, read from csrc/topk.hip: select_topk_kernel writes its list length M to m_out after every
+    segment's re-scoring (rescore_select: overwritten after segment 0, added after the later ones). The sample's select has no
+    m_out and leaves its list empty, so segment 0's list is that segment's fresh survivors alone; each later list is the K
+    heads the previous select kept plus the segment's fresh survivors. Hook = fresh pairs of all segments + K x (segments - 1)
+    per query (every list here is longer than K). The count must lie between the restatement's pairs that pass by more than
+    the f32 rounding of the two compared quantities and its pairs that pass or miss by no more than that (count_band states
+    the band: 4 ulp for int8; for bf16 the accumulation bound E 2^-24 ||x^|| ||q^|| + 2 ulp of the threshold)."""
+    _, kind, E, copy, Q = c
+    db, q = rows(kind, E)
+    if E not in _exact:
+        _exact[E] = np.stack([topk_oracle.scores(db, q[i]) for i in range(64)], axis=1)      # the oracle's f32 scores
+    if (E, copy) not in _copy:
+        _copy[(E, copy)] = ct.I8Copy(db) if copy == "int8" else ct.Bf16Copy(db)
+    _, surv, _ = measure(clipmi, gpu, c)
+    sure, maybe, nseg = ct.count_band(db, q[:Q], K, _exact[E][:, :Q], copy, cp=_copy[(E, copy)])
+    heads = K * Q * (nseg - 1)
+    print(f"{case_id(c)}: hook {surv}, restatement {sure + heads} .. {maybe + heads} ({heads} kept heads, {nseg} segments)")
+    assert nseg == 2
+    assert sure + heads <= surv <= maybe + heads

@@ -4,6 +4,7 @@ restatement of the int8 superset bound with the constants the library uses at E 
 import numpy as np
 import pytest
 
+from coarse_tight import i8_survivors
 from conftest import unit_rows
 
 
@@ -58,63 +59,15 @@ def test_repl_gates_use_the_same_predicate(clipmi):
 
 def _int8_bound_survivors(E, N, Q, K, seed):
     """The int8 coarse test as csrc/topk.hip computes it (quantize_rows_i8_kernel, coarse_prep_kernel, scan_coarse_kernel),
-    in f32 where the kernels use f32; exact scores in f64 (so this checks the bound's shape and constants, not its last ulp).
-    Returns (superset held in every segment, mean and largest count of fresh survivors per query)."""
-    f32 = np.float32
+    in f32 where the kernels use f32 - tests/coarse_tight.py::i8_survivors, the one restatement of the suite -; exact scores in
+    f64 (so this checks the bound's shape and constants, not its last ulp).
+    Returns (superset held in every segment, segments, mean and largest count of fresh survivors per query)."""
     rng = np.random.default_rng(seed)
     db = unit_rows(rng, N, E)
     q = unit_rows(rng, Q, E)
-    perm = np.argsort(np.abs(db).max(axis=1), kind="stable")          # rows ordered by their largest |component|
-    N32 = (N + 31) // 32 * 32
-    xp = np.zeros((N32, E), f32)
-    xp[:N] = db[perm]
-    s = np.abs(xp).reshape(N32 // 32, -1).max(axis=1) / f32(127.0)    # one scale per 32-row block
-    s[s == 0] = 1.0
-    srow = np.repeat(s.astype(f32), 32)
-    q8 = np.clip(np.rint(xp * (f32(1.0) / srow)[:, None]), -127, 127).astype(f32)
-    a = (np.linalg.norm(xp - srow[:, None] * q8, axis=1).astype(f32) * f32(1.001)).astype(f32)      # error norms x 1.001
-    a[N:] = 0
-    rmax = f32(np.linalg.norm(db.astype(np.float64), axis=1).max() * (1 + 1e-6))
-    amax = f32(a.max() * (1 + 1e-6))
-    t = (np.abs(q).max(axis=1) / f32(127.0)).astype(f32)               # the query digit
-    inv = (f32(1.0) / t).astype(f32)
-    p = np.clip(np.rint(q * inv[:, None]), -127, 127).astype(f32)
-    f = q - t[:, None] * p
-    F = (np.linalg.norm(f, axis=1).astype(f32) * f32(1.001)).astype(f32)
-    Y = np.linalg.norm(q, axis=1).astype(f32)
-    slack = f32(1e-4) * f32(E / 512.0)                                 # i8_round_slack<E>: 1e-4 at 512, 1.5e-4 at 768
-    margin = (f32(1.001) * (rmax + amax) * F + slack * rmax * Y).astype(f32)
-    yt = (f32(1.001) * Y * inv).astype(f32)
-    D = q8 @ p.T                                                       # exact: |D| <= E * 127^2 < 2^24
-    assert np.abs(D).max() < 2 ** 24 and np.array_equal(D, np.rint(D))
-    lhs = (D * srow[:, None] + (a[:, None] * yt[None, :])).astype(f32)
     exact = db.astype(np.float64) @ q.astype(np.float64).T              # [row][query]
-    slot_row = np.full(N32, -1)
-    slot_row[:N] = perm
-
-    def kth(rows):
-        return np.sort(exact[rows], axis=0)[-K]
-
-    S1 = 12288
-    S2 = max(min((N * K // 2048 + 31) & ~31, (N // 8) & ~31), 32768, S1)
-    N1 = max((N // 4) & ~31, 4 * S2)
-    segs = [(0, S2), (S2, N1), (N1, N32)] if N1 + 65536 <= N else [(0, S2), (S2, N32)]
-    final = np.sort(exact, axis=0)[-K]
-    tau = kth(np.arange(S1))                                           # level 1: the first S1 ROWS, exactly scored
-    tot = np.zeros(Q)
-    seen = np.zeros(N, bool)
-    ok = True
-    for r0, r1 in segs:
-        sl = np.arange(r0, r1)
-        sl = sl[slot_row[sl] >= 0]
-        thr = ((tau.astype(f32) - margin) * inv).astype(f32)           # select_topk_kernel: (tau - margin) / t_q
-        passed = lhs[sl] >= thr[None, :]
-        tot += passed.sum(axis=0)
-        need = exact[slot_row[sl]] >= final[None, :]                   # rows of the true top-K in this segment
-        ok &= bool((passed | ~need).all())
-        seen[slot_row[sl]] = True
-        tau = np.sort(exact[seen], axis=0)[-K]                         # exact K-th best of the rows seen so far
-    return ok, len(segs), tot.mean(), tot.max()
+    ok, _, nseg, tot = i8_survivors(db, q, K, exact, wide=False)
+    return ok, nseg, tot.mean(), tot.max()
 
 
 def test_int8_superset_bound_restated_in_numpy_at_768():

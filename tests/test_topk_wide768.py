@@ -5,6 +5,7 @@ library uses at E = 768."""
 import numpy as np
 import pytest
 
+from coarse_tight import i8_survivors, wide_segments
 from conftest import unit_rows
 
 CHUNK = 1024          # csrc/topk.hip WIDE768_MAX_Q
@@ -74,16 +75,6 @@ def test_read_index_passes_the_flag(clipmi, tmp_path, monkeypatch):
     assert not clipmi.read_index(path, device="cpu", coarse="int8")._wide_768_on()
 
 
-def wide_segments(N, S1=12288):
-    """csrc/topk.hip wide_segments: boundaries from 64 k rows, ratio 4."""
-    s = (max(65536, S1) + 31) & ~31
-    b = []
-    while len(b) < 7 and s * 2 <= N and s + 65536 <= N:
-        b.append(s)
-        s = (s * 4) & ~31
-    return b + [N]
-
-
 def test_wide_segment_plan():
     assert wide_segments(70001) == [70001]
     assert wide_segments(65536) == [65536]
@@ -94,74 +85,17 @@ def test_wide_segment_plan():
 
 def _wide_bound_survivors(E, N, Q, K, seed):
     """The wide scan's test as csrc/topk.hip computes it (quantize_rows_i8_kernel, coarse_prep_kernel's wide form,
-    scan_coarse_wide_kernel), in f32 where the kernels use f32; exact scores in f64. The shape of
-    test_topk_e768.py::_int8_bound_survivors with each row's error norm replaced by its block's largest, the wide segment
-    plan and the sample of the first 12 288 rows.
+    scan_coarse_wide_kernel), in f32 where the kernels use f32 - tests/coarse_tight.py::i8_survivors in its wide form: each
+    row's error norm replaced by its block's largest, the wide segment plan, the sample of the first 12 288 rows -; exact
+    scores in f64.
     Returns (superset held in every segment, the integer pre-test rejected no lane with a passing row, segments, mean and
     largest count of fresh survivors per query)."""
-    f32 = np.float32
     rng = np.random.default_rng(seed)
     db = unit_rows(rng, N, E)
     q = unit_rows(rng, Q, E)
-    perm = np.argsort(np.abs(db).max(axis=1), kind="stable")
-    N32 = (N + 31) // 32 * 32
-    xp = np.zeros((N32, E), f32)
-    xp[:N] = db[perm]
-    s = np.abs(xp).reshape(N32 // 32, -1).max(axis=1) / f32(127.0)
-    s[s == 0] = 1.0
-    s = s.astype(f32)
-    srow = np.repeat(s, 32)
-    q8 = np.clip(np.rint(xp * (f32(1.0) / srow)[:, None]), -127, 127).astype(f32)
-    a = (np.linalg.norm(xp - srow[:, None] * q8, axis=1).astype(f32) * f32(1.001)).astype(f32)
-    a[N:] = 0
-    ablk = a.reshape(-1, 32).max(axis=1)                               # bmeta[block].y
-    arow = np.repeat(ablk, 32)
-    rmax = f32(np.linalg.norm(db.astype(np.float64), axis=1).max() * (1 + 1e-6))
-    amax = f32(a.max() * (1 + 1e-6))
-    t = (np.abs(q).max(axis=1) / f32(127.0)).astype(f32)
-    inv = (f32(1.0) / t).astype(f32)
-    p = np.clip(np.rint(q * inv[:, None]), -127, 127).astype(f32)
-    f = q - t[:, None] * p
-    F = (np.linalg.norm(f, axis=1).astype(f32) * f32(1.001)).astype(f32)
-    Y = np.linalg.norm(q, axis=1).astype(f32)
-    slack = f32(1e-4) * f32(E / 512.0)                                 # i8_round_slack<768> = 1.5e-4
-    margin = (f32(1.001) * (rmax + amax) * F + slack * rmax * Y).astype(f32)
-    yt = (f32(1.001) * Y * inv).astype(f32)
-    D = q8 @ p.T
-    assert np.abs(D).max() <= E * 127 * 127 < 2 ** 24 and np.array_equal(D, np.rint(D))
-    lhs = (D * srow[:, None] + (arow[:, None] * yt[None, :]).astype(f32)).astype(f32)
     exact = db.astype(np.float64) @ q.astype(np.float64).T
-    slot_row = np.full(N32, -1)
-    slot_row[:N] = perm
-    bnd = wide_segments(N)
-    final = np.sort(exact, axis=0)[-K]
-    tau = np.sort(exact[:12288], axis=0)[-K]                           # the sample: the first 12 288 ROWS, exactly scored
-    tot = np.zeros(Q)
-    seen = np.zeros(N, bool)
-    ok = pre_ok = True
-    inv_s = (f32(1.0) / s).astype(f32)
-    r0 = 0
-    for r1 in bnd:
-        r1 = (r1 + 31) // 32 * 32 if r1 == N else r1
-        sl = np.arange(r0, r1)
-        live = slot_row[sl] >= 0
-        thr = ((tau.astype(f32) - margin) * inv).astype(f32)
-        passed = (lhs[sl] >= thr[None, :]) & live[:, None]             # rows beyond last_row32 never pass
-        tot += passed.sum(axis=0)
-        need = np.zeros_like(passed)
-        need[live] = exact[slot_row[sl[live]]] >= final[None, :]
-        ok &= bool((passed | ~need).all())
-        # the integer pre-test of a block and query: dmin = floor(xq - 2 - |xq| 2e-6), xq = (T - amax_block Y) / s
-        b0, b1 = r0 // 32, r1 // 32
-        xq = ((thr[None, :].astype(np.float64) - ablk[b0:b1, None].astype(np.float64) * yt[None, :]).astype(f32) * inv_s[b0:b1, None]).astype(f32)
-        xq = np.clip(xq, f32(-1e9), f32(1e9))
-        xq = ((xq - f32(2.0)).astype(f32) - (np.abs(xq) * f32(2e-6)).astype(f32)).astype(f32)
-        dmin = np.floor(xq)
-        pre_ok &= bool((~passed | (D[sl] >= np.repeat(dmin, 32, axis=0))).all())
-        seen[slot_row[sl[live]]] = True
-        tau = np.sort(exact[seen], axis=0)[-K]
-        r0 = r1
-    return ok, pre_ok, len(bnd), tot.mean(), tot.max()
+    ok, pre_ok, nseg, tot = i8_survivors(db, q, K, exact, wide=True)
+    return ok, pre_ok, nseg, tot.mean(), tot.max()
 
 
 def test_wide_int8_bound_restated_in_numpy_at_768():
