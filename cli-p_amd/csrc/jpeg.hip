@@ -4,10 +4,16 @@
 // through - 8-bit baseline / extended-sequential Huffman, one interleaved scan, grey or YCbCr with luma sampling 1x1 /
 // 2x1 / 2x2 and 1x1 chroma, with or without restart intervals - and produces Pillow's bytes (tests/test_jpeg_gpu.py compares with
 // Pillow itself; oracle/jpeg_oracle.py is the CPU restatement, pinned against Pillow in tests/test_jpeg.py).
+// Where the host opts in (jpeg_parse.parse(layouts=True)) the records also name luma sampling 1x2 (4:4:0: jdsample.c's
+// h1v2_fancy_upsample), 4x1 (4:1:1) and 1x4 (int_upsample: replication), and a colour transform of "none" for the files libjpeg
+// takes for RGB-coded: further values of JpegGeom's `mode` and its `rgb` flag (tests/test_jpeg_layouts_gpu.py).
 // Everything else (CMYK, ...) stays with Pillow in the decode workers; PNG files have png.hip.
 //
 // Kernels, one batch of images per call (every kernel takes an image's block and plane layout from jpeg_geom):
-//   jpeg_unstuff_kernel      the 0x00 behind every 0xFF removed in place, for segments the host hands over as they are in the file
+//   jpeg_unstuff_kernel      the baseline record's first reader and its checker (jp_record_ok): a record whose sampling factors,
+//                            colour transform or size the kernels do not take is emptied in place, for jpeg_huffman_kernel to
+//                            report (status 1) and every later kernel to pass over. Then, for segments the host hands over as
+//                            they are in the file, the 0x00 behind every 0xFF removed in place
 //   jpeg_build_luts_kernel   canonical Huffman codes of the batch's distinct DHT tables -> 10-bit look-up + slow-path arrays
 //                            (jpeg_build_pluts_kernel: the progressive form of the entries; one builder, jp_build_lut)
 //   jpeg_huffman_kernel      the entropy-coded segment -> int16 coefficients (DC still differential). Huffman decoding is a
@@ -48,9 +54,26 @@ struct JpegImage {             // mirrors clipmi_jpeg_image (include/clipmi.h)
     int hs, vs;
     int dc_tbl[3], ac_tbl[3];
     int restart_interval, n_intervals;
-    int stuffed, reserved;
+    int stuffed, transform;    // transform: clipmi_jpeg_image.reserved - 0 YCbCr -> RGB, 1 none (the components are R, G, B)
     unsigned char quant[3][64];
 };
+
+// The luma sampling factors the kernels take (chroma is 1 x 1): 1x1, 2x1, 2x2, and 1x2, 4x1, 1x4
+__device__ __forceinline__ bool jp_sampling_ok(int hs, int vs) {
+    return (hs == 1 && (vs == 1 || vs == 2 || vs == 4)) || (hs == 2 && (vs == 1 || vs == 2)) || (hs == 4 && vs == 1);
+}
+
+// What every kernel behind the record's first reader relies on. A record outside it is reported (status 1), never decoded: its
+// first reader (jpeg_unstuff_kernel; jpeg_progressive_kernel for its own records) leaves an empty grey image in its place.
+__device__ __forceinline__ bool jp_record_ok(int ncomp, int width, int height, int hs, int vs, int transform) {
+    return width >= 1 && height >= 1 && (ncomp == 1 ? transform == 0 : ncomp == 3 && jp_sampling_ok(hs, vs) && (transform == 0 || transform == 1));
+}
+
+// Chroma upsampling (JpegGeom.mode). 0, 1, 2 are luma 1x1, 2x1, 2x2 - every file before the layouts switch -, and the pixel
+// functions test for these three first and run the code they always ran; the other two go through the `_more` functions. (With
+// all five in one chain, the mode a chain of branches and the colour transform loaded in front of it, jpeg_color_kernel - a pixel
+// per thread - took 8.9 instead of 8.2 ms over 435 photos of 2 000 x 1 500 and the fused kernel 7.6 instead of 7.0.)
+enum { JM_COPY = 0, JM_H2V1 = 1, JM_H2V2 = 2, JM_H1V2 = 3, JM_REPL = 4 };
 
 // An image's blocks and planes. Coefficients (int16 [64] per block, from coef_all + coef_off * 64) come in scan order: MCU
 // after MCU, each the hv luma blocks, then Cb, Cr. Planes of an image (bytes from planes + coef_off * 64):
@@ -62,9 +85,11 @@ struct JpegGeom {
     int mx, my;                    // MCUs per row, per column
     long long nmcu;                // mx my
     int yw, cw;                    // bytes per row of the luma plane, of a chroma plane
-    int dw, dh;                    // chroma columns, rows under the image at 2 x sampling (fancy upsampling's edges)
-    int mode;                      // chroma upsampling: 0 1x1 (copy), 1 h2v1, 2 h2v2
+    int dw, dh;                    // chroma columns, rows under the image: ceil(W / hs), ceil(H / vs) (fancy upsampling's edges)
+    int mode;                      // chroma upsampling: JM_COPY 1x1, JM_H2V1, JM_H2V2, JM_H1V2 (fancy), JM_REPL 4x1 / 1x4 (replication)
+    int sx, sy;                    // log2 hs, log2 vs: the chroma sample of pixel (x, y) without filtering is (x >> sx, y >> sy)
     bool color;
+    bool rgb;                      // no colour conversion: the three planes are R, G, B
     const unsigned char* py;       // the planes: luma, Cb and Cr (only from jpeg_geom with the planes' base)
     const unsigned char* pc[2];
     // bytes from the luma plane to the plane of component c = 1 (Cb), 2 (Cr)
@@ -75,6 +100,7 @@ struct JpegGeom {
 // reference parameter lets the compiler load every field up front, which cost jpeg_huffman_kernel a VGPR and two spilled SGPRs.)
 __device__ __forceinline__ JpegGeom jpeg_geom(const JpegImage* im, const unsigned char* planes = nullptr) {
     JpegGeom g;
+    const int tf = im->transform;
     g.color = im->ncomp != 1;
     g.hs = im->ncomp == 1 ? 1 : im->hs;
     g.vs = im->ncomp == 1 ? 1 : im->vs;
@@ -87,9 +113,15 @@ __device__ __forceinline__ JpegGeom jpeg_geom(const JpegImage* im, const unsigne
     g.nmcu = (long long)g.mx * g.my;
     g.yw = g.mx * g.hs * 8;
     g.cw = g.mx * 8;
-    g.dw = (g.W + 1) >> 1;
-    g.dh = (g.H + 1) >> 1;
-    g.mode = g.hs == 1 ? 0 : (g.vs == 1 ? 1 : 2);
+    g.sx = g.hs >> 1;              // (1, 2, 4 -> 0, 1, 2)
+    g.sy = g.vs >> 1;
+    g.dw = (g.W + g.hs - 1) >> g.sx;
+    g.dh = (g.H + g.vs - 1) >> g.sy;
+    // (selects, not branches; and the transform - 0 or 1 in a record that passed jp_record_ok, 0 in a grey one - is read with no
+    // test in front of it and used only behind the samples' loads, see jp_pixel)
+    static_assert(JM_H2V1 == 1 && JM_H2V2 == 2, "hs == 2: the mode is vs");
+    g.mode = g.hs == 2 ? g.vs : (g.vs == 2 ? JM_H1V2 : (g.hv == 4 ? JM_REPL : JM_COPY));
+    g.rgb = tf != 0;
     g.py = planes + im->coef_off * 64;
     g.pc[0] = g.py + g.plane_off(1);
     g.pc[1] = g.py + g.plane_off(2);
@@ -140,7 +172,21 @@ __device__ const unsigned char jp_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10,
 // tagged (stuffed = 2) and jpeg_huffman_kernel reports the file (status 3: Pillow decides).
 __global__ void __launch_bounds__(256) jpeg_unstuff_kernel(unsigned char* __restrict__ streams, JpegImage* __restrict__ images) {
     JpegImage& im = images[blockIdx.x];
-    if (im.stuffed != 1) return;
+    // the record's first reader: one the kernels do not take (a sampling, a colour transform, a size) becomes an empty grey image
+    // without data, which gives no later kernel anything to do and which jpeg_huffman_kernel reports (status 1: no pixels). Thread 0
+    // decides and rewrites; the others read the record behind the barrier.
+    __shared__ int s_ok;
+    if (threadIdx.x == 0) {
+        s_ok = jp_record_ok(im.ncomp, im.width, im.height, im.hs, im.vs, im.transform);
+        if (!s_ok) {
+            im.width = im.height = 0;
+            im.ncomp = im.hs = im.vs = 1;
+            im.transform = im.stuffed = 0;
+            im.stream_bytes = im.restart_interval = im.n_intervals = 0;
+        }
+    }
+    __syncthreads();
+    if (!s_ok || im.stuffed != 1) return;
     __shared__ int wsum[4];
     __shared__ unsigned char lastb[256];
     __shared__ int s_marker;
@@ -461,7 +507,7 @@ __global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char*
     if (tid < 64) sh.nat[tid] = jp_natural[tid];
     if (tid == 0) {
         sh.end_p = -1;
-        sh.bad = 0;
+        sh.bad = im.width < 1;                          // (the empty image jpeg_unstuff_kernel left for a record it refused: status 1)
     }
     if (im.stuffed == 2) {                              // jpeg_unstuff_kernel found a marker inside the scan
         if (tid == 0) status[blockIdx.x] = 3;
@@ -775,11 +821,11 @@ __device__ __forceinline__ unsigned jp_rgb(int Y, int cbs, int crs) {          /
 }
 
 // The chroma sample of source column x: r0 = the chroma row of the pixel's own row, r1 = the context row (2x2 only), both indexed
-// by chroma column - `off`. mode (JpegGeom): 0 copy, 1 h2v1_fancy_upsample, 2 h2v2_fancy_upsample
+// by chroma column - `off`. mode (JpegGeom): JM_COPY, JM_H2V1 h2v1_fancy_upsample, JM_H2V2 h2v2_fancy_upsample
 __device__ __forceinline__ int jp_chroma(const unsigned char* r0, const unsigned char* r1, int off, int x, int dw, int mode) {
-    if (mode == 0) return r0[x - off];
+    if (mode == JM_COPY) return r0[x - off];
     const int cx = x >> 1, i = cx - off;
-    if (mode == 1) {
+    if (mode == JM_H2V1) {
         const int p = r0[i];
         if (x & 1) return cx == dw - 1 ? p : (3 * p + r0[i + 1] + 2) >> 2;
         return cx == 0 ? p : (3 * p + r0[i - 1] + 1) >> 2;
@@ -789,9 +835,34 @@ __device__ __forceinline__ int jp_chroma(const unsigned char* r0, const unsigned
     return cx == 0 ? (4 * s + 8) >> 4 : (3 * s + 3 * r0[i - 1] + r1[i - 1] + 8) >> 4;
 }
 
-__device__ __forceinline__ int jp_context_row(const JpegGeom& g, int y) {      // h2v2: the other chroma row of source row y
+__device__ __forceinline__ int jp_context_row(const JpegGeom& g, int y) {      // h2v2, h1v2: the other chroma row of source row y
     const int cy = y >> 1;
     return (y & 1) ? (cy + 1 < g.dh ? cy + 1 : g.dh - 1) : (cy > 0 ? cy - 1 : 0);
+}
+
+// jp_chroma for any mode: also JM_H1V2 h1v2_fancy_upsample (r1: the context row; k: the rounding bias, 1 in
+// an even row and 2 in an odd one; no horizontal filtering, at any width) and JM_REPL int_upsample (k: JpegGeom.sx)
+__device__ __forceinline__ int jp_chroma_more(const unsigned char* r0, const unsigned char* r1, int off, int x, int dw, int samp, int k) {
+    if (samp == JM_H1V2) return (3 * r0[x - off] + r1[x - off] + k) >> 2;
+    if (samp == JM_REPL) return r0[(x >> k) - off];
+    return jp_chroma(r0, r1, off, x, dw, samp);
+}
+
+// The pixel of three upsampled samples: jdcolor.c's conversion, or none for an RGB-coded file (JpegGeom.rgb). Both are computed and
+// one is selected, so that the record's transform is needed only here, behind the loads of the samples.
+__device__ __forceinline__ unsigned jp_color(bool rgb, int c0, int c1, int c2) {
+    const unsigned v = jp_rgb(c0, c1, c2), raw = (unsigned)c0 | ((unsigned)c1 << 8) | ((unsigned)c2 << 16);
+    return rgb ? raw : v;
+}
+
+// jp_pixel for the modes behind the first three: a colour pixel of luma sample Y
+__device__ __forceinline__ unsigned jp_pixel_more(const JpegGeom& g, int x, int y, int Y) {
+    const bool vfancy = g.mode == JM_H1V2;
+    const int cy = y >> g.sy, oy = vfancy ? jp_context_row(g, y) : cy;
+    const int k = vfancy ? 1 + (y & 1) : g.sx;
+    int cc[2];
+    for (int c = 0; c < 2; ++c) cc[c] = jp_chroma_more(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, g.mode, k);
+    return jp_color(g.rgb, Y, cc[0], cc[1]);
 }
 
 // One pixel (x, y) of the image straight from the planes in memory
@@ -801,15 +872,17 @@ __device__ __forceinline__ unsigned jp_pixel(const JpegGeom& g, int x, int y) {
     int cc[2];
     // (the sampling decided once for both chroma planes, a constant for jp_chroma in each branch: with jp_chroma left to decide per
     // plane, jpeg_color_kernel took 8.5 instead of 8.1 ms over 435 photos of 2 000 x 1 500)
-    if (g.mode == 0) {
-        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, 0);
-    } else if (g.mode == 1) {
-        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, 1);
-    } else {
+    if (g.mode == JM_COPY) {
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, JM_COPY);
+    } else if (g.mode == JM_H2V1) {
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)y * g.cw, nullptr, 0, x, g.dw, JM_H2V1);
+    } else if (g.mode == JM_H2V2) {
         const int cy = y >> 1, oy = jp_context_row(g, y);
-        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, 2);
+        for (int c = 0; c < 2; ++c) cc[c] = jp_chroma(g.pc[c] + (size_t)cy * g.cw, g.pc[c] + (size_t)oy * g.cw, 0, x, g.dw, JM_H2V2);
+    } else {
+        return jp_pixel_more(g, x, y, Y);
     }
-    return jp_rgb(Y, cc[0], cc[1]);
+    return jp_color(g.rgb, Y, cc[0], cc[1]);
 }
 
 __device__ __forceinline__ unsigned jp_pixel_clamped(const JpegGeom& g, int x, int y) {       // coordinates clamped into the image
@@ -877,8 +950,11 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
     unsigned char* dst = scratch + j.tmp_off + (size_t)row0 * n_px * 3;
     // the band's source rows (consecutive; clamped into the image whatever the job says)
     const int ylo = min(max(j.r0 + row0, 0), g.H - 1), yhi = min(max(j.r0 + row0 + nr - 1, 0), g.H - 1);
-    const int cylo = g.mode == 2 ? max((ylo >> 1) - 1, 0) : ylo;                       // first staged chroma row
-    const int ncr = g.mode == 2 ? min((yhi >> 1) + 1, g.dh - 1) - cylo + 1 : nr;      // staged chroma rows (2x2: <= JF_ROWS / 2 + 3)
+    // the staged chroma rows: with vertical fancy upsampling (2x2, 1x2) a band's own rows and their neighbours, <= JF_ROWS / 2 + 3;
+    // else the rows y >> sy of the band's rows - the band's rows themselves (sy = 0), or at most three (1x4)
+    const bool vfancy = g.mode == JM_H2V2 || g.mode == JM_H1V2, hfancy = g.mode == JM_H2V1 || g.mode == JM_H2V2;
+    const int cylo = vfancy ? max((ylo >> 1) - 1, 0) : g.sy ? ylo >> g.sy : ylo;       // first staged chroma row
+    const int ncr = vfancy ? min((yhi >> 1) + 1, g.dh - 1) - cylo + 1 : g.sy ? (yhi >> g.sy) - cylo + 1 : nr;
 
     for (int x0 = 0; x0 < n_px;) {
         // ---- the chunk: outputs [x0, x1) read the source columns [sx0, sx1)
@@ -910,9 +986,12 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
         // ---- stage
         const int yb = sx0 & ~7, ye = min((sx1 + 7) & ~7, g.yw);
         int cb = yb, ce = ye;
-        if (g.mode) {
+        if (hfancy) {
             cb = max((sx0 >> 1) - 1, 0) & ~7;
             ce = min((min(((sx1 - 1) >> 1) + 1, g.dw - 1) + 8) & ~7, g.cw);
+        } else if (g.sx && span > 0) {                                          // 4x1: a quarter of the columns
+            cb = (sx0 >> g.sx) & ~7;
+            ce = min((((sx1 - 1) >> g.sx) + 8) & ~7, g.cw);
         }
         if (span > 0) {
             const int nu = (ye - yb) >> 3;
@@ -924,7 +1003,7 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
                 const int nc = (ce - cb) >> 3;
                 for (int i = tid; i < 2 * ncr * nc; i += JF_T) {
                     const int c = i / (ncr * nc), t = i - c * ncr * nc, r = t / nc, u = t - r * nc;
-                    const int cy = g.mode == 2 ? cylo + r : min(ylo + r, g.H - 1);
+                    const int cy = vfancy || g.sy ? cylo + r : min(ylo + r, g.H - 1);
                     *reinterpret_cast<uint2*>(&s_c[c][r][8 * u]) = *reinterpret_cast<const uint2*>((c ? g.pc[1] : g.pc[0]) + (size_t)cy * g.cw + cb + 8 * u);
                 }
             }
@@ -941,14 +1020,18 @@ __global__ void __launch_bounds__(JF_T) jpeg_color_resize_h_kernel(const JpegIma
         // ---- convert
         for (int r = 0; r < nr; ++r) {
             const int y = min(ylo + r, g.H - 1);
-            const int t0 = g.mode == 2 ? (y >> 1) - cylo : r, t1 = g.mode == 2 ? jp_context_row(g, y) - cylo : r;
-            for (int p = tid; p < span; p += JF_T) {
-                const int x = sx0 + p;
-                const int Y = s_y[r][x - yb];
-                unsigned v = (unsigned)Y * 0x010101u;
-                if (g.color) v = jp_rgb(Y, jp_chroma(s_c[0][t0], s_c[0][t1], cb, x, g.dw, g.mode), jp_chroma(s_c[1][t0], s_c[1][t1], cb, x, g.dw, g.mode));
-                s_rgb[r][p] = v;
-            }
+            const int t0 = vfancy || g.sy ? (y >> g.sy) - cylo : r, t1 = vfancy ? jp_context_row(g, y) - cylo : t0;
+            const int k = g.mode == JM_H1V2 ? 1 + (y & 1) : g.sx;                  // jp_chroma_more's last argument
+            // (the mode decided once per row, a constant for jp_chroma in each loop, as in jp_pixel)
+            const unsigned char *yr = s_y[r], *a0 = s_c[0][t0], *a1 = s_c[0][t1], *b0 = s_c[1][t0], *b1 = s_c[1][t1];
+            const auto row = [&](auto&& px) {
+                for (int p = tid; p < span; p += JF_T) s_rgb[r][p] = px(sx0 + p, (int)yr[sx0 + p - yb]);
+            };
+            if (!g.color) row([&](int, int Y) { return (unsigned)Y * 0x010101u; });
+            else if (g.rgb || g.mode > JM_H2V2) row([&](int x, int Y) { return jp_color(g.rgb, Y, jp_chroma_more(a0, a1, cb, x, g.dw, g.mode, k), jp_chroma_more(b0, b1, cb, x, g.dw, g.mode, k)); });
+            else if (g.mode == JM_COPY) row([&](int x, int Y) { return jp_rgb(Y, jp_chroma(a0, a1, cb, x, g.dw, JM_COPY), jp_chroma(b0, b1, cb, x, g.dw, JM_COPY)); });
+            else if (g.mode == JM_H2V1) row([&](int x, int Y) { return jp_rgb(Y, jp_chroma(a0, a1, cb, x, g.dw, JM_H2V1), jp_chroma(b0, b1, cb, x, g.dw, JM_H2V1)); });
+            else row([&](int x, int Y) { return jp_rgb(Y, jp_chroma(a0, a1, cb, x, g.dw, JM_H2V2), jp_chroma(b0, b1, cb, x, g.dw, JM_H2V2)); });
         }
         __syncthreads();
         // ---- resample
@@ -1012,7 +1095,8 @@ struct JpegProgImage {         // mirrors clipmi_jpeg_progressive_image
     int ncomp;
     int hs, vs;
     int first_scan, n_scans;
-    int reserved[5];
+    int transform;             // clipmi_jpeg_progressive_image.reserved[0]: as JpegImage's
+    int reserved[4];
     unsigned char quant[3][64];
 };
 
@@ -1098,8 +1182,8 @@ __global__ void __launch_bounds__(JPP_T) jpeg_progressive_kernel(const unsigned 
     const int ncomp = pim.ncomp;
     const int nsc = pim.n_scans, s0 = pim.first_scan;
     short* coef = coef_all + pim.coef_off * 64;
-    const bool valid = nsc >= 1 && nsc <= JPP_MAX_SCANS && s0 >= 0 && s0 <= nscans_all - nsc && (ncomp == 1 || ncomp == 3) &&
-                       pim.width >= 1 && pim.height >= 1 && (ncomp == 1 || (pim.hs >= 1 && pim.hs <= 2 && pim.vs >= 1 && pim.vs <= pim.hs));
+    const bool valid = nsc >= 1 && nsc <= JPP_MAX_SCANS && s0 >= 0 && s0 <= nscans_all - nsc &&
+                       jp_record_ok(ncomp, pim.width, pim.height, pim.hs, pim.vs, pim.transform);
     JpegImage r{};                                      // the record jpeg_idct_kernel / jpeg_color_kernel read
     r.coef_off = pim.coef_off;
     r.out_off = pim.out_off;
@@ -1111,6 +1195,7 @@ __global__ void __launch_bounds__(JPP_T) jpeg_progressive_kernel(const unsigned 
         r.ncomp = ncomp;
         r.hs = pim.hs;
         r.vs = pim.vs;
+        r.transform = pim.transform;
     }
     const JpegGeom g = jpeg_geom(&r);                    // (of the record written: no division by a sampling factor not checked)
     const int hs = g.hs, vs = g.vs, hv = g.hv, bpm = g.bpm, mx = g.mx, my = g.my;

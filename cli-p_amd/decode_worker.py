@@ -169,7 +169,7 @@ JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then w
 
 class HDR:
     """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, device_stage.py reads them
-    through these names); [24..31] are zero. Offsets count bytes from the region's start."""
+    through these names); [26..31] are zero. Offsets count bytes from the region's start."""
     KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA or KIND_PNG_INDEX
     NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
     COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
@@ -183,6 +183,8 @@ class HDR:
     TABLES_OFF, N_TABLES = 20, 21                                   # progressive: the scans' Huffman tables
     DEPTH, CTYPE, ENTRIES = 20, 21, 22                              # KIND_PNG_ALPHA, KIND_PNG_INDEX: bit depth, colour type, palette
     #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF
+    TRANSFORM, LAYOUT = 24, 25                                      # baseline, progressive: the colour transform (0 YCbCr -> RGB, 1 none:
+    #                                                                 R, G, B components); 1: a file only LAYOUTS_BIT lets through
 
 
 KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
@@ -216,12 +218,13 @@ def _no_room(p, total):
     return p.width, p.height, -total                      # the file does not fit its region: what it would need
 
 
-def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0)):
-    """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23]) and the plan's coefficient blocks"""
+def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0)):
+    """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23], layout = TRANSFORM LAYOUT) and the plan's
+    coefficient blocks"""
     nh, nv = plan["hcoef"].size, plan["vcoef"].size
     ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
     ints[:] = [kind, p.width, p.height, *sampling, count, blocks, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
-               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific] + [0] * 8
+               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific, *layout] + [0] * 6
     if nh + nv:
         co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
         co[:nh] = plan["hcoef"]
@@ -238,12 +241,18 @@ def _write_stream(region, off, stream):
     region[off + len(stream):_stream_end(off, len(stream))] = 0
 
 
-def stage_jpeg(path, n_px, region, data=None):
+def _layout(p):
+    """HDR.TRANSFORM and HDR.LAYOUT of a record of jpeg_parse's"""
+    return p.transform, int(jpeg_parse.is_layout(p))
+
+
+def stage_jpeg(path, n_px, region, data=None, layouts=False):
     """For the decode on the device (csrc/jpeg.hip): read the file, walk its markers (jpeg_parse.parse) and lay out in `region`
     [header | quantisation steps | Huffman tables | resize plan coefficients | entropy-coded segment, followed by >= 16 zero
     bytes | the restart intervals' offsets]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit the region;
-    raises jpeg_parse.Unsupported for files Pillow has to decode."""
-    p = jpeg_parse.parse(_contents(path, data), keep_stuffing=True)     # (a plain slice where the file allows: the device removes the byte stuffing)
+    raises jpeg_parse.Unsupported for files Pillow has to decode. layouts: the request allows luma 1x2 / 4x1 / 1x4 and RGB-coded
+    files (jpeg_parse.parse(layouts=True)); without it such a file raises Unsupported, as ever."""
+    p = jpeg_parse.parse(_contents(path, data), keep_stuffing=True, layouts=layouts)     # (a plain slice where the file allows: the device removes the byte stuffing)
     plan = _plan(p.width, p.height, n_px)
     o_stream = _data_off(plan)
     o_int = _stream_end(o_stream, len(p.stream))
@@ -251,7 +260,8 @@ def stage_jpeg(path, n_px, region, data=None):
     total = (o_int + 4 * n_int + 15) // 16 * 16
     if total > region.size:
         return _no_room(p, total)
-    _write_head(region, KIND_BASELINE, p, (p.ncomp, p.hs, p.vs), len(p.stream), p.blocks(), plan, (p.ri, n_int, o_int, p.stuffed))
+    _write_head(region, KIND_BASELINE, p, (p.ncomp, p.hs, p.vs), len(p.stream), p.blocks(), plan, (p.ri, n_int, o_int, p.stuffed),
+                _layout(p))
     region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
     region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 6 * jpeg_parse.TABLE_BYTES] = np.frombuffer(b"".join(p.tables), np.uint8)
     _write_stream(region, o_stream, p.stream)
@@ -264,14 +274,14 @@ def stage_jpeg(path, n_px, region, data=None):
 PROG_SCAN_BYTES = 64      # one scan record in a progressive region: jpeg.SCAN's layout (clipmi_jpeg_scan), offsets region-relative
 
 
-def stage_jpeg_progressive(path, n_px, region, data=None):
+def stage_jpeg_progressive(path, n_px, region, data=None, layouts=False):
     """For the progressive decode on the device (csrc/jpeg.hip jpeg_progressive_kernel): read the file, walk its markers
     (jpeg_parse.parse_progressive) and lay out in `region` [header | quantisation steps | resize plan coefficients | scan records |
     the scans' Huffman tables | the scans' entropy-coded segments without byte stuffing, each 16-byte aligned and followed by
     >= 16 zero bytes]. A scan record's stream_off counts from the region's start and its table indices from the region's first
     table. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises jpeg_parse.Unsupported for files
-    Pillow has to decode."""
-    p = jpeg_parse.parse_progressive(_contents(path, data))
+    Pillow has to decode. layouts: as stage_jpeg's."""
+    p = jpeg_parse.parse_progressive(_contents(path, data), layouts=layouts)
     plan = _plan(p.width, p.height, n_px)
     tables = {}
     for sc in p.scans:
@@ -287,7 +297,8 @@ def stage_jpeg_progressive(path, n_px, region, data=None):
         total = _stream_end(total, len(sc.stream))
     if total > region.size:
         return _no_room(p, total)
-    _write_head(region, KIND_PROGRESSIVE, p, (p.ncomp, p.hs, p.vs), len(p.scans), p.blocks(), plan, (o_tab, len(tables), 0, 0))
+    _write_head(region, KIND_PROGRESSIVE, p, (p.ncomp, p.hs, p.vs), len(p.scans), p.blocks(), plan, (o_tab, len(tables), 0, 0),
+                _layout(p))
     region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
     rec = np.frombuffer(region, dtype=np.int32, count=PROG_SCAN_BYTES // 4 * len(p.scans), offset=o_scans).reshape(len(p.scans), -1)
     rec[:] = 0
@@ -363,6 +374,9 @@ PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
           # alpha, palette and low-depth PNG files: one bit of the mode for both kinds, one stats key
           Kind(KIND_PNG_ALPHA, 16, "png", _stage_png_kind(KIND_PNG_ALPHA), "png_mode_files", "decoded"),
           Kind(KIND_PNG_INDEX, 16, "png", _stage_png_kind(KIND_PNG_INDEX), "png_mode_files", "decoded"))
+LAYOUTS_BIT = 32           # a bit of the mode that adds no kind: the two JPEG stagers run with layouts=True (jpeg_parse.parse(layouts=True));
+#                            encode_files counts the files it lets through (HDR.LAYOUT) under LAYOUTS_STAT
+LAYOUTS_STAT = "jpeg_layout_files"
 PARSED_KINDS = frozenset(k.kind for k in PARSED)
 REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + PARSED)
 WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
@@ -371,7 +385,7 @@ WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a large
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (the bits of FULL_SIZE and PARSED) |
+         what the region may take (the bits of FULL_SIZE and PARSED, and LAYOUTS_BIT) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
@@ -423,7 +437,7 @@ def serve(fin, fout):
                     if full is not None or wanted is not None or not mode & k.bit or magic != k.magic:
                         continue
                     try:
-                        full = k.stager(fname, n_px, region, data)
+                        full = k.stager(fname, n_px, region, data, **({"layouts": True} if mode & LAYOUTS_BIT and k.magic == "jpeg" else {}))
                     except Exception:                          # not a file for this device decoder: the next one, or Pillow
                         full = None
                     if full is not None and full[2] < 0:

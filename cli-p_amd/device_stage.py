@@ -82,6 +82,7 @@ def jpeg_records(bigview, n, cap, slots, comp, n_px):
     recs["ncomp"], recs["hs"], recs["vs"] = hd[:, HDR.NCOMP], hd[:, HDR.HS], hd[:, HDR.VS]
     recs["restart_interval"], recs["n_intervals"] = hd[:, HDR.RESTART_INTERVAL], hd[:, HDR.N_INTERVALS]
     recs["intervals_off"], recs["stuffed"] = slots * cap + hd[:, HDR.INTERVALS_OFF], hd[:, HDR.STUFFED]
+    recs["reserved"] = hd[:, HDR.TRANSFORM]                  # (the colour transform, clipmi_jpeg_image)
     recs["quant"] = st(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n3, 3, 64)
     # the Huffman tables: distinct six-table sets first (files of one encoder share theirs), then distinct tables
     tabs = st(bigview[JPEG_TABLES_OFF:], shape=(n, 6 * J.TABLE_BYTES), strides=(cap, 1))[slots]
@@ -112,6 +113,7 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
     recs["coef_off"], recs["out_off"], recs["width"], recs["height"] = np.cumsum(blocks) - blocks, out_off, hd[:, HDR.W], hd[:, HDR.H]
     recs["ncomp"], recs["hs"], recs["vs"] = hd[:, HDR.NCOMP], hd[:, HDR.HS], hd[:, HDR.VS]
     recs["first_scan"], recs["n_scans"] = np.cumsum(nscans) - nscans, nscans
+    recs["reserved"][:, 0] = hd[:, HDR.TRANSFORM]            # (the colour transform, clipmi_jpeg_progressive_image)
     recs["quant"] = np.lib.stride_tricks.as_strided(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n4, 3, 64)
     scans = np.zeros(int(nscans.sum()), dtype=J.SCAN)
     pool_t = {}
@@ -249,6 +251,12 @@ def jpeg_fused_default():
     return os.environ.get("CLIPMI_DEVICE_JPEG_FUSED", "0") not in ("", "0")
 
 
+def jpeg_layouts_default():
+    """$CLIPMI_DEVICE_JPEG_LAYOUTS ("1" = on), off when unset"""
+    import os
+    return os.environ.get("CLIPMI_DEVICE_JPEG_LAYOUTS", "0") not in ("", "0")
+
+
 def file_need(hd, fmt, n_px):
     """Bytes of HBM each file of one kind needs while its group is decoded, out of the region headers hd ([n][JPEG_HDR_INTS]) and the
     kind's row fmt of formats(): what its decoder needs, its full-size decoded rows (none where the decode entry transforms too)
@@ -278,7 +286,7 @@ class PinnedRing:
 
 class Pending:
     """What the consumer checks behind a batch's encode step, and what has to live until then"""
-    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good")
+    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good", "layout_files")
 
     def __init__(self):
         self.keep = []           # device tensors the queued kernels read and write
@@ -286,14 +294,16 @@ class Pending:
         self.slots = None        # the slot of each status
         self.count_ok = []       # (stats key, lo, hi): ranges of `status` whose zeros count as files the device decoded
         self.chunk = self.good = None      # the batch's paths and its mask of good slots, for the files that go back to Pillow
+        self.layout_files = 0    # staged JPEG files that only the layouts switch lets through (HDR.LAYOUT; decode_worker.LAYOUTS_STAT)
 
 
 # One group of a kind's files: its packed arrays on the device and their offsets, its files, its largest nrows, its decode entry's name
 # and call (see _jpeg_group), where its statuses start in the batch's tensor (bytes)
 GroupCall = namedtuple("GroupCall", "dsmall offs n_files max_rows name decode status_off")
 # The decodes and transforms of a batch's files of one kind, ready for the side stream: the groups run one after the other through one
-# workspace, one buffer of decoded rows (None: the decode entry transforms too) and one of scratch rows
-KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch")
+# workspace, one buffer of decoded rows (None: the decode entry transforms too) and one of scratch rows; layout_files: how many of the
+# files only the layouts switch lets through (HDR.LAYOUT, 0 in a PNG region)
+KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files", defaults=(0,))
 
 
 class DeviceStage:
@@ -344,7 +354,7 @@ class DeviceStage:
         ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
         rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev) if fmt.entry is not None else None
         scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
-        return KindLaunch(fmt, calls, ws, rgb, scratch)
+        return KindLaunch(fmt, calls, ws, rgb, scratch, int(hd[:, HDR.LAYOUT].sum()))
 
     def _launch_kind(self, k, base, devt, status):
         for c in k.calls:
@@ -402,6 +412,7 @@ class DeviceStage:
                     continue
                 k = self._stage_kind(self.formats[kind.kind], bigview, n, cap, slots, comp, status_at)
                 kind_launches.append(k)
+                pending.layout_files += k.layout_files
                 pending.keep += [c.dsmall for c in k.calls] + [k.ws, k.rgb, k.scratch]
                 if kind.counts == "decoded":
                     pending.count_ok.append((kind.stat, status_at, status_at + len(slots)))

@@ -4,18 +4,20 @@ The host walks the markers (and removes the 0xFF00 byte stuffing, unless it leav
 rest (Huffman decode in self-synchronising subsequences, DC prediction, jpeg_idct_islow, fancy upsampling, YCbCr -> RGB) and leaves Pillow's
 bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_crop_rgb8` takes (resize.py). Files this
 parser does not let through (progressive, CMYK / RGB-coded, 12-bit, odd sampling, anything that is not a
-JPEG) raise `Unsupported` and stay with Pillow in the decode workers - that is a choice of decoder per file format, made
-on the host from the file's own header; a file the device then reports (status != 0: 1 an invalid Huffman code, 2 the data
-ended early or ran over, 3 a marker inside a segment handed over with its stuffing, 4 a block whose IDCT leaves the range where
+JPEG; with `layouts=True` luma 1x2 / 4x1 / 1x4 and RGB-coded files pass) raise `Unsupported` and stay with Pillow in the
+decode workers - that is a choice of decoder per file format, made on the host from the file's own header; a file the
+device then reports (status != 0: 1 an invalid Huffman code, 2 the data ended early or ran over, 3 a marker inside a segment handed over with its stuffing, 4 a block whose IDCT leaves the range where
 libjpeg-turbo's provably equals the device's) goes the same way, so that Pillow's error handling stays the reference's.
 `transform_files` goes one step further: decode and the CLIP transform's resize + crop in one library call, without the full-size
 RGB rows in between (clipmi_jpeg_decode_transform_rgb8, opt-in in the pipeline: encode_files(jpeg_fused=True)).
 """
+from functools import partial
+
 import numpy as np
 import torch
 
 from . import _lib
-from .jpeg_parse import TABLE_BYTES, Parsed, Progressive, Unsupported, parse, parse_progressive  # noqa: F401
+from .jpeg_parse import TABLE_BYTES, Parsed, Progressive, Unsupported, is_layout, parse, parse_progressive  # noqa: F401
 
 IMAGE = np.dtype([("stream_off", "<i8"), ("coef_off", "<i8"), ("out_off", "<i8"), ("intervals_off", "<i8"), ("stream_bytes", "<i4"),
                   ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("dc_tbl", "<i4", 3),
@@ -24,8 +26,16 @@ IMAGE = np.dtype([("stream_off", "<i8"), ("coef_off", "<i8"), ("out_off", "<i8")
 assert IMAGE.itemsize == 288
 
 
-def pack(items):
-    """Parsed records -> (IMAGE array, tables uint8 [nt][288], streams uint8, out_bytes, total_blocks, max_blocks, max_pixels)"""
+def _opted_in(items, layouts):
+    """The records of the layouts that are opt-in (jpeg_parse.parse(layouts=True)) pass only where the caller opted in too"""
+    if not layouts and any(is_layout(it) for it in items):
+        raise Unsupported("a record of parse(layouts=True) packed without layouts=True")
+
+
+def pack(items, layouts=False):
+    """Parsed records -> (IMAGE array, tables uint8 [nt][288], streams uint8, out_bytes, total_blocks, max_blocks, max_pixels)
+    layouts: the records may be those parse(layouts=True) adds - their sampling factors and colour transform travel in the record"""
+    _opted_in(items, layouts)
     recs = np.zeros(len(items), dtype=IMAGE)
     pool = {}
     soff = coff = ooff = 0
@@ -38,7 +48,7 @@ def pack(items):
         idx = [pool.setdefault(t, len(pool)) for t in it.tables]
         r["dc_tbl"], r["ac_tbl"] = idx[0::2], idx[1::2]
         r["quant"] = it.quant
-        r["stuffed"] = it.stuffed
+        r["stuffed"], r["reserved"] = it.stuffed, it.transform      # (reserved: the colour transform, clipmi_jpeg_image)
         pad = (-len(it.stream)) % 16 + 16
         pieces.append(it.stream)
         pieces.append(b"\0" * pad)
@@ -87,10 +97,11 @@ def _decode_device(items, device, packer, workspace, entry):
     return out, recs, status
 
 
-def decode_device(items, device, stream=None):
+def decode_device(items, device, stream=None, layouts=False):
     """Parsed records -> (out uint8 device tensor, records, status int32 device tensor): the RGB rows of image k start at
     records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is."""
-    return _decode_device(items, device, pack, lambda L, n, blocks, nt: L.clipmi_jpeg_workspace_bytes(blocks, nt), "clipmi_jpeg_decode_rgb8")
+    return _decode_device(items, device, partial(pack, layouts=layouts), lambda L, n, blocks, nt: L.clipmi_jpeg_workspace_bytes(blocks, nt),
+                          "clipmi_jpeg_decode_rgb8")
 
 
 def _decode_files(blobs, device, parser, decode):
@@ -116,11 +127,13 @@ def _decode_files(blobs, device, parser, decode):
     return res
 
 
-def decode_files(blobs, device, keep_stuffing=False):
+def decode_files(blobs, device, keep_stuffing=False, layouts=False):
     """JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
     device reported it corrupt). Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM.
-    keep_stuffing: hand the segments over as they are in the file and let the device remove the byte stuffing (the pipeline's form)."""
-    return _decode_files(blobs, device, lambda b: parse(b, keep_stuffing=keep_stuffing), decode_device)
+    keep_stuffing: hand the segments over as they are in the file and let the device remove the byte stuffing (the pipeline's form).
+    layouts: also decode luma 1x2 / 4x1 / 1x4 and RGB-coded files (jpeg_parse.parse(layouts=True))."""
+    return _decode_files(blobs, device, lambda b: parse(b, keep_stuffing=keep_stuffing, layouts=layouts),
+                         partial(decode_device, layouts=layouts))
 
 
 # ---- progressive files (jpeg_parse.parse_progressive; csrc/jpeg.hip jpeg_progressive_kernel). Opt-in in the pipeline.
@@ -131,9 +144,10 @@ SCAN = np.dtype([("stream_off", "<i8"), ("stream_bytes", "<i4"), ("ncomp", "<i4"
 assert PIMAGE.itemsize == 256 and SCAN.itemsize == 64
 
 
-def pack_progressive(items):
+def pack_progressive(items, layouts=False):
     """Progressive records -> (PIMAGE array, SCAN array, tables uint8 [nt][288], streams uint8, out_bytes, total_blocks,
-    max_blocks, max_pixels)"""
+    max_blocks, max_pixels); layouts: as pack's"""
+    _opted_in(items, layouts)
     recs = np.zeros(len(items), dtype=PIMAGE)
     scans = np.zeros(sum(len(it.scans) for it in items), dtype=SCAN)
     pool = {}
@@ -146,6 +160,7 @@ def pack_progressive(items):
         r["coef_off"], r["out_off"] = coff, ooff
         r["width"], r["height"], r["ncomp"], r["hs"], r["vs"] = it.width, it.height, it.ncomp, it.hs, it.vs
         r["first_scan"], r["n_scans"] = ns, len(it.scans)
+        r["reserved"][0] = it.transform                     # (the colour transform, clipmi_jpeg_progressive_image)
         r["quant"] = it.quant
         for sc in it.scans:
             s = scans[ns]
@@ -167,17 +182,17 @@ def pack_progressive(items):
     return recs, scans, tables, np.frombuffer(b"".join(pieces), np.uint8), ooff, coff, max_blocks, max_pixels
 
 
-def decode_progressive_device(items, device, stream=None):
+def decode_progressive_device(items, device, stream=None, layouts=False):
     """Progressive records -> (out uint8 device tensor, records, status int32 device tensor), as decode_device: the RGB rows of
     image k start at records[k]["out_off"]. Asynchronous on torch's current stream of `device`."""
-    return _decode_device(items, device, pack_progressive, lambda L, n, blocks, nt: L.clipmi_jpeg_progressive_workspace_bytes(n, blocks, nt),
+    return _decode_device(items, device, partial(pack_progressive, layouts=layouts), lambda L, n, blocks, nt: L.clipmi_jpeg_progressive_workspace_bytes(n, blocks, nt),
                           "clipmi_jpeg_decode_progressive_rgb8")
 
 
-def decode_progressive_files(blobs, device):
+def decode_progressive_files(blobs, device, layouts=False):
     """Progressive JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder
-    or the device reported it). Synchronises; a convenience for tests and tools."""
-    return _decode_files(blobs, device, parse_progressive, decode_progressive_device)
+    or the device reported it). Synchronises; a convenience for tests and tools. layouts: as decode_files'."""
+    return _decode_files(blobs, device, partial(parse_progressive, layouts=layouts), partial(decode_progressive_device, layouts=layouts))
 
 
 # ---- decode + the transform in one call (csrc/jpeg.hip jpeg_color_resize_h_kernel): baseline and progressive files straight to
@@ -187,10 +202,11 @@ class Staged:
     __slots__ = ("n", "n_px", "device", "groups", "keep")
 
 
-def stage_transform(blobs, n_px, device, keep_stuffing=False):
+def stage_transform(blobs, n_px, device, keep_stuffing=False, layouts=False):
     """JPEG file contents (or records parse / parse_progressive returned) -> Staged: the records of both kinds packed, the
     transform planned with decode_worker's planner (resize.pack_jobs: job k writes block k of the output, whichever kind file k
-    is), everything copied to the device, workspaces allocated. Raises Unsupported for a file neither parser takes."""
+    is), everything copied to the device, workspaces allocated. Raises Unsupported for a file neither parser takes.
+    layouts: the parsers run with layouts=True, and records of those layouts are taken."""
     from . import resize
     device = torch.device(device)
     if device.type != "cuda":
@@ -200,9 +216,9 @@ def stage_transform(blobs, n_px, device, keep_stuffing=False):
     for k, b in enumerate(blobs):
         if not isinstance(b, (Parsed, Progressive)):
             try:
-                b = parse(b, keep_stuffing=keep_stuffing)
+                b = parse(b, keep_stuffing=keep_stuffing, layouts=layouts)
             except Unsupported:
-                b = parse_progressive(b)
+                b = parse_progressive(b, layouts=layouts)
         kinds[isinstance(b, Progressive)].append((k, b))
     st = Staged()
     st.n, st.n_px, st.device, st.groups, st.keep = len(blobs), n_px, device, [], []
@@ -211,11 +227,11 @@ def stage_transform(blobs, n_px, device, keep_stuffing=False):
             continue
         items = [it for _, it in members]
         if progressive:
-            recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items)
+            recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items, layouts)
             arrays = [recs, scans, tables]
             ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(items), total_blocks, len(tables)))
         else:
-            recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items)
+            recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items, layouts)
             arrays = [recs, tables]
             ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, len(tables)))
         jobs, coef, _, scratch_bytes, max_rows = resize.pack_jobs([(it.height, it.width) for it in items], n_px)
@@ -264,8 +280,9 @@ def run_transform(st, fused=True):
     return out, status[:st.n]
 
 
-def transform_files(blobs, n_px, device, fused=True):
+def transform_files(blobs, n_px, device, fused=True, layouts=False):
     """JPEG file contents, baseline and progressive alike -> (uint8 [n][3][n_px][n_px] device tensor: Pillow's decode + bicubic resize
     of the shorter side to n_px + centre crop, as decode_worker.load_uint8; int32 [n] status device tensor, as the decode entries').
-    fused=False computes the same through the decode entries and clipmi_resize_crop_rgb8, with the full-size RGB rows between."""
-    return run_transform(stage_transform(blobs, n_px, device), fused)
+    fused=False computes the same through the decode entries and clipmi_resize_crop_rgb8, with the full-size RGB rows between.
+    layouts: as stage_transform's."""
+    return run_transform(stage_transform(blobs, n_px, device, layouts=layouts), fused)

@@ -7,6 +7,11 @@ everything else (progressive, CMYK / RGB-coded, 12-bit, arithmetic coding, odd s
 Pillow refuses (a marker either does not know, a second SOI, sampling factors outside 1..4, Huffman codes that overflow their
 lengths, more than JPEG_MAX_DIMENSION or Pillow's decompression-bomb limit of pixels): those files stay with Pillow.
 That is a choice of decoder per file format, made on the host from the file's own header.
+
+`layouts=True` (both parsers; opt-in, encode_files(device_jpeg_layouts=True)) also lets through YCbCr files with luma sampling
+1x2 (4:4:0), 4x1 (4:1:1) or 1x4 and 1x1 chroma, and the three-component files libjpeg takes for RGB-coded (no JFIF marker and an
+Adobe marker with transform 0 or the component ids R, G, B) at any luma sampling the device takes: `transform` = 1 in the record,
+the three upsampled planes are the pixels. Luma 4x2, 2x4, a factor of 3, subsampled luma and CMYK / YCCK stay refused.
 """
 import re
 
@@ -35,7 +40,8 @@ class Unsupported(Exception):
 
 
 class Parsed:
-    __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "tables", "stream", "ri", "starts", "stuffed")
+    __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "tables", "stream", "ri", "starts", "stuffed", "transform")
+    # transform: the colour transform, 0 = YCbCr -> RGB (and grey), 1 = none: the components are R, G, B (parse(layouts=True) only);
     # ri: restart interval in MCUs (0: none); starts: uint32 byte offsets into `stream` of the restart intervals (None without);
     # stuffed: 1 = `stream` is the file's segment as it is, 0xFF00 stuffing included (parse(keep_stuffing=True))
 
@@ -47,12 +53,38 @@ class Parsed:
         return self.mcus() * (self.hs * self.vs + 2 if self.ncomp == 3 else 1)
 
 
-def parse(data, keep_stuffing=False):
+SAMPLINGS = ((1, 1), (2, 1), (2, 2))                 # luma sampling factors the device takes (chroma 1x1) ...
+LAYOUT_SAMPLINGS = ((1, 2), (4, 1), (1, 4))          # ... and those `layouts=True` adds
+
+
+def _sampling(comps, jfif, adobe, adobe_tf, width, layouts):
+    """The two parsers' rule for a three-component frame -> (hs, vs, transform); raises Unsupported"""
+    ids = (comps[0][0], comps[1][0], comps[2][0])
+    # jdapimin.c default_decompress_parms: which three-component files are YCbCr
+    ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
+    if not ycc and not layouts:
+        raise Unsupported("RGB-coded JPEG")
+    hs, vs = comps[0][1], comps[0][2]
+    if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1) or \
+            (hs, vs) not in (SAMPLINGS + LAYOUT_SAMPLINGS if layouts else SAMPLINGS):
+        raise Unsupported("sampling factors")
+    if hs == 2 and (width + 1) // 2 <= 2:
+        raise Unsupported("too narrow for fancy upsampling")
+    return hs, vs, 0 if ycc else 1
+
+
+def is_layout(p):
+    """Whether `layouts=True` was needed for this record (Parsed or Progressive): the files the switch adds"""
+    return p.ncomp == 3 and (p.transform != 0 or (p.hs, p.vs) in LAYOUT_SAMPLINGS)
+
+
+def parse(data, keep_stuffing=False, layouts=False):
     """JPEG file bytes -> Parsed (header fields, quantisation steps in natural order, the six Huffman tables a scan can
     name as raw 288-byte records, the entropy-coded segment without byte stuffing). Raises Unsupported.
     keep_stuffing: a file without restart intervals that ends with its EOI marker is only SLICED - the segment keeps its stuffing
     (Parsed.stuffed = 1) and the device removes it and looks for markers inside (csrc/jpeg.hip jpeg_unstuff_kernel): no pass over
-    the data on the host at all."""
+    the data on the host at all.
+    layouts: also take luma 1x2 / 4x1 / 1x4 and RGB-coded files (the module's docstring)."""
     if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
         raise Unsupported("not a JPEG file")
     n = len(data)
@@ -155,18 +187,9 @@ def parse(data, keep_stuffing=False):
     while len(tables) < 6:
         tables += tables[:2]
     if nc == 3:
-        ids = (comps[0][0], comps[1][0], comps[2][0])
-        # jdapimin.c default_decompress_parms: which three-component files are YCbCr
-        ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
-        if not ycc:
-            raise Unsupported("RGB-coded JPEG")
-        if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1) or (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)):
-            raise Unsupported("sampling factors")
-        out.hs, out.vs = comps[0][1], comps[0][2]
-        if out.hs == 2 and (width + 1) // 2 <= 2:
-            raise Unsupported("too narrow for fancy upsampling")
+        out.hs, out.vs, out.transform = _sampling(comps, jfif, adobe, adobe_tf, width, layouts)
     else:
-        out.hs = out.vs = 1
+        out.hs, out.vs, out.transform = 1, 1, 0
     out.quant, out.tables = quant, tables
     # the entropy-coded segment ends at the first marker that is not a stuffed 0xFF00 (C-speed searches: a photo's segment
     # holds thousands of stuffed bytes)
@@ -244,7 +267,7 @@ class Scan:
 
 
 class Progressive:
-    __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "scans")
+    __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "scans", "transform")      # transform: as Parsed's
 
     def mcus(self):
         hs, vs = (self.hs, self.vs) if self.ncomp == 3 else (1, 1)
@@ -274,11 +297,12 @@ def _dht(data, k, end, huff):
         k += 17 + cnt
 
 
-def parse_progressive(data):
+def parse_progressive(data, layouts=False):
     """Progressive JPEG file bytes -> Progressive (header fields, quantisation steps in natural order, the scans in file order
     with their own Huffman tables and segments). Raises Unsupported for every file the device decoder does not vouch for:
       * anything `parse` refuses in a frame header (marker whitelist, size and decompression-bomb limits, Huffman codes that
-        overflow, the YCbCr / Adobe rule, grey or luma 1x1 / 2x1 / 2x2 with 1x1 chroma, too narrow for fancy upsampling);
+        overflow, the YCbCr / Adobe rule, grey or luma 1x1 / 2x1 / 2x2 with 1x1 chroma, too narrow for fancy upsampling;
+        layouts=True widens the last two rules exactly as it does for `parse`);
       * a frame other than SOF2 (baseline files go to `parse`; SOF10 and the other arithmetic-coded frames stay with Pillow);
       * scan parameters libjpeg refuses (jdphuff.c start_pass_phuff_decoder: a DC scan with Se != 0, an AC scan of more than one
         component, Ss > Se, Se > 63, Al > 13, Ah neither 0 nor Al + 1) or only warns about (jdphuff.c: a "bogus progression" -
@@ -354,17 +378,9 @@ def parse_progressive(data):
     out = Progressive()
     out.width, out.height, out.ncomp = width, height, nc
     if nc == 3:
-        ids = (comps[0][0], comps[1][0], comps[2][0])
-        ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
-        if not ycc:
-            raise Unsupported("RGB-coded JPEG")
-        if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1) or (comps[0][1], comps[0][2]) not in ((1, 1), (2, 1), (2, 2)):
-            raise Unsupported("sampling factors")
-        out.hs, out.vs = comps[0][1], comps[0][2]
-        if out.hs == 2 and (width + 1) // 2 <= 2:
-            raise Unsupported("too narrow for fancy upsampling")
+        out.hs, out.vs, out.transform = _sampling(comps, jfif, adobe, adobe_tf, width, layouts)
     else:
-        out.hs = out.vs = 1
+        out.hs, out.vs, out.transform = 1, 1, 0
     quant = np.zeros((3, 64), np.uint8)
     for c in range(nc):
         q = qt.get(comps[c][3])

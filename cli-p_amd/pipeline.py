@@ -16,9 +16,9 @@ import numpy as np
 import torch
 
 # the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
-from .decode_worker import PARSED, PARSED_KINDS, REGION_TAGS, WANTED_TAG, load_uint8
+from .decode_worker import LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, REGION_TAGS, WANTED_TAG, load_uint8
 from .device_stage import (DeviceStage, PinnedRing, _FORMATS, _groups, _headers, _pack16, file_need, formats, jpeg_fused_default,  # noqa: F401 (the moved names stay reachable as pipeline.<name>)
-                           jpeg_records, png_records, progressive_records)
+                           jpeg_layouts_default, jpeg_records, png_records, progressive_records)
 
 
 class DecodePool:
@@ -404,6 +404,7 @@ class _Encoder:
             for k in PARSED:
                 if k.counts == "staged":
                     self.count(k.stat, sum(1 for v in d.full.values() if v[0] == k.kind))
+            self.count(LAYOUTS_STAT, r.pending.layout_files if r.pending is not None else 0)      # (DeviceStage counted: it read the headers)
         return r
 
     def submit(self, dec, cpy, j):
@@ -412,7 +413,8 @@ class _Encoder:
 
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
-                 jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None):
+                 jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None,
+                 device_jpeg_layouts=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -441,12 +443,18 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8, which convert and resample straight from
     the decoder's sample planes: the same bytes, and no full-size RGB rows (3 bytes per pixel) in HBM, so that a group under
     jpeg_group_mb holds more files. Off, nothing changes for any file.
+    device_jpeg_layouts (default $CLIPMI_DEVICE_JPEG_LAYOUTS, else off; "1" = on; takes effect only with the JPEG decode on the
+    device above): YCbCr files with luma sampling 1x2 (4:4:0: what a lossless 90-degree rotation makes of a 4:2:2 file), 4x1
+    (4:1:1) or 1x4 and the three-component files libjpeg takes for RGB-coded take the device too - baseline files, and progressive
+    ones with device_progressive, plain or through the jpeg_fused entries (jpeg_parse.parse(layouts=True)) -, the same bytes as
+    Pillow's; files the device reports go back to Pillow. Off, such files stay with Pillow as before.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
     shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoders, under the
     keys of decode_worker.PARSED (jpeg_files, jpeg_progressive_files: files staged for the device; png_files: files it decoded and
-    did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only)."""
+    did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only;
+    jpeg_layout_files: those of jpeg_files and jpeg_progressive_files that device_jpeg_layouts added, 0 with it off)."""
     n_px = model.visual.input_resolution
     dev = model.device
     use_gpu = dev.type == "cuda"
@@ -493,9 +501,12 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         device_png_modes = os.environ.get("CLIPMI_DEVICE_PNG_MODES", "0") not in ("", "0")
     if jpeg_fused is None:
         jpeg_fused = jpeg_fused_default()
+    if device_jpeg_layouts is None:
+        device_jpeg_layouts = jpeg_layouts_default()
     kind_formats = formats(jpeg_fused)
     full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
-                 (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0))
+                 (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0) |
+                 (LAYOUTS_BIT if jpeg_cap and device_jpeg_layouts else 0))
     chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
     enc = _Encoder(model, chunks, batch, pool, stats, copy_stream, resize_cap, jpeg_cap, full_cap, full_mode, jpeg_group_bytes, kind_formats)
     if pool is not None:

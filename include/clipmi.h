@@ -284,7 +284,16 @@ int clipmi_resize_crop_rgb8(const void* raw_dev, const void* jobs_dev, int njobs
  * layout clipmi_resize_crop_rgb8 takes. status_dev[i]: 0 decoded; 1 invalid Huffman code; 2 the data ended early or ran
  * over; 3 a marker inside a segment handed over with its stuffing; 4 a block outside the range where libjpeg-turbo's IDCT equals
  * the device's (a dequantised coefficient or pass-1 value beyond int16, an output beyond [-512, 511]) - such a file goes back to Pillow, whose error handling is the reference's. total_blocks = sum of the images' 8x8 blocks
- * (coef_off counts in blocks), max_blocks / max_pixels = the largest image's. */
+ * (coef_off counts in blocks), max_blocks / max_pixels = the largest image's.
+ * Further layouts (an addition to ABI 8 in the sense of the PNG note below: no new entry point, no new struct, a caller that
+ * writes 0 into `reserved` gets what it got before, CLIPMI_ABI_VERSION stays 8): the records of this entry and of the progressive
+ * one may also name luma sampling 1x2 (4:4:0, libjpeg-turbo's h1v2_fancy_upsample), 4x1 (4:1:1) or 1x4 (replication), and a colour
+ * transform of "none" for the three-component files libjpeg takes for RGB-coded - the host lets those through where its caller opts
+ * in (jpeg_parse.parse(layouts=True)). A record with other sampling factors, another transform or a size below 1 is reported with
+ * status 1 and nothing of it is decoded. Such a record comes back EMPTIED in images_dev: beside `stuffed` and `stream_bytes`, which
+ * the device rewrites in any record it unstuffs, a refused record has width, height, stream_bytes, restart_interval, n_intervals,
+ * stuffed and reserved set to 0 and ncomp, hs, vs set to 1 (an empty grey image, which gives the later kernels nothing to do). The
+ * progressive entry does not write to its records. */
 typedef struct clipmi_jpeg_image {
     int64_t stream_off;           /* bytes from streams_dev */
     int64_t coef_off;             /* the image's first block in the workspace's coefficient / sample buffers */
@@ -293,13 +302,13 @@ typedef struct clipmi_jpeg_image {
     int32_t stream_bytes;
     int32_t width, height;
     int32_t ncomp;                /* 1 or 3 */
-    int32_t hs, vs;               /* luma sampling factors (1,1) (2,1) (2,2) */
+    int32_t hs, vs;               /* luma sampling factors (1,1) (2,1) (2,2), and (1,2) (4,1) (1,4); chroma is 1x1 */
     int32_t dc_tbl[3], ac_tbl[3]; /* per component: index into tables_dev */
     int32_t restart_interval;     /* MCUs per restart interval (DRI), 0 = none */
     int32_t n_intervals;          /* ceil(MCUs / restart_interval); the RSTn markers themselves are removed from the segment */
     int32_t stuffed;              /* 1: the segment still holds the 0xFF00 byte stuffing (no restart intervals then) - the device
                                      removes it IN PLACE and rewrites stream_bytes and this field (0 done, 2 marker inside the scan) */
-    int32_t reserved;
+    int32_t reserved;             /* colour transform: 0 = YCbCr -> RGB as before, 1 = none (components are R, G, B) */
     uint8_t quant[3][64];         /* per component: quantisation steps, natural (row-major) order */
 } clipmi_jpeg_image;
 int64_t clipmi_jpeg_workspace_bytes(int64_t total_blocks, int ntables);
@@ -333,10 +342,10 @@ typedef struct clipmi_jpeg_progressive_image {
     int64_t out_off;
     int32_t width, height;
     int32_t ncomp;                /* 1 or 3 */
-    int32_t hs, vs;               /* luma sampling factors (1,1) (2,1) (2,2) */
+    int32_t hs, vs;               /* luma sampling factors (1,1) (2,1) (2,2), and (1,2) (4,1) (1,4); chroma is 1x1 */
     int32_t first_scan;           /* index into scans_dev */
     int32_t n_scans;
-    int32_t reserved[5];
+    int32_t reserved[5];          /* [0]: colour transform: 0 = YCbCr -> RGB as before, 1 = none (components are R, G, B); [1..4]: 0 */
     uint8_t quant[3][64];         /* per component: quantisation steps, natural (row-major) order */
 } clipmi_jpeg_progressive_image;
 int64_t clipmi_jpeg_progressive_workspace_bytes(int n, int64_t total_blocks, int ntables);
