@@ -64,4 +64,26 @@ __device__ __forceinline__ unsigned char rz_clip8(int v) {
 constexpr int NUM_CU = 256;           // MI355X
 constexpr int LDS_BYTES = 160 * 1024; // per CU
 
+// What an entry point has to clear, it clears with a KERNEL, not hipMemsetAsync: in a captured call the memset becomes a memset
+// node, and a replay of clipmi_jpeg_decode_transform_rgb8 was seen to decode with its coefficient block still holding what the
+// stream's previous kernel had filled the workspace with (every file status 4) - the kernel nodes of the same chain kept their
+// order in every run (tests/test_graph_capture_gpu.py). A kernel also keeps a captured call a chain of kernel nodes only.
+// [p, p + bytes) exactly; p and bytes multiples of 4 (of 16: 16-byte stores).
+static __global__ void __launch_bounds__(256) zero16_kernel(uint4* __restrict__ p, size_t n16) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n16; i += (size_t)gridDim.x * 256) p[i] = make_uint4(0u, 0u, 0u, 0u);
+}
+static __global__ void __launch_bounds__(256) zero4_kernel(unsigned* __restrict__ p, size_t n4) {
+    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += (size_t)gridDim.x * 256) p[i] = 0u;
+}
+inline hipError_t zero_async(void* p, size_t bytes, hipStream_t st) {
+    if (bytes == 0) return hipSuccess;
+    if ((reinterpret_cast<uintptr_t>(p) | bytes) & 3) return hipErrorInvalidValue;
+    const bool wide = ((reinterpret_cast<uintptr_t>(p) | bytes) & 15) == 0;
+    const size_t n = bytes / (wide ? 16 : 4), want = (n + 255) / 256;
+    const unsigned grid = (unsigned)(want < (size_t)NUM_CU * 8 ? want : (size_t)NUM_CU * 8);
+    if (wide) hipLaunchKernelGGL(zero16_kernel, dim3(grid), dim3(256), 0, st, static_cast<uint4*>(p), n);
+    else hipLaunchKernelGGL(zero4_kernel, dim3(grid), dim3(256), 0, st, static_cast<unsigned*>(p), n);
+    return hipGetLastError();
+}
+
 }  // namespace clipmi

@@ -1417,7 +1417,7 @@ static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images
     JpegImage* images = static_cast<JpegImage*>(images_dev);
     hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3((unsigned)n), dim3(256), 0, st, static_cast<unsigned char*>(streams_dev), images);
     CLIPMI_CHECK_LAUNCH("jpeg_unstuff_kernel");
-    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: memset", who);
+    if (zero_async(coef, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: zero_async", who);
     hipLaunchKernelGGL(jpeg_build_luts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
     CLIPMI_CHECK_LAUNCH("jpeg_build_luts_kernel");
     hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n), dim3(JP_T), 0, st, static_cast<const unsigned char*>(streams_dev), images,
@@ -1512,7 +1512,7 @@ static int jpeg_progressive_planes(const char* who, const void* streams_dev, con
     JpegImage* images = ar.take<JpegImage>((size_t)n);
     short* coef = ar.take<short>((size_t)total_blocks * 64);
     unsigned char* planes = ar.take<unsigned char>((size_t)total_blocks * 64);
-    if (hipMemsetAsync(coef, 0, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: memset", who);
+    if (zero_async(coef, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: zero_async", who);
     hipLaunchKernelGGL(jpeg_build_pluts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
     CLIPMI_CHECK_LAUNCH("jpeg_build_pluts_kernel");
     hipLaunchKernelGGL(jpeg_progressive_kernel, dim3((unsigned)n), dim3(JPP_T), 0, st, static_cast<const unsigned char*>(streams_dev),

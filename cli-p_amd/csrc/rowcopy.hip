@@ -262,7 +262,7 @@ extern "C" int clipmi_quantize_rows_i8(const float* db_dev, int64_t N, int E, co
 extern "C" int clipmi_rows_stats(const float* db_dev, int64_t N, int E, const float* meta_dev, float* stats2_dev, void* stream) {
     if (!db_dev || !stats2_dev || N < 1 || E < 4 || E % 4 != 0)
         return set_err(CLIPMI_EINVAL, "rows_stats: bad arguments (N=%lld E=%d; E must be a multiple of 4)", (long long)N, E);
-    if (hipMemsetAsync(stats2_dev, 0, 2 * sizeof(float), as_stream(stream)) != hipSuccess) return set_err(CLIPMI_EHIP, "rows_stats: memset");
+    if (zero_async(stats2_dev, 2 * sizeof(float), as_stream(stream)) != hipSuccess) return set_err(CLIPMI_EHIP, "rows_stats: zero_async");
     const long long want = (N + 3) / 4;
     const unsigned grid = (unsigned)(want < 8 * NUM_CU ? want : 8 * NUM_CU);
     hipLaunchKernelGGL(rows_stats_kernel, dim3(grid), dim3(256), 0, as_stream(stream), db_dev, (long long)N, E,

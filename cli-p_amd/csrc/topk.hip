@@ -953,7 +953,7 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
     if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
 
     // candidate counters: zeroed once here; every select_topk_kernel re-zeroes the ones it consumed
-    if (hipMemsetAsync(gcnt, 0, 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "hipMemsetAsync");
+    if (zero_async(gcnt, 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "topk_ip: zero_async");
     for (int q0 = 0; q0 < Q; q0 += p.QA) {
         const int qa = (Q - q0) < p.QA ? (Q - q0) : p.QA;
         ScanArgs a;

@@ -13,6 +13,9 @@
  *     (a hipStream_t passed as void*; NULL = the default stream) and is graph-capturable;
  *   - scratch memory is a caller-owned workspace whose size the matching *_workspace_bytes()
  *     function returns (0 from that function = unsupported arguments, see clipmi_last_error);
+ *   - what a workspace, scratch rows and every output hold on entry is arbitrary - a call reads nothing of them that it has
+ *     not written itself, so one workspace may serve calls of any size one after the other without being cleared -, and
+ *     `status_dev[i]` is written for every image of the call, 0 included (tests/ws_cases.py has the table, region by region);
  *   - return value 0 = enqueued; non-zero = a CLIPMI_E* code, nothing was enqueued (or, for
  *     CLIPMI_EHIP, a launch failed); the message is in clipmi_last_error() (thread-local);
  *   - re-entrant: no global mutable state apart from that thread-local error string.

@@ -10,7 +10,11 @@ row). Progressive has no file of the first kind: jpeg_parse.parse_progressive le
 (test_jpeg_progressive.py::test_parser_never_accepts_a_file_pillow_refuses holds it to that over the malformed corpus, and none of
 that corpus' files qualifies), while the baseline parser, which leaves the byte stuffing to the device, cannot see a marker inside
 the scan, and the PNG parser does not inflate the stream. Beside them an RGB BMP (full size in its region, resized on the
-device) and an RGBA PNG (Pillow's)."""
+device) and an RGBA PNG (Pillow's).
+
+The second test runs the same worker under a poisoning allocator: every CUDA tensor torch.empty returns during the device runs - the
+status tensor DeviceStage.run allocates, the workspaces, the decoded and the scratch rows, the batch tensor - starts as 0xFF bytes. A
+decoder that wrote a status only where it found an error, or read a workspace it had not written, would change the result."""
 import io
 import os
 import re
@@ -81,7 +85,29 @@ def reported_png(rng):
     return cut, no_adler
 
 
-def _mixed_worker(tmp):
+class _PoisonedEmpty:
+    """While active, every CUDA tensor torch.empty returns holds 0xFF bytes (and the device has finished writing them)"""
+
+    def __enter__(self):
+        import torch
+        self.torch, self.empty, self.count = torch, torch.empty, 0
+
+        def empty(*a, **kw):
+            t = self.empty(*a, **kw)
+            if t.is_cuda and t.numel():
+                t.view(-1).view(torch.uint8).fill_(0xFF)
+                torch.cuda.synchronize(t.device)
+                self.count += 1
+            return t
+        torch.empty = empty
+        return self
+
+    def __exit__(self, *exc):
+        self.torch.empty = self.empty
+
+
+def _mixed_worker(tmp, poison=False):
+    import contextlib
     import sys
     ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, ROOT)
@@ -136,8 +162,10 @@ def _mixed_worker(tmp):
         host = list(clipmi.pipeline.encode_files(model, files, batch=8, pool=pool, device_resize_mb=0, device_jpeg_kb=0))
         kw = dict(batch=8, pool=pool, device_resize_mb=8, device_jpeg_kb=2048, device_progressive=True, device_png=True)
         st_on, st_grp = {}, {}
-        on = list(clipmi.pipeline.encode_files(model, files, stats=st_on, **kw))
-        grp = list(clipmi.pipeline.encode_files(model, files, stats=st_grp, jpeg_group_mb=1, **kw))
+        with (_PoisonedEmpty() if poison else contextlib.nullcontext()) as poisoned:
+            on = list(clipmi.pipeline.encode_files(model, files, stats=st_on, **kw))
+            grp = list(clipmi.pipeline.encode_files(model, files, stats=st_grp, jpeg_group_mb=1, **kw))
+        assert not poison or (poisoned.count >= 8 and torch.empty is poisoned.empty), "the device runs allocate through torch.empty"
     assert [p for h in host for p in h[2]] == [base_refused, png_refused]
     assert [len(h[0]) for h in host] == [6, 8]
     for other, st in ((on, st_on), (grp, st_grp)):
@@ -149,12 +177,22 @@ def _mixed_worker(tmp):
     open(os.path.join(tmp, "ok"), "w").write("1")
 
 
-def test_statuses_reach_their_files_when_three_formats_share_a_batch(tmp_path):
+def _run_worker(tmp_path, poison):
     import subprocess
     import sys
     here = os.path.dirname(os.path.abspath(__file__))
     code = f"import sys; sys.path.insert(0, {os.path.dirname(here)!r}); sys.path.insert(0, {here!r}); " \
-           f"import test_mixed_formats_pipeline_gpu as t; t._mixed_worker({str(tmp_path)!r})"
+           f"import test_mixed_formats_pipeline_gpu as t; t._mixed_worker({str(tmp_path)!r}, poison={poison!r})"
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     assert (tmp_path / "ok").read_text() == "1"
+
+
+def test_statuses_reach_their_files_when_three_formats_share_a_batch(tmp_path):
+    _run_worker(tmp_path, poison=False)
+
+
+def test_the_same_under_an_allocator_that_poisons_every_device_tensor(tmp_path):
+    """The same vectors, failed lists and counters as the host path, with and without jpeg_group_mb=1, when nothing the device path
+    allocates starts out as zeros"""
+    _run_worker(tmp_path, poison=True)
