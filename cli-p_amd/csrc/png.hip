@@ -1,15 +1,19 @@
 // png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8), and
 // the file's own-mode pixels for alpha, palette and low-depth files (clipmi_png_decode_px8: the same inflate and Adler-32
 // kernels, png_unfilter_px_kernel with a filter unit of 1, 2 or 4 bytes and an "alpha" or "index" store).
-// The host (cli-p_amd/png_parse.py) lets through 8-bit grey and RGB files that are not interlaced and hands over the DEFLATE
-// stream behind the zlib header. Three kernels:
+// The host (cli-p_amd/png_parse.py) lets through 8-bit grey and RGB files and hands over the DEFLATE stream behind the zlib
+// header. A record may say that its file is Adam7-interlaced (bit 16 of reserved[0], see png_interlaced): the stream then holds
+// up to seven reduced images one after the other, each filtered on its own, and the unfilter kernels reconstruct them in file
+// order and scatter their pixels (PngPass, png_pixel); inflate and Adler-32 only see a byte string of another length
+// (png_scanline_bytes). Three kernels:
 //   png_inflate_kernel   one wave per image: RFC 1951 inflate into the workspace's scanline buffer, with zlib's own table checks
 //   png_unfilter_kernel  one wave per image: PNG reconstruction (None, Sub, Up, Average, Paeth) as a 64-row diagonal wavefront,
 //                        RGB8 rows out
 //   png_adler_kernel     one block per image: Adler-32 of the scanlines against the stream's trailer
 // PNG is lossless, so a file either comes back with exactly Pillow's bytes (status 0) or goes back to Pillow. Status 0 is given
 // only where zlib certainly accepts: valid data that ends with the final block's end-of-block code after exactly
-// height x (1 + width x channels) bytes, filter bytes <= 4, and a present, matching Adler-32. That covers the image data only:
+// height x (1 + width x channels) bytes (Adam7: the sum of that over the non-empty passes), filter bytes <= 4, and a present,
+// matching Adler-32. That covers the image data only:
 // that Pillow does not refuse the file for a chunk in front of or behind it is the host parser's part (png_parse.py).
 // These kernels read untrusted bytes: every stream read is bounded by stream_bytes + the 16 pad bytes, every scanline write by
 // the image's own byte count, every table index by the table's size; a malformed file ends in a status.
@@ -33,16 +37,19 @@ constexpr int PNG_PAD = 16;                 // zero bytes behind every stream
 constexpr int PNG_MAX_WIDTH = 16384;        // the unfilter kernel holds one row in LDS (48 KiB); png_parse.MAX_WIDTH
 constexpr int PNG_MAX_ROW = 49152;          // ... that many bytes: what bounds the rows of clipmi_png_decode_px8; png_parse.MAX_ROW_BYTES
 
-// The bytes of one scanline without its filter byte, and whether the record is one its entry takes. modes == 0
-// (clipmi_png_decode_rgb8): 8-bit grey or RGB, `reserved` not looked at. modes == 1 (clipmi_png_decode_px8): reserved[0] =
-// colour type << 8 | bit depth, reserved[1] = palette entries; RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4.
-__device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int64_t& row) {
+// The bytes of one scanline without its filter byte, the bits of one pixel, and whether the record is one its entry takes.
+// modes == 0 (clipmi_png_decode_rgb8): 8-bit grey or RGB, `reserved` not looked at except for the Adam7 mark (png_interlaced).
+// modes == 1 (clipmi_png_decode_px8): reserved[0] = Adam7 << 16 | colour type << 8 | bit depth, reserved[1] = palette entries;
+// RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4.
+__device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int64_t& row, int& bpp) {
     if (im.width < 1 || im.width > PNG_MAX_WIDTH) return false;
     if (!modes) {
         row = (int64_t)im.width * im.channels;
+        bpp = 8 * im.channels;
         return im.channels == 1 || im.channels == 3;
     }
-    const int ctype = im.reserved[0] >> 8, depth = im.reserved[0] & 255;
+    if (im.reserved[0] >> 17) return false;
+    const int ctype = (im.reserved[0] >> 8) & 255, depth = im.reserved[0] & 255;
     const bool low = depth == 1 || depth == 2 || depth == 4;
     int samples;
     if (ctype == 6 && depth == 8) samples = 4;
@@ -50,8 +57,59 @@ __device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int
     else if (ctype == 3 && (low || depth == 8) && im.reserved[1] >= 1 && im.reserved[1] <= (1 << depth)) samples = 1;
     else if (ctype == 0 && low) samples = 1;
     else return false;
-    row = ((int64_t)im.width * samples * depth + 7) >> 3;
+    bpp = samples * depth;
+    row = ((int64_t)im.width * bpp + 7) >> 3;
     return im.channels == samples && row <= PNG_MAX_ROW;
+}
+
+// Whether the record's file is Adam7-interlaced. clipmi_png_decode_px8: bit 16 of reserved[0]. clipmi_png_decode_rgb8 never
+// looked at `reserved`, so only the one value 1 << 16 means Adam7 there and every other value means what it meant before.
+__device__ __forceinline__ bool png_interlaced(const PngImage& im, int modes) {
+    return modes ? ((im.reserved[0] >> 16) & 1) != 0 : im.reserved[0] == (1 << 16);
+}
+
+// Adam7: pass p holds the pixels (x0 + i dx, y0 + j dy) of the image, i < w, j < h, as an image of w x h pixels of its own. The
+// seven passes partition the image; w or h is 0 where the image has no pixel of the pass, and such a pass has no bytes at all.
+struct PngPass {
+    int x0, y0, dx, dy, w, h;
+};
+
+// (x0, y0, dx, dy) of pass p = 0 .. 6, one nibble each: (0,0,8,8) (4,0,8,8) (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2);
+// png_parse.ADAM7. width, height >= 1.
+__device__ __forceinline__ PngPass png_pass(int width, int height, int p) {
+    const int s = 4 * p;
+    PngPass ps;
+    ps.x0 = (0x0102040 >> s) & 15;
+    ps.y0 = (0x1020400 >> s) & 15;
+    ps.dx = (0x1224488 >> s) & 15;
+    ps.dy = (0x2244888 >> s) & 15;
+    ps.w = width > ps.x0 ? (width - ps.x0 - 1) / ps.dx + 1 : 0;
+    ps.h = height > ps.y0 ? (height - ps.y0 - 1) / ps.dy + 1 : 0;
+    return ps;
+}
+
+// The one pass of a file that is not interlaced: the image
+__device__ __forceinline__ PngPass png_whole(int width, int height) { return PngPass{0, 0, 1, 1, width, height}; }
+
+// Bytes of filtered scanlines of the record, interlace included: what the stream has to inflate to, what the Adler-32 covers and
+// what the unfilter kernels walk. row, bpp: png_row_bytes'. A pass row of w pixels has 1 + ceil(w x bpp / 8) bytes, never more
+// than a full row.
+__device__ __forceinline__ int64_t png_scanline_bytes(const PngImage& im, int modes, int64_t row, int bpp) {
+    if (im.height < 1) return 0;
+    if (!png_interlaced(im, modes)) return (int64_t)im.height * (1 + row);
+    int64_t n = 0;
+    for (int p = 0; p < 7; p++) {
+        const PngPass ps = png_pass(im.width, im.height, p);
+        if (ps.w && ps.h) n += (int64_t)ps.h * (1 + (((int64_t)ps.w * bpp + 7) >> 3));
+    }
+    return n;
+}
+
+// The image pixel (counted row by row) of pixel x of row `row` of a pass
+template <bool LACE>
+__device__ __forceinline__ int64_t png_pixel(const PngPass& ps, int width, int row, int x) {
+    if (!LACE) return (int64_t)row * width + x;
+    return ((int64_t)ps.y0 + (int64_t)row * ps.dy) * width + ps.x0 + x * ps.dx;
 }
 
 __constant__ unsigned char png_cl_order[19] = {16, 17, 18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15};
@@ -166,8 +224,9 @@ __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char*
     const int lane = threadIdx.x;
     const PngImage im = images[blockIdx.x];
     int64_t row_bytes = 0;
-    const bool known = png_row_bytes(im, modes, row_bytes);
-    const int64_t raw_bytes64 = (int64_t)im.height * (1 + row_bytes);
+    int bpp = 0;
+    const bool known = png_row_bytes(im, modes, row_bytes, bpp);
+    const int64_t raw_bytes64 = known ? png_scanline_bytes(im, modes, row_bytes, bpp) : 0;
     if (!known || im.height < 1 || im.stream_bytes < 0 || im.stream_off < 0 ||
         raw_bytes64 > 0x7fffffffLL || raw_bytes64 > max_raw || im.raw_off < 0 || (im.raw_off & 15) ||
         im.raw_off + raw_bytes64 > total_raw) {
@@ -428,24 +487,43 @@ __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, Store&
     }
 }
 
-// rows of width * 3 RGB bytes, grey replicated: what clipmi_png_decode_rgb8 leaves
-template <int CH>
+// rows of width * 3 RGB bytes, grey replicated: what clipmi_png_decode_rgb8 leaves. The stores below get the rows of one pass
+// (`ps`: the image itself where the file is not interlaced, LACE false) and put each pixel where png_pixel says it belongs in
+// the image of `width` columns: x < ps.w and row < ps.h keep every store inside the image's width x height pixels.
+template <int CH, bool LACE>
 struct PngRgbStore {
     unsigned char* out;
-    int w;
+    int width;
+    PngPass ps;
     __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
-        unsigned char* drow = out + (int64_t)row * w * 3;
 #pragma unroll
         for (int q = 0; q < 4 * CH; q++) {
             const int x = x0 + q / CH, k = q % CH;
             const unsigned char v = (unsigned char)(res[q >> 2] >> (8 * (q & 3)));
-            if (x < w) {
-                if (CH == 3) drow[(int64_t)x * 3 + k] = v;
-                else drow[(int64_t)x * 3] = drow[(int64_t)x * 3 + 1] = drow[(int64_t)x * 3 + 2] = v;
+            if (x < ps.w) {
+                unsigned char* d = out + png_pixel<LACE>(ps, width, row, x) * 3;
+                if (CH == 3) d[k] = v;
+                else d[0] = d[1] = d[2] = v;
             }
         }
     }
 };
+
+// The record's passes in file order (one, the image, where LACE is false): each non-empty pass is an image of its own - its
+// first row has a zero row above it (png_unfilter_image reads `prev` from the second band on only), its filter bytes are
+// checked, and its bytes start where the previous pass's end. png_unfilter_image ends every band with a barrier, so the LDS row
+// is free when the next pass begins. The early passes are short of rows for the 64-row wavefront (pass 1 has height / 8).
+template <int CH, bool LACE>
+__device__ void png_unfilter_rgb(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
+                                 bool& bad) {
+    for (int p = 0; p < (LACE ? 7 : 1); p++) {
+        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
+        if (ps.w == 0 || ps.h == 0) continue;
+        PngRgbStore<CH, LACE> store{out, im.width, ps};
+        png_unfilter_image<CH>(raw, store, prev, ps.w, ps.h, lane, bad);
+        raw += (int64_t)ps.h * (1 + (int64_t)ps.w * CH);
+    }
+}
 
 __global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
                                                              unsigned char* __restrict__ out, int32_t* status) {
@@ -453,13 +531,14 @@ __global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __r
     if (status[blockIdx.x] != 0) return;               // nothing was inflated: the record or the stream was refused
     const PngImage im = images[blockIdx.x];            // (width <= PNG_MAX_WIDTH: png_inflate_kernel gave status 1 otherwise)
     const int lane = threadIdx.x;
+    const unsigned char* raw = rawbuf + im.raw_off;
     bool bad = false;
-    if (im.channels == 3) {
-        PngRgbStore<3> store{out + im.out_off, im.width};
-        png_unfilter_image<3>(rawbuf + im.raw_off, store, prev, im.width, im.height, lane, bad);
+    if (png_interlaced(im, 0)) {
+        if (im.channels == 3) png_unfilter_rgb<3, true>(im, raw, out + im.out_off, prev, lane, bad);
+        else png_unfilter_rgb<1, true>(im, raw, out + im.out_off, prev, lane, bad);
     } else {
-        PngRgbStore<1> store{out + im.out_off, im.width};
-        png_unfilter_image<1>(rawbuf + im.raw_off, store, prev, im.width, im.height, lane, bad);
+        if (im.channels == 3) png_unfilter_rgb<3, false>(im, raw, out + im.out_off, prev, lane, bad);
+        else png_unfilter_rgb<1, false>(im, raw, out + im.out_off, prev, lane, bad);
     }
     if (__syncthreads_or(bad ? 1 : 0) && lane == 0) status[blockIdx.x] = 3;
 }
@@ -468,23 +547,27 @@ __global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __r
 // alpha as L L L A, grey at depth 2 / 4 as v*85 / v*17 three times and 255 (Pillow opens those files as L with these values).
 // "index": rows of width bytes, one unpacked sample each, for palette files and 1-bit grey; the most significant bits of a
 // byte come first, the padding bits at a row's end are dropped, and a sample >= `entries` sets over (status 5).
+// Like PngRgbStore the store gets the rows of one pass `ps` and scatters them: below depth 8 a pass row is packed on its own,
+// ceil(ps.w x depth / 8) bytes, and its padding bits are dropped at ps.w.
+template <bool LACE>
 struct PngPxStore {
     unsigned char* out;
     int width, ctype, depth, entries;
+    PngPass ps;
     bool over;
     __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
         if (ctype == 6 || ctype == 4) {
-            unsigned* drow = reinterpret_cast<unsigned*>(out) + (int64_t)row * width;    // (out_off is a multiple of 16)
+            unsigned* dst = reinterpret_cast<unsigned*>(out);                             // (out_off is a multiple of 16)
 #pragma unroll
             for (int p = 0; p < 4; p++) {
-                if (x0 + p >= width) break;
+                if (x0 + p >= ps.w) break;
                 unsigned v;
                 if (ctype == 6) v = res[p];
                 else {
                     const unsigned la = res[p >> 1] >> (16 * (p & 1));
                     v = (la & 255u) * 0x010101u | (la & 0xff00u) << 16;
                 }
-                drow[x0 + p] = v;
+                dst[png_pixel<LACE>(ps, width, row, x0 + p)] = v;
             }
             return;
         }
@@ -495,18 +578,39 @@ struct PngPxStore {
             const int64_t px0 = ((int64_t)x0 + q) * per;
             for (int s = 0; s < per; s++) {
                 const int64_t px = px0 + s;
-                if (px >= width) return;
+                if (px >= ps.w) return;
                 const unsigned v = (byte >> (8 - depth * (s + 1))) & mask;
+                const int64_t at = png_pixel<LACE>(ps, width, row, (int)px);
                 if (ctype == 0 && depth != 1) {
-                    reinterpret_cast<unsigned*>(out)[(int64_t)row * width + px] = v * (depth == 2 ? 85u : 17u) * 0x010101u | 0xff000000u;
+                    reinterpret_cast<unsigned*>(out)[at] = v * (depth == 2 ? 85u : 17u) * 0x010101u | 0xff000000u;
                 } else {
                     if ((int)v >= entries) over = true;
-                    out[(int64_t)row * width + px] = (unsigned char)v;
+                    out[at] = (unsigned char)v;
                 }
             }
         }
     }
 };
+
+// png_unfilter_rgb for the records of clipmi_png_decode_px8. -> a sample beyond the palette was seen (status 5)
+template <bool LACE>
+__device__ bool png_unfilter_px(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
+                                bool& bad) {
+    const int ctype = (im.reserved[0] >> 8) & 255, depth = im.reserved[0] & 255;
+    bool over = false;
+    for (int p = 0; p < (LACE ? 7 : 1); p++) {
+        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
+        if (ps.w == 0 || ps.h == 0) continue;
+        PngPxStore<LACE> store{out, im.width, ctype, depth, ctype == 3 ? im.reserved[1] : 2, ps, false};
+        const int row_bytes = (int)(((int64_t)ps.w * im.channels * depth + 7) >> 3);      // <= PNG_MAX_ROW: png_row_bytes
+        if (ctype == 6) png_unfilter_image<4>(raw, store, prev, ps.w, ps.h, lane, bad);
+        else if (ctype == 4) png_unfilter_image<2>(raw, store, prev, ps.w, ps.h, lane, bad);
+        else png_unfilter_image<1>(raw, store, prev, row_bytes, ps.h, lane, bad);
+        over |= store.over;
+        raw += (int64_t)ps.h * (1 + row_bytes);
+    }
+    return over;
+}
 
 __global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
                                                                 unsigned char* __restrict__ out, int32_t* status) {
@@ -515,15 +619,13 @@ __global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* 
     const PngImage im = images[blockIdx.x];
     const int lane = threadIdx.x;
     int64_t row_bytes = 0;
-    if (!png_row_bytes(im, 1, row_bytes)) return;      // (not reached: png_inflate_kernel gave status 1)
-    const int ctype = im.reserved[0] >> 8, depth = im.reserved[0] & 255;
-    PngPxStore store{out + im.out_off, im.width, ctype, depth, ctype == 3 ? im.reserved[1] : 2, false};
+    int bpp = 0;
+    if (!png_row_bytes(im, 1, row_bytes, bpp)) return; // (not reached: png_inflate_kernel gave status 1)
     const unsigned char* raw = rawbuf + im.raw_off;
     bool bad = false;
-    if (ctype == 6) png_unfilter_image<4>(raw, store, prev, (int)row_bytes / 4, im.height, lane, bad);
-    else if (ctype == 4) png_unfilter_image<2>(raw, store, prev, (int)row_bytes / 2, im.height, lane, bad);
-    else png_unfilter_image<1>(raw, store, prev, (int)row_bytes, im.height, lane, bad);
-    const int is_bad = __syncthreads_or(bad ? 1 : 0), is_over = __syncthreads_or(store.over ? 1 : 0);
+    const bool over = png_interlaced(im, 1) ? png_unfilter_px<true>(im, raw, out + im.out_off, prev, lane, bad)
+                                            : png_unfilter_px<false>(im, raw, out + im.out_off, prev, lane, bad);
+    const int is_bad = __syncthreads_or(bad ? 1 : 0), is_over = __syncthreads_or(over ? 1 : 0);
     if (lane == 0 && (is_bad || is_over)) status[blockIdx.x] = is_bad ? 3 : 5;
 }
 
@@ -539,8 +641,9 @@ __global__ void __launch_bounds__(PNG_ADLER_T) png_adler_kernel(const PngImage* 
     if (status[blockIdx.x] != 0) return;
     const PngImage im = images[blockIdx.x];
     int64_t row_bytes = 0;
-    png_row_bytes(im, modes, row_bytes);
-    const unsigned n = (unsigned)((int64_t)im.height * (1 + row_bytes));
+    int bpp = 0;
+    png_row_bytes(im, modes, row_bytes, bpp);
+    const unsigned n = (unsigned)png_scanline_bytes(im, modes, row_bytes, bpp);
     const unsigned char* raw = rawbuf + im.raw_off;
     const int tid = threadIdx.x;
     unsigned long long s1 = 0, s2 = 0;

@@ -169,7 +169,7 @@ JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then w
 
 class HDR:
     """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, device_stage.py reads them
-    through these names); [26..31] are zero. Offsets count bytes from the region's start."""
+    through these names); [27..31] are zero. Offsets count bytes from the region's start."""
     KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA or KIND_PNG_INDEX
     NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
     COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
@@ -185,6 +185,8 @@ class HDR:
     #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF
     TRANSFORM, LAYOUT = 24, 25                                      # baseline, progressive: the colour transform (0 YCbCr -> RGB, 1 none:
     #                                                                 R, G, B components); 1: a file only LAYOUTS_BIT lets through
+    INTERLACE = 26                                                  # the PNG kinds: 1 an Adam7 file, which only PNG_INTERLACED_BIT lets
+    #                                                                 through (its scanlines are those of its passes); 0 in a JPEG region
 
 
 KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
@@ -218,13 +220,14 @@ def _no_room(p, total):
     return p.width, p.height, -total                      # the file does not fit its region: what it would need
 
 
-def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0)):
+def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0), interlace=0):
     """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23], layout = TRANSFORM LAYOUT) and the plan's
     coefficient blocks"""
     nh, nv = plan["hcoef"].size, plan["vcoef"].size
     ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
     ints[:] = [kind, p.width, p.height, *sampling, count, blocks, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
-               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific, *layout] + [0] * 6
+               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific, *layout,
+               interlace] + [0] * 5
     if nh + nv:
         co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
         co[:nh] = plan["hcoef"]
@@ -320,7 +323,7 @@ PNG_MAX_RAW = 16 << 20      # filtered scanlines of a file the device takes: one
                             # DESIGN 4.9), so a larger file would hold up its batch on the side stream; Pillow decodes those
 
 
-def stage_png(path, n_px, region, data=None, modes=False):
+def stage_png(path, n_px, region, data=None, modes=False, interlaced=False):
     """For the PNG decode on the device (csrc/png.hip): read the file, walk its chunks (png_parse.parse) and lay out in `region`
     [header | resize plan coefficients | DEFLATE stream without the zlib header, 16-byte aligned and followed by >= 16 zero
     bytes]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises png_parse.Unsupported for files
@@ -329,8 +332,10 @@ def stage_png(path, n_px, region, data=None, modes=False):
     layout under the kinds KIND_PNG_ALPHA and KIND_PNG_INDEX (HDR.KIND), with depth, colour type and palette entries in the
     header (HDR.DEPTH ..); an index file's palette lies at JPEG_TABLES_OFF and its "coefficient blocks" are nearest_plan's two
     tables. Without it such a file raises Unsupported, as ever.
+    interlaced: the request allows Adam7 files of the kinds let through (png_parse.parse(interlaced=True)); the region has the
+    same layout and says so in HDR.INTERLACE. Without it such a file raises Unsupported, as ever.
     data: the file's contents, when the caller has read them."""
-    p = png_parse.parse(_contents(path, data), modes=modes)
+    p = png_parse.parse(_contents(path, data), modes=modes, interlaced=interlaced)
     if p.raw_bytes() > PNG_MAX_RAW:
         raise png_parse.Unsupported("more than PNG_MAX_RAW bytes of scanlines")
     plan = _plan(p.width, p.height, n_px, nearest=p.kind == "index")
@@ -339,10 +344,10 @@ def stage_png(path, n_px, region, data=None, modes=False):
     if total > region.size:
         return _no_room(p, total)
     if p.kind == "rgb":
-        _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan)
+        _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan, interlace=p.interlace)
     else:
         _write_head(region, KIND_PNG_INDEX if p.kind == "index" else KIND_PNG_ALPHA, p, (p.channels, 0, 0), len(p.stream), 0, plan,
-                    (p.depth, p.ctype, p.n_entries, 0))
+                    (p.depth, p.ctype, p.n_entries, 0), interlace=p.interlace)
         if p.kind == "index":
             region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 768] = p.palette.reshape(-1)
     _write_stream(region, o_stream, p.stream)
@@ -351,13 +356,13 @@ def stage_png(path, n_px, region, data=None, modes=False):
 
 def _stage_png_kind(kind):
     """stage_png(modes=True) for the files of one of the new kinds only: a launch group holds one kind (PARSED)"""
-    def stage(path, n_px, region, data=None):
+    def stage(path, n_px, region, data=None, interlaced=False):
         data = _contents(path, data)
         ctype, depth = data[25], data[24]                         # IHDR, before any work: which kind the file would be
         index = ctype == 3 or (ctype == 0 and depth == 1)
         if (ctype, depth) in ((0, 8), (2, 8)) or index != (kind == KIND_PNG_INDEX):
             raise png_parse.Unsupported("a file of another kind")
-        return stage_png(path, n_px, region, data, modes=True)
+        return stage_png(path, n_px, region, data, modes=True, interlaced=interlaced)
     return stage
 
 
@@ -377,6 +382,17 @@ PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
 LAYOUTS_BIT = 32           # a bit of the mode that adds no kind: the two JPEG stagers run with layouts=True (jpeg_parse.parse(layouts=True));
 #                            encode_files counts the files it lets through (HDR.LAYOUT) under LAYOUTS_STAT
 LAYOUTS_STAT = "jpeg_layout_files"
+PNG_INTERLACED_BIT = 64    # another such bit: the PNG stagers run with interlaced=True (png_parse.parse(interlaced=True)), so it takes
+#                            effect only beside the bits of the PNG kinds; encode_files counts the files it lets through and the
+#                            device did not report (HDR.INTERLACE) under PNG_INTERLACED_STAT, and not under the kind's own key
+PNG_INTERLACED_STAT = "png_interlaced_files"
+
+
+def _stager_switches(mode, magic):
+    """The keyword arguments the mode's kind-less bits give the stagers of the files with that magic"""
+    if magic == "jpeg":
+        return {"layouts": True} if mode & LAYOUTS_BIT else {}
+    return {"interlaced": True} if mode & PNG_INTERLACED_BIT else {}
 PARSED_KINDS = frozenset(k.kind for k in PARSED)
 REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + PARSED)
 WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
@@ -385,7 +401,7 @@ WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a large
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (the bits of FULL_SIZE and PARSED, and LAYOUTS_BIT) |
+         what the region may take (the bits of FULL_SIZE and PARSED, LAYOUTS_BIT and PNG_INTERLACED_BIT) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
@@ -437,7 +453,7 @@ def serve(fin, fout):
                     if full is not None or wanted is not None or not mode & k.bit or magic != k.magic:
                         continue
                     try:
-                        full = k.stager(fname, n_px, region, data, **({"layouts": True} if mode & LAYOUTS_BIT and k.magic == "jpeg" else {}))
+                        full = k.stager(fname, n_px, region, data, **_stager_switches(mode, k.magic))
                     except Exception:                          # not a file for this device decoder: the next one, or Pillow
                         full = None
                     if full is not None and full[2] < 0:

@@ -133,9 +133,14 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
 
 def _png_scanlines(hd, px=3):
     """Bytes of filtered scanlines per file. A KIND_PNG region's header does not carry the depth (stage_png leaves [20..23] zero for
-    grey / RGB files, which are 8 bits deep); the regions of the other kinds do (HDR.DEPTH)."""
+    grey / RGB files, which are 8 bits deep); the regions of the other kinds do (HDR.DEPTH). An Adam7 file (HDR.INTERLACE) holds
+    the scanlines of its passes (png_parse.adam7_raw_bytes)."""
+    from .png_parse import adam7_raw_bytes
     depth = 8 if px == 3 else hd[:, HDR.DEPTH]
-    return hd[:, HDR.H] * (1 + (hd[:, HDR.W] * hd[:, HDR.NCOMP] * depth + 7) // 8)
+    bits = hd[:, HDR.NCOMP] * depth
+    plain = hd[:, HDR.H] * (1 + (hd[:, HDR.W] * bits + 7) // 8)
+    lace = hd[:, HDR.INTERLACE] != 0
+    return np.where(lace, adam7_raw_bytes(hd[:, HDR.W], hd[:, HDR.H], bits), plain) if lace.any() else plain
 
 
 def png_records(bigview, n, cap, slots, comp, n_px, px=3):
@@ -154,6 +159,7 @@ def png_records(bigview, n, cap, slots, comp, n_px, px=3):
     recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = hd[:, HDR.COUNT], hd[:, HDR.W], hd[:, HDR.H], hd[:, HDR.NCOMP]
     if px != 3:
         recs["reserved"] = np.stack([hd[:, HDR.CTYPE] << 8 | hd[:, HDR.DEPTH], hd[:, HDR.ENTRIES]], axis=1)
+    recs["reserved"][:, 0] |= np.where(hd[:, HDR.INTERLACE] != 0, P.INTERLACE_BIT, 0).astype(np.int32)
     return recs, jobs, out_sz, raw_sz
 
 
@@ -286,7 +292,7 @@ class PinnedRing:
 
 class Pending:
     """What the consumer checks behind a batch's encode step, and what has to live until then"""
-    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good", "layout_files")
+    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good", "layout_files", "interlaced")
 
     def __init__(self):
         self.keep = []           # device tensors the queued kernels read and write
@@ -295,6 +301,7 @@ class Pending:
         self.count_ok = []       # (stats key, lo, hi): ranges of `status` whose zeros count as files the device decoded
         self.chunk = self.good = None      # the batch's paths and its mask of good slots, for the files that go back to Pillow
         self.layout_files = 0    # staged JPEG files that only the layouts switch lets through (HDR.LAYOUT; decode_worker.LAYOUTS_STAT)
+        self.interlaced = None   # bool per status: an Adam7 PNG file (HDR.INTERLACE; decode_worker.PNG_INTERLACED_STAT)
 
 
 # One group of a kind's files: its packed arrays on the device and their offsets, its files, its largest nrows, its decode entry's name
@@ -302,8 +309,9 @@ class Pending:
 GroupCall = namedtuple("GroupCall", "dsmall offs n_files max_rows name decode status_off")
 # The decodes and transforms of a batch's files of one kind, ready for the side stream: the groups run one after the other through one
 # workspace, one buffer of decoded rows (None: the decode entry transforms too) and one of scratch rows; layout_files: how many of the
-# files only the layouts switch lets through (HDR.LAYOUT, 0 in a PNG region)
-KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files", defaults=(0,))
+# files only the layouts switch lets through (HDR.LAYOUT, 0 in a PNG region); interlaced: which of the files are Adam7 PNG files
+# (HDR.INTERLACE, 0 in a JPEG region), bool per file
+KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files interlaced", defaults=(0, None))
 
 
 class DeviceStage:
@@ -354,7 +362,7 @@ class DeviceStage:
         ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
         rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev) if fmt.entry is not None else None
         scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
-        return KindLaunch(fmt, calls, ws, rgb, scratch, int(hd[:, HDR.LAYOUT].sum()))
+        return KindLaunch(fmt, calls, ws, rgb, scratch, int(hd[:, HDR.LAYOUT].sum()), hd[:, HDR.INTERLACE] != 0)
 
     def _launch_kind(self, k, base, devt, status):
         for c in k.calls:
@@ -403,6 +411,7 @@ class DeviceStage:
             if n_status:
                 pending.status = torch.empty(n_status, dtype=torch.int32, device=dev)
                 pending.slots = np.concatenate(parsed)
+                pending.interlaced = np.zeros(n_status, dtype=bool)
             if len(e2):
                 djobs, scratch, max_rows = self._stage_full(bigview, full, e2, cap, comp)
                 pending.keep += [djobs, scratch]
@@ -413,6 +422,7 @@ class DeviceStage:
                 k = self._stage_kind(self.formats[kind.kind], bigview, n, cap, slots, comp, status_at)
                 kind_launches.append(k)
                 pending.layout_files += k.layout_files
+                pending.interlaced[status_at:status_at + len(slots)] = k.interlaced
                 pending.keep += [c.dsmall for c in k.calls] + [k.ws, k.rgb, k.scratch]
                 if kind.counts == "decoded":
                     pending.count_ok.append((kind.stat, status_at, status_at + len(slots)))

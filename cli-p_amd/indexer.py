@@ -28,6 +28,8 @@ CLIPMI_DEVICE_PROGRESSIVE (default 0 = off; 1: progressive JPEG files take the d
 while the progressive decode is slower than Pillow in the workers; needs CLIPMI_DEVICE_JPEG_KB on),
 CLIPMI_DEVICE_PNG (default 0 = off; 1: 8-bit grey and RGB PNG files that are not interlaced take the device decoder - csrc/png.hip,
 Pillow's bytes; every other PNG file stays with Pillow; needs CLIPMI_DEVICE_JPEG_KB on),
+CLIPMI_DEVICE_PNG_INTERLACED (default 0 = off; 1: Adam7-interlaced PNG files of the colour types and depths CLIPMI_DEVICE_PNG - and
+CLIPMI_DEVICE_PNG_MODES, DESIGN §4.9b - let through take the device decoder too, Pillow's bytes; needs CLIPMI_DEVICE_PNG on),
 CLIPMI_DEVICE_JPEG_LAYOUTS (default 0 = off; 1: JPEG files with luma sampling 1x2 - 4:4:0, what a lossless 90-degree rotation makes of
 a 4:2:2 file -, 4x1 or 1x4 and RGB-coded files take the device decoder too, Pillow's bytes; needs CLIPMI_DEVICE_JPEG_KB
 on, and CLIPMI_DEVICE_PROGRESSIVE for the progressive ones),

@@ -16,7 +16,8 @@ import numpy as np
 import torch
 
 # the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
-from .decode_worker import LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, REGION_TAGS, WANTED_TAG, load_uint8
+from .decode_worker import (LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, PNG_INTERLACED_BIT, PNG_INTERLACED_STAT, REGION_TAGS,
+                            WANTED_TAG, load_uint8)
 from .device_stage import (DeviceStage, PinnedRing, _FORMATS, _groups, _headers, _pack16, file_need, formats, jpeg_fused_default,  # noqa: F401 (the moved names stay reachable as pipeline.<name>)
                            jpeg_layouts_default, jpeg_records, png_records, progressive_records)
 
@@ -377,8 +378,10 @@ class _Encoder:
             feats = self.encode(devt)
             if pending is not None and pending.status is not None:
                 stc = pending.status.cpu().numpy()            # (behind the encode step: nothing waits for it in the common case)
-                for key, lo, hi in pending.count_ok:
-                    self.count(key, int((stc[lo:hi] == 0).sum()))
+                for key, lo, hi in pending.count_ok:       # (an Adam7 file counts under the switch's key, not its kind's)
+                    kept, lace = stc[lo:hi] == 0, pending.interlaced[lo:hi]
+                    self.count(key, int((kept & ~lace).sum()))
+                    self.count(PNG_INTERLACED_STAT, int((kept & lace).sum()))
                 if stc.any():
                     ok, bad, devt = self.redo_on_host([int(s_) for s_ in pending.slots[stc != 0]], pending, ok, bad, devt)
                     feats = self.encode(devt) if len(ok) else None
@@ -405,6 +408,7 @@ class _Encoder:
                 if k.counts == "staged":
                     self.count(k.stat, sum(1 for v in d.full.values() if v[0] == k.kind))
             self.count(LAYOUTS_STAT, r.pending.layout_files if r.pending is not None else 0)      # (DeviceStage counted: it read the headers)
+            self.count(PNG_INTERLACED_STAT, 0)             # (the key exists from here on; consume() counts, behind the statuses)
         return r
 
     def submit(self, dec, cpy, j):
@@ -414,7 +418,7 @@ class _Encoder:
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
                  jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None,
-                 device_jpeg_layouts=None):
+                 device_jpeg_layouts=None, device_png_interlaced=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -430,7 +434,7 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     progressive JPEG files take the device too (jpeg_parse.parse_progressive in the workers, clipmi_jpeg_decode_progressive_rgb8
     + clipmi_resize_crop_rgb8 beside the baseline decode), the same bytes as Pillow's; files it reports go back to Pillow.
     device_png (default $CLIPMI_DEVICE_PNG, else off; "1" = on; needs the JPEG decode on the device above, whose regions it
-    shares): 8-bit grey and RGB PNG files that are not interlaced and hold at most decode_worker.PNG_MAX_RAW (16 MiB) of
+    shares): 8-bit grey and RGB PNG files that are not interlaced (see device_png_interlaced) and hold at most decode_worker.PNG_MAX_RAW (16 MiB) of
     scanlines take the device too (png_parse.parse in the workers,
     clipmi_png_decode_rgb8 + clipmi_resize_crop_rgb8 on the side stream beside the JPEG decodes, grouped under jpeg_group_mb
     like them), the same bytes as Pillow's; every other PNG file and every file the device reports goes back to Pillow. With
@@ -439,6 +443,11 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     alpha, palette (depth 1/2/4/8, with or without tRNS) and grey depth 1/2/4 files that are not interlaced take the device as
     well (png_parse.parse(modes=True), clipmi_png_decode_px8, then clipmi_resize_crop_rgba8 or clipmi_nearest_crop_p8: Pillow
     resamples such files in their own mode), the same bytes as Pillow's. Off, such files stay with Pillow as before.
+    device_png_interlaced (default $CLIPMI_DEVICE_PNG_INTERLACED, else off; "1" = on; takes effect only with device_png on):
+    Adam7-interlaced files of the colour types and depths the two switches above let through take the device as well
+    (png_parse.parse(interlaced=True); the same two decode entries reconstruct the seven passes and leave the pixels laid out as
+    those of the picture stored without interlace, so the transform behind them is the same), the same bytes as Pillow's.
+    Interlaced alpha, palette and low-depth files need device_png_modes too. Off, every interlaced file stays with Pillow as before.
     jpeg_fused (default $CLIPMI_DEVICE_JPEG_FUSED, else off; "1" = on): baseline and progressive files on the device go through
     clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8, which convert and resample straight from
     the decoder's sample planes: the same bytes, and no full-size RGB rows (3 bytes per pixel) in HBM, so that a group under
@@ -454,7 +463,9 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     shared memory -> device incl. the decode / resize kernels, encode_s) and the files that took the device decoders, under the
     keys of decode_worker.PARSED (jpeg_files, jpeg_progressive_files: files staged for the device; png_files: files it decoded and
     did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only;
-    jpeg_layout_files: those of jpeg_files and jpeg_progressive_files that device_jpeg_layouts added, 0 with it off)."""
+    jpeg_layout_files: those of jpeg_files and jpeg_progressive_files that device_jpeg_layouts added, 0 with it off;
+    png_interlaced_files: the interlaced files of every kind that device_png_interlaced added and the device did not hand back, 0
+    with it off - png_files and png_mode_files keep counting files that are not interlaced only)."""
     n_px = model.visual.input_resolution
     dev = model.device
     use_gpu = dev.type == "cuda"
@@ -499,6 +510,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         device_png = os.environ.get("CLIPMI_DEVICE_PNG", "0") not in ("", "0")
     if device_png_modes is None:
         device_png_modes = os.environ.get("CLIPMI_DEVICE_PNG_MODES", "0") not in ("", "0")
+    if device_png_interlaced is None:
+        device_png_interlaced = os.environ.get("CLIPMI_DEVICE_PNG_INTERLACED", "0") not in ("", "0")
     if jpeg_fused is None:
         jpeg_fused = jpeg_fused_default()
     if device_jpeg_layouts is None:
@@ -506,7 +519,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     kind_formats = formats(jpeg_fused)
     full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
                  (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0) |
-                 (LAYOUTS_BIT if jpeg_cap and device_jpeg_layouts else 0))
+                 (LAYOUTS_BIT if jpeg_cap and device_jpeg_layouts else 0) |
+                 (PNG_INTERLACED_BIT if jpeg_cap and device_png and device_png_interlaced else 0))
     chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
     enc = _Encoder(model, chunks, batch, pool, stats, copy_stream, resize_cap, jpeg_cap, full_cap, full_mode, jpeg_group_bytes, kind_formats)
     if pool is not None:

@@ -4,7 +4,9 @@ The host walks the chunks (png_parse.parse) and lets through 8-bit grey and RGB 
 inflates the IDAT stream (one wave per image), undoes the scanline filters and checks the Adler-32, and leaves Pillow's
 bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_crop_rgb8` takes. With `modes=True` alpha,
 palette and low-depth files decode too, to the pixels of their own mode (clipmi_png_decode_px8; status 5: a palette index beyond
-the palette), and `transform_files` runs the transform of each kind on the device. PNG is lossless, so there is
+the palette), and `transform_files` runs the transform of each kind on the device. With `interlaced=True` Adam7
+files of the same colour types and depths decode as well, to the layout of the same picture stored without interlace (the record
+carries INTERLACE_BIT; the unfilter kernels reconstruct the seven passes one after the other). PNG is lossless, so there is
 no tolerance: a file comes back with exactly Pillow's pixels (status 0) or goes back to Pillow - every file the parser
 refuses (`Unsupported`) and every file the device reports (1 invalid DEFLATE data, 2 the stream ended early, produced too
 little or wants to produce more, 3 a filter byte above 4, 4 the Adler-32 differs), so that Pillow's error handling stays the
@@ -22,11 +24,13 @@ assert IMAGE.itemsize == 48
 
 
 PX_BYTES = {"rgb": 3, "alpha": 4, "index": 1}          # bytes per decoded pixel, by Parsed.kind
+INTERLACE_BIT = 1 << 16                                # in reserved[0] of a record: the file is Adam7-interlaced (include/clipmi.h)
 
 
 def pack(items):
     """Parsed records -> (IMAGE array, streams uint8, out_bytes, total_raw_bytes, max_raw_bytes). Records of the kinds "alpha" and
-    "index" (clipmi_png_decode_px8) carry colour type, depth and palette entries in `reserved`."""
+    "index" (clipmi_png_decode_px8) carry colour type, depth and palette entries in `reserved`; the record of an Adam7 file
+    (Parsed.interlace) carries INTERLACE_BIT there, and its scanline sizes are those of its passes (Parsed.raw_bytes)."""
     recs = np.zeros(len(items), dtype=IMAGE)
     soff = roff = ooff = 0
     max_raw = 1
@@ -37,6 +41,8 @@ def pack(items):
         r["width"], r["height"], r["channels"] = it.width, it.height, it.channels
         if it.kind != "rgb":
             r["reserved"] = (it.ctype << 8 | it.depth, it.n_entries)
+        if it.interlace:
+            r["reserved"][0] |= INTERLACE_BIT
         pad = (-len(it.stream)) % 16 + 16
         pieces.append(it.stream)
         pieces.append(b"\0" * pad)
@@ -80,25 +86,26 @@ def decode_device(items, device, stream=None):
     return out, recs, status
 
 
-def _parsed(blobs, modes):
+def _parsed(blobs, modes, interlaced=False):
     """-> [(position, Parsed)] of the files the parser lets through, split into the "rgb" files and the others"""
     rgb, px8 = [], []
     for k, b in enumerate(blobs):
         try:
-            it = parse(b, modes=modes)
+            it = parse(b, modes=modes, interlaced=interlaced)
         except Unsupported:
             continue
         (rgb if it.kind == "rgb" else px8).append((k, it))
     return rgb, px8
 
 
-def decode_files(blobs, device, modes=False):
+def decode_files(blobs, device, modes=False, interlaced=False):
     """PNG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
     device reported it). modes=True: alpha, palette and low-depth files decode too (png_parse.parse(modes=True)) - files of kind
-    "alpha" come back as uint8 [H,W,4], files of kind "index" as (uint8 [H,W], palette uint8 [256,3]).
+    "alpha" come back as uint8 [H,W,4], files of kind "index" as (uint8 [H,W], palette uint8 [256,3]). interlaced=True: Adam7
+    files of the kinds let through decode too, to the same arrays as the picture stored without interlace.
     Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM."""
     res = [None] * len(blobs)
-    for group in _parsed(blobs, modes):
+    for group in _parsed(blobs, modes, interlaced):
         if not group:
             continue
         out, recs, status = decode_device([it for _, it in group], device)
@@ -152,13 +159,13 @@ def transform_device(items, out_rows, n_px, out, decoded, recs, device):
     _lib.check(rc, name)
 
 
-def transform_files(blobs, n_px, device):
+def transform_files(blobs, n_px, device, interlaced=False):
     """PNG file contents -> per file the transform's pixels, uint8 [3,n_px,n_px] as decode_worker.load_uint8 gives them (None
     where the file is not for the device or the device reported it): decode on the device + the transform entry of the file's
-    kind, "rgb" included. Synchronises; a convenience for tests and tools like decode_files."""
+    kind, "rgb" included; interlaced=True: Adam7 files too. Synchronises; a convenience for tests and tools like decode_files."""
     device = torch.device(device)
     res = [None] * len(blobs)
-    rgb, px8 = _parsed(blobs, True)
+    rgb, px8 = _parsed(blobs, True, interlaced)
     groups = [rgb, [e for e in px8 if e[1].kind == "alpha"], [e for e in px8 if e[1].kind == "index"]]
     out = torch.zeros((max(len(blobs), 1), 3, n_px, n_px), dtype=torch.uint8, device=device)
     keep = []

@@ -3,9 +3,11 @@
 `parse(data)` lets through 8-bit grey (colour type 0) and RGB (colour type 2) files that are not interlaced and carry no
 `tRNS` and no APNG chunk (`parse(data, modes=True)` also RGBA, grey + alpha, palette files at depth 1/2/4/8, with or without
 `tRNS`, and grey files at depth 1/2/4: kinds "alpha" and "index", see Parsed), and returns the IDAT payloads joined, without the 2-byte zlib header; the Adler-32 and anything
-behind it stay in place (the device finds the trailer behind the final block itself). Everything else raises `Unsupported`
+behind it stay in place (the device finds the trailer behind the final block itself). `parse(data, interlaced=True)` also lets
+Adam7 files (interlace method 1) of the colour types and depths the other argument allows through: the same stream, whose
+scanlines are those of the seven passes (adam7_passes), one pass after the other. Everything else raises `Unsupported`
 and stays with Pillow: palette, alpha, 16-bit and 1/2/4-bit files (the transform resamples those modes differently), Adam7
-files, and any file whose chunks this parser cannot vouch for - in front of the image data AND behind it: Pillow's load_end()
+files without that argument, and any file whose chunks this parser cannot vouch for - in front of the image data AND behind it: Pillow's load_end()
 runs its chunk handlers on everything up to IEND, and a handler that raises there makes `convert("RGB")` fail although the
 pixels are complete. Pure Python plus zlib.crc32, no Pillow: decode_worker.py imports it under both import forms, like jpeg_parse.
 """
@@ -47,6 +49,23 @@ _CID = re.compile(rb"\w\w\w\w")                                # Pillow's is_cid
 # raise), eXIf (kept as is, but an orientation tag is a caller's business), acTL / fcTL / fdAT (APNG), unknown chunks.
 
 
+# Adam7: (x0, y0, dx, dy) of the seven passes in file order - pass p holds the pixels (x0 + i dx, y0 + j dy)
+ADAM7 = ((0, 0, 8, 8), (4, 0, 8, 8), (0, 4, 4, 8), (2, 0, 4, 4), (0, 2, 2, 4), (1, 0, 2, 2), (0, 1, 1, 2))
+
+
+def adam7_passes(width, height):
+    """[(x0, y0, dx, dy, pw, ph)] of the seven passes of a width x height image: pass p is an image of pw x ph pixels of its own,
+    pw = ceil((width - x0) / dx), ph likewise; a pass with pw == 0 or ph == 0 has no bytes in the file, not even filter bytes.
+    width, height >= 1: ints, or integer numpy arrays (x0 < dx and y0 < dy, so the rounded-up quotients are never negative)."""
+    return [(x0, y0, dx, dy, (width - x0 + dx - 1) // dx, (height - y0 + dy - 1) // dy) for x0, y0, dx, dy in ADAM7]
+
+
+def adam7_raw_bytes(width, height, bits):
+    """bytes of filtered scanlines of an Adam7 file whose pixels have `bits` bits: ph x (1 + ceil(pw x bits / 8)) over the
+    non-empty passes. Ints, or integer numpy arrays (device_stage sizes a batch's files at once)."""
+    return sum((pw > 0) * ph * (1 + (pw * bits + 7) // 8) for _, _, _, _, pw, ph in adam7_passes(width, height))
+
+
 class Unsupported(Exception):
     """Not a file for the device decoder: Pillow decodes it (or reports it)."""
 
@@ -55,19 +74,22 @@ class Parsed:
     """kind: what the device decodes the file to - "rgb" (3 bytes per pixel, clipmi_png_decode_rgb8), "alpha" (4 bytes per pixel:
     RGBA, grey + alpha, grey at depth 2/4) or "index" (1 byte per pixel: palette files, 1-bit grey), both clipmi_png_decode_px8.
     channels: samples per pixel; palette: uint8 [256][3], zero beyond the n_entries entries (None for "rgb" and "alpha"; 1-bit grey
-    is the two-entry palette black, white)."""
-    __slots__ = ("width", "height", "channels", "stream", "kind", "depth", "ctype", "palette", "n_entries")
+    is the two-entry palette black, white). interlace: 0, or 1 for an Adam7 file (parse(interlaced=True))."""
+    __slots__ = ("width", "height", "channels", "stream", "kind", "depth", "ctype", "palette", "n_entries", "interlace")
 
-    def __init__(self, width, height, channels, stream, kind="rgb", depth=8, ctype=None, palette=None, n_entries=0):
+    def __init__(self, width, height, channels, stream, kind="rgb", depth=8, ctype=None, palette=None, n_entries=0, interlace=0):
         self.width, self.height, self.channels, self.stream = width, height, channels, stream
         self.kind, self.depth, self.ctype = kind, depth, (2 if channels == 3 else 0) if ctype is None else ctype
-        self.palette, self.n_entries = palette, n_entries
+        self.palette, self.n_entries, self.interlace = palette, n_entries, interlace
 
     def row_bytes(self):
+        """bytes of a full row of the image without its filter byte (no pass row of an Adam7 file is longer)"""
         return (self.width * self.channels * self.depth + 7) // 8
 
     def raw_bytes(self):
         """size of the filtered scanlines the stream has to produce"""
+        if self.interlace:
+            return adam7_raw_bytes(self.width, self.height, self.channels * self.depth)
         return self.height * (1 + self.row_bytes())
 
 
@@ -82,8 +104,9 @@ def _palette(body, n_entries):
     return pal
 
 
-def parse(data, modes=False):
-    """PNG file contents -> Parsed; raises Unsupported(reason). modes: also let the files of kinds "alpha" and "index" through."""
+def parse(data, modes=False, interlaced=False):
+    """PNG file contents -> Parsed; raises Unsupported(reason). modes: also let the files of kinds "alpha" and "index" through.
+    interlaced: also let Adam7 files (interlace method 1) of the colour types and depths let through anyway through."""
     data = bytes(data)
     if data[:8] != SIGNATURE:
         raise Unsupported("not a PNG file")
@@ -126,7 +149,7 @@ def parse(data, modes=False):
                 raise Unsupported("bit depth %d, colour type %d" % (depth, ctype))
             if comp != 0 or filt != 0:
                 raise Unsupported("unknown compression or filter method")
-            if lace != 0:
+            if lace != 0 and not (interlaced and lace == 1):
                 raise Unsupported("interlaced")
             if width < 1 or height < 1:
                 raise Unsupported("empty image")
@@ -184,11 +207,11 @@ def parse(data, modes=False):
     if len(stream) - 2 >= 1 << 31:
         raise Unsupported("stream too large")
     if rgb:
-        return Parsed(width, height, channels, stream[2:])
+        return Parsed(width, height, channels, stream[2:], interlace=lace)
     if ctype == 3:
         if plte is None:
             raise Unsupported("no PLTE chunk")
-        return Parsed(width, height, 1, stream[2:], "index", depth, 3, _palette(plte, len(plte) // 3), len(plte) // 3)
+        return Parsed(width, height, 1, stream[2:], "index", depth, 3, _palette(plte, len(plte) // 3), len(plte) // 3, interlace=lace)
     if ctype == 0 and depth == 1:
-        return Parsed(width, height, 1, stream[2:], "index", 1, 0, _palette(b"\0\0\0\xff\xff\xff", 2), 2)
-    return Parsed(width, height, channels, stream[2:], "alpha", depth, ctype)
+        return Parsed(width, height, 1, stream[2:], "index", 1, 0, _palette(b"\0\0\0\xff\xff\xff", 2), 2, interlace=lace)
+    return Parsed(width, height, channels, stream[2:], "alpha", depth, ctype, interlace=lace)

@@ -421,6 +421,19 @@ int64_t clipmi_png_px8_workspace_bytes(int n, int64_t total_raw_bytes);
 int clipmi_png_decode_px8(const void* streams_dev, const void* images_dev, int n, int64_t total_raw_bytes, int64_t max_raw_bytes,
                           void* out_dev, int32_t* status_dev, void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- Adam7-interlaced PNG files (a further addition to ABI 8 in the sense of the two notes above: no new entry point and no
+ * new struct; a caller that leaves `reserved` as it was gets what it got before). Both decode entries take a record of a file
+ * written with interlace method 1, for the colour types and depths they take anyway:
+ *   clipmi_png_decode_px8:  bit 16 of reserved[0] set (colour type and depth stay in bits 0-15; bits above 16 must be zero);
+ *   clipmi_png_decode_rgb8: reserved[0] exactly 1 << 16. Every other value is not looked at, as before.
+ * The stream, the filters and the Adler-32 are the same. The scanlines of such a record are those of its up to seven passes
+ * one after the other: pass p = 1 .. 7 holds the pixels (x0 + i dx, y0 + j dy) with (x0, y0, dx, dy) = (0,0,8,8) (4,0,8,8)
+ * (0,4,4,8) (2,0,4,4) (0,2,2,4) (1,0,2,2) (0,1,1,2), that is pw = ceil((width - x0) / dx) by ph = ceil((height - y0) / dy)
+ * pixels, and contributes ph x (1 + ceil(pw x channels x depth / 8)) bytes, or nothing at all where pw or ph is 0. The sizes
+ * and offsets (raw_off, total_raw_bytes, max_raw_bytes) count that sum. The output layouts ("rgb", "alpha", "index"), out_off and
+ * the status codes 0-5 keep their meaning: the decoded pixels are laid out as those of the same picture stored without
+ * interlace, every byte of the image's block of out_dev written once and none outside it. */
+
 /* The transform for those pixels, bit for bit what Pillow's resize (in the file's mode) + crop + convert("RGB") gives.
  * clipmi_resize_crop_rgba8: arguments and jobs of clipmi_resize_crop_rgb8 with 4 bytes per source and scratch pixel (rows of
  * w*4 bytes; nrows*n_px*4 scratch bytes per job, tmp_off a multiple of 4). A job that resamples an axis premultiplies each
