@@ -25,7 +25,7 @@ SYMBOLS = [
     "clipmi_topk_ip_wide_workspace_bytes", "clipmi_topk_ip_wide_i8", "clipmi_dbg_topk_wide_i8_scan_ms",
     "clipmi_dbg_quantize_rows_fp8", "clipmi_dbg_gemm_fp8",
     "clipmi_merge_topk_workspace_bytes", "clipmi_merge_topk", "clipmi_merge_topk_packed",
-    "clipmi_l2_normalize_rows", "clipmi_resize_crop_rgb8", "clipmi_jpeg_workspace_bytes", "clipmi_jpeg_decode_rgb8", "clipmi_jpeg_progressive_workspace_bytes", "clipmi_jpeg_decode_progressive_rgb8", "clipmi_jpeg_decode_transform_rgb8", "clipmi_jpeg_decode_progressive_transform_rgb8", "clipmi_png_workspace_bytes", "clipmi_png_decode_rgb8", "clipmi_png_px8_workspace_bytes", "clipmi_png_decode_px8", "clipmi_resize_crop_rgba8", "clipmi_nearest_crop_p8", "clipmi_last_error", "clipmi_abi_version",
+    "clipmi_l2_normalize_rows", "clipmi_resize_crop_rgb8", "clipmi_jpeg_workspace_bytes", "clipmi_jpeg_decode_rgb8", "clipmi_jpeg_progressive_workspace_bytes", "clipmi_jpeg_decode_progressive_rgb8", "clipmi_jpeg_decode_transform_rgb8", "clipmi_jpeg_decode_progressive_transform_rgb8", "clipmi_png_workspace_bytes", "clipmi_png_decode_rgb8", "clipmi_png_px8_workspace_bytes", "clipmi_png_decode_px8", "clipmi_resize_crop_rgba8", "clipmi_nearest_crop_p8", "clipmi_jpeg_decode_cmyk8", "clipmi_resize_crop_cmyk8", "clipmi_last_error", "clipmi_abi_version",
     "clipmi_dbg_gemm_bf16", "clipmi_dbg_layernorm", "clipmi_dbg_attention", "clipmi_dbg_topk_scan_ms",
     "clipmi_dbg_encode_image_probe_ms", "clipmi_dbg_encode_image_probe3_ms",
     "clipmi_dbg_split_stats", "clipmi_dbg_gemm_ln", "clipmi_dbg_gemm_resid_ln", "clipmi_dbg_gemm_resid_ln_leaf", "clipmi_dbg_gemm_ln_leaf", "clipmi_dbg_quantize_rows_fp8mx", "clipmi_dbg_gemm_fp8_bsa",
@@ -162,6 +162,10 @@ def lib():
     L.clipmi_png_decode_px8.argtypes = [vp, vp, i32, i64, i64, vp, vp, vp, i64, vp]
     L.clipmi_resize_crop_rgba8.restype = i32
     L.clipmi_resize_crop_rgba8.argtypes = [vp, vp, i32, i32, vp, i32, vp, vp, vp]
+    L.clipmi_jpeg_decode_cmyk8.restype = i32
+    L.clipmi_jpeg_decode_cmyk8.argtypes = L.clipmi_jpeg_decode_rgb8.argtypes
+    L.clipmi_resize_crop_cmyk8.restype = i32
+    L.clipmi_resize_crop_cmyk8.argtypes = L.clipmi_resize_crop_rgba8.argtypes
     L.clipmi_nearest_crop_p8.restype = i32
     L.clipmi_nearest_crop_p8.argtypes = [vp, vp, i32, vp, i32, vp, vp]
     L.clipmi_dbg_gemm_bf16.restype = i32

@@ -7,7 +7,10 @@
 // Where the host opts in (jpeg_parse.parse(layouts=True)) the records also name luma sampling 1x2 (4:4:0: jdsample.c's
 // h1v2_fancy_upsample), 4x1 (4:1:1) and 1x4 (int_upsample: replication), and a colour transform of "none" for the files libjpeg
 // takes for RGB-coded: further values of JpegGeom's `mode` and its `rgb` flag (tests/test_jpeg_layouts_gpu.py).
-// Everything else (CMYK, ...) stays with Pillow in the decode workers; PNG files have png.hip.
+// Four-component files (jpeg_parse.parse(cmyk=True): CMYK as stored and YCCK, components 1-3 sampled 1x1) go through the same
+// chain over their own record, clipmi_jpeg_image4, to Pillow's mode-CMYK bytes (clipmi_jpeg_decode_cmyk8, jpeg_cmyk_kernel;
+// tests/test_jpeg_cmyk_gpu.py); resize.hip's clipmi_resize_crop_cmyk8 resamples those and converts them to RGB as Pillow does.
+// Everything else (12-bit, arithmetic coding, ...) stays with Pillow in the decode workers; PNG files have png.hip.
 //
 // Kernels, one batch of images per call (every kernel takes an image's block and plane layout from jpeg_geom):
 //   jpeg_unstuff_kernel      the baseline record's first reader and its checker (jp_record_ok): a record whose sampling factors,
@@ -37,6 +40,8 @@
 //   jpeg_color_resize_h_kernel   the transform entries' form of the last step: the same upsampling and colour conversion fused with
 //                            Pillow's horizontal resampling pass (resize.hip's resize_h_kernel), over the rows and columns the
 //                            transform's window needs only - the full-size RGB rows are never written
+//   jpeg_cmyk_kernel         the last step for a four-component record: the same upsampling per plane, then Pillow's CMYK bytes,
+//                            rows of width*4 (the kernels in front of it are instantiated over the wider record, JpegImage4)
 //   jpeg_progressive_kernel  progressive files: every scan of an image applied to its coefficients, in place of
 //                            jpeg_huffman_kernel and jpeg_dc_kernel; jpeg_idct_kernel and the colour kernels follow as above
 #include <type_traits>
@@ -46,17 +51,26 @@
 namespace clipmi {
 namespace {
 
-struct JpegImage {             // mirrors clipmi_jpeg_image (include/clipmi.h)
+// The baseline record at the two component counts it comes in: clipmi_jpeg_image (1 or 3 components; JpegImage) and
+// clipmi_jpeg_image4 (4: CMYK / YCCK files; JpegImage4). The decode chain up to the sample planes is written once over the record
+// type (kernel templates over Im below), instantiated per record, so that the three-component kernels are compiled from the code
+// they always had, with the count a constant.
+template <int NC_>
+struct JpegImageT {            // mirrors clipmi_jpeg_image / clipmi_jpeg_image4 (include/clipmi.h)
+    static constexpr int NC = NC_;
     long long stream_off, coef_off, out_off, intervals_off;
     int stream_bytes;
     int width, height;
     int ncomp;
     int hs, vs;
-    int dc_tbl[3], ac_tbl[3];
+    int dc_tbl[NC_], ac_tbl[NC_];
     int restart_interval, n_intervals;
-    int stuffed, transform;    // transform: clipmi_jpeg_image.reserved - 0 YCbCr -> RGB, 1 none (the components are R, G, B)
-    unsigned char quant[3][64];
+    int stuffed, transform;    // transform: the records' `reserved` - 0 YCbCr -> RGB, 1 none (the components are R, G, B); four
+                               // components: 2 CMYK as stored, 3 YCCK
+    unsigned char quant[NC_][64];
 };
+using JpegImage = JpegImageT<3>;
+using JpegImage4 = JpegImageT<4>;
 
 // The luma sampling factors the kernels take (chroma is 1 x 1): 1x1, 2x1, 2x2, and 1x2, 4x1, 1x4
 __device__ __forceinline__ bool jp_sampling_ok(int hs, int vs) {
@@ -68,6 +82,10 @@ __device__ __forceinline__ bool jp_sampling_ok(int hs, int vs) {
 __device__ __forceinline__ bool jp_record_ok(int ncomp, int width, int height, int hs, int vs, int transform) {
     return width >= 1 && height >= 1 && (ncomp == 1 ? transform == 0 : ncomp == 3 && jp_sampling_ok(hs, vs) && (transform == 0 || transform == 1));
 }
+// The same for a clipmi_jpeg_image4: four components, component 0 at one of the samplings above, CMYK as stored or YCCK
+__device__ __forceinline__ bool jp_record4_ok(int ncomp, int width, int height, int hs, int vs, int transform) {
+    return width >= 1 && height >= 1 && ncomp == 4 && jp_sampling_ok(hs, vs) && (transform == 2 || transform == 3);
+}
 
 // Chroma upsampling (JpegGeom.mode). 0, 1, 2 are luma 1x1, 2x1, 2x2 - every file before the layouts switch -, and the pixel
 // functions test for these three first and run the code they always ran; the other two go through the `_more` functions. (With
@@ -77,7 +95,8 @@ enum { JM_COPY = 0, JM_H2V1 = 1, JM_H2V2 = 2, JM_H1V2 = 3, JM_REPL = 4 };
 
 // An image's blocks and planes. Coefficients (int16 [64] per block, from coef_all + coef_off * 64) come in scan order: MCU
 // after MCU, each the hv luma blocks, then Cb, Cr. Planes of an image (bytes from planes + coef_off * 64):
-// Y [my vs 8][mx hs 8], then Cb, Cr [my 8][mx 8]
+// Y [my vs 8][mx hs 8], then Cb, Cr [my 8][mx 8]. A four-component record (JpegImage4) has the same layout with a third
+// one-by-one component behind the two: hv + 3 blocks per MCU, a fourth plane [my 8][mx 8].
 struct JpegGeom {
     int W, H;
     int hs, vs;                    // luma sampling factors (grey: 1, whatever the file says); chroma is 1 x 1
@@ -92,20 +111,24 @@ struct JpegGeom {
     bool rgb;                      // no colour conversion: the three planes are R, G, B
     const unsigned char* py;       // the planes: luma, Cb and Cr (only from jpeg_geom with the planes' base)
     const unsigned char* pc[2];
-    // bytes from the luma plane to the plane of component c = 1 (Cb), 2 (Cr)
+    // bytes from the luma plane to the plane of component c = 1 (Cb), 2 (Cr) - and 3, the fourth component of a four-component
+    // record, whose planes follow each other the same way (its pixel kernel takes that plane from here; pc holds the first two)
     __device__ __forceinline__ long long plane_off(int c) const { return (long long)mx * my * hv * 64 + (long long)(c - 1) * mx * my * 64; }
 };
 
 // (The record by pointer, and the sampling factors read behind the test for grey, as the kernels did before they shared this: a
 // reference parameter lets the compiler load every field up front, which cost jpeg_huffman_kernel a VGPR and two spilled SGPRs.)
-__device__ __forceinline__ JpegGeom jpeg_geom(const JpegImage* im, const unsigned char* planes = nullptr) {
+// Im: JpegImage or JpegImage4 - a record that is not grey has Im::NC components, hv blocks of the first and one of each other
+// per MCU (a four-component record's `rgb` flag means nothing: its pixel kernel reads the transform itself).
+template <class Im>
+__device__ __forceinline__ JpegGeom jpeg_geom(const Im* im, const unsigned char* planes = nullptr) {
     JpegGeom g;
     const int tf = im->transform;
     g.color = im->ncomp != 1;
     g.hs = im->ncomp == 1 ? 1 : im->hs;
     g.vs = im->ncomp == 1 ? 1 : im->vs;
     g.hv = g.hs * g.vs;
-    g.bpm = im->ncomp == 1 ? 1 : g.hv + 2;
+    g.bpm = im->ncomp == 1 ? 1 : g.hv + (Im::NC - 1);
     g.W = im->width;
     g.H = im->height;
     g.mx = (g.W + 8 * g.hs - 1) / (8 * g.hs);
@@ -170,14 +193,16 @@ __device__ const unsigned char jp_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10,
 // bytes written back at their compacted positions (never in front of a byte still to be read: the tile is in registers, and the
 // output only falls behind the input). Any 0xFF followed by something else than 0x00 is a marker inside the scan: the record is
 // tagged (stuffed = 2) and jpeg_huffman_kernel reports the file (status 3: Pillow decides).
-__global__ void __launch_bounds__(256) jpeg_unstuff_kernel(unsigned char* __restrict__ streams, JpegImage* __restrict__ images) {
-    JpegImage& im = images[blockIdx.x];
+template <class Im>
+__global__ void __launch_bounds__(256) jpeg_unstuff_kernel(unsigned char* __restrict__ streams, Im* __restrict__ images) {
+    Im& im = images[blockIdx.x];
     // the record's first reader: one the kernels do not take (a sampling, a colour transform, a size) becomes an empty grey image
     // without data, which gives no later kernel anything to do and which jpeg_huffman_kernel reports (status 1: no pixels). Thread 0
     // decides and rewrites; the others read the record behind the barrier.
     __shared__ int s_ok;
     if (threadIdx.x == 0) {
-        s_ok = jp_record_ok(im.ncomp, im.width, im.height, im.hs, im.vs, im.transform);
+        s_ok = Im::NC == 4 ? jp_record4_ok(im.ncomp, im.width, im.height, im.hs, im.vs, im.transform)
+                           : jp_record_ok(im.ncomp, im.width, im.height, im.hs, im.vs, im.transform);
         if (!s_ok) {
             im.width = im.height = 0;
             im.ncomp = im.hs = im.vs = 1;
@@ -312,8 +337,9 @@ struct JpState {
     unsigned bz;     // (block within the MCU) << 8 | index of the next coefficient (0 = the block's DC symbol comes next)
 };
 
-struct JpShared {
-    JpLut lut[6];                              // [component][DC, AC]
+template <int NC>
+struct JpSharedT {
+    JpLut lut[2 * NC];                         // [component][DC, AC]
     unsigned words[JP_T * 33 + 40];            // the chunk's big-endian words, word i at i + i / 32 (subsequence i at 33 i: bank spread)
     JpState exit_state[JP_T];
     JpState start_state[JP_T];
@@ -323,6 +349,7 @@ struct JpShared {
     int end_p;
     int bad;
 };
+using JpShared = JpSharedT<3>;
 
 // The table entry of the symbol whose code starts the 32-bit window x (0: no such code)
 __device__ __forceinline__ unsigned jp_lookup(const JpLut& L, unsigned x, bool ac) {
@@ -349,8 +376,8 @@ __device__ __forceinline__ int jp_comp(unsigned blk, int hv) { return blk < (uns
 // One subsequence: symbols from state (p, bz) while p < end. WRITE: also stores the coefficients of blocks ablk, ablk+1, ...
 // (stops behind block `total` - 1). Returns the number of blocks completed.
 // GLOBAL: the words come straight from the image's segment in memory (restart intervals: a thread walks a whole interval).
-template <bool WRITE, bool GLOBAL = false>
-__device__ __forceinline__ int jp_decode(JpShared& sh, unsigned cw0, int bpm, int hv, unsigned& p, unsigned& bz, unsigned end,
+template <bool WRITE, bool GLOBAL = false, class Sh = JpShared>
+__device__ __forceinline__ int jp_decode(Sh& sh, unsigned cw0, int bpm, int hv, unsigned& p, unsigned& bz, unsigned end,
                                          short* __restrict__ coef, long long ablk, long long total,
                                          const unsigned* __restrict__ src = nullptr, unsigned nwords = 0) {
     unsigned blk = bz >> 8, z = bz & 255;
@@ -421,7 +448,8 @@ __device__ __forceinline__ int jp_decode(JpShared& sh, unsigned cw0, int bpm, in
 // with its block (the next block may use other tables).
 constexpr int JP_WIN = 4;          // 64-bit pieces of a wave's window: the look-ups of all pieces are in flight together, so the
                                    // two LDS round trips in front of a walk are paid once per JP_WIN * 64 bits
-__device__ __forceinline__ int jp_decode_wave(JpShared& sh, unsigned cw0, int bpm, int hv, unsigned& p_, unsigned& bz_, unsigned end) {
+template <class Sh>
+__device__ __forceinline__ int jp_decode_wave(Sh& sh, unsigned cw0, int bpm, int hv, unsigned& p_, unsigned& bz_, unsigned end) {
     const unsigned lane = __builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u));
     unsigned p = p_, blk = bz_ >> 8, z = bz_ & 255;
     int done = 0;
@@ -480,15 +508,27 @@ __device__ __forceinline__ int jp_decode_wave(JpShared& sh, unsigned cw0, int bp
     return done;
 }
 
-__global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char* __restrict__ streams, const JpegImage* __restrict__ images,
+// (a four-component record's eight tables in LDS: 47 KB with the chunk's words, against 40 KB)
+template <class Im>
+__global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char* __restrict__ streams, const Im* __restrict__ images,
                                                            const JpLut* __restrict__ luts, short* __restrict__ coef_all,
                                                            int* __restrict__ status) {
-    __shared__ JpShared sh;
-    const JpegImage& im = images[blockIdx.x];
+    __shared__ JpSharedT<Im::NC> sh;
+    const Im& im = images[blockIdx.x];
     const int tid = threadIdx.x;
     const JpegGeom g = jpeg_geom(&im);
-    const int hv = g.hv, bpm = g.bpm;
-    const long long nmcu = g.nmcu, total = nmcu * bpm;
+    // Four components that all name ONE pair of tables - what Pillow's encoder writes for CMYK: the block within the MCU then
+    // decides nothing about a symbol, but as part of the state it would keep subsequences from ever agreeing with their
+    // predecessors (a start that guessed block 0 stays off by a constant, with nothing in the data to correct it), and every image
+    // would take the serial walk. Such a record is walked as one component's blocks (hv = bpm = 1: the state is bit position and
+    // coefficient index, as for a grey file); only the block counts (rbpm) keep the real MCU.
+    bool one_pair = false;
+    if constexpr (Im::NC == 4)
+        one_pair = im.dc_tbl[1] == im.dc_tbl[0] && im.dc_tbl[2] == im.dc_tbl[0] && im.dc_tbl[3] == im.dc_tbl[0] &&
+                   im.ac_tbl[1] == im.ac_tbl[0] && im.ac_tbl[2] == im.ac_tbl[0] && im.ac_tbl[3] == im.ac_tbl[0];
+    const int hv = one_pair ? 1 : g.hv, bpm = one_pair ? 1 : g.bpm;
+    const int rbpm = Im::NC == 4 ? g.bpm : bpm;            // blocks per MCU of the image (bpm: of the walk)
+    const long long nmcu = g.nmcu, total = nmcu * rbpm;
     const unsigned nbits = (unsigned)im.stream_bytes * 8u;
     short* coef = coef_all + im.coef_off * 64;
     const unsigned* src = reinterpret_cast<const unsigned*>(streams + im.stream_off);
@@ -523,9 +563,9 @@ __global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char*
         for (int k = tid; k < im.n_intervals; k += JP_T) {
             unsigned p = offs[k] * 8u, bz = 0;
             const unsigned end = (k + 1 < im.n_intervals ? offs[k + 1] : (unsigned)im.stream_bytes) * 8u;
-            const long long left = nmcu - k * ri, want = (left < ri ? left : ri) * bpm;
+            const long long left = nmcu - k * ri, want = (left < ri ? left : ri) * rbpm;
             const int done = end <= nbits && p <= end
-                                 ? jp_decode<true, true>(sh, 0, bpm, hv, p, bz, end, coef, k * ri * bpm, k * ri * bpm + want, src, nwords)
+                                 ? jp_decode<true, true>(sh, 0, bpm, hv, p, bz, end, coef, k * ri * rbpm, k * ri * rbpm + want, src, nwords)
                                  : -1;
             if (done != want || p > end) sh.first[0] = 1;          // the interval's data ended early or ran over
         }
@@ -648,9 +688,11 @@ __global__ void __launch_bounds__(JP_T) jpeg_huffman_kernel(const unsigned char*
 }
 
 // DC prediction (jdhuff.c: last_dc_val per component): running sums over the blocks in scan order
-__global__ void __launch_bounds__(256) jpeg_dc_kernel(const JpegImage* __restrict__ images, short* __restrict__ coef_all) {
-    __shared__ int part[3][256];
-    const JpegImage& im = images[blockIdx.x];
+template <class Im>
+__global__ void __launch_bounds__(256) jpeg_dc_kernel(const Im* __restrict__ images, short* __restrict__ coef_all) {
+    constexpr int NC = Im::NC;
+    __shared__ int part[NC][256];
+    const Im& im = images[blockIdx.x];
     const int tid = threadIdx.x;
     const JpegGeom g = jpeg_geom(&im);
     const int hv = g.hv, bpm = g.bpm;
@@ -661,7 +703,7 @@ __global__ void __launch_bounds__(256) jpeg_dc_kernel(const JpegImage* __restric
     if (im.restart_interval > 0) {                      // predictions start at 0 in every restart interval: a thread per interval
         const long long ri = im.restart_interval;
         for (long long k = tid; k * ri < nmcu; k += 256) {
-            int run[3] = {0, 0, 0};
+            int run[NC] = {};
             const long long e = (k + 1) * ri < nmcu ? (k + 1) * ri : nmcu;
             for (long long m = k * ri; m < e; ++m)
                 for (int b = 0; b < bpm; ++b) {
@@ -672,20 +714,20 @@ __global__ void __launch_bounds__(256) jpeg_dc_kernel(const JpegImage* __restric
         }
         return;
     }
-    int s[3] = {0, 0, 0};
+    int s[NC] = {};
     for (long long m = m0; m < m1; ++m)
         for (int b = 0; b < bpm; ++b) s[b < hv ? 0 : b - hv + 1] += coef[(m * bpm + b) * 64];
-    for (int c = 0; c < 3; ++c) part[c][tid] = s[c];
+    for (int c = 0; c < NC; ++c) part[c][tid] = s[c];
     __syncthreads();
     for (int d = 1; d < 256; d <<= 1) {
-        int a[3];
-        for (int c = 0; c < 3; ++c) a[c] = tid >= d ? part[c][tid - d] : 0;
+        int a[NC];
+        for (int c = 0; c < NC; ++c) a[c] = tid >= d ? part[c][tid - d] : 0;
         __syncthreads();
-        for (int c = 0; c < 3; ++c) part[c][tid] += a[c];
+        for (int c = 0; c < NC; ++c) part[c][tid] += a[c];
         __syncthreads();
     }
-    int run[3];
-    for (int c = 0; c < 3; ++c) run[c] = part[c][tid] - s[c];
+    int run[NC];
+    for (int c = 0; c < NC; ++c) run[c] = part[c][tid] - s[c];
     for (long long m = m0; m < m1; ++m)
         for (int b = 0; b < bpm; ++b) {
             const int c = b < hv ? 0 : b - hv + 1;
@@ -746,9 +788,10 @@ __device__ __forceinline__ void jp_idct8(const int* v, int stride, int* o, int o
 // transform's coefficients (61 214) keeps every pre-shift output under 2^31, so the wrap-around of any partial sum cancels.
 // A file outside the range goes back to Pillow (status 4) - whatever the SIMD level of the machine that decodes it there.
 // Files Pillow encodes itself stay far inside it (tests/test_jpeg.py).
-__global__ void __launch_bounds__(128) jpeg_idct_kernel(const JpegImage* __restrict__ images, const short* __restrict__ coef_all,
+template <class Im>
+__global__ void __launch_bounds__(128) jpeg_idct_kernel(const Im* __restrict__ images, const short* __restrict__ coef_all,
                                                         unsigned char* __restrict__ planes, int* __restrict__ status) {
-    const JpegImage& im = images[blockIdx.y];
+    const Im& im = images[blockIdx.y];
     const JpegGeom g = jpeg_geom(&im, planes);
     const int hs = g.hs, vs = g.vs, hv = g.hv, bpm = g.bpm, mx = g.mx;
     const long long b = (long long)blockIdx.x * 128 + threadIdx.x;
@@ -899,6 +942,40 @@ __global__ void __launch_bounds__(256) jpeg_color_kernel(const JpegImage* __rest
     const unsigned v = jp_pixel(g, x, y);
     unsigned char* o = out + im.out_off + ((size_t)y * g.W + x) * 3;
     o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16);
+}
+
+// ---- Four-component files (clipmi_jpeg_decode_cmyk8): Pillow's mode-CMYK bytes, rows of width*4. Pillow reads libjpeg's CMYK
+// output with rawmode CMYK;I - every byte inverted - whatever the markers say. With p0..p3 the four upsampled samples (components
+// 1-3 upsampled exactly as chroma is, per plane: jp_chroma_more):
+//   transform 2, CMYK as stored: libjpeg copies the samples        -> (255 - p0, 255 - p1, 255 - p2, 255 - p3)
+//   transform 3, YCCK: jdcolor.c ycck_cmyk_convert gives (255 - R, 255 - G, 255 - B, p3) with R, G, B jp_rgb's of (p0, p1, p2)
+//                                                                   -> (R, G, B, 255 - p3)
+// One pixel per thread, the four bytes in one store where the image's rows are 4-byte aligned.
+__global__ void __launch_bounds__(256) jpeg_cmyk_kernel(const JpegImage4* __restrict__ images, const unsigned char* __restrict__ planes,
+                                                        unsigned char* __restrict__ out) {
+    const JpegImage4& im = images[blockIdx.y];
+    const JpegGeom g = jpeg_geom(&im, planes);
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (!g.color || idx >= (long long)g.W * g.H) return;        // (a record jpeg_unstuff_kernel emptied has no pixels)
+    const int y = (int)(idx / g.W), x = (int)(idx - (long long)y * g.W);
+    const int p0 = g.py[(size_t)y * g.yw + x];
+    const bool vfancy = g.mode == JM_H2V2 || g.mode == JM_H1V2;
+    const int cy = y >> g.sy, oy = vfancy ? jp_context_row(g, y) : cy;
+    const int k = g.mode == JM_H1V2 ? 1 + (y & 1) : g.sx;      // jp_chroma_more's last argument
+    int p[3];
+    for (int c = 0; c < 3; ++c) {
+        const unsigned char* pl = g.py + g.plane_off(c + 1);
+        p[c] = jp_chroma_more(pl + (size_t)cy * g.cw, pl + (size_t)oy * g.cw, 0, x, g.dw, g.mode, k);
+    }
+    const unsigned stored = ~((unsigned)p0 | ((unsigned)p[0] << 8) | ((unsigned)p[1] << 16) | ((unsigned)p[2] << 24));
+    const unsigned ycck = jp_rgb(p0, p[0], p[1]) | ((255u - (unsigned)p[2]) << 24);
+    const unsigned v = im.transform == 3 ? ycck : stored;
+    unsigned char* o = out + im.out_off + ((size_t)y * g.W + x) * 4;
+    if ((reinterpret_cast<uintptr_t>(o) & 3) == 0) {
+        *reinterpret_cast<unsigned*>(o) = v;
+    } else {
+        o[0] = (unsigned char)v; o[1] = (unsigned char)(v >> 8); o[2] = (unsigned char)(v >> 16); o[3] = (unsigned char)(v >> 24);
+    }
 }
 
 // ---- jpeg_color_kernel + resize_h_kernel (resize.hip) in one pass, for the transform entries: the full-size RGB image is never
@@ -1401,11 +1478,14 @@ static bool jpeg_args_ok(const void* streams_dev, const void* images_dev, int n,
            max_blocks >= 1 && max_blocks <= total_blocks;
 }
 
-// The baseline decode up to the sample planes (shared by the decode and the transform entry) -> 0 and the planes, or an error
+// The baseline decode up to the sample planes (shared by the decode and the transform entry, and by the four-component decode
+// entry: Im = JpegImage4 launches that record's instantiation of each kernel) -> 0 and the planes, or an error
+template <class Im = JpegImage>
 static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
                                 int64_t total_blocks, int64_t max_blocks, int32_t* status_dev, void* ws_dev, int64_t ws_bytes,
                                 hipStream_t st, unsigned char** planes_out) {
     static_assert(sizeof(JpegImage) == sizeof(clipmi_jpeg_image) && sizeof(JpegImage) == 288, "clipmi_jpeg_image layout");
+    static_assert(sizeof(JpegImage4) == sizeof(clipmi_jpeg_image4) && sizeof(JpegImage4) == 360, "clipmi_jpeg_image4 layout");
     if (ws_bytes < clipmi_jpeg_workspace_bytes(total_blocks, ntables))
         return set_err(CLIPMI_EINVAL, "%s: workspace of %lld bytes, %lld needed", who, (long long)ws_bytes,
                        (long long)clipmi_jpeg_workspace_bytes(total_blocks, ntables));
@@ -1414,19 +1494,21 @@ static int jpeg_baseline_planes(const char* who, void* streams_dev, void* images
     JpLut* luts = ar.take<JpLut>((size_t)ntables);
     short* coef = ar.take<short>((size_t)total_blocks * 64);
     unsigned char* planes = ar.take<unsigned char>((size_t)total_blocks * 64);
-    JpegImage* images = static_cast<JpegImage*>(images_dev);
-    hipLaunchKernelGGL(jpeg_unstuff_kernel, dim3((unsigned)n), dim3(256), 0, st, static_cast<unsigned char*>(streams_dev), images);
+    Im* images = static_cast<Im*>(images_dev);
+    hipLaunchKernelGGL(jpeg_unstuff_kernel<Im>, dim3((unsigned)n), dim3(256), 0, st, static_cast<unsigned char*>(streams_dev), images);
     CLIPMI_CHECK_LAUNCH("jpeg_unstuff_kernel");
     if (zero_async(coef, (size_t)total_blocks * 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "%s: zero_async", who);
     hipLaunchKernelGGL(jpeg_build_luts_kernel, dim3((unsigned)ntables), dim3(256), 0, st, static_cast<const unsigned char*>(tables_dev), luts);
     CLIPMI_CHECK_LAUNCH("jpeg_build_luts_kernel");
-    hipLaunchKernelGGL(jpeg_huffman_kernel, dim3((unsigned)n), dim3(JP_T), 0, st, static_cast<const unsigned char*>(streams_dev), images,
-                       luts, coef, status_dev);
-    CLIPMI_CHECK_LAUNCH("jpeg_huffman_kernel");
-    hipLaunchKernelGGL(jpeg_dc_kernel, dim3((unsigned)n), dim3(256), 0, st, images, coef);
-    CLIPMI_CHECK_LAUNCH("jpeg_dc_kernel");
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
+    const unsigned char* streams = static_cast<const unsigned char*>(streams_dev);
+    const dim3 idct_grid((unsigned)((max_blocks + 127) / 128), (unsigned)n);
+    hipLaunchKernelGGL(jpeg_huffman_kernel<Im>, dim3((unsigned)n), dim3(JP_T), 0, st, streams, static_cast<const Im*>(images), luts, coef,
                        status_dev);
+    CLIPMI_CHECK_LAUNCH("jpeg_huffman_kernel");
+    hipLaunchKernelGGL(jpeg_dc_kernel<Im>, dim3((unsigned)n), dim3(256), 0, st, static_cast<const Im*>(images), coef);
+    CLIPMI_CHECK_LAUNCH("jpeg_dc_kernel");
+    hipLaunchKernelGGL(jpeg_idct_kernel<Im>, idct_grid, dim3(128), 0, st, static_cast<const Im*>(images), static_cast<const short*>(coef),
+                       planes, status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
     *planes_out = planes;
     return 0;
@@ -1455,6 +1537,26 @@ extern "C" int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int 
                                       status_dev, ws_dev, ws_bytes, st, &planes))
         return rc;
     return jpeg_color_tail("jpeg_decode_rgb8", static_cast<const JpegImage*>(images_dev), planes, n, max_pixels, out_dev, st);
+}
+
+// Four-component files to Pillow's mode-CMYK rows: the baseline chain over clipmi_jpeg_image4 records, then jpeg_cmyk_kernel
+extern "C" int clipmi_jpeg_decode_cmyk8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                                        int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
+                                        void* ws_dev, int64_t ws_bytes, void* stream) {
+    if (n == 0) return 0;
+    if (!jpeg_args_ok(streams_dev, images_dev, n, tables_dev, ntables, total_blocks, max_blocks, status_dev, ws_dev) || !out_dev ||
+        max_pixels < 1)
+        return set_err(CLIPMI_EINVAL, "jpeg_decode_cmyk8: bad arguments");
+    if ((max_pixels + 255) / 256 > 0x7fffffffLL) return set_err(CLIPMI_EINVAL, "jpeg_decode_cmyk8: batch too large for one launch");
+    hipStream_t st = as_stream(stream);
+    unsigned char* planes = nullptr;
+    if (int rc = jpeg_baseline_planes<JpegImage4>("jpeg_decode_cmyk8", streams_dev, images_dev, n, tables_dev, ntables, total_blocks,
+                                                  max_blocks, status_dev, ws_dev, ws_bytes, st, &planes))
+        return rc;
+    hipLaunchKernelGGL(jpeg_cmyk_kernel, dim3((unsigned)((max_pixels + 255) / 256), (unsigned)n), dim3(256), 0, st,
+                       static_cast<const JpegImage4*>(images_dev), planes, static_cast<unsigned char*>(out_dev));
+    CLIPMI_CHECK_LAUNCH("jpeg_cmyk_kernel");
+    return 0;
 }
 
 // The transform entries' tail: the fused colour conversion + horizontal pass over the planes, then resize.hip's vertical pass
@@ -1519,8 +1621,8 @@ static int jpeg_progressive_planes(const char* who, const void* streams_dev, con
                        static_cast<const JpegProgImage*>(images_dev), static_cast<const JpegScan*>(scans_dev), nscans, luts, ntables,
                        images, coef, status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_progressive_kernel");
-    hipLaunchKernelGGL(jpeg_idct_kernel, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st, images, coef, planes,
-                       status_dev);
+    hipLaunchKernelGGL(jpeg_idct_kernel<JpegImage>, dim3((unsigned)((max_blocks + 127) / 128), (unsigned)n), dim3(128), 0, st,
+                       static_cast<const JpegImage*>(images), static_cast<const short*>(coef), planes, status_dev);
     CLIPMI_CHECK_LAUNCH("jpeg_idct_kernel");
     *planes_out = planes;
     *images_out = images;

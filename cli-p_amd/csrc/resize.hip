@@ -97,13 +97,28 @@ __device__ __forceinline__ unsigned rz_load_rgba(const unsigned char* p, bool pr
     return o;
 }
 
-__global__ void __launch_bounds__(256) resize_h_rgba_kernel(const unsigned char* __restrict__ raw, const ResizeJob* __restrict__ jobs,
-                                                            const int* __restrict__ coef, int n_px, unsigned char* __restrict__ scratch) {
+// The two passes over 4 bytes a pixel are written once (the `_px4` bodies) for the two pixel kinds that take them:
+//   RZ_RGBA  as above: premultiplied while a job resamples, un-premultiplied and alpha dropped in front of the store
+//   RZ_CMYK  (clipmi_resize_crop_cmyk8) Pillow resamples mode CMYK as four plain bands - no premultiplication - and
+//            `convert("RGB")` is, per pixel, nk = 255 - K, out_c = clip8(nk - muldiv255(c, nk)) for c in C, M, Y with
+//            muldiv255(a, b): t = a b + 128, ((t >> 8) + t) >> 8 (Convert.c cmyk2rgb) - applied in front of the vertical pass's
+//            store, whether or not the job resamples
+enum { RZ_RGBA = 0, RZ_CMYK = 1 };
+
+__device__ __forceinline__ int rz_cmyk2rgb(int c, int nk) {
+    const int t = c * nk + 128;
+    const int v = nk - (((t >> 8) + t) >> 8);
+    return v < 0 ? 0 : (v > 255 ? 255 : v);
+}
+
+template <int KIND>
+__device__ __forceinline__ void resize_h_px4(const unsigned char* __restrict__ raw, const ResizeJob* __restrict__ jobs,
+                                             const int* __restrict__ coef, int n_px, unsigned char* __restrict__ scratch) {
     const ResizeJob j = jobs[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int row = idx / n_px, x = idx - row * n_px;
     if (row >= j.nrows) return;
-    const bool premul = j.need_h || j.need_v;
+    const bool premul = KIND == RZ_RGBA && (j.need_h || j.need_v);
     const unsigned char* src = raw + j.src_off + (size_t)(j.r0 + row) * j.w * 4;
     unsigned char* dst = scratch + j.tmp_off + ((size_t)row * n_px + x) * 4;      // (tmp_off: a multiple of 4)
     if (!j.need_h) {
@@ -117,7 +132,7 @@ __global__ void __launch_bounds__(256) resize_h_rgba_kernel(const unsigned char*
     const unsigned char* p = src + (size_t)xmin * 4;
     for (int k = 0; k < cnt; ++k) {
         const int c = kk[k];
-        const unsigned v = rz_load_rgba(p + 4 * k, true);
+        const unsigned v = rz_load_rgba(p + 4 * k, KIND == RZ_RGBA);
         a0 += (int)(v & 255u) * c; a1 += (int)((v >> 8) & 255u) * c; a2 += (int)((v >> 16) & 255u) * c; a3 += (int)(v >> 24) * c;
     }
     // four byte stores, as resize_h_kernel's: with the four clips or-ed into one word hipcc (ROCm 7.2) picks v_ashr_pk_u8_i32 for
@@ -126,8 +141,18 @@ __global__ void __launch_bounds__(256) resize_h_rgba_kernel(const unsigned char*
     dst[0] = rz_clip8(a0); dst[1] = rz_clip8(a1); dst[2] = rz_clip8(a2); dst[3] = rz_clip8(a3);
 }
 
-__global__ void __launch_bounds__(256) resize_v_rgba_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ coef, int n_px,
-                                                            const unsigned char* __restrict__ scratch, unsigned char* __restrict__ out) {
+__global__ void __launch_bounds__(256) resize_h_rgba_kernel(const unsigned char* __restrict__ raw, const ResizeJob* __restrict__ jobs,
+                                                            const int* __restrict__ coef, int n_px, unsigned char* __restrict__ scratch) {
+    resize_h_px4<RZ_RGBA>(raw, jobs, coef, n_px, scratch);
+}
+__global__ void __launch_bounds__(256) resize_h_cmyk_kernel(const unsigned char* __restrict__ raw, const ResizeJob* __restrict__ jobs,
+                                                            const int* __restrict__ coef, int n_px, unsigned char* __restrict__ scratch) {
+    resize_h_px4<RZ_CMYK>(raw, jobs, coef, n_px, scratch);
+}
+
+template <int KIND>
+__device__ __forceinline__ void resize_v_px4(const ResizeJob* __restrict__ jobs, const int* __restrict__ coef, int n_px,
+                                             const unsigned char* __restrict__ scratch, unsigned char* __restrict__ out) {
     const ResizeJob j = jobs[blockIdx.y];
     const int idx = blockIdx.x * 256 + threadIdx.x;
     const int y = idx / n_px, x = idx - y * n_px;
@@ -152,10 +177,22 @@ __global__ void __launch_bounds__(256) resize_v_rgba_kernel(const ResizeJob* __r
         }
         c0 = rz_clip8(a0); c1 = rz_clip8(a1); c2 = rz_clip8(a2); a = rz_clip8(a3);
     }
-    if ((j.need_h || j.need_v) && a != 0 && a != 255) {        // Pillow's RGBa -> RGBA: copy at alpha 0 and 255, else clip(255 c / a)
+    if (KIND == RZ_CMYK) {                                     // the fourth byte is K
+        const int nk = 255 - a;
+        c0 = rz_cmyk2rgb(c0, nk); c1 = rz_cmyk2rgb(c1, nk); c2 = rz_cmyk2rgb(c2, nk);
+    } else if ((j.need_h || j.need_v) && a != 0 && a != 255) {        // Pillow's RGBa -> RGBA: copy at alpha 0 and 255, else clip(255 c / a)
         c0 = min(255, 255 * c0 / a); c1 = min(255, 255 * c1 / a); c2 = min(255, 255 * c2 / a);
     }
     o[0] = (unsigned char)c0; o[plane] = (unsigned char)c1; o[2 * plane] = (unsigned char)c2;
+}
+
+__global__ void __launch_bounds__(256) resize_v_rgba_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ coef, int n_px,
+                                                            const unsigned char* __restrict__ scratch, unsigned char* __restrict__ out) {
+    resize_v_px4<RZ_RGBA>(jobs, coef, n_px, scratch, out);
+}
+__global__ void __launch_bounds__(256) resize_v_cmyk_kernel(const ResizeJob* __restrict__ jobs, const int* __restrict__ coef, int n_px,
+                                                            const unsigned char* __restrict__ scratch, unsigned char* __restrict__ out) {
+    resize_v_px4<RZ_CMYK>(jobs, coef, n_px, scratch, out);
 }
 
 // ---- index rows (clipmi_nearest_crop_p8): Pillow resizes palette and 1-bit images with NEAREST whatever filter is asked for;
@@ -213,22 +250,36 @@ extern "C" int clipmi_resize_crop_rgb8(const void* raw_dev, const void* jobs_dev
     return launch_resize_v_rgb8(jobs_dev, njobs, coef_dev, n_px, scratch_dev, out_dev, st);
 }
 
-extern "C" int clipmi_resize_crop_rgba8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
-                                        int n_px, void* out_dev, void* scratch_dev, void* stream) {
+// The two entries over 4-byte pixels: the same checks and launches, each with its instantiation of the passes
+template <class H, class V>
+static int resize_crop_px4(const char* who, H h_kernel, V v_kernel, const void* raw_dev, const void* jobs_dev, int njobs, int max_rows,
+                           const int32_t* coef_dev, int n_px, void* out_dev, void* scratch_dev, void* stream) {
     if (njobs == 0) return 0;
     if (!raw_dev || !jobs_dev || !coef_dev || !out_dev || !scratch_dev || njobs < 0 || n_px < 1 || n_px > 4096 || max_rows < 1)
-        return set_err(CLIPMI_EINVAL, "resize_crop_rgba8: bad arguments");
+        return set_err(CLIPMI_EINVAL, "%s: bad arguments", who);
     hipStream_t st = as_stream(stream);
     const long long per_h = (long long)max_rows * n_px, per_v = (long long)n_px * n_px;
-    hipLaunchKernelGGL(resize_h_rgba_kernel, dim3((unsigned)((per_h + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
+    hipLaunchKernelGGL(h_kernel, dim3((unsigned)((per_h + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
                        static_cast<const unsigned char*>(raw_dev), static_cast<const ResizeJob*>(jobs_dev), coef_dev, n_px,
                        static_cast<unsigned char*>(scratch_dev));
-    CLIPMI_CHECK_LAUNCH("resize_h_rgba_kernel");
-    hipLaunchKernelGGL(resize_v_rgba_kernel, dim3((unsigned)((per_v + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
+    CLIPMI_CHECK_LAUNCH("resize_h_px4");
+    hipLaunchKernelGGL(v_kernel, dim3((unsigned)((per_v + 255) / 256), (unsigned)njobs), dim3(256), 0, st,
                        static_cast<const ResizeJob*>(jobs_dev), coef_dev, n_px, static_cast<const unsigned char*>(scratch_dev),
                        static_cast<unsigned char*>(out_dev));
-    CLIPMI_CHECK_LAUNCH("resize_v_rgba_kernel");
+    CLIPMI_CHECK_LAUNCH("resize_v_px4");
     return 0;
+}
+
+extern "C" int clipmi_resize_crop_rgba8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
+                                        int n_px, void* out_dev, void* scratch_dev, void* stream) {
+    return resize_crop_px4("resize_crop_rgba8", resize_h_rgba_kernel, resize_v_rgba_kernel, raw_dev, jobs_dev, njobs, max_rows, coef_dev,
+                           n_px, out_dev, scratch_dev, stream);
+}
+
+extern "C" int clipmi_resize_crop_cmyk8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
+                                        int n_px, void* out_dev, void* scratch_dev, void* stream) {
+    return resize_crop_px4("resize_crop_cmyk8", resize_h_cmyk_kernel, resize_v_cmyk_kernel, raw_dev, jobs_dev, njobs, max_rows, coef_dev,
+                           n_px, out_dev, scratch_dev, stream);
 }
 
 extern "C" int clipmi_nearest_crop_p8(const void* raw_dev, const void* jobs_dev, int njobs, const void* tabs_dev, int n_px,

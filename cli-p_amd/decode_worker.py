@@ -165,12 +165,17 @@ JPEG_HDR_INTS = 32        # header of a region that holds a parsed file (stage_j
 JPEG_QUANT_OFF = 128      # 3 x 64 quantisation steps, natural order
 JPEG_TABLES_OFF = 320     # six raw Huffman tables (jpeg_parse.TABLE_BYTES each): DC, AC per component
 JPEG_COEF_OFF = 2048      # the resize plan's coefficient blocks (int32), then what the format stores (16-byte aligned)
+# A four-component file's region (stage_jpeg_cmyk, KIND_JPEG_CMYK) has the same parts at offsets of its own - four rows of steps and
+# eight tables do not fit the gaps above; the other kinds' regions keep theirs:
+CMYK_QUANT_OFF = 128      # 4 x 64 quantisation steps, natural order
+CMYK_TABLES_OFF = 384     # eight raw Huffman tables: DC, AC per component
+CMYK_COEF_OFF = 2688      # the resize plan's coefficient blocks (HDR.COEF_OFF says so), then the segment and the intervals' offsets
 
 
 class HDR:
     """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, device_stage.py reads them
     through these names); [27..31] are zero. Offsets count bytes from the region's start."""
-    KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA or KIND_PNG_INDEX
+    KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA, KIND_PNG_INDEX or KIND_JPEG_CMYK
     NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
     COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
     BLOCKS = 7                # 8 x 8 blocks of the image (PNG: 0)
@@ -178,19 +183,22 @@ class HDR:
     NROWS = 9
     N_HCOEF, N_VCOEF = 16, 17                                       # ints in the horizontal and the vertical coefficient block
     DATA_OFF, COEF_OFF = 18, 19                                     # the format's data behind the coefficient blocks; the blocks
-    RESTART_INTERVAL, N_INTERVALS, INTERVALS_OFF, STUFFED = 20, 21, 22, 23     # baseline: DRI, number of intervals, offset of their
+    #                                                                 (JPEG_COEF_OFF; CMYK_COEF_OFF in a KIND_JPEG_CMYK region)
+    RESTART_INTERVAL, N_INTERVALS, INTERVALS_OFF, STUFFED = 20, 21, 22, 23     # baseline, KIND_JPEG_CMYK: DRI, number of intervals, offset of their
     #                                                                 uint32 byte offsets into the segment, 1: the segment keeps its stuffing
     TABLES_OFF, N_TABLES = 20, 21                                   # progressive: the scans' Huffman tables
     DEPTH, CTYPE, ENTRIES = 20, 21, 22                              # KIND_PNG_ALPHA, KIND_PNG_INDEX: bit depth, colour type, palette
     #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF
     TRANSFORM, LAYOUT = 24, 25                                      # baseline, progressive: the colour transform (0 YCbCr -> RGB, 1 none:
-    #                                                                 R, G, B components); 1: a file only LAYOUTS_BIT lets through
+    #                                                                 R, G, B components; KIND_JPEG_CMYK: 2 CMYK as stored, 3 YCCK);
+    #                                                                 1: a file only LAYOUTS_BIT lets through
     INTERLACE = 26                                                  # the PNG kinds: 1 an Adam7 file, which only PNG_INTERLACED_BIT lets
     #                                                                 through (its scanlines are those of its passes); 0 in a JPEG region
 
 
 KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
 KIND_PNG_ALPHA, KIND_PNG_INDEX = 7, 8                     # png_parse's kinds "alpha" and "index" (clipmi_png_decode_px8)
+KIND_JPEG_CMYK = 9                                        # four-component baseline files, CMYK as stored and YCCK (clipmi_jpeg_decode_cmyk8)
 _plans = {}
 
 
@@ -211,25 +219,25 @@ def _plan(w, h, n_px, nearest=False):
     return plan
 
 
-def _data_off(plan):
+def _data_off(plan, coef_off=JPEG_COEF_OFF):
     """The first free 16-aligned offset behind the header, the tables and the plan's coefficient blocks"""
-    return (JPEG_COEF_OFF + 4 * (plan["hcoef"].size + plan["vcoef"].size) + 15) // 16 * 16
+    return (coef_off + 4 * (plan["hcoef"].size + plan["vcoef"].size) + 15) // 16 * 16
 
 
 def _no_room(p, total):
     return p.width, p.height, -total                      # the file does not fit its region: what it would need
 
 
-def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0), interlace=0):
+def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0), interlace=0, coef_off=JPEG_COEF_OFF):
     """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23], layout = TRANSFORM LAYOUT) and the plan's
-    coefficient blocks"""
+    coefficient blocks (at coef_off)"""
     nh, nv = plan["hcoef"].size, plan["vcoef"].size
     ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
     ints[:] = [kind, p.width, p.height, *sampling, count, blocks, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
-               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan), JPEG_COEF_OFF, *specific, *layout,
+               plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan, coef_off), coef_off, *specific, *layout,
                interlace] + [0] * 5
     if nh + nv:
-        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=JPEG_COEF_OFF)
+        co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=coef_off)
         co[:nh] = plan["hcoef"]
         co[nh:] = plan["vcoef"]
 
@@ -256,22 +264,38 @@ def stage_jpeg(path, n_px, region, data=None, layouts=False):
     raises jpeg_parse.Unsupported for files Pillow has to decode. layouts: the request allows luma 1x2 / 4x1 / 1x4 and RGB-coded
     files (jpeg_parse.parse(layouts=True)); without it such a file raises Unsupported, as ever."""
     p = jpeg_parse.parse(_contents(path, data), keep_stuffing=True, layouts=layouts)     # (a plain slice where the file allows: the device removes the byte stuffing)
+    return _lay_out_baseline(region, KIND_BASELINE, p, n_px, JPEG_QUANT_OFF, JPEG_TABLES_OFF, JPEG_COEF_OFF)
+
+
+def _lay_out_baseline(region, kind, p, n_px, quant_off, tables_off, coef_off):
+    """stage_jpeg's and stage_jpeg_cmyk's body: the record `parse` returned into `region`, its parts at the kind's offsets"""
     plan = _plan(p.width, p.height, n_px)
-    o_stream = _data_off(plan)
+    o_stream = _data_off(plan, coef_off)
     o_int = _stream_end(o_stream, len(p.stream))
     n_int = len(p.starts) if p.ri else 0
     total = (o_int + 4 * n_int + 15) // 16 * 16
     if total > region.size:
         return _no_room(p, total)
-    _write_head(region, KIND_BASELINE, p, (p.ncomp, p.hs, p.vs), len(p.stream), p.blocks(), plan, (p.ri, n_int, o_int, p.stuffed),
-                _layout(p))
-    region[JPEG_QUANT_OFF:JPEG_QUANT_OFF + 192] = p.quant.reshape(-1)
-    region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 6 * jpeg_parse.TABLE_BYTES] = np.frombuffer(b"".join(p.tables), np.uint8)
+    _write_head(region, kind, p, (p.ncomp, p.hs, p.vs), len(p.stream), p.blocks(), plan, (p.ri, n_int, o_int, p.stuffed),
+                _layout(p), coef_off=coef_off)
+    region[quant_off:quant_off + p.quant.size] = p.quant.reshape(-1)
+    region[tables_off:tables_off + len(p.tables) * jpeg_parse.TABLE_BYTES] = np.frombuffer(b"".join(p.tables), np.uint8)
     _write_stream(region, o_stream, p.stream)
     if n_int:
         np.frombuffer(region, dtype=np.uint32, count=n_int, offset=o_int)[:] = p.starts
         region[o_int + 4 * n_int:total] = 0
     return p.width, p.height, total
+
+
+def stage_jpeg_cmyk(path, n_px, region, data=None, layouts=False):
+    """stage_jpeg for the four-component files jpeg_parse.parse(cmyk=True) lets through (clipmi_jpeg_decode_cmyk8): the same parts
+    - [header | quantisation steps | Huffman tables | resize plan coefficients | segment | the restart intervals' offsets] - at
+    CMYK_QUANT_OFF, CMYK_TABLES_OFF and CMYK_COEF_OFF, four rows of steps and eight tables. A grey or three-component file raises
+    Unsupported: those are stage_jpeg's (a launch group holds one kind of record). layouts: component 0 may be sampled 1x2 / 4x1 / 1x4."""
+    p = jpeg_parse.parse(_contents(path, data), keep_stuffing=True, layouts=layouts, cmyk=True)
+    if p.ncomp != 4:
+        raise jpeg_parse.Unsupported("not a four-component file")
+    return _lay_out_baseline(region, KIND_JPEG_CMYK, p, n_px, CMYK_QUANT_OFF, CMYK_TABLES_OFF, CMYK_COEF_OFF)
 
 
 PROG_SCAN_BYTES = 64      # one scan record in a progressive region: jpeg.SCAN's layout (clipmi_jpeg_scan), offsets region-relative
@@ -379,6 +403,10 @@ PARSED = (Kind(KIND_BASELINE, 2, "jpeg", stage_jpeg, "jpeg_files", "staged"),
           # alpha, palette and low-depth PNG files: one bit of the mode for both kinds, one stats key
           Kind(KIND_PNG_ALPHA, 16, "png", _stage_png_kind(KIND_PNG_ALPHA), "png_mode_files", "decoded"),
           Kind(KIND_PNG_INDEX, 16, "png", _stage_png_kind(KIND_PNG_INDEX), "png_mode_files", "decoded"))
+# Kinds added behind the five above. They are kept apart because PARSED is also the list of kinds every pull of
+# device_stage.formats() covers; serve(), the reply tags, DeviceStage and the status layout run over ALL_PARSED.
+PARSED_MORE = (Kind(KIND_JPEG_CMYK, 128, "jpeg", stage_jpeg_cmyk, "jpeg_cmyk_files", "staged"),)
+ALL_PARSED = PARSED + PARSED_MORE
 LAYOUTS_BIT = 32           # a bit of the mode that adds no kind: the two JPEG stagers run with layouts=True (jpeg_parse.parse(layouts=True));
 #                            encode_files counts the files it lets through (HDR.LAYOUT) under LAYOUTS_STAT
 LAYOUTS_STAT = "jpeg_layout_files"
@@ -393,21 +421,21 @@ def _stager_switches(mode, magic):
     if magic == "jpeg":
         return {"layouts": True} if mode & LAYOUTS_BIT else {}
     return {"interlaced": True} if mode & PNG_INTERLACED_BIT else {}
-PARSED_KINDS = frozenset(k.kind for k in PARSED)
-REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + PARSED)
+PARSED_KINDS = frozenset(k.kind for k in ALL_PARSED)
+REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + ALL_PARSED)
 WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
 
 
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (the bits of FULL_SIZE and PARSED, LAYOUTS_BIT and PNG_INTERLACED_BIT) |
+         what the region may take (the bits of FULL_SIZE and ALL_PARSED, LAYOUTS_BIT and PNG_INTERLACED_BIT) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |
-              a Kind's tag (FULL_SIZE, PARSED) + <iiq (w, h, bytes)>: the file sits in the region as that kind's stager left it,
+              a Kind's tag (FULL_SIZE, ALL_PARSED) + <iiq (w, h, bytes)>: the file sits in the region as that kind's stager left it,
               with its resize plan |
-              WANTED_TAG + <iiq (w, h, bytes)>: as b"1", and the file would have been one of PARSED with a region of that many
+              WANTED_TAG + <iiq (w, h, bytes)>: as b"1", and the file would have been one of ALL_PARSED with a region of that many
               bytes."""
     import mmap
     import os
@@ -442,14 +470,14 @@ def serve(fin, fout):
                 full = None
                 # the file is read once and its first bytes choose the parser (a PNG file used to be read by each of them in turn)
                 data = magic = None
-                if any(mode & k.bit for k in PARSED):
+                if any(mode & k.bit for k in ALL_PARSED):
                     try:
                         data = _contents(fname, None)
                     except OSError:                            # unreadable: Pillow reports it
                         data = None
                     if data is not None:
                         magic = "png" if data[:8] == b"\x89PNG\r\n\x1a\n" else "jpeg" if data[:2] == b"\xff\xd8" else None
-                for k in PARSED:
+                for k in ALL_PARSED:
                     if full is not None or wanted is not None or not mode & k.bit or magic != k.magic:
                         continue
                     try:

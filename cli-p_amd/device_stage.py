@@ -13,8 +13,8 @@ import numpy as np
 import torch
 
 from . import _lib
-from .decode_worker import (FULL_SIZE, HDR, KIND_BASELINE, KIND_PNG, KIND_PNG_ALPHA, KIND_PNG_INDEX, KIND_PROGRESSIVE, PARSED,
-                            PLAN_INTS)
+from .decode_worker import (ALL_PARSED, FULL_SIZE, HDR, KIND_BASELINE, KIND_JPEG_CMYK, KIND_PNG, KIND_PNG_ALPHA, KIND_PNG_INDEX,
+                            KIND_PROGRESSIVE, PARSED, PLAN_INTS)  # noqa: F401 (PARSED: the kinds formats() covers)
 
 
 def _headers(bigview, n, cap, slots):
@@ -62,36 +62,40 @@ def _decoded_jobs(hd, cap, slots, comp, n_px, px=3):
     return jobs, out_off, out_sz
 
 
-def jpeg_records(bigview, n, cap, slots, comp, n_px):
+def jpeg_records(bigview, n, cap, slots, comp, n_px, nc=3):
     """The device decoder's records out of a batch's regions of the big segment (decode_worker.stage_jpeg wrote them): every field
     comes out of the regions' headers as one strided numpy gather - no Python per image except the table-set look-up.
     bigview: the segment (uint8, n regions of cap bytes); slots: the regions that hold a parsed JPEG file; comp: slot -> row of the
     batch's tensor. -> (clipmi_jpeg_image records with offsets into the segment, distinct raw Huffman tables uint8, clipmi_resize_job
-    records whose sources are the decoder's outputs laid out back to back, output bytes per image, blocks per image, number of tables)"""
+    records whose sources are the decoder's outputs laid out back to back, output bytes per image, blocks per image, number of tables)
+    nc = 4: the regions decode_worker.stage_jpeg_cmyk wrote - clipmi_jpeg_image4 records, four rows of steps and eight tables at that
+    kind's offsets, decoded rows of 4 bytes a pixel."""
     from . import jpeg as J
-    from .decode_worker import JPEG_QUANT_OFF, JPEG_TABLES_OFF
+    from . import decode_worker as W
+    quant_off, tables_off = (W.CMYK_QUANT_OFF, W.CMYK_TABLES_OFF) if nc == 4 else (W.JPEG_QUANT_OFF, W.JPEG_TABLES_OFF)
+    nt = 2 * nc
     slots = np.asarray(slots, dtype=np.int64)
     n3 = len(slots)
     st = np.lib.stride_tricks.as_strided
     hd = _headers(bigview, n, cap, slots)
-    jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px)
+    jobs, out_off, out_sz = _decoded_jobs(hd, cap, slots, comp, n_px, 4 if nc == 4 else 3)
     blocks = hd[:, HDR.BLOCKS]
-    recs = np.zeros(n3, dtype=J.IMAGE)
+    recs = np.zeros(n3, dtype=J.IMAGE4 if nc == 4 else J.IMAGE)
     recs["stream_off"], recs["coef_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(blocks) - blocks, out_off
     recs["stream_bytes"], recs["width"], recs["height"] = hd[:, HDR.COUNT], hd[:, HDR.W], hd[:, HDR.H]
     recs["ncomp"], recs["hs"], recs["vs"] = hd[:, HDR.NCOMP], hd[:, HDR.HS], hd[:, HDR.VS]
     recs["restart_interval"], recs["n_intervals"] = hd[:, HDR.RESTART_INTERVAL], hd[:, HDR.N_INTERVALS]
     recs["intervals_off"], recs["stuffed"] = slots * cap + hd[:, HDR.INTERVALS_OFF], hd[:, HDR.STUFFED]
     recs["reserved"] = hd[:, HDR.TRANSFORM]                  # (the colour transform, clipmi_jpeg_image)
-    recs["quant"] = st(bigview[JPEG_QUANT_OFF:], shape=(n, 192), strides=(cap, 1))[slots].reshape(n3, 3, 64)
-    # the Huffman tables: distinct six-table sets first (files of one encoder share theirs), then distinct tables
-    tabs = st(bigview[JPEG_TABLES_OFF:], shape=(n, 6 * J.TABLE_BYTES), strides=(cap, 1))[slots]
-    sets, pool_t, set_idx = {}, {}, np.zeros((n3, 6), np.int32)
+    recs["quant"] = st(bigview[quant_off:], shape=(n, nc * 64), strides=(cap, 1))[slots].reshape(n3, nc, 64)
+    # the Huffman tables: distinct six-table (eight-table) sets first (files of one encoder share theirs), then distinct tables
+    tabs = st(bigview[tables_off:], shape=(n, nt * J.TABLE_BYTES), strides=(cap, 1))[slots]
+    sets, pool_t, set_idx = {}, {}, np.zeros((n3, nt), np.int32)
     for k in range(n3):
         key = tabs[k].tobytes()
         idx = sets.get(key)
         if idx is None:
-            idx = sets[key] = [pool_t.setdefault(key[t * J.TABLE_BYTES:(t + 1) * J.TABLE_BYTES], len(pool_t)) for t in range(6)]
+            idx = sets[key] = [pool_t.setdefault(key[t * J.TABLE_BYTES:(t + 1) * J.TABLE_BYTES], len(pool_t)) for t in range(nt)]
         set_idx[k] = idx
     recs["dc_tbl"], recs["ac_tbl"] = set_idx[:, 0::2], set_idx[:, 1::2]
     tables = np.frombuffer(b"".join(pool_t), np.uint8)
@@ -190,10 +194,10 @@ def _pack16(arrays):
 Transform = namedtuple("Transform", "max_rows n_px out scratch")
 
 
-def _jpeg_group(L, r, progressive=False, fused=False):
+def _jpeg_group(L, r, progressive=False, fused=False, cmyk=False):
     recs, *scans, tables, jobs, out_sz, blocks, nt = r            # scans: [the scan records] of progressive files, else []
     total, most, pixels = int(blocks.sum()), int(blocks.max()), int((recs["width"].astype(np.int64) * recs["height"]).max())
-    name = "clipmi_jpeg_decode_" + ("progressive_" if progressive else "") + ("transform_" if fused else "") + "rgb8"
+    name = "clipmi_jpeg_decode_" + ("progressive_" if progressive else "") + ("transform_" if fused else "") + ("cmyk8" if cmyk else "rgb8")
     ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(recs), total, nt) if progressive else L.clipmi_jpeg_workspace_bytes(total, nt))
 
     def decode(base, sb, offs, rgb, status, ws, stream, tr):
@@ -251,10 +255,28 @@ def formats(jpeg_fused=False):
     return {**_FORMATS, **_FUSED_FORMATS} if jpeg_fused else _FORMATS
 
 
+# The kinds of decode_worker.PARSED_MORE: four-component JPEG files decode to CMYK rows (jpeg_records(nc=4), clipmi_jpeg_decode_cmyk8)
+# and clipmi_resize_crop_cmyk8 transforms them - with jpeg_fused too: the fused entries do not take four components.
+cmyk_records = partial(jpeg_records, nc=4)
+_cmyk_group = partial(_jpeg_group, cmyk=True)
+_MORE_FORMATS = {KIND_JPEG_CMYK: Format(cmyk_records, lambda hd: hd[:, HDR.BLOCKS] * 192, _cmyk_group, 4, "clipmi_resize_crop_cmyk8")}
+
+
+def all_formats(jpeg_fused=False):
+    """formats(jpeg_fused) and the rows of the kinds added behind them: one row per kind of decode_worker.ALL_PARSED"""
+    return {**formats(jpeg_fused), **_MORE_FORMATS}
+
+
 def jpeg_fused_default():
     """$CLIPMI_DEVICE_JPEG_FUSED ("1" = on), off when unset"""
     import os
     return os.environ.get("CLIPMI_DEVICE_JPEG_FUSED", "0") not in ("", "0")
+
+
+def jpeg_cmyk_default():
+    """$CLIPMI_DEVICE_JPEG_CMYK ("1" = on), off when unset"""
+    import os
+    return os.environ.get("CLIPMI_DEVICE_JPEG_CMYK", "0") not in ("", "0")
 
 
 def jpeg_layouts_default():
@@ -296,7 +318,7 @@ class Pending:
 
     def __init__(self):
         self.keep = []           # device tensors the queued kernels read and write
-        self.status = None       # int32 device tensor: the decoders' per-file status, the kinds in PARSED's order (None: no parsed file)
+        self.status = None       # int32 device tensor: the decoders' per-file status, the kinds in ALL_PARSED's order (None: no parsed file)
         self.slots = None        # the slot of each status
         self.count_ok = []       # (stats key, lo, hi): ranges of `status` whose zeros count as files the device decoded
         self.chunk = self.good = None      # the batch's paths and its mask of good slots, for the files that go back to Pillow
@@ -316,7 +338,7 @@ KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files int
 
 class DeviceStage:
     """The batch's regions of the big segment -> their rows of the batch's tensor (run). pool: the DecodePool that owns the
-    segments; group_bytes: the HBM a group of parsed files may need (file_need); formats: formats()'s table."""
+    segments; group_bytes: the HBM a group of parsed files may need (file_need); formats: all_formats()'s table."""
 
     def __init__(self, pool, dev, copy_stream, n_px, group_bytes, formats):
         self.pool, self.dev, self.copy_stream, self.n_px, self.group_bytes, self.formats = pool, dev, copy_stream, n_px, group_bytes, formats
@@ -379,7 +401,7 @@ class DeviceStage:
         their rows of devt, on the copy stream behind devt's own copy: ONE H2D copy of the segment where it lies (it is page-locked:
         no packing copy on the host - packing 1 GB per batch of photo-sized images with one thread was slower than Pillow's resize),
         then clipmi_resize_crop_rgb8 for the full-size images (decode_worker.FULL_SIZE) and, for each kind of parsed file in
-        decode_worker.PARSED's order, its decode entry and its transform entry (the kind's Format).
+        decode_worker.ALL_PARSED's order, its decode entry and its transform entry (the kind's Format).
         The copy stream carries the copies only; the kernels go to the process's ONE side stream (_lib.side_stream: this ROCm gives a
         process three hardware queues) behind an event, so that the next batch's copy runs beside this batch's kernels instead of
         behind them, and the consumer finds them queued in front of its encode step.
@@ -393,8 +415,8 @@ class DeviceStage:
         cap = bigview.size // n
         used = (max(full) + 1) * cap
         e2 = np.array(sorted(s_ for s_, v in full.items() if v[0] == FULL_SIZE.kind), dtype=np.int64)
-        parsed = [np.array(sorted(s_ for s_, v in full.items() if v[0] == k.kind), dtype=np.int64) for k in PARSED]
-        n_status = sum(len(slots) for slots in parsed)      # one status tensor: the kinds in PARSED's order
+        parsed = [np.array(sorted(s_ for s_, v in full.items() if v[0] == k.kind), dtype=np.int64) for k in ALL_PARSED]
+        n_status = sum(len(slots) for slots in parsed)      # one status tensor: the kinds in ALL_PARSED's order
         in_place = self.pool.pin_segment(2 + seg_index)
         if in_place:
             slot = None
@@ -416,7 +438,7 @@ class DeviceStage:
                 djobs, scratch, max_rows = self._stage_full(bigview, full, e2, cap, comp)
                 pending.keep += [djobs, scratch]
             status_at = 0
-            for kind, slots in zip(PARSED, parsed):          # the kinds follow each other on the side stream in PARSED's order
+            for kind, slots in zip(ALL_PARSED, parsed):      # the kinds follow each other on the side stream in ALL_PARSED's order
                 if not len(slots):
                     continue
                 k = self._stage_kind(self.formats[kind.kind], bigview, n, cap, slots, comp, status_at)

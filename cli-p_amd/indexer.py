@@ -33,6 +33,8 @@ CLIPMI_DEVICE_PNG_MODES, DESIGN §4.9b - let through take the device decoder too
 CLIPMI_DEVICE_JPEG_LAYOUTS (default 0 = off; 1: JPEG files with luma sampling 1x2 - 4:4:0, what a lossless 90-degree rotation makes of
 a 4:2:2 file -, 4x1 or 1x4 and RGB-coded files take the device decoder too, Pillow's bytes; needs CLIPMI_DEVICE_JPEG_KB
 on, and CLIPMI_DEVICE_PROGRESSIVE for the progressive ones),
+CLIPMI_DEVICE_JPEG_CMYK (default 0 = off; 1: four-component baseline JPEG files, CMYK as stored and YCCK, take the device decoder too,
+Pillow's bytes; progressive ones and Adobe transform 1 stay with Pillow; needs CLIPMI_DEVICE_JPEG_KB on),
 CLIPMI_WORKERS (decode workers per rank, default min(16, CPUs / ranks on the node)), CLIPMI_DECODE (`procs`, the default: worker processes started before
 the GPU is touched — 23 k images/s end to end from 224 x 224 JPEGs on 16 workers against 4 k on threads, which the GIL
 binds; `threads`: the old form).

@@ -8,6 +8,9 @@ JPEG; with `layouts=True` luma 1x2 / 4x1 / 1x4 and RGB-coded files pass) raise `
 decode workers - that is a choice of decoder per file format, made on the host from the file's own header; a file the
 device then reports (status != 0: 1 an invalid Huffman code, 2 the data ended early or ran over, 3 a marker inside a segment handed over with its stuffing, 4 a block whose IDCT leaves the range where
 libjpeg-turbo's provably equals the device's) goes the same way, so that Pillow's error handling stays the reference's.
+`cmyk=True` down the stack (opt-in, encode_files(device_jpeg_cmyk=True)) adds the four-component files jpeg_parse.parse(cmyk=True)
+lets through, CMYK as stored and YCCK: their records are IMAGE4 (clipmi_jpeg_image4), clipmi_jpeg_decode_cmyk8 leaves Pillow's
+mode-CMYK bytes, rows of width*4, and clipmi_resize_crop_cmyk8 is their transform (Pillow resamples in mode CMYK and converts after).
 `transform_files` goes one step further: decode and the CLIP transform's resize + crop in one library call, without the full-size
 RGB rows in between (clipmi_jpeg_decode_transform_rgb8, opt-in in the pipeline: encode_files(jpeg_fused=True)).
 """
@@ -19,24 +22,37 @@ import torch
 from . import _lib
 from .jpeg_parse import TABLE_BYTES, Parsed, Progressive, Unsupported, is_layout, parse, parse_progressive  # noqa: F401
 
-IMAGE = np.dtype([("stream_off", "<i8"), ("coef_off", "<i8"), ("out_off", "<i8"), ("intervals_off", "<i8"), ("stream_bytes", "<i4"),
-                  ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("dc_tbl", "<i4", 3),
-                  ("ac_tbl", "<i4", 3), ("restart_interval", "<i4"), ("n_intervals", "<i4"), ("stuffed", "<i4"), ("reserved", "<i4"),
-                  ("quant", "u1", (3, 64))], align=True)
-assert IMAGE.itemsize == 288
+def _image_dtype(nc):
+    """clipmi_jpeg_image (nc = 3) / clipmi_jpeg_image4 (nc = 4): nc table indices of each class, nc rows of quantisation steps"""
+    return np.dtype([("stream_off", "<i8"), ("coef_off", "<i8"), ("out_off", "<i8"), ("intervals_off", "<i8"), ("stream_bytes", "<i4"),
+                     ("width", "<i4"), ("height", "<i4"), ("ncomp", "<i4"), ("hs", "<i4"), ("vs", "<i4"), ("dc_tbl", "<i4", nc),
+                     ("ac_tbl", "<i4", nc), ("restart_interval", "<i4"), ("n_intervals", "<i4"), ("stuffed", "<i4"), ("reserved", "<i4"),
+                     ("quant", "u1", (nc, 64))], align=True)
 
 
-def _opted_in(items, layouts):
-    """The records of the layouts that are opt-in (jpeg_parse.parse(layouts=True)) pass only where the caller opted in too"""
+IMAGE, IMAGE4 = _image_dtype(3), _image_dtype(4)      # IMAGE4: the record of a four-component file (parse(cmyk=True))
+assert IMAGE.itemsize == 288 and IMAGE4.itemsize == 360
+
+
+def _opted_in(items, layouts, cmyk=False):
+    """The records of the layouts that are opt-in (jpeg_parse.parse(layouts=True), parse(cmyk=True)) pass only where the caller
+    opted in too; three- and four-component records have different C records and entries, so one call takes one of the two"""
     if not layouts and any(is_layout(it) for it in items):
         raise Unsupported("a record of parse(layouts=True) packed without layouts=True")
+    four = [it.ncomp == 4 for it in items]
+    if any(four) and not cmyk:
+        raise Unsupported("a record of parse(cmyk=True) packed without cmyk=True")
+    if any(four) and not all(four):
+        raise Unsupported("four-component records and others in one batch")
 
 
-def pack(items, layouts=False):
+def pack(items, layouts=False, cmyk=False):
     """Parsed records -> (IMAGE array, tables uint8 [nt][288], streams uint8, out_bytes, total_blocks, max_blocks, max_pixels)
-    layouts: the records may be those parse(layouts=True) adds - their sampling factors and colour transform travel in the record"""
-    _opted_in(items, layouts)
-    recs = np.zeros(len(items), dtype=IMAGE)
+    layouts: the records may be those parse(layouts=True) adds - their sampling factors and colour transform travel in the record
+    cmyk: the records may be those parse(cmyk=True) adds, all of them or none: an IMAGE4 array then, the outputs w*h*4 bytes"""
+    _opted_in(items, layouts, cmyk)
+    px = 4 if items and items[0].ncomp == 4 else 3
+    recs = np.zeros(len(items), dtype=IMAGE4 if px == 4 else IMAGE)
     pool = {}
     soff = coff = ooff = 0
     max_blocks = max_pixels = 1
@@ -61,7 +77,7 @@ def pack(items, layouts=False):
             soff += len(raw)
         nb = it.blocks()
         coff += nb
-        ooff += (it.width * it.height * 3 + 15) // 16 * 16
+        ooff += (it.width * it.height * px + 15) // 16 * 16
         max_blocks, max_pixels = max(max_blocks, nb), max(max_pixels, it.width * it.height)
     tables = np.frombuffer(b"".join(pool), np.uint8).reshape(-1, TABLE_BYTES) if pool else np.zeros((0, TABLE_BYTES), np.uint8)
     return recs, tables, np.frombuffer(b"".join(pieces), np.uint8), ooff, coff, max_blocks, max_pixels
@@ -97,11 +113,13 @@ def _decode_device(items, device, packer, workspace, entry):
     return out, recs, status
 
 
-def decode_device(items, device, stream=None, layouts=False):
+def decode_device(items, device, stream=None, layouts=False, cmyk=False):
     """Parsed records -> (out uint8 device tensor, records, status int32 device tensor): the RGB rows of image k start at
-    records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is."""
-    return _decode_device(items, device, partial(pack, layouts=layouts), lambda L, n, blocks, nt: L.clipmi_jpeg_workspace_bytes(blocks, nt),
-                          "clipmi_jpeg_decode_rgb8")
+    records[k]["out_off"]. Asynchronous on torch's current stream of `device`; status is valid once that stream is.
+    cmyk: four-component records (all of them, or none: pack) go to clipmi_jpeg_decode_cmyk8 - rows of width*4 CMYK bytes."""
+    four = cmyk and any(it.ncomp == 4 for it in items)
+    return _decode_device(items, device, partial(pack, layouts=layouts, cmyk=cmyk), lambda L, n, blocks, nt: L.clipmi_jpeg_workspace_bytes(blocks, nt),
+                          "clipmi_jpeg_decode_cmyk8" if four else "clipmi_jpeg_decode_rgb8")
 
 
 def _decode_files(blobs, device, parser, decode):
@@ -116,24 +134,30 @@ def _decode_files(blobs, device, parser, decode):
     res = [None] * len(blobs)
     if not items:
         return res
-    out, recs, status = decode(items, device)
-    st = status.cpu().numpy()
-    host = out.cpu().numpy()
-    for t, k in enumerate(where):
-        if st[t] == 0:
-            r = recs[t]
-            h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
-            res[k] = host[o:o + h * w * 3].reshape(h, w, 3)
+    # (four-component records decode in a call of their own: another record, another entry, 4 bytes a pixel)
+    for px in (3, 4):
+        sel = [t for t, it in enumerate(items) if (getattr(it, "ncomp", 3) == 4) == (px == 4)]
+        if not sel:
+            continue
+        out, recs, status = decode([items[t] for t in sel], device)
+        st = status.cpu().numpy()
+        host = out.cpu().numpy()
+        for u, t in enumerate(sel):
+            if st[u] == 0:
+                r = recs[u]
+                h, w, o = int(r["height"]), int(r["width"]), int(r["out_off"])
+                res[where[t]] = host[o:o + h * w * px].reshape(h, w, px)
     return res
 
 
-def decode_files(blobs, device, keep_stuffing=False, layouts=False):
+def decode_files(blobs, device, keep_stuffing=False, layouts=False, cmyk=False):
     """JPEG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
     device reported it corrupt). Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM.
     keep_stuffing: hand the segments over as they are in the file and let the device remove the byte stuffing (the pipeline's form).
-    layouts: also decode luma 1x2 / 4x1 / 1x4 and RGB-coded files (jpeg_parse.parse(layouts=True))."""
-    return _decode_files(blobs, device, lambda b: parse(b, keep_stuffing=keep_stuffing, layouts=layouts),
-                         partial(decode_device, layouts=layouts))
+    layouts: also decode luma 1x2 / 4x1 / 1x4 and RGB-coded files (jpeg_parse.parse(layouts=True)).
+    cmyk: also decode four-component files (jpeg_parse.parse(cmyk=True)): [H,W,4] arrays, np.asarray(Image.open(f)) of a CMYK file."""
+    return _decode_files(blobs, device, lambda b: parse(b, keep_stuffing=keep_stuffing, layouts=layouts, cmyk=cmyk),
+                         partial(decode_device, layouts=layouts, cmyk=cmyk))
 
 
 # ---- progressive files (jpeg_parse.parse_progressive; csrc/jpeg.hip jpeg_progressive_kernel). Opt-in in the pipeline.
@@ -202,45 +226,48 @@ class Staged:
     __slots__ = ("n", "n_px", "device", "groups", "keep")
 
 
-def stage_transform(blobs, n_px, device, keep_stuffing=False, layouts=False):
+def stage_transform(blobs, n_px, device, keep_stuffing=False, layouts=False, cmyk=False):
     """JPEG file contents (or records parse / parse_progressive returned) -> Staged: the records of both kinds packed, the
     transform planned with decode_worker's planner (resize.pack_jobs: job k writes block k of the output, whichever kind file k
     is), everything copied to the device, workspaces allocated. Raises Unsupported for a file neither parser takes.
-    layouts: the parsers run with layouts=True, and records of those layouts are taken."""
+    layouts: the parsers run with layouts=True, and records of those layouts are taken.
+    cmyk: `parse` runs with cmyk=True, and the four-component files are a third group, which run_transform decodes to CMYK rows
+    and hands to clipmi_resize_crop_cmyk8 whatever `fused` says (the fused entries do not take four components)."""
     from . import resize
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.ClipmiError("jpeg.stage_transform needs the HIP path (no CPU fallback)")
     L = _lib.lib()
-    kinds = ([], [])                                      # (position, record) of the baseline and of the progressive files
+    kinds = ([], [], [])                                  # (position, record) of the baseline, the progressive and the four-component files
     for k, b in enumerate(blobs):
         if not isinstance(b, (Parsed, Progressive)):
             try:
-                b = parse(b, keep_stuffing=keep_stuffing, layouts=layouts)
+                b = parse(b, keep_stuffing=keep_stuffing, layouts=layouts, cmyk=cmyk)
             except Unsupported:
                 b = parse_progressive(b, layouts=layouts)
-        kinds[isinstance(b, Progressive)].append((k, b))
+        kinds[2 if b.ncomp == 4 else isinstance(b, Progressive)].append((k, b))
     st = Staged()
     st.n, st.n_px, st.device, st.groups, st.keep = len(blobs), n_px, device, [], []
-    for progressive, members in enumerate(kinds):
+    for which, members in enumerate(kinds):
         if not members:
             continue
         items = [it for _, it in members]
+        progressive, px = which == 1, 4 if which == 2 else 3
         if progressive:
             recs, scans, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack_progressive(items, layouts)
             arrays = [recs, scans, tables]
             ws_bytes = int(L.clipmi_jpeg_progressive_workspace_bytes(len(items), total_blocks, len(tables)))
         else:
-            recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items, layouts)
+            recs, tables, streams, out_bytes, total_blocks, max_blocks, max_pixels = pack(items, layouts, cmyk)
             arrays = [recs, tables]
             ws_bytes = int(L.clipmi_jpeg_workspace_bytes(total_blocks, len(tables)))
-        jobs, coef, _, scratch_bytes, max_rows = resize.pack_jobs([(it.height, it.width) for it in items], n_px)
+        jobs, coef, _, scratch_bytes, max_rows = resize.pack_jobs([(it.height, it.width) for it in items], n_px, px=px)
         jobs["out_index"] = [k for k, _ in members]
         jobs["src_off"] = recs["out_off"]                 # (the decoder's rows: what the unfused form's resize reads)
         arrays += [jobs, coef, streams]
         dev, offs, host = _lib.to_device16(arrays, device)
         st.keep.append(host)
-        st.groups.append(dict(progressive=bool(progressive), n=len(items), dev=dev, offs=offs, nscans=len(scans) if progressive else 0,
+        st.groups.append(dict(progressive=progressive, px=px, n=len(items), dev=dev, offs=offs, nscans=len(scans) if progressive else 0,
                               ntables=len(tables), total_blocks=total_blocks, max_blocks=max_blocks, max_pixels=max_pixels,
                               out_bytes=out_bytes, max_rows=max_rows, ws_bytes=ws_bytes,
                               ws=torch.empty(ws_bytes, dtype=torch.uint8, device=device),
@@ -252,7 +279,8 @@ def stage_transform(blobs, n_px, device, keep_stuffing=False, layouts=False):
 def run_transform(st, fused=True):
     """Staged -> (uint8 [n][3][n_px][n_px] device tensor, int32 [n] status device tensor; a file with a non-zero status has
     unspecified pixels). fused: clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8; not fused: the decode
-    entries into full-size RGB rows, then clipmi_resize_crop_rgb8 over them. Asynchronous on torch's current stream."""
+    entries into full-size RGB rows, then clipmi_resize_crop_rgb8 over them; a group of four-component files (stage_transform(cmyk=True))
+    always takes the second form, through clipmi_jpeg_decode_cmyk8 and clipmi_resize_crop_cmyk8. Asynchronous on torch's current stream."""
     L = _lib.lib()
     out = torch.empty((st.n, 3, st.n_px, st.n_px), dtype=torch.uint8, device=st.device)
     status = torch.zeros(max(st.n, 1), dtype=torch.int32, device=st.device)
@@ -264,25 +292,25 @@ def run_transform(st, fused=True):
         head += (g["ntables"], g["total_blocks"], g["max_blocks"])
         jobs, coef = base + o[-3], base + o[-2]
         tail = (gst.data_ptr(), g["ws"].data_ptr(), g["ws_bytes"], stream)
-        if fused:
+        if fused and g["px"] == 3:
             name = "clipmi_jpeg_decode_progressive_transform_rgb8" if g["progressive"] else "clipmi_jpeg_decode_transform_rgb8"
             rc = getattr(L, name)(*head, jobs, g["max_rows"], coef, st.n_px, out.data_ptr(), g["scratch"].data_ptr(), *tail)
             _lib.check(rc, name)
         else:
-            name = "clipmi_jpeg_decode_progressive_rgb8" if g["progressive"] else "clipmi_jpeg_decode_rgb8"
+            name = "clipmi_jpeg_decode_cmyk8" if g["px"] == 4 else "clipmi_jpeg_decode_progressive_rgb8" if g["progressive"] else "clipmi_jpeg_decode_rgb8"
+            resize = "clipmi_resize_crop_cmyk8" if g["px"] == 4 else "clipmi_resize_crop_rgb8"
             rgb = torch.empty(max(g["out_bytes"], 16), dtype=torch.uint8, device=st.device)
             _lib.check(getattr(L, name)(*head, g["max_pixels"], rgb.data_ptr(), *tail), name)
-            rc = L.clipmi_resize_crop_rgb8(rgb.data_ptr(), jobs, g["n"], g["max_rows"], coef, st.n_px, out.data_ptr(),
-                                           g["scratch"].data_ptr(), stream)
-            _lib.check(rc, "clipmi_resize_crop_rgb8")
+            rc = getattr(L, resize)(rgb.data_ptr(), jobs, g["n"], g["max_rows"], coef, st.n_px, out.data_ptr(), g["scratch"].data_ptr(), stream)
+            _lib.check(rc, resize)
             rgb.record_stream(torch.cuda.current_stream(st.device))
         status.index_copy_(0, g["where"], gst)
     return out, status[:st.n]
 
 
-def transform_files(blobs, n_px, device, fused=True, layouts=False):
+def transform_files(blobs, n_px, device, fused=True, layouts=False, cmyk=False):
     """JPEG file contents, baseline and progressive alike -> (uint8 [n][3][n_px][n_px] device tensor: Pillow's decode + bicubic resize
     of the shorter side to n_px + centre crop, as decode_worker.load_uint8; int32 [n] status device tensor, as the decode entries').
     fused=False computes the same through the decode entries and clipmi_resize_crop_rgb8, with the full-size RGB rows between.
-    layouts: as stage_transform's."""
-    return run_transform(stage_transform(blobs, n_px, device, layouts=layouts), fused)
+    layouts, cmyk: as stage_transform's."""
+    return run_transform(stage_transform(blobs, n_px, device, layouts=layouts, cmyk=cmyk), fused)

@@ -11,7 +11,13 @@ That is a choice of decoder per file format, made on the host from the file's ow
 `layouts=True` (both parsers; opt-in, encode_files(device_jpeg_layouts=True)) also lets through YCbCr files with luma sampling
 1x2 (4:4:0), 4x1 (4:1:1) or 1x4 and 1x1 chroma, and the three-component files libjpeg takes for RGB-coded (no JFIF marker and an
 Adobe marker with transform 0 or the component ids R, G, B) at any luma sampling the device takes: `transform` = 1 in the record,
-the three upsampled planes are the pixels. Luma 4x2, 2x4, a factor of 3, subsampled luma and CMYK / YCCK stay refused.
+the three upsampled planes are the pixels. Luma 4x2, 2x4, a factor of 3 and subsampled luma stay refused.
+
+`cmyk=True` (`parse` only; opt-in, encode_files(device_jpeg_cmyk=True)) also lets through four-component files whose components
+1-3 are sampled 1x1 and whose component 0 has a sampling the device takes (the LAYOUT_SAMPLINGS with layouts=True as well):
+`ncomp` = 4, eight tables, `quant` [4][64], `transform` = 2 (CMYK as stored: no Adobe marker, or Adobe transform 0) or 3 (YCCK:
+Adobe transform 2) - libjpeg's default_decompress_parms for four components, where a JFIF marker plays no part. Adobe transform
+1, component 3 sampled like component 0 (IJG's own YCCK default) and progressive four-component files stay refused.
 """
 import re
 
@@ -42,15 +48,16 @@ class Unsupported(Exception):
 class Parsed:
     __slots__ = ("width", "height", "ncomp", "hs", "vs", "quant", "tables", "stream", "ri", "starts", "stuffed", "transform")
     # transform: the colour transform, 0 = YCbCr -> RGB (and grey), 1 = none: the components are R, G, B (parse(layouts=True) only);
+    # 2 = CMYK as stored, 3 = YCCK (four components: parse(cmyk=True) only);
     # ri: restart interval in MCUs (0: none); starts: uint32 byte offsets into `stream` of the restart intervals (None without);
     # stuffed: 1 = `stream` is the file's segment as it is, 0xFF00 stuffing included (parse(keep_stuffing=True))
 
     def mcus(self):
-        hs, vs = (self.hs, self.vs) if self.ncomp == 3 else (1, 1)
+        hs, vs = (self.hs, self.vs) if self.ncomp != 1 else (1, 1)
         return -(-self.width // (8 * hs)) * -(-self.height // (8 * vs))
 
     def blocks(self):
-        return self.mcus() * (self.hs * self.vs + 2 if self.ncomp == 3 else 1)
+        return self.mcus() * (self.hs * self.vs + self.ncomp - 1 if self.ncomp != 1 else 1)
 
 
 SAMPLINGS = ((1, 1), (2, 1), (2, 2))                 # luma sampling factors the device takes (chroma 1x1) ...
@@ -58,33 +65,43 @@ LAYOUT_SAMPLINGS = ((1, 2), (4, 1), (1, 4))          # ... and those `layouts=Tr
 
 
 def _sampling(comps, jfif, adobe, adobe_tf, width, layouts):
-    """The two parsers' rule for a three-component frame -> (hs, vs, transform); raises Unsupported"""
-    ids = (comps[0][0], comps[1][0], comps[2][0])
-    # jdapimin.c default_decompress_parms: which three-component files are YCbCr
-    ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
-    if not ycc and not layouts:
-        raise Unsupported("RGB-coded JPEG")
+    """The two parsers' rule for a three-component frame, and `parse`'s for a four-component one -> (hs, vs, transform); raises
+    Unsupported"""
+    if len(comps) == 4:
+        # jdapimin.c default_decompress_parms, four components: CMYK unless an Adobe marker says YCCK (a JFIF marker plays no part);
+        # another transform value libjpeg warns about and takes for YCCK - Pillow's file
+        tf = {0: 2, 2: 3}.get(adobe_tf if adobe else 0)
+        if tf is None:
+            raise Unsupported("Adobe transform of a four-component file")
+    else:
+        ids = (comps[0][0], comps[1][0], comps[2][0])
+        # jdapimin.c default_decompress_parms: which three-component files are YCbCr
+        ycc = True if jfif else (adobe_tf != 0) if adobe else ids != (0x52, 0x47, 0x42)
+        if not ycc and not layouts:
+            raise Unsupported("RGB-coded JPEG")
+        tf = 0 if ycc else 1
     hs, vs = comps[0][1], comps[0][2]
-    if (comps[1][1], comps[1][2], comps[2][1], comps[2][2]) != (1, 1, 1, 1) or \
+    if any((h, v) != (1, 1) for _, h, v, _ in comps[1:]) or \
             (hs, vs) not in (SAMPLINGS + LAYOUT_SAMPLINGS if layouts else SAMPLINGS):
         raise Unsupported("sampling factors")
     if hs == 2 and (width + 1) // 2 <= 2:
         raise Unsupported("too narrow for fancy upsampling")
-    return hs, vs, 0 if ycc else 1
+    return hs, vs, tf
 
 
 def is_layout(p):
     """Whether `layouts=True` was needed for this record (Parsed or Progressive): the files the switch adds"""
-    return p.ncomp == 3 and (p.transform != 0 or (p.hs, p.vs) in LAYOUT_SAMPLINGS)
+    return (p.ncomp == 3 and p.transform != 0) or (p.ncomp != 1 and (p.hs, p.vs) in LAYOUT_SAMPLINGS)
 
 
-def parse(data, keep_stuffing=False, layouts=False):
+def parse(data, keep_stuffing=False, layouts=False, cmyk=False):
     """JPEG file bytes -> Parsed (header fields, quantisation steps in natural order, the six Huffman tables a scan can
     name as raw 288-byte records, the entropy-coded segment without byte stuffing). Raises Unsupported.
     keep_stuffing: a file without restart intervals that ends with its EOI marker is only SLICED - the segment keeps its stuffing
     (Parsed.stuffed = 1) and the device removes it and looks for markers inside (csrc/jpeg.hip jpeg_unstuff_kernel): no pass over
     the data on the host at all.
-    layouts: also take luma 1x2 / 4x1 / 1x4 and RGB-coded files (the module's docstring)."""
+    layouts: also take luma 1x2 / 4x1 / 1x4 and RGB-coded files (the module's docstring).
+    cmyk: also take four-component files, CMYK as stored or YCCK (the module's docstring): eight tables, quant [4][64]."""
     if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
         raise Unsupported("not a JPEG file")
     n = len(data)
@@ -165,7 +182,7 @@ def parse(data, keep_stuffing=False, layouts=False):
         raise Unsupported("no frame header")
     height, width, comps = frame
     nc = len(comps)
-    if width == 0 or height == 0 or nc not in (1, 3):
+    if width == 0 or height == 0 or nc not in ((1, 3, 4) if cmyk else (1, 3)):
         raise Unsupported("frame")
     ns = data[i + 4]
     if ns != nc or L != 6 + 2 * ns or data[i + 5 + 2 * ns] != 0 or data[i + 6 + 2 * ns] != 63 or data[i + 7 + 2 * ns] != 0:
@@ -173,7 +190,7 @@ def parse(data, keep_stuffing=False, layouts=False):
     out = Parsed()
     out.width, out.height, out.ncomp = width, height, nc
     tables = []
-    quant = np.zeros((3, 64), np.uint8)
+    quant = np.zeros((4 if nc == 4 else 3, 64), np.uint8)
     for c in range(nc):
         cid, td_ta = data[i + 5 + 2 * c], data[i + 6 + 2 * c]
         if cid != comps[c][0]:
@@ -186,7 +203,7 @@ def parse(data, keep_stuffing=False, layouts=False):
         quant[c] = np.frombuffer(q, np.uint8)[_INV_NATURAL]
     while len(tables) < 6:
         tables += tables[:2]
-    if nc == 3:
+    if nc != 1:
         out.hs, out.vs, out.transform = _sampling(comps, jfif, adobe, adobe_tf, width, layouts)
     else:
         out.hs, out.vs, out.transform = 1, 1, 0

@@ -16,10 +16,10 @@ import numpy as np
 import torch
 
 # the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
-from .decode_worker import (LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, PNG_INTERLACED_BIT, PNG_INTERLACED_STAT, REGION_TAGS,
-                            WANTED_TAG, load_uint8)
-from .device_stage import (DeviceStage, PinnedRing, _FORMATS, _groups, _headers, _pack16, file_need, formats, jpeg_fused_default,  # noqa: F401 (the moved names stay reachable as pipeline.<name>)
-                           jpeg_layouts_default, jpeg_records, png_records, progressive_records)
+from .decode_worker import (ALL_PARSED, KIND_JPEG_CMYK, LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, PARSED_MORE, PNG_INTERLACED_BIT,  # noqa: F401
+                            PNG_INTERLACED_STAT, REGION_TAGS, WANTED_TAG, load_uint8)
+from .device_stage import (DeviceStage, PinnedRing, _FORMATS, _groups, _headers, _pack16, all_formats, file_need, formats, jpeg_cmyk_default,  # noqa: F401 (the moved names stay reachable as pipeline.<name>)
+                           jpeg_fused_default, jpeg_layouts_default, jpeg_records, png_records, progressive_records)
 
 
 class DecodePool:
@@ -404,7 +404,7 @@ class _Encoder:
         r = self.copy_out(d, ok, bad, self.chunks[j])
         self.count("copy_s", time.perf_counter() - t0)
         if self.stats is not None and d.full is not None:
-            for k in PARSED:
+            for k in ALL_PARSED:
                 if k.counts == "staged":
                     self.count(k.stat, sum(1 for v in d.full.values() if v[0] == k.kind))
             self.count(LAYOUTS_STAT, r.pending.layout_files if r.pending is not None else 0)      # (DeviceStage counted: it read the headers)
@@ -418,7 +418,7 @@ class _Encoder:
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
                  jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None,
-                 device_jpeg_layouts=None, device_png_interlaced=None):
+                 device_jpeg_layouts=None, device_png_interlaced=None, device_jpeg_cmyk=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -457,6 +457,13 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     (4:1:1) or 1x4 and the three-component files libjpeg takes for RGB-coded take the device too - baseline files, and progressive
     ones with device_progressive, plain or through the jpeg_fused entries (jpeg_parse.parse(layouts=True)) -, the same bytes as
     Pillow's; files the device reports go back to Pillow. Off, such files stay with Pillow as before.
+    device_jpeg_cmyk (default $CLIPMI_DEVICE_JPEG_CMYK, else off; "1" = on; takes effect only with the JPEG decode on the device
+    above): four-component baseline files - CMYK as stored (no Adobe marker, or Adobe transform 0) and YCCK (Adobe transform 2),
+    components 1-3 sampled 1x1 - take the device too (jpeg_parse.parse(cmyk=True), clipmi_jpeg_decode_cmyk8, then
+    clipmi_resize_crop_cmyk8: Pillow resamples such files in mode CMYK and converts afterwards; also with jpeg_fused, whose entries
+    do not take four components), the same bytes as Pillow's; files the device reports go back to Pillow. Progressive
+    four-component files, Adobe transform 1 and a fourth component sampled like the first stay with Pillow. Off, every
+    four-component file stays with Pillow as before.
     jpeg_group_mb: the device decodes a batch's JPEG files in groups whose decoded form (~22 bytes per pixel) stays under that
     many MB of HBM - one group for a batch of thumbnails, several for a batch of photos.
     stats: a dict that receives the seconds each of the three pipelined stages was busy (decode_s: worker processes, copy_s:
@@ -465,7 +472,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only;
     jpeg_layout_files: those of jpeg_files and jpeg_progressive_files that device_jpeg_layouts added, 0 with it off;
     png_interlaced_files: the interlaced files of every kind that device_png_interlaced added and the device did not hand back, 0
-    with it off - png_files and png_mode_files keep counting files that are not interlaced only)."""
+    with it off - png_files and png_mode_files keep counting files that are not interlaced only; jpeg_cmyk_files: the
+    four-component files staged for the device, 0 with device_jpeg_cmyk off)."""
     n_px = model.visual.input_resolution
     dev = model.device
     use_gpu = dev.type == "cuda"
@@ -516,11 +524,14 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         jpeg_fused = jpeg_fused_default()
     if device_jpeg_layouts is None:
         device_jpeg_layouts = jpeg_layouts_default()
-    kind_formats = formats(jpeg_fused)
+    if device_jpeg_cmyk is None:
+        device_jpeg_cmyk = jpeg_cmyk_default()
+    kind_formats = all_formats(jpeg_fused)
     full_mode = ((1 if resize_cap else 0) | (2 if jpeg_cap else 0) | (4 if jpeg_cap and device_progressive else 0) |
                  (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0) |
                  (LAYOUTS_BIT if jpeg_cap and device_jpeg_layouts else 0) |
-                 (PNG_INTERLACED_BIT if jpeg_cap and device_png and device_png_interlaced else 0))
+                 (PNG_INTERLACED_BIT if jpeg_cap and device_png and device_png_interlaced else 0) |
+                 (PARSED_MORE[0].bit if jpeg_cap and device_jpeg_cmyk else 0))
     chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
     enc = _Encoder(model, chunks, batch, pool, stats, copy_stream, resize_cap, jpeg_cap, full_cap, full_mode, jpeg_group_bytes, kind_formats)
     if pool is not None:

@@ -319,6 +319,38 @@ int clipmi_jpeg_decode_rgb8(void* streams_dev, void* images_dev, int n, const vo
                             int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
                             void* ws_dev, int64_t ws_bytes, void* stream);
 
+/* ---- Four-component JPEG files, CMYK as stored and YCCK (an addition to ABI 8 in the sense of the PNG note below: two new entry
+ * points - this one and clipmi_resize_crop_cmyk8 - and one new record, nothing existing changes, CLIPMI_ABI_VERSION stays 8).
+ * clipmi_jpeg_decode_cmyk8 takes clipmi_jpeg_decode_rgb8's argument list over clipmi_jpeg_image4 records: clipmi_jpeg_image with
+ * four table indices of each class, four rows of quantisation steps and the colour transform in `reserved` - 2 = CMYK as stored (a
+ * file without an Adobe marker, or with Adobe transform 0), 3 = YCCK (Adobe transform 2). The host lets through, where its caller
+ * opts in (jpeg_parse.parse(cmyk=True)), 8-bit baseline / extended-sequential Huffman files with one interleaved scan of four
+ * components, components 1-3 sampled 1x1 and component 0 at one of the luma samplings above. Still Pillow's: progressive
+ * four-component files, Adobe transform 1, a file whose component 3 is sampled like component 0 (IJG's own YCCK default of
+ * 2x2,1x1,1x1,2x2), and anything above the parser's size caps.
+ * out_dev: per image, at out_off (4-byte aligned for full store width; any offset works), height rows of width*4 bytes - what
+ * np.asarray(Image.open(f)) holds for such a file, mode CMYK. With p0..p3 the four decoded, upsampled samples (components 1-3
+ * upsampled as chroma is): transform 2 gives (255-p0, 255-p1, 255-p2, 255-p3); transform 3 gives (R, G, B, 255-p3) with R, G, B
+ * the YCbCr -> RGB conversion of (p0, p1, p2) above. The layout clipmi_resize_crop_cmyk8 takes.
+ * Workspace: clipmi_jpeg_workspace_bytes(total_blocks, ntables) with an image's blocks counted at hs*vs + 3 per MCU. status_dev:
+ * 0-4 as clipmi_jpeg_decode_rgb8. A record with ncomp != 4, other sampling factors, a transform other than 2 / 3 or a size below
+ * 1 is reported with status 1, nothing of it is decoded, and it comes back emptied as a refused clipmi_jpeg_image does. The fused
+ * entries (clipmi_jpeg_decode_transform_rgb8 ...) do not take four components: ncomp = 4 in their records is status 1. */
+typedef struct clipmi_jpeg_image4 {
+    int64_t stream_off, coef_off, out_off, intervals_off;     /* as clipmi_jpeg_image */
+    int32_t stream_bytes;
+    int32_t width, height;
+    int32_t ncomp;                /* 4 */
+    int32_t hs, vs;               /* sampling factors of component 0; components 1-3 are 1x1 */
+    int32_t dc_tbl[4], ac_tbl[4]; /* per component: index into tables_dev */
+    int32_t restart_interval, n_intervals, stuffed;           /* as clipmi_jpeg_image */
+    int32_t reserved;             /* colour transform: 2 = CMYK as stored, 3 = YCCK */
+    uint8_t quant[4][64];         /* per component: quantisation steps, natural (row-major) order */
+} clipmi_jpeg_image4;
+int clipmi_jpeg_decode_cmyk8(void* streams_dev, void* images_dev, int n, const void* tables_dev, int ntables,
+                             int64_t total_blocks, int64_t max_blocks, int64_t max_pixels, void* out_dev, int32_t* status_dev,
+                             void* ws_dev, int64_t ws_bytes, void* stream);
+
 /* ---- ABI 7. Progressive JPEG files on the device (SOF2, 8-bit, Huffman): the same bytes as Pillow's `convert("RGB")`, for the
  * files the host parser lets through (cli-p_amd/jpeg_parse.py parse_progressive: grey or YCbCr with luma sampling 1x1, 2x1 or
  * 2x2 and 1x1 chroma, no restart intervals, a scan script libjpeg accepts without a warning and that brings every coefficient of
@@ -455,6 +487,12 @@ int clipmi_resize_crop_rgba8(const void* raw_dev, const void* jobs_dev, int njob
                              int n_px, void* out_dev, void* scratch_dev, void* stream);
 int clipmi_nearest_crop_p8(const void* raw_dev, const void* jobs_dev, int njobs, const void* tabs_dev, int n_px, void* out_dev,
                            void* stream);
+/* clipmi_resize_crop_cmyk8 (with clipmi_jpeg_decode_cmyk8 above): arguments, jobs, 4 bytes per source and scratch pixel and scratch
+ * sizing of clipmi_resize_crop_rgba8, for rows of C M Y K bytes. Pillow resamples mode CMYK as four plain bands, so nothing is
+ * premultiplied; its convert("RGB") - nk = 255 - K, out_c = clip8(nk - muldiv255(c, nk)) for c in C, M, Y, with muldiv255(a, b):
+ * t = a*b + 128, ((t >> 8) + t) >> 8 - is applied in front of the store, also in a job that resamples neither axis. */
+int clipmi_resize_crop_cmyk8(const void* raw_dev, const void* jobs_dev, int njobs, int max_rows, const int32_t* coef_dev,
+                             int n_px, void* out_dev, void* scratch_dev, void* stream);
 
 /* thread-local message of the last failing call on this thread ("" if none) */
 const char* clipmi_last_error(void);
