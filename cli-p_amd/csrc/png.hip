@@ -1,6 +1,7 @@
 // png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8), and
 // the file's own-mode pixels for alpha, palette and low-depth files (clipmi_png_decode_px8: the same inflate and Adler-32
-// kernels, png_unfilter_px_kernel with a filter unit of 1, 2 or 4 bytes and an "alpha" or "index" store).
+// kernels, png_unfilter_px_kernel with a filter unit of 1, 2 or 4 bytes and an "alpha" or "index" store; for files of depth 16 -
+// RGB, RGBA, grey + alpha - a filter unit of 6, 8 or 4 bytes and PngDeepStore, which keeps each sample's high byte as Pillow does).
 // The host (cli-p_amd/png_parse.py) lets through 8-bit grey and RGB files and hands over the DEFLATE stream behind the zlib
 // header. A record may say that its file is Adam7-interlaced (bit 16 of reserved[0], see png_interlaced): the stream then holds
 // up to seven reduced images one after the other, each filtered on its own, and the unfilter kernels reconstruct them in file
@@ -40,7 +41,8 @@ constexpr int PNG_MAX_ROW = 49152;          // ... that many bytes: what bounds 
 // The bytes of one scanline without its filter byte, the bits of one pixel, and whether the record is one its entry takes.
 // modes == 0 (clipmi_png_decode_rgb8): 8-bit grey or RGB, `reserved` not looked at except for the Adam7 mark (png_interlaced).
 // modes == 1 (clipmi_png_decode_px8): reserved[0] = Adam7 << 16 | colour type << 8 | bit depth, reserved[1] = palette entries;
-// RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4.
+// RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4; and at 16 bits RGB, RGBA and grey + alpha (png_deep), whose
+// rows of 6, 8 and 4 bytes a pixel are bounded by PNG_MAX_ROW like the others: 8192, 6144 and 12288 pixels.
 __device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int64_t& row, int& bpp) {
     if (im.width < 1 || im.width > PNG_MAX_WIDTH) return false;
     if (!modes) {
@@ -56,6 +58,7 @@ __device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int
     else if (ctype == 4 && depth == 8) samples = 2;
     else if (ctype == 3 && (low || depth == 8) && im.reserved[1] >= 1 && im.reserved[1] <= (1 << depth)) samples = 1;
     else if (ctype == 0 && low) samples = 1;
+    else if (depth == 16 && (ctype == 2 || ctype == 6 || ctype == 4)) samples = ctype == 2 ? 3 : ctype == 6 ? 4 : 2;   // png_deep
     else return false;
     bpp = samples * depth;
     row = ((int64_t)im.width * bpp + 7) >> 3;
@@ -612,6 +615,63 @@ __device__ bool png_unfilter_px(const PngImage& im, const unsigned char* __restr
     return over;
 }
 
+// Depth 16 (colour types 2, 6, 4): a sample is two bytes, the high one first, and PNG filters such rows byte by byte at the
+// distance of one pixel, so png_unfilter_image runs with units of CH = 6, 8 or 4 bytes and reconstructs both bytes of every
+// sample - Sub, Average and Paeth of the high bytes' neighbours do not depend on the low bytes, but the reconstruction of a row
+// is only complete with them and the Adler-32 covers them. What Pillow keeps of such a file is every sample's high byte (modes
+// RGB, RGBA, and RGBA as L L L A), and that is what this store keeps of a finished step: colour type 2 as rows of width * 3 bytes
+// (PngRgbStore's layout), 6 as R G B A and 4 as L L L A, four bytes a pixel (PngPxStore's "alpha" layout).
+template <int CH, bool LACE>
+struct PngDeepStore {
+    unsigned char* out;
+    int width;
+    PngPass ps;
+    static __device__ __forceinline__ unsigned high(const unsigned* res, int p, int s) {     // the high byte of sample s of unit p
+        const int i = p * CH + 2 * s;
+        return (res[i >> 2] >> (8 * (i & 3))) & 255u;
+    }
+    __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
+#pragma unroll
+        for (int p = 0; p < 4; p++) {
+            if (x0 + p < ps.w) {
+                const int64_t at = png_pixel<LACE>(ps, width, row, x0 + p);
+                if (CH == 6) {
+                    unsigned char* d = out + at * 3;
+                    d[0] = (unsigned char)high(res, p, 0);
+                    d[1] = (unsigned char)high(res, p, 1);
+                    d[2] = (unsigned char)high(res, p, 2);
+                } else if (CH == 8) {
+                    reinterpret_cast<unsigned*>(out)[at] = high(res, p, 0) | high(res, p, 1) << 8 | high(res, p, 2) << 16 | high(res, p, 3) << 24;
+                } else {
+                    reinterpret_cast<unsigned*>(out)[at] = high(res, p, 0) * 0x010101u | high(res, p, 1) << 24;
+                }
+            }
+        }
+    }
+};
+
+// png_unfilter_px for the depth-16 records; CH: bytes per pixel
+template <int CH, bool LACE>
+__device__ void png_unfilter_deep(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
+                                  bool& bad) {
+    for (int p = 0; p < (LACE ? 7 : 1); p++) {
+        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
+        if (ps.w == 0 || ps.h == 0) continue;
+        PngDeepStore<CH, LACE> store{out, im.width, ps};
+        png_unfilter_image<CH>(raw, store, prev, ps.w, ps.h, lane, bad);      // ceil(ps.w / 4) * CH words of `prev`: <= PNG_MAX_ROW / 4,
+        raw += (int64_t)ps.h * (1 + (int64_t)ps.w * CH);                      // since PNG_MAX_ROW / CH is a multiple of 4
+    }
+}
+
+template <bool LACE>
+__device__ void png_unfilter_deep(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
+                                  bool& bad) {
+    const int ctype = (im.reserved[0] >> 8) & 255;
+    if (ctype == 2) png_unfilter_deep<6, LACE>(im, raw, out, prev, lane, bad);
+    else if (ctype == 6) png_unfilter_deep<8, LACE>(im, raw, out, prev, lane, bad);
+    else png_unfilter_deep<4, LACE>(im, raw, out, prev, lane, bad);
+}
+
 __global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
                                                                 unsigned char* __restrict__ out, int32_t* status) {
     __shared__ unsigned prev[PNG_MAX_ROW / 4];         // a band's last row: PNG_MAX_ROW bytes (png_inflate_kernel refused longer rows)
@@ -622,9 +682,14 @@ __global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* 
     int bpp = 0;
     if (!png_row_bytes(im, 1, row_bytes, bpp)) return; // (not reached: png_inflate_kernel gave status 1)
     const unsigned char* raw = rawbuf + im.raw_off;
-    bool bad = false;
-    const bool over = png_interlaced(im, 1) ? png_unfilter_px<true>(im, raw, out + im.out_off, prev, lane, bad)
-                                            : png_unfilter_px<false>(im, raw, out + im.out_off, prev, lane, bad);
+    bool bad = false, over = false;
+    if ((im.reserved[0] & 255) == 16) {                // depth 16: no palette, so never status 5
+        if (png_interlaced(im, 1)) png_unfilter_deep<true>(im, raw, out + im.out_off, prev, lane, bad);
+        else png_unfilter_deep<false>(im, raw, out + im.out_off, prev, lane, bad);
+    } else {
+        over = png_interlaced(im, 1) ? png_unfilter_px<true>(im, raw, out + im.out_off, prev, lane, bad)
+                                     : png_unfilter_px<false>(im, raw, out + im.out_off, prev, lane, bad);
+    }
     const int is_bad = __syncthreads_or(bad ? 1 : 0), is_over = __syncthreads_or(over ? 1 : 0);
     if (lane == 0 && (is_bad || is_over)) status[blockIdx.x] = is_bad ? 3 : 5;
 }

@@ -174,7 +174,7 @@ CMYK_COEF_OFF = 2688      # the resize plan's coefficient blocks (HDR.COEF_OFF s
 
 class HDR:
     """Where each of the JPEG_HDR_INTS ints of a parsed file's region header lies (_write_head writes them, device_stage.py reads them
-    through these names); [27..31] are zero. Offsets count bytes from the region's start."""
+    through these names); [28..31] are zero. Offsets count bytes from the region's start."""
     KIND, W, H = 0, 1, 2      # KIND: KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG, KIND_PNG_ALPHA, KIND_PNG_INDEX or KIND_JPEG_CMYK
     NCOMP, HS, VS = 3, 4, 5   # components (PNG: samples per pixel), luma sampling factors (PNG: 0 0)
     COUNT = 6                 # baseline, PNG: bytes of the stream at DATA_OFF; progressive: scan records at DATA_OFF
@@ -188,12 +188,17 @@ class HDR:
     #                                                                 uint32 byte offsets into the segment, 1: the segment keeps its stuffing
     TABLES_OFF, N_TABLES = 20, 21                                   # progressive: the scans' Huffman tables
     DEPTH, CTYPE, ENTRIES = 20, 21, 22                              # KIND_PNG_ALPHA, KIND_PNG_INDEX: bit depth, colour type, palette
-    #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF
+    #                                                                 entries; an index file's palette (768 bytes) lies at JPEG_TABLES_OFF.
+    #                                                                 KIND_PNG: 0 0 0 for the 8-bit grey and RGB files, 16 2 0 for a 16-bit
+    #                                                                 RGB file - in every PNG kind depth 16 marks a file only PNG_DEEP_BIT
+    #                                                                 lets through, and clipmi_png_decode_px8 decodes it
     TRANSFORM, LAYOUT = 24, 25                                      # baseline, progressive: the colour transform (0 YCbCr -> RGB, 1 none:
     #                                                                 R, G, B components; KIND_JPEG_CMYK: 2 CMYK as stored, 3 YCCK);
     #                                                                 1: a file only LAYOUTS_BIT lets through
     INTERLACE = 26                                                  # the PNG kinds: 1 an Adam7 file, which only PNG_INTERLACED_BIT lets
     #                                                                 through (its scanlines are those of its passes); 0 in a JPEG region
+    CHUNKS = 27                                                     # the PNG kinds: 1 a file with a chunk only PNG_CHUNKS_BIT lets through
+    #                                                                 (png_parse.Parsed.chunks); 0 in a JPEG region
 
 
 KIND_BASELINE, KIND_PROGRESSIVE, KIND_PNG = 3, 4, 6       # (2: decode_full's full-size pixels; 5: WANTED_TAG)
@@ -228,14 +233,14 @@ def _no_room(p, total):
     return p.width, p.height, -total                      # the file does not fit its region: what it would need
 
 
-def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0), interlace=0, coef_off=JPEG_COEF_OFF):
+def _write_head(region, kind, p, sampling, count, blocks, plan, specific=(0, 0, 0, 0), layout=(0, 0), interlace=0, coef_off=JPEG_COEF_OFF, chunks=0):
     """The header (HDR: sampling = NCOMP HS VS, specific = the four ints at [20..23], layout = TRANSFORM LAYOUT) and the plan's
     coefficient blocks (at coef_off)"""
     nh, nv = plan["hcoef"].size, plan["vcoef"].size
     ints = np.frombuffer(region, dtype=np.int32, count=JPEG_HDR_INTS)
     ints[:] = [kind, p.width, p.height, *sampling, count, blocks, plan["r0"], plan["nrows"], plan["need_h"], plan["need_v"],
                plan["left"], plan["top"], plan["hk"], plan["vk"], nh, nv, _data_off(plan, coef_off), coef_off, *specific, *layout,
-               interlace] + [0] * 5
+               interlace, chunks] + [0] * 4
     if nh + nv:
         co = np.frombuffer(region, dtype=np.int32, count=nh + nv, offset=coef_off)
         co[:nh] = plan["hcoef"]
@@ -347,7 +352,7 @@ PNG_MAX_RAW = 16 << 20      # filtered scanlines of a file the device takes: one
                             # DESIGN 4.9), so a larger file would hold up its batch on the side stream; Pillow decodes those
 
 
-def stage_png(path, n_px, region, data=None, modes=False, interlaced=False):
+def stage_png(path, n_px, region, data=None, modes=False, interlaced=False, chunks=False, deep=False):
     """For the PNG decode on the device (csrc/png.hip): read the file, walk its chunks (png_parse.parse) and lay out in `region`
     [header | resize plan coefficients | DEFLATE stream without the zlib header, 16-byte aligned and followed by >= 16 zero
     bytes]. -> (w, h, bytes used), (w, h, -bytes needed) when the file does not fit; raises png_parse.Unsupported for files
@@ -358,8 +363,12 @@ def stage_png(path, n_px, region, data=None, modes=False, interlaced=False):
     tables. Without it such a file raises Unsupported, as ever.
     interlaced: the request allows Adam7 files of the kinds let through (png_parse.parse(interlaced=True)); the region has the
     same layout and says so in HDR.INTERLACE. Without it such a file raises Unsupported, as ever.
+    chunks: the request allows files with metadata chunks (png_parse.parse(chunks=True)); the same region, and HDR.CHUNKS says that
+    the file needed it. deep: the request allows files of depth 16 (png_parse.parse(deep=True)): RGB ones as KIND_PNG with depth
+    and colour type in the header (16, 2), RGBA and grey + alpha ones (with modes) as KIND_PNG_ALPHA with HDR.DEPTH 16. Without
+    either such a file raises Unsupported, as ever.
     data: the file's contents, when the caller has read them."""
-    p = png_parse.parse(_contents(path, data), modes=modes, interlaced=interlaced)
+    p = png_parse.parse(_contents(path, data), modes=modes, interlaced=interlaced, chunks=chunks, deep=deep)
     if p.raw_bytes() > PNG_MAX_RAW:
         raise png_parse.Unsupported("more than PNG_MAX_RAW bytes of scanlines")
     plan = _plan(p.width, p.height, n_px, nearest=p.kind == "index")
@@ -368,10 +377,11 @@ def stage_png(path, n_px, region, data=None, modes=False, interlaced=False):
     if total > region.size:
         return _no_room(p, total)
     if p.kind == "rgb":
-        _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan, interlace=p.interlace)
+        _write_head(region, KIND_PNG, p, (p.channels, 0, 0), len(p.stream), 0, plan, (16, 2, 0, 0) if p.depth == 16 else (0, 0, 0, 0),
+                    interlace=p.interlace, chunks=p.chunks)
     else:
         _write_head(region, KIND_PNG_INDEX if p.kind == "index" else KIND_PNG_ALPHA, p, (p.channels, 0, 0), len(p.stream), 0, plan,
-                    (p.depth, p.ctype, p.n_entries, 0), interlace=p.interlace)
+                    (p.depth, p.ctype, p.n_entries, 0), interlace=p.interlace, chunks=p.chunks)
         if p.kind == "index":
             region[JPEG_TABLES_OFF:JPEG_TABLES_OFF + 768] = p.palette.reshape(-1)
     _write_stream(region, o_stream, p.stream)
@@ -380,13 +390,13 @@ def stage_png(path, n_px, region, data=None, modes=False, interlaced=False):
 
 def _stage_png_kind(kind):
     """stage_png(modes=True) for the files of one of the new kinds only: a launch group holds one kind (PARSED)"""
-    def stage(path, n_px, region, data=None, interlaced=False):
+    def stage(path, n_px, region, data=None, interlaced=False, chunks=False, deep=False):
         data = _contents(path, data)
         ctype, depth = data[25], data[24]                         # IHDR, before any work: which kind the file would be
         index = ctype == 3 or (ctype == 0 and depth == 1)
-        if (ctype, depth) in ((0, 8), (2, 8)) or index != (kind == KIND_PNG_INDEX):
+        if (ctype, depth) in ((0, 8), (2, 8), (2, 16)) or index != (kind == KIND_PNG_INDEX):      # (16-bit RGB is KIND_PNG's)
             raise png_parse.Unsupported("a file of another kind")
-        return stage_png(path, n_px, region, data, modes=True, interlaced=interlaced)
+        return stage_png(path, n_px, region, data, modes=True, interlaced=interlaced, chunks=chunks, deep=deep)
     return stage
 
 
@@ -414,13 +424,19 @@ PNG_INTERLACED_BIT = 64    # another such bit: the PNG stagers run with interlac
 #                            effect only beside the bits of the PNG kinds; encode_files counts the files it lets through and the
 #                            device did not report (HDR.INTERLACE) under PNG_INTERLACED_STAT, and not under the kind's own key
 PNG_INTERLACED_STAT = "png_interlaced_files"
+PNG_CHUNKS_BIT = 256       # two more such bits, for the PNG stagers as well: chunks=True (png_parse.parse(chunks=True): files with metadata
+PNG_DEEP_BIT = 512         # chunks) and deep=True (files of depth 16; RGBA and grey + alpha ones need the bit of their kinds too).
+#                            encode_files counts the files the device did not report under ONE key each: a 16-bit file (HDR.DEPTH)
+#                            under PNG_DEEP_STAT, else an Adam7 file under PNG_INTERLACED_STAT, else a file with HDR.CHUNKS under
+#                            PNG_CHUNKS_STAT, else under its kind's own key - so every key counts the files its switch added
+PNG_CHUNKS_STAT, PNG_DEEP_STAT = "png_chunk_files", "png_deep_files"
 
 
 def _stager_switches(mode, magic):
     """The keyword arguments the mode's kind-less bits give the stagers of the files with that magic"""
     if magic == "jpeg":
         return {"layouts": True} if mode & LAYOUTS_BIT else {}
-    return {"interlaced": True} if mode & PNG_INTERLACED_BIT else {}
+    return {name: True for bit, name in ((PNG_INTERLACED_BIT, "interlaced"), (PNG_CHUNKS_BIT, "chunks"), (PNG_DEEP_BIT, "deep")) if mode & bit}
 PARSED_KINDS = frozenset(k.kind for k in ALL_PARSED)
 REGION_TAGS = frozenset(b"%d" % k.kind for k in (FULL_SIZE,) + ALL_PARSED)
 WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a larger region would have taken the parsed file
@@ -429,7 +445,7 @@ WANTED_TAG = b"5"          # the transform's pixels are in the slot, and a large
 def serve(fin, fout):
     """Answer requests until stdin closes. Request line (tab separated):
          n_px | small segment or - | byte offset of the slot | big segment or - | byte offset of the region | its size |
-         what the region may take (the bits of FULL_SIZE and ALL_PARSED, LAYOUTS_BIT and PNG_INTERLACED_BIT) |
+         what the region may take (the bits of FULL_SIZE and ALL_PARSED, LAYOUTS_BIT, PNG_INTERLACED_BIT, PNG_CHUNKS_BIT, PNG_DEEP_BIT) |
          path as hex (file names may contain newlines and tabs)
        Reply, 17 bytes when a segment was named (status + <iiq, zero where unused): b"0" failed | b"1" the transform's n_px x n_px
               pixels are in the slot (no segment named: b"1" + the pixels) |

@@ -138,13 +138,20 @@ def progressive_records(bigview, n, cap, slots, comp, n_px):
 def _png_scanlines(hd, px=3):
     """Bytes of filtered scanlines per file. A KIND_PNG region's header does not carry the depth (stage_png leaves [20..23] zero for
     grey / RGB files, which are 8 bits deep); the regions of the other kinds do (HDR.DEPTH). An Adam7 file (HDR.INTERLACE) holds
-    the scanlines of its passes (png_parse.adam7_raw_bytes)."""
+    the scanlines of its passes (png_parse.adam7_raw_bytes). A 16-bit RGB file is a KIND_PNG region that does carry its depth
+    (_png_deep); the 16-bit files of KIND_PNG_ALPHA carry it like every file of that kind."""
     from .png_parse import adam7_raw_bytes
-    depth = 8 if px == 3 else hd[:, HDR.DEPTH]
+    depth = np.where(_png_deep(hd), 16, 8) if px == 3 else hd[:, HDR.DEPTH]
     bits = hd[:, HDR.NCOMP] * depth
     plain = hd[:, HDR.H] * (1 + (hd[:, HDR.W] * bits + 7) // 8)
     lace = hd[:, HDR.INTERLACE] != 0
     return np.where(lace, adam7_raw_bytes(hd[:, HDR.W], hd[:, HDR.H], bits), plain) if lace.any() else plain
+
+
+def _png_deep(hd):
+    """Which of the headers are those of PNG regions with a 16-bit file (HDR.DEPTH; a JPEG region keeps other things there)"""
+    png = (hd[:, HDR.KIND] == KIND_PNG) | (hd[:, HDR.KIND] == KIND_PNG_ALPHA) | (hd[:, HDR.KIND] == KIND_PNG_INDEX)
+    return png & (hd[:, HDR.DEPTH] == 16)
 
 
 def png_records(bigview, n, cap, slots, comp, n_px, px=3):
@@ -152,7 +159,9 @@ def png_records(bigview, n, cap, slots, comp, n_px, px=3):
     the segment and the scanline and output buffers laid out back to back, the transform's job records whose sources are the
     decoder's outputs, output bytes per image, scanline bytes per image, each rounded up to 16).
     px: bytes per decoded pixel - 3 for grey / RGB files (KIND_PNG), 4 "alpha" and 1 "index" for the files of png_parse's other kinds
-    (stage_png(modes=True)), whose records carry colour type, depth and palette entries for clipmi_png_decode_px8."""
+    (stage_png(modes=True)), whose records carry colour type, depth and palette entries for clipmi_png_decode_px8. So do the
+    records of 16-bit RGB files among the KIND_PNG regions (px 3), which that entry decodes too: _png_group sends a group of them
+    there, and DeviceStage keeps them in groups of their own."""
     from . import png as P
     slots = np.asarray(slots, dtype=np.int64)
     hd = _headers(bigview, n, cap, slots)
@@ -161,7 +170,9 @@ def png_records(bigview, n, cap, slots, comp, n_px, px=3):
     raw_sz = (_png_scanlines(hd, px) + 15) // 16 * 16
     recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(raw_sz) - raw_sz, out_off
     recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = hd[:, HDR.COUNT], hd[:, HDR.W], hd[:, HDR.H], hd[:, HDR.NCOMP]
-    if px != 3:
+    if px == 3:
+        recs["reserved"][:, 0] = np.where(_png_deep(hd), hd[:, HDR.CTYPE] << 8 | 16, 0)
+    else:
         recs["reserved"] = np.stack([hd[:, HDR.CTYPE] << 8 | hd[:, HDR.DEPTH], hd[:, HDR.ENTRIES]], axis=1)
     recs["reserved"][:, 0] |= np.where(hd[:, HDR.INTERLACE] != 0, P.INTERLACE_BIT, 0).astype(np.int32)
     return recs, jobs, out_sz, raw_sz
@@ -177,6 +188,16 @@ def _groups(need, budget):
             lo, acc = k, 0
         acc += int(need[k])
     return groups + [(lo, len(need))] if len(need) else groups
+
+
+def _split(groups, flag):
+    """The [lo, hi) ranges cut where `flag` (bool per file) changes, so that each holds files of one value: the 16-bit RGB files
+    among a batch's KIND_PNG regions go to another decode entry than the 8-bit ones (_png_group)"""
+    out = []
+    for lo, hi in groups:
+        cuts = [lo] + [k for k in range(lo + 1, hi) if flag[k] != flag[k - 1]] + [hi]
+        out += list(zip(cuts[:-1], cuts[1:]))
+    return out
 
 
 def _pack16(arrays):
@@ -213,6 +234,10 @@ def _jpeg_group(L, r, progressive=False, fused=False, cmyk=False):
 def _png_group(L, r, entry="clipmi_png_decode_rgb8", workspace="clipmi_png_workspace_bytes"):
     recs, jobs, out_sz, raw_sz = r
     total, most = int(raw_sz.sum()), int(raw_sz.max())
+    if entry == "clipmi_png_decode_rgb8" and (recs["reserved"][:, 0] & 0xffff).any():      # 16-bit RGB files (png_records): the other entry
+        if not (recs["reserved"][:, 0] & 0xffff).all():
+            raise ValueError("a group of KIND_PNG files mixes 8-bit and 16-bit files")
+        entry, workspace = "clipmi_png_decode_px8", "clipmi_png_px8_workspace_bytes"
     ws_bytes = int(getattr(L, workspace)(len(recs), total))
 
     def decode(base, sb, offs, rgb, status, ws, stream, tr):
@@ -314,7 +339,7 @@ class PinnedRing:
 
 class Pending:
     """What the consumer checks behind a batch's encode step, and what has to live until then"""
-    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good", "layout_files", "interlaced")
+    __slots__ = ("keep", "status", "slots", "count_ok", "chunk", "good", "layout_files", "interlaced", "chunked", "deep")
 
     def __init__(self):
         self.keep = []           # device tensors the queued kernels read and write
@@ -324,6 +349,8 @@ class Pending:
         self.chunk = self.good = None      # the batch's paths and its mask of good slots, for the files that go back to Pillow
         self.layout_files = 0    # staged JPEG files that only the layouts switch lets through (HDR.LAYOUT; decode_worker.LAYOUTS_STAT)
         self.interlaced = None   # bool per status: an Adam7 PNG file (HDR.INTERLACE; decode_worker.PNG_INTERLACED_STAT)
+        self.chunked = None      # bool per status: a PNG file with metadata chunks (HDR.CHUNKS; decode_worker.PNG_CHUNKS_STAT)
+        self.deep = None         # bool per status: a 16-bit PNG file (HDR.DEPTH; decode_worker.PNG_DEEP_STAT)
 
 
 # One group of a kind's files: its packed arrays on the device and their offsets, its files, its largest nrows, its decode entry's name
@@ -332,8 +359,8 @@ GroupCall = namedtuple("GroupCall", "dsmall offs n_files max_rows name decode st
 # The decodes and transforms of a batch's files of one kind, ready for the side stream: the groups run one after the other through one
 # workspace, one buffer of decoded rows (None: the decode entry transforms too) and one of scratch rows; layout_files: how many of the
 # files only the layouts switch lets through (HDR.LAYOUT, 0 in a PNG region); interlaced: which of the files are Adam7 PNG files
-# (HDR.INTERLACE, 0 in a JPEG region), bool per file
-KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files interlaced", defaults=(0, None))
+# (HDR.INTERLACE, 0 in a JPEG region), bool per file; chunked, deep: likewise HDR.CHUNKS and the 16-bit PNG files (_png_deep)
+KindLaunch = namedtuple("KindLaunch", "fmt calls ws rgb scratch layout_files interlaced chunked deep", defaults=(0, None, None, None))
 
 
 class DeviceStage:
@@ -373,7 +400,7 @@ class DeviceStage:
         n_px, dev = self.n_px, self.dev
         hd = _headers(bigview, n, cap, slots)
         calls, ws_max, rgb_max, tmp_max = [], 0, 0, 0
-        for lo, hi in _groups(file_need(hd, fmt, n_px), self.group_bytes):
+        for lo, hi in _split(_groups(file_need(hd, fmt, n_px), self.group_bytes), _png_deep(hd)):
             arrays, out_sz, ws_bytes, name, decode = fmt.group(self.L, fmt.records(bigview, n, cap, slots[lo:hi], comp, n_px))
             small, offs = _pack16(arrays)
             dsmall = torch.from_numpy(small).to(dev)
@@ -384,7 +411,8 @@ class DeviceStage:
         ws = torch.empty(ws_max, dtype=torch.uint8, device=dev)
         rgb = torch.empty(max(rgb_max, 16), dtype=torch.uint8, device=dev) if fmt.entry is not None else None
         scratch = torch.empty(max(tmp_max, 1), dtype=torch.uint8, device=dev)
-        return KindLaunch(fmt, calls, ws, rgb, scratch, int(hd[:, HDR.LAYOUT].sum()), hd[:, HDR.INTERLACE] != 0)
+        return KindLaunch(fmt, calls, ws, rgb, scratch, int(hd[:, HDR.LAYOUT].sum()), hd[:, HDR.INTERLACE] != 0,
+                          hd[:, HDR.CHUNKS] != 0, _png_deep(hd))
 
     def _launch_kind(self, k, base, devt, status):
         for c in k.calls:
@@ -416,6 +444,9 @@ class DeviceStage:
         used = (max(full) + 1) * cap
         e2 = np.array(sorted(s_ for s_, v in full.items() if v[0] == FULL_SIZE.kind), dtype=np.int64)
         parsed = [np.array(sorted(s_ for s_, v in full.items() if v[0] == k.kind), dtype=np.int64) for k in ALL_PARSED]
+        # a kind's 16-bit PNG files behind its others, so that _split cuts a kind's groups once (a no-op without such files)
+        parsed = [slots[np.argsort(_png_deep(_headers(bigview, n, cap, slots)), kind="stable")] if len(slots) and k.magic == "png" else slots
+                  for k, slots in zip(ALL_PARSED, parsed)]
         n_status = sum(len(slots) for slots in parsed)      # one status tensor: the kinds in ALL_PARSED's order
         in_place = self.pool.pin_segment(2 + seg_index)
         if in_place:
@@ -434,6 +465,7 @@ class DeviceStage:
                 pending.status = torch.empty(n_status, dtype=torch.int32, device=dev)
                 pending.slots = np.concatenate(parsed)
                 pending.interlaced = np.zeros(n_status, dtype=bool)
+                pending.chunked, pending.deep = np.zeros(n_status, dtype=bool), np.zeros(n_status, dtype=bool)
             if len(e2):
                 djobs, scratch, max_rows = self._stage_full(bigview, full, e2, cap, comp)
                 pending.keep += [djobs, scratch]
@@ -445,6 +477,8 @@ class DeviceStage:
                 kind_launches.append(k)
                 pending.layout_files += k.layout_files
                 pending.interlaced[status_at:status_at + len(slots)] = k.interlaced
+                pending.chunked[status_at:status_at + len(slots)] = k.chunked
+                pending.deep[status_at:status_at + len(slots)] = k.deep
                 pending.keep += [c.dsmall for c in k.calls] + [k.ws, k.rgb, k.scratch]
                 if kind.counts == "decoded":
                     pending.count_ok.append((kind.stat, status_at, status_at + len(slots)))

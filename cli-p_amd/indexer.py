@@ -30,6 +30,11 @@ CLIPMI_DEVICE_PNG (default 0 = off; 1: 8-bit grey and RGB PNG files that are not
 Pillow's bytes; every other PNG file stays with Pillow; needs CLIPMI_DEVICE_JPEG_KB on),
 CLIPMI_DEVICE_PNG_INTERLACED (default 0 = off; 1: Adam7-interlaced PNG files of the colour types and depths CLIPMI_DEVICE_PNG - and
 CLIPMI_DEVICE_PNG_MODES, DESIGN §4.9b - let through take the device decoder too, Pillow's bytes; needs CLIPMI_DEVICE_PNG on),
+CLIPMI_DEVICE_PNG_CHUNKS (default 0 = off; 1: PNG files that carry iCCP, iTXt, zTXt, eXIf, tRNS on 8-bit grey or RGB, or chunks Pillow
+has no handler for - screenshots, editors' exports - take the device decoder too, each chunk checked on the host under the rule of
+Pillow's handler; needs CLIPMI_DEVICE_PNG on),
+CLIPMI_DEVICE_PNG_DEEP (default 0 = off; 1: 16-bit RGB PNG files - and with CLIPMI_DEVICE_PNG_MODES 16-bit RGBA and grey + alpha ones -
+take the device decoder too, Pillow's bytes; 16-bit grey stays with Pillow; needs CLIPMI_DEVICE_PNG on),
 CLIPMI_DEVICE_JPEG_LAYOUTS (default 0 = off; 1: JPEG files with luma sampling 1x2 - 4:4:0, what a lossless 90-degree rotation makes of
 a 4:2:2 file -, 4x1 or 1x4 and RGB-coded files take the device decoder too, Pillow's bytes; needs CLIPMI_DEVICE_JPEG_KB
 on, and CLIPMI_DEVICE_PROGRESSIVE for the progressive ones),

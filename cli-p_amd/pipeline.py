@@ -17,7 +17,7 @@ import torch
 
 # the Pillow part of the transform and the kinds of regions (decode_worker.Kind) live beside the worker script
 from .decode_worker import (ALL_PARSED, KIND_JPEG_CMYK, LAYOUTS_BIT, LAYOUTS_STAT, PARSED, PARSED_KINDS, PARSED_MORE, PNG_INTERLACED_BIT,  # noqa: F401
-                            PNG_INTERLACED_STAT, REGION_TAGS, WANTED_TAG, load_uint8)
+                            PNG_CHUNKS_BIT, PNG_CHUNKS_STAT, PNG_DEEP_BIT, PNG_DEEP_STAT, PNG_INTERLACED_STAT, REGION_TAGS, WANTED_TAG, load_uint8)
 from .device_stage import (DeviceStage, PinnedRing, _FORMATS, _groups, _headers, _pack16, all_formats, file_need, formats, jpeg_cmyk_default,  # noqa: F401 (the moved names stay reachable as pipeline.<name>)
                            jpeg_fused_default, jpeg_layouts_default, jpeg_records, png_records, progressive_records)
 
@@ -378,10 +378,12 @@ class _Encoder:
             feats = self.encode(devt)
             if pending is not None and pending.status is not None:
                 stc = pending.status.cpu().numpy()            # (behind the encode step: nothing waits for it in the common case)
-                for key, lo, hi in pending.count_ok:       # (an Adam7 file counts under the switch's key, not its kind's)
-                    kept, lace = stc[lo:hi] == 0, pending.interlaced[lo:hi]
-                    self.count(key, int((kept & ~lace).sum()))
-                    self.count(PNG_INTERLACED_STAT, int((kept & lace).sum()))
+                for key, lo, hi in pending.count_ok:       # (a file that a switch added counts under that switch's key, not its kind's:
+                    kept = stc[lo:hi] == 0                 # a 16-bit file first, else an Adam7 file, else one with metadata chunks)
+                    for stat, mark in ((PNG_DEEP_STAT, pending.deep), (PNG_INTERLACED_STAT, pending.interlaced), (PNG_CHUNKS_STAT, pending.chunked)):
+                        self.count(stat, int((kept & mark[lo:hi]).sum()))
+                        kept = kept & ~mark[lo:hi]
+                    self.count(key, int(kept.sum()))
                 if stc.any():
                     ok, bad, devt = self.redo_on_host([int(s_) for s_ in pending.slots[stc != 0]], pending, ok, bad, devt)
                     feats = self.encode(devt) if len(ok) else None
@@ -408,7 +410,8 @@ class _Encoder:
                 if k.counts == "staged":
                     self.count(k.stat, sum(1 for v in d.full.values() if v[0] == k.kind))
             self.count(LAYOUTS_STAT, r.pending.layout_files if r.pending is not None else 0)      # (DeviceStage counted: it read the headers)
-            self.count(PNG_INTERLACED_STAT, 0)             # (the key exists from here on; consume() counts, behind the statuses)
+            for stat in (PNG_INTERLACED_STAT, PNG_CHUNKS_STAT, PNG_DEEP_STAT):
+                self.count(stat, 0)                        # (the keys exist from here on; consume() counts, behind the statuses)
         return r
 
     def submit(self, dec, cpy, j):
@@ -418,7 +421,8 @@ class _Encoder:
 
 def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb=None, device_jpeg_kb=None, stats=None,
                  jpeg_group_mb=32768, device_progressive=None, device_png=None, device_png_modes=None, jpeg_fused=None,
-                 device_jpeg_layouts=None, device_png_interlaced=None, device_jpeg_cmyk=None):
+                 device_jpeg_layouts=None, device_png_interlaced=None, device_jpeg_cmyk=None, device_png_chunks=None,
+                 device_png_deep=None):
     """Generator over batches: yields (ok_paths, features f32 [n,E] numpy normalised, failed_paths).
     Decode runs in the worker processes of `pool` (a DecodePool) when given, else on `workers` threads (Pillow
     releases the GIL while decoding, which is enough for large photos and not for small images).
@@ -448,6 +452,14 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     (png_parse.parse(interlaced=True); the same two decode entries reconstruct the seven passes and leave the pixels laid out as
     those of the picture stored without interlace, so the transform behind them is the same), the same bytes as Pillow's.
     Interlaced alpha, palette and low-depth files need device_png_modes too. Off, every interlaced file stays with Pillow as before.
+    device_png_chunks (default $CLIPMI_DEVICE_PNG_CHUNKS, else off; "1" = on; takes effect only with device_png on): files that
+    carry iCCP, zTXt, iTXt, eXIf, tRNS (8-bit grey, RGB) or chunks Pillow has no handler for - what screenshots and editors' exports
+    carry - take the device as well, each chunk under the rule of Pillow's handler (png_parse.parse(chunks=True): the workers
+    inflate the compressed ones, bounded like Pillow); the device sees the same stream. Off, such files stay with Pillow as before.
+    device_png_deep (default $CLIPMI_DEVICE_PNG_DEEP, else off; "1" = on; takes effect only with device_png on): RGB files of depth
+    16 take the device as well, and with device_png_modes RGBA and grey + alpha files of depth 16 (png_parse.parse(deep=True);
+    clipmi_png_decode_px8 keeps the samples' high bytes as Pillow does, then the transform of the 8-bit file), the same bytes as
+    Pillow's. 16-bit grey stays with Pillow, which resamples it in 16 bits. Off, every 16-bit file stays with Pillow as before.
     jpeg_fused (default $CLIPMI_DEVICE_JPEG_FUSED, else off; "1" = on): baseline and progressive files on the device go through
     clipmi_jpeg_decode_transform_rgb8 / clipmi_jpeg_decode_progressive_transform_rgb8, which convert and resample straight from
     the decoder's sample planes: the same bytes, and no full-size RGB rows (3 bytes per pixel) in HBM, so that a group under
@@ -472,7 +484,10 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
     did not hand back; png_mode_files: the same for the files device_png_modes adds - png_files keeps counting grey / RGB only;
     jpeg_layout_files: those of jpeg_files and jpeg_progressive_files that device_jpeg_layouts added, 0 with it off;
     png_interlaced_files: the interlaced files of every kind that device_png_interlaced added and the device did not hand back, 0
-    with it off - png_files and png_mode_files keep counting files that are not interlaced only; jpeg_cmyk_files: the
+    with it off - png_files and png_mode_files keep counting files that are not interlaced only; png_deep_files: the 16-bit
+    files device_png_deep added and the device did not hand back, interlaced ones included; png_chunk_files: the same for the files
+    with metadata chunks that device_png_chunks added and neither of the two keys before counts; both 0 with their switch off;
+    jpeg_cmyk_files: the
     four-component files staged for the device, 0 with device_jpeg_cmyk off)."""
     n_px = model.visual.input_resolution
     dev = model.device
@@ -520,6 +535,10 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
         device_png_modes = os.environ.get("CLIPMI_DEVICE_PNG_MODES", "0") not in ("", "0")
     if device_png_interlaced is None:
         device_png_interlaced = os.environ.get("CLIPMI_DEVICE_PNG_INTERLACED", "0") not in ("", "0")
+    if device_png_chunks is None:
+        device_png_chunks = os.environ.get("CLIPMI_DEVICE_PNG_CHUNKS", "0") not in ("", "0")
+    if device_png_deep is None:
+        device_png_deep = os.environ.get("CLIPMI_DEVICE_PNG_DEEP", "0") not in ("", "0")
     if jpeg_fused is None:
         jpeg_fused = jpeg_fused_default()
     if device_jpeg_layouts is None:
@@ -531,6 +550,8 @@ def encode_files(model, paths, batch=256, workers=8, pool=None, device_resize_mb
                  (8 if jpeg_cap and device_png else 0) | (16 if jpeg_cap and device_png and device_png_modes else 0) |
                  (LAYOUTS_BIT if jpeg_cap and device_jpeg_layouts else 0) |
                  (PNG_INTERLACED_BIT if jpeg_cap and device_png and device_png_interlaced else 0) |
+                 (PNG_CHUNKS_BIT if jpeg_cap and device_png and device_png_chunks else 0) |
+                 (PNG_DEEP_BIT if jpeg_cap and device_png and device_png_deep else 0) |
                  (PARSED_MORE[0].bit if jpeg_cap and device_jpeg_cmyk else 0))
     chunks = [paths[i:i + batch] for i in range(0, len(paths), batch)]
     enc = _Encoder(model, chunks, batch, pool, stats, copy_stream, resize_cap, jpeg_cap, full_cap, full_mode, jpeg_group_bytes, kind_formats)

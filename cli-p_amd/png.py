@@ -6,7 +6,11 @@ bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_cro
 palette and low-depth files decode too, to the pixels of their own mode (clipmi_png_decode_px8; status 5: a palette index beyond
 the palette), and `transform_files` runs the transform of each kind on the device. With `interlaced=True` Adam7
 files of the same colour types and depths decode as well, to the layout of the same picture stored without interlace (the record
-carries INTERLACE_BIT; the unfilter kernels reconstruct the seven passes one after the other). PNG is lossless, so there is
+carries INTERLACE_BIT; the unfilter kernels reconstruct the seven passes one after the other). With `deep=True` RGB files of
+depth 16 decode too, and with `modes=True` beside it RGBA and grey + alpha files of depth 16: clipmi_png_decode_px8 reconstructs
+the 16-bit scanlines and keeps every sample's high byte, which is what Pillow opens such a file as; the transform is that of
+the 8-bit file (16-bit RGB is of kind "rgb": Parsed.px8 says which entry decodes a file). `chunks=True` is the host's business
+alone (png_parse.parse(chunks=True)): files with metadata chunks, the same stream. PNG is lossless, so there is
 no tolerance: a file comes back with exactly Pillow's pixels (status 0) or goes back to Pillow - every file the parser
 refuses (`Unsupported`) and every file the device reports (1 invalid DEFLATE data, 2 the stream ended early, produced too
 little or wants to produce more, 3 a filter byte above 4, 4 the Adler-32 differs), so that Pillow's error handling stays the
@@ -39,7 +43,7 @@ def pack(items):
         r = recs[k]
         r["stream_off"], r["raw_off"], r["out_off"], r["stream_bytes"] = soff, roff, ooff, len(it.stream)
         r["width"], r["height"], r["channels"] = it.width, it.height, it.channels
-        if it.kind != "rgb":
+        if it.px8:
             r["reserved"] = (it.ctype << 8 | it.depth, it.n_entries)
         if it.interlace:
             r["reserved"][0] |= INTERLACE_BIT
@@ -55,16 +59,16 @@ def pack(items):
 
 
 def decode_device(items, device, stream=None):
-    """Parsed records, all of kind "rgb" or none of them -> (out uint8 device tensor, records, status int32 device tensor): the
+    """Parsed records, all for one decode entry (Parsed.px8: 8-bit grey / RGB files, or the others) -> (out uint8 device tensor, records, status int32 device tensor): the
     decoded rows of image k (PX_BYTES of its kind per pixel) start at records[k]["out_off"]. Asynchronous on torch's current
     stream of `device`; status is valid once that stream is."""
     device = torch.device(device)
     if device.type != "cuda":
         raise _lib.ClipmiError("png.decode_device needs the HIP path (no CPU fallback)")
     L = _lib.lib()
-    px8 = bool(items) and items[0].kind != "rgb"
-    if any((it.kind != "rgb") != px8 for it in items):
-        raise ValueError("png.decode_device: \"rgb\" files and files of the other kinds go to different entries")
+    px8 = bool(items) and items[0].px8
+    if any(it.px8 != px8 for it in items):
+        raise ValueError("png.decode_device: 8-bit \"rgb\" files and the other files go to different entries")
     size_of, decode, name = ((L.clipmi_png_px8_workspace_bytes, L.clipmi_png_decode_px8, "clipmi_png_decode_px8") if px8 else
                              (L.clipmi_png_workspace_bytes, L.clipmi_png_decode_rgb8, "clipmi_png_decode_rgb8"))
     recs, streams, out_bytes, total_raw, max_raw = pack(items)
@@ -86,26 +90,28 @@ def decode_device(items, device, stream=None):
     return out, recs, status
 
 
-def _parsed(blobs, modes, interlaced=False):
-    """-> [(position, Parsed)] of the files the parser lets through, split into the "rgb" files and the others"""
+def _parsed(blobs, modes, interlaced=False, chunks=False, deep=False):
+    """-> [(position, Parsed)] of the files the parser lets through, split into the files of clipmi_png_decode_rgb8 and the others"""
     rgb, px8 = [], []
     for k, b in enumerate(blobs):
         try:
-            it = parse(b, modes=modes, interlaced=interlaced)
+            it = parse(b, modes=modes, interlaced=interlaced, chunks=chunks, deep=deep)
         except Unsupported:
             continue
-        (rgb if it.kind == "rgb" else px8).append((k, it))
+        (px8 if it.px8 else rgb).append((k, it))
     return rgb, px8
 
 
-def decode_files(blobs, device, modes=False, interlaced=False):
+def decode_files(blobs, device, modes=False, interlaced=False, chunks=False, deep=False):
     """PNG file contents -> list of uint8 [H,W,3] numpy arrays (None where the file is not for the device decoder or the
     device reported it). modes=True: alpha, palette and low-depth files decode too (png_parse.parse(modes=True)) - files of kind
     "alpha" come back as uint8 [H,W,4], files of kind "index" as (uint8 [H,W], palette uint8 [256,3]). interlaced=True: Adam7
-    files of the kinds let through decode too, to the same arrays as the picture stored without interlace.
+    files of the kinds let through decode too, to the same arrays as the picture stored without interlace. chunks=True: files with
+    metadata chunks too (png_parse.parse(chunks=True)). deep=True: 16-bit RGB files too, and with modes RGBA and grey + alpha ones, as
+    uint8 [H,W,3] and [H,W,4] of the samples' high bytes.
     Synchronises; a convenience for tests and tools - the pipeline keeps the pixels in HBM."""
     res = [None] * len(blobs)
-    for group in _parsed(blobs, modes, interlaced):
+    for group in _parsed(blobs, modes, interlaced, chunks, deep):
         if not group:
             continue
         out, recs, status = decode_device([it for _, it in group], device)
@@ -159,14 +165,15 @@ def transform_device(items, out_rows, n_px, out, decoded, recs, device):
     _lib.check(rc, name)
 
 
-def transform_files(blobs, n_px, device, interlaced=False):
+def transform_files(blobs, n_px, device, interlaced=False, chunks=False, deep=False):
     """PNG file contents -> per file the transform's pixels, uint8 [3,n_px,n_px] as decode_worker.load_uint8 gives them (None
     where the file is not for the device or the device reported it): decode on the device + the transform entry of the file's
-    kind, "rgb" included; interlaced=True: Adam7 files too. Synchronises; a convenience for tests and tools like decode_files."""
+    kind, "rgb" included; interlaced=True: Adam7 files too; chunks=True: files with metadata chunks too; deep=True: files of depth 16
+    too. Synchronises; a convenience for tests and tools like decode_files."""
     device = torch.device(device)
     res = [None] * len(blobs)
-    rgb, px8 = _parsed(blobs, True, interlaced)
-    groups = [rgb, [e for e in px8 if e[1].kind == "alpha"], [e for e in px8 if e[1].kind == "index"]]
+    rgb, px8 = _parsed(blobs, True, interlaced, chunks, deep)
+    groups = [rgb] + [[e for e in px8 if e[1].kind == kind] for kind in ("rgb", "alpha", "index")]       # (px8's "rgb": 16-bit RGB)
     out = torch.zeros((max(len(blobs), 1), 3, n_px, n_px), dtype=torch.uint8, device=device)
     keep = []
     for group in groups:

@@ -466,6 +466,19 @@ int clipmi_png_decode_px8(const void* streams_dev, const void* images_dev, int n
  * the status codes 0-5 keep their meaning: the decoded pixels are laid out as those of the same picture stored without
  * interlace, every byte of the image's block of out_dev written once and none outside it. */
 
+/* ---- PNG files of depth 16 (a further addition to ABI 8 in the sense of the notes above: no new entry point and no new struct;
+ * every record that was valid before decodes to the same bytes and statuses). clipmi_png_decode_px8 also takes, in
+ * reserved[0] = colour type << 8 | bit depth (bit 16: Adam7, as above), three values of depth 16, with `channels` 3, 4, 2:
+ *   colour type 2 (RGB):          "rgb" layout - rows of width*3 bytes R G B, what clipmi_png_decode_rgb8 leaves and
+ *                                 clipmi_resize_crop_rgb8 takes; the image's block of out_dev holds width x height x 3 bytes;
+ *   colour type 6 (RGBA):         "alpha" layout, R G B A;
+ *   colour type 4 (grey + alpha): "alpha" layout, L L L A.
+ * Each output byte is the high (first) byte of its 16-bit sample, which is what Pillow keeps of such a file; the low bytes are
+ * reconstructed with the rest (the filters run byte by byte at the distance of one pixel: 6, 8, 4 bytes) and dropped by the
+ * store. A scanline holds width x channels x 2 bytes behind its filter byte, at most 49152: 8192, 6144 and 12288 pixels. The
+ * sizes and offsets (raw_off, total_raw_bytes, max_raw_bytes) count these scanlines; status 0-4 as before, never 5.
+ * Colour type 0 at depth 16 is not taken (status 1): Pillow resamples it in 16 bits. clipmi_png_decode_rgb8 is unchanged. */
+
 /* The transform for those pixels, bit for bit what Pillow's resize (in the file's mode) + crop + convert("RGB") gives.
  * clipmi_resize_crop_rgba8: arguments and jobs of clipmi_resize_crop_rgb8 with 4 bytes per source and scratch pixel (rows of
  * w*4 bytes; nrows*n_px*4 scratch bytes per job, tmp_off a multiple of 4). A job that resamples an axis premultiplies each
