@@ -65,8 +65,10 @@ typedef int i32x4 __attribute__((ext_vector_type(4)));
 //     (convert - exact -, multiply inside the fma, the product a_r * yt, the fma) and the right side three (subtract,
 //     multiply by 1/t_q, the margin's own sum), each of a quantity <= 1.35 R_max ||y|| / t_q (A_max <= 0.11 R_max and
 //     ||f_q|| <= 0.11 ||y|| at E <= 768: half a step times sqrt(E) against a largest component of 127 steps): < 16 u in all;
-//   * the norms ||y||, ||f_q||, a_r are sums of E squares in f32 (relative error < (E + 2) u / 2 each after the root):
-//     covered by their own 1.001 factors (1e-3 against < 2.3e-5).
+//   * the norms ||y||, ||f_q||, a_r are upper bounds by themselves (f64 sums of squares, roots rounded up: norm_up); their
+//     1.001 factors stay (they were sized for f32 sums: 1e-3 against < 2.3e-5) and the budget does not lean on them.
+//   All of this is relative. Where a rounding is absolute - the subnormal grid - or a side can overflow, coarse_prep_kernel
+//   sets the margin to +inf instead (I8_TINY .. COARSE_HUGE_RY in i8_layout.hpp).
 // Needed: (2 E + 16) u = 6.2e-5 at E = 512, 9.3e-5 at E = 768. The constant is 1e-4 * E / 512: 1e-4 at 512 (unchanged, bit for
 // bit), 1.5e-4 at 768 - the same 1.6 x head room at both widths instead of 1.08 x; it is < 1 % of the query half of the margin
 // (1.001 (R + A) ||f_q|| ~ 7.6e-3 R ||y|| on unit data), so the survivor count does not notice.
@@ -105,32 +107,41 @@ __global__ void __launch_bounds__(256) coarse_prep_kernel(const float* __restric
         return;
     }
     const float* y = q + (size_t)qi * E;
-    float mx = 0.f, ss = 0.f;
-    for (int k = lane; k < E; k += 64) { const float v = y[k]; mx = fmaxf(mx, fabsf(v)); ss = fmaf(v, v, ss); }
+    // ||y|| and ||f_q||: f64 sums of squares, roots rounded up (norm_up) - upper bounds at any magnitude of the query
+    float mx = 0.f;
+    double ss = 0.0;
+    for (int k = lane; k < E; k += 64) { const float v = y[k]; mx = fmaxf(mx, fabsf(v)); ss = fma((double)v, (double)v, ss); }
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o)); ss += __shfl_xor(ss, o); }
     const float t = mx > 0.f ? mx / 127.0f : 1.0f;
     const float inv = I8 ? 1.0f / t : 1.0f;
     // the int8 digit of component v; the query images below use the same expression
     auto digit = [&](float v) -> float { return fminf(fmaxf(rintf(v * inv), -127.f), 127.f); };
-    float ff = 0.f;
+    double ff = 0.0;
     if (I8) {
         for (int k = lane; k < E; k += 64) {
-            const float f = fmaf(-t, digit(y[k]), y[k]);       // what the digit leaves: f_q
-            ff = fmaf(f, f, ff);
+            const double f = fma(-(double)t, (double)digit(y[k]), (double)y[k]);       // what the digit leaves: f_q (exact in f64)
+            ff = fma(f, f, ff);
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) ff += __shfl_xor(ff, o);
     }
     if (lane == 0) {
-        const float Y = sqrtf(ss), F = sqrtf(ff) * 1.001f;
+        const float Y = norm_up(ss), F = norm_up(ff) * 1.001f;
         float margin = I8 ? 1.001f * (rmax + amax) * F + i8_round_slack<ET>() * rmax * Y : bf16_margin_coef<ET>() * rmax * Y * 1.001f;
         // A query with a NaN or infinite component has no usable coarse bound: its margin is +inf, which the selects turn into a
         // threshold of -inf whatever the K-th best is (inf - inf would be a NaN that passes nothing) - every row then passes, the
         // lists overflow and the exact fallback answers the call, as the contract promises for any data. The other two
         // constants stay finite so that the scans' left-hand sides do (round 5: an infinite component used to give inv = 0 and
         // Y inv = NaN, and such a query came back empty - test_non_finite_queries_through_the_permuted_int8_copy).
-        const bool finite_q = fabsf(Y) < INFINITY && fabsf(mx) < INFINITY && fabsf(margin) < INFINITY;      // false for NaN too
+        // The same holds where the f32 arithmetic of the bound is not proved (i8_layout.hpp, I8_TINY ..): a query or a database
+        // so small that 1 / t_q overflows or that roundings on the subnormal grid (absolute, E half-steps of 2^-149 in a score)
+        // outgrow the relative slack, or so large that a score or a scaled side can overflow. R_max ||y|| bounds every score
+        // and every partial sum of its fmaf chain.
+        constexpr float TINY = I8 ? I8_TINY : BF16_TINY;
+        const float RY = rmax * Y;
+        const bool in_range = mx >= TINY && mx <= COARSE_HUGE && rmax >= TINY && rmax <= COARSE_HUGE && RY >= TINY && RY <= COARSE_HUGE_RY;
+        const bool finite_q = in_range && fabsf(Y) < INFINITY && fabsf(mx) < INFINITY && fabsf(margin) < INFINITY;      // false for NaN too
         if (!finite_q) margin = INFINITY;
         qmeta[qi] = finite_q ? inv : 1.0f;
         qmeta[qs + qi] = I8 && finite_q ? 1.001f * Y * inv : 0.f;

@@ -27,6 +27,23 @@ inline const unsigned* i8_slot_rows(const float2* rmeta, int64_t N) {
     return reinterpret_cast<const unsigned*>(rmeta + i8_row_meta_entries(N) + i8_block_meta_entries(N));
 }
 
+// The norms of the superset bounds (||y||, ||f_q||, a_r, R_max) are UPPER bounds: the squares are summed in f64 - the square of
+// an f32 neither under- nor overflows there, and E <= 768 of them lose < 2^-43 relative - and the root is rounded UP to f32.
+// (An f32 sum of squares drops every component below 2^-63 - a query scaled by 2^-70 had ||y|| = 0 and no margin at all.)
+__device__ __forceinline__ float norm_up(double sumsq) {
+    const double nd = sqrt(sumsq);
+    float nf = (float)nd;
+    if ((double)nf < nd) nf = nextafterf(nf, INFINITY);           // NaN stays NaN, +inf stays +inf
+    return nf;
+}
+
+// Magnitudes the f32 arithmetic of a coarse bound is proved for. Below I8_TINY the scales, products and scores of the int8 test
+// approach the subnormal grid, where a rounding is an ABSOLUTE 2^-150 that the relative slack c(E) R_max ||y|| does not cover;
+// the bf16 test stops earlier, at BF16_TINY: a bf16 below 2^-126 keeps fewer than 8 bits (or is flushed by the matrix core).
+// A block of rows below I8_TINY is stored as zero codes with scale 1 (a_r = its rows' norms: exact, no small product);
+// a query or database outside [TINY, COARSE_HUGE] gets the margin +inf (coarse_prep_kernel) and the exact fallback answers.
+constexpr float I8_TINY = 0x1p-110f, BF16_TINY = 0x1p-90f, COARSE_HUGE = 0x1p110f, COARSE_HUGE_RY = 0x1p120f;
+
 // The bf16 copy is row-major [N][E]; its elements - and the bf16 query image - are rounded to nearest even, two at a time.
 typedef __bf16 bf16x2v __attribute__((ext_vector_type(2)));
 typedef float f32x2v __attribute__((ext_vector_type(2)));

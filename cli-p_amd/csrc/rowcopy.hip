@@ -11,6 +11,9 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // The int8 copy, in the layout of i8_layout.hpp: one workgroup per 32-row block.
 // Row r: s_r = (max |x| over r's 32-row block) / 127, q_rk = rint(x_rk / s_r) in [-127, 127], a_r = 1.001 * ||x_r - s_r q_r||_2.
+// a_r is an upper bound at any magnitude: e = x - s q is exact in f64 (24 + 7 significant bits against 24), its squares are
+// summed in f64 and the root is rounded up (norm_up). A block whose largest |x| is below I8_TINY (1 / s would overflow from
+// 2^-121 on, and 0 * inf is a NaN the clamp codes as -127) keeps scale 1 and zero codes, as an all-zero block does: a_r = ||x_r||.
 __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __restrict__ db, long long N, int E,
                                                                const unsigned* __restrict__ perm,
                                                                signed char* __restrict__ out, float2* __restrict__ meta,
@@ -33,7 +36,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
     if (lane == 0) red[wave] = mx;
     __syncthreads();
     mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
-    const float s = mx > 0.f ? mx / 127.0f : 1.0f;
+    const float s = mx >= I8_TINY ? mx / 127.0f : 1.0f;
     const float inv = 1.0f / s;
     signed char* oblk = out + (size_t)blk * 32 * E;
     float amax_w = 0.f;
@@ -41,7 +44,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
         const int rloc = wave * 8 + i;
         const long long t = r0 + rloc;                             // slot
         const long long r = t < N ? (perm ? (long long)perm[t] : t) : N;
-        float ee = 0.f;
+        double ee = 0.0;
         for (int k = lane * 4; k < E; k += 256) {
             float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
             if (r < N) v = *reinterpret_cast<const float4*>(db + (size_t)r * E + k);
@@ -51,8 +54,8 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 qv[j] = fminf(fmaxf(qv[j], -127.f), 127.f);
-                const float e = xv[j] - s * qv[j];
-                ee = fmaf(e, e, ee);
+                const double e = fma(-(double)s, (double)qv[j], (double)xv[j]);
+                ee = fma(e, e, ee);
                 pk |= ((unsigned)(int)qv[j] & 0xffu) << (8 * j);
             }
             const int ks = k >> 5, h = (k >> 4) & 1, b = k & 15;
@@ -60,7 +63,7 @@ __global__ void __launch_bounds__(256) quantize_rows_i8_kernel(const float* __re
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) ee += __shfl_xor(ee, o);
-        const float a_r = r < N ? sqrtf(ee) * 1.001f : 0.f;
+        const float a_r = r < N ? norm_up(ee) * 1.001f : 0.f;
         if (lane == 0) {
             meta[t] = make_float2(s, a_r);
             slot_rows[t] = r < N ? (unsigned)r : 0xffffffffu;
@@ -91,9 +94,7 @@ __global__ void __launch_bounds__(256) rows_stats_kernel(const float* __restrict
         }
 #pragma unroll
         for (int o = 32; o >= 1; o >>= 1) acc += __shfl_xor(acc, o);
-        const double nd = sqrt(acc);
-        float nf = (float)nd;
-        if ((double)nf < nd) nf = nextafterf(nf, INFINITY);
+        const float nf = norm_up(acc);
         // a NaN row (or NaN error norm) must surface as a non-finite maximum: the index then keeps the search on the exact
         // path (index.py: isfinite(rmax)); `nf > best` alone would silently drop it
         best = !(nf == nf) ? INFINITY : (nf > best ? nf : best);

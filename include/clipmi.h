@@ -224,6 +224,10 @@ int clipmi_topk_ip_coarse_i8(const void* db_dev, const void* db_i8_dev, const fl
 /* ---- ABI 8. The same search with a ONE-PASS wide scan at E = 768 as well - opt-in: clipmi_topk_ip_coarse_i8 and its workspace
  * function keep their behaviour byte for byte. Arguments, contract (asynchronous, no allocation, exact for any data and any row
  * permutation, exact fallback when a list overflows) and results are those of clipmi_topk_ip_coarse_i8.
+ * "Any data" includes any magnitude: the norms of the coarse bounds (||y||, ||f_q||, a_r, rmax) are f64 sums of squares rounded
+ * up, and a query or database whose largest |component|, rmax or rmax ||y|| lies outside [2^-110, 2^110 (2^120 for the product)]
+ * - bf16 copy: below 2^-90 - has no coarse bound: every row is re-scored or the exact fallback answers (DESIGN.md 4.1m;
+ * tests/test_topk_magnitude_gpu.py holds all four search entries to the oracle from 2^-126 to 2^100).
  * E = 512, or Q <= 64: it IS that function, and the workspace size is clipmi_topk_ip_coarse_workspace_bytes'.
  * E = 768, Q > 64: chunks of <= 1024 queries, each ONE pass of the copy on `stream` (v_mfma_i32_32x32x32_i8, 24 k-steps, query
  * tiles of 128 = 96 KiB resident in LDS, four-wave workgroups); the workspace is the larger of the 64-query one and the wide

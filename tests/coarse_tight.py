@@ -20,6 +20,8 @@ units, `term_row` = 1.001 a_r ||y|| (the int8 row term; the block's largest a_r 
 (int8: its query half 1.001 (R_max + A_max) F_q; bf16: all of it) and `seg`, the segment the row's slot is scanned in."""
 import numpy as np
 
+import topk_magnitude as tm
+
 f32 = np.float32
 S1 = 12288                              # csrc/topk.hip sample_rows: the sample is the first 12 288 rows, exactly scored
 FRAC = 125.0 / 256.0                    # 1/2 - delta, delta = 0.0117: a digit's error just under half a step, exact in binary
@@ -67,7 +69,9 @@ def bf16_coef(E, old=False):
 class I8Copy:
     """quantize_rows_i8_kernel + clipmi_rows_stats: slots ordered by largest |component| (stable), one scale per 32 slots."""
 
-    def __init__(self, db):
+    def __init__(self, db, form=None):
+        """form: the norm computations (tests/topk_magnitude.py; None: `current`, what the kernels compute)."""
+        form = self.form = form or tm.current
         N, E = db.shape
         self.N, self.E = N, E
         self.perm = np.argsort(np.abs(db).max(axis=1), kind="stable")
@@ -84,11 +88,10 @@ class I8Copy:
             xp = np.zeros((b1 - b0, E), f32)
             live = min(b1, N) - b0
             xp[:live] = db[self.perm[b0:b0 + live]]
-            sb = np.abs(xp).reshape((b1 - b0) // 32, -1).max(axis=1) / f32(127.0)
-            sb[sb == 0] = 1.0
-            sr = np.repeat(sb.astype(f32), 32)
-            q8 = np.clip(np.rint(xp * (f32(1.0) / sr)[:, None]), -127, 127).astype(f32)
-            a[b0:b1] = (np.linalg.norm(xp - sr[:, None] * q8, axis=1).astype(f32) * f32(1.001)).astype(f32)
+            sb = form.block_scale(np.abs(xp).reshape((b1 - b0) // 32, -1).max(axis=1))
+            sr = np.repeat(sb, 32)
+            q8 = tm.digits(xp, (f32(1.0) / sr)[:, None])
+            a[b0:b1] = form.err_norm(xp, sr, q8)
             s[b0 // 32:b1 // 32] = sb
             self.q8[b0:b1] = q8.astype(np.int8)
         a[N:] = 0
@@ -103,13 +106,14 @@ class I8Copy:
 class I8Queries:
     """coarse_prep_kernel<I8 = true>: t_q, 1 / t_q, the digits p_q, 1.001 ||f_q||, ||y||."""
 
-    def __init__(self, q):
-        self.t = (np.abs(q).max(axis=1) / f32(127.0)).astype(f32)
-        self.inv = (f32(1.0) / self.t).astype(f32)
-        self.p = np.clip(np.rint(q * self.inv[:, None]), -127, 127).astype(f32)
-        f = q - self.t[:, None] * self.p
-        self.F = (np.linalg.norm(f, axis=1).astype(f32) * f32(1.001)).astype(f32)
-        self.Y = np.linalg.norm(q, axis=1).astype(f32)
+    def __init__(self, q, form=None):
+        form = self.form = form or tm.current
+        self.mx = np.abs(q).max(axis=1).astype(f32)
+        self.t = np.where(self.mx > 0, self.mx / f32(127.0), f32(1.0)).astype(f32)
+        with np.errstate(over="ignore"):
+            self.inv = (f32(1.0) / self.t).astype(f32)
+        self.p = tm.digits(q, self.inv[:, None])
+        self.Y, self.F = form.query_norms(q, self.t, self.p)
 
 
 def exact_scores(db, q, special, oracle):
@@ -162,9 +166,20 @@ def i8_sides(cp, qm, E, wide, mut=None, nb=1):
     slack = f32(1e-4) * f32(E / 512.0)                                   # i8_round_slack<E>
     qhalf = (f32(1.001) * (rmax + cp.amax) * F).astype(f32)
     if mut == "q_off": qhalf = np.zeros_like(qhalf)
-    margin = (qhalf + slack * rmax * Y).astype(f32)
-    yt = (f32(1.001) * Y * inv).astype(f32)
-    return a, yt, margin, inv
+    with np.errstate(over="ignore", invalid="ignore"):
+        margin = (qhalf + slack * rmax * Y).astype(f32)
+        yt = (f32(1.001) * Y * inv).astype(f32)
+    # no usable bound (coarse_prep_kernel's finite_q: a magnitude outside the proved range, or a non-finite margin): margin
+    # +inf - the threshold is then -inf -, 1 / t_q read as 1 and the row term as 0
+    ok = qm.form.in_range(qm.mx, qm.Y, cp.rmax, True) & np.isfinite(margin)
+    return a, np.where(ok, yt, f32(0)), np.where(ok, margin, f32(np.inf)), np.where(ok, inv, f32(1))
+
+
+def _thr(taus, margin, inv):
+    """select_topk_kernel: (tau - margin) * (1 / t_q), and -inf whatever tau is where the margin is +inf."""
+    with np.errstate(invalid="ignore", over="ignore"):
+        thr = ((taus - margin[None, :]) * inv[None, :]).astype(f32)
+    return np.where(np.isinf(margin)[None, :], f32(-np.inf), thr)
 
 
 def i8_pairs(cp, qm, q, K, taus, bounds, rows, wide, mut=None, nb=1):
@@ -178,7 +193,7 @@ def i8_pairs(cp, qm, q, K, taus, bounds, rows, wide, mut=None, nb=1):
     assert np.abs(D).max() < 2 ** 24 and np.array_equal(D, np.rint(D))
     ay = (a[slots] * yt[:, None]).astype(f32)
     lhs = _fma32(D, cp.srow[slots], ay)
-    thr_seg = ((taus - margin[None, :]) * inv[None, :]).astype(f32)      # select_topk_kernel: (tau - margin) * (1 / t_q)
+    thr_seg = _thr(taus, margin, inv)
     thr = thr_seg[seg, np.arange(Q)[:, None]]
     passed = lhs >= thr
     if wide:                                                             # i8_pretest_dmin of the slot's block
@@ -189,7 +204,7 @@ def i8_pairs(cp, qm, q, K, taus, bounds, rows, wide, mut=None, nb=1):
         xq = ((xq - f32(2.0)).astype(f32) - (np.abs(xq) * f32(2e-6)).astype(f32)).astype(f32)
         passed &= D >= np.floor(xq)
     t64 = qm.t.astype(np.float64)[:, None]
-    return dict(passed=passed, seg=seg, room=(lhs.astype(np.float64) - thr) * t64,
+    return dict(passed=passed, seg=seg, room=(lhs.astype(np.float64) - thr) * t64, lhs=lhs, thr=thr, margin=margin,
                 term_row=f32(1.001) * cp.a[slots].astype(np.float64) * qm.Y[:, None] if not wide
                 else f32(1.001) * cp.ablk[slots // 32].astype(np.float64) * qm.Y[:, None],
                 term_q=(f32(1.001) * (cp.rmax + cp.amax) * qm.F).astype(np.float64)[:, None] * np.ones(rows.shape))
@@ -206,38 +221,42 @@ class Bf16Copy:
         self.slot_row = np.arange(self.N)
 
 
-def bf16_margin(cp, q, mut=None):
-    """coarse_prep_kernel<I8 = false>: bf16_margin_coef<E> * rmax * ||q|| * 1.001."""
-    Y = np.linalg.norm(q, axis=1).astype(f32)
+def bf16_margin(cp, q, mut=None, form=None):
+    """coarse_prep_kernel<I8 = false>: bf16_margin_coef<E> * rmax * ||q|| * 1.001; +inf where there is no usable bound."""
+    form = form or tm.current
+    Y = form.query_norms(q, None, None)[0]
     rmax = cp.rmean if mut == "rmax_mean" else cp.rmax
     assert mut in (None, "coef_old", "rmax_mean"), mut
-    return (bf16_coef(cp.E, old=(mut == "coef_old")) * rmax * Y * f32(1.001)).astype(f32)
+    with np.errstate(over="ignore"):
+        margin = (bf16_coef(cp.E, old=(mut == "coef_old")) * rmax * Y * f32(1.001)).astype(f32)
+    ok = form.in_range(np.abs(q).max(axis=1).astype(f32), Y, cp.rmax, False) & np.isfinite(margin)
+    return np.where(ok, margin, f32(np.inf))
 
 
-def bf16_pairs(cp, q, K, taus, bounds, rows, mut=None):
+def bf16_pairs(cp, q, K, taus, bounds, rows, mut=None, form=None):
     """The bf16 keep test of scan_coarse_kernel<.., I8 = false>: c = f32 sum of the products of the bf16-rounded operands."""
     Q = q.shape[0]
-    margin = bf16_margin(cp, q, mut)
+    margin = bf16_margin(cp, q, mut, form)
     seg = _seg_of(rows, bounds)
     c = np.einsum("qke,qe->qk", cp.dbh[rows], bf16_round(q)).astype(f32)
-    thr = (taus - margin[None, :]).astype(f32)[seg, np.arange(Q)[:, None]]
-    return dict(passed=c >= thr, seg=seg, room=c.astype(np.float64) - thr,
+    thr = _thr(taus, margin, np.ones(Q, f32))[seg, np.arange(Q)[:, None]]
+    return dict(passed=c >= thr, seg=seg, room=c.astype(np.float64) - thr, lhs=c, thr=thr, margin=margin,
                 term_q=margin.astype(np.float64)[:, None] * np.ones(rows.shape))
 
 
-def i8_survivors(db, q, K, exact, wide):
+def i8_survivors(db, q, K, exact, wide, form=None):
     """The int8 keep test on EVERY (query, row) pair, segment by segment (what tests/test_topk_e768.py and
     tests/test_topk_wide768.py check on unit rows). exact: [row][query] scores (f64 or the oracle's f32).
     Returns (every row of the true top K passes in its segment, the wide form's integer pre-test rejects no passing row -
     True on the 64-query form -, number of segments, fresh survivors per query)."""
     N, E = db.shape
     Q = q.shape[0]
-    cp, qm = I8Copy(db), I8Queries(q)
+    cp, qm = I8Copy(db, form), I8Queries(q, form)
     a, yt, margin, inv = i8_sides(cp, qm, E, wide)
     bounds = wide_segments(N) if wide else coarse_segments(N, K)
     taus = running_taus(exact, K, bounds, cp.slot_row)
     final = np.partition(exact, N - K, axis=0)[N - K]
-    thr_seg = ((taus - margin[None, :]) * inv[None, :]).astype(f32)
+    thr_seg = _thr(taus, margin, inv)
     tot = np.zeros(Q)
     ok = pre_ok = True
     for b0 in range(0, cp.N32, 1 << 15):
@@ -302,9 +321,9 @@ def count_band(db, q, K, exact, kind, mut=None, cp=None):
     band, pairs that pass or miss by no more than it), and the number of segments. The band, from the operations of the
     kernel's test (u = 2^-24, an ulp of x is at most 2 u |x|):
       int8  lhs = fmaf(D, s_r, fl(a_r yt)), D exact: half an ulp of lhs + half an ulp of a_r yt <= |lhs| near the threshold;
-            thr = fl(fl(tau - margin) / t_q): two half ulps; the inputs a_r, ||y||, ||f_q|| (sums of E squares in another
-            order than numpy's) move a_r yt and the margin, both < 0.1 |thr| on unit rows, by a few ulp of THEIRS: under one
-            ulp of thr. Taken: 4 ulp of max(|lhs|, |thr|).
+            thr = fl(fl(tau - margin) / t_q): two half ulps; the inputs a_r, ||y||, ||f_q|| (f64 sums of E squares, in another
+            order than numpy's, rounded up to f32: an ulp at the most apart) move a_r yt and the margin, both < 0.1 |thr| on
+            unit rows, by an ulp of THEIRS: under one ulp of thr. Taken: 4 ulp of max(|lhs|, |thr|).
       bf16  lhs = c is an f32 accumulation of E exact products in the matrix core's order: within E u ||x^|| ||q^|| of the sum
             in real numbers (computed here in f64); thr as above: + 2 ulp of |thr|."""
     N, E = db.shape
@@ -327,7 +346,7 @@ def count_band(db, q, K, exact, kind, mut=None, cp=None):
         band_l = E * U24 * np.linalg.norm(cp.dbh.astype(np.float64), axis=1)[:, None] * np.linalg.norm(qh, axis=1)[None, :]
         thr_ulps = 2
     taus = running_taus(exact, K, bounds, cp.slot_row)
-    thr_seg = ((taus - margin[None, :]) * inv[None, :]).astype(f32)
+    thr_seg = _thr(taus, margin, inv)
     sure = maybe = 0
     r0 = 0
     for g, r1 in enumerate(bounds):

@@ -1,7 +1,9 @@
 """-m gpu: how many (query, row) pairs each coarse scan hands to the exact re-scoring pass, against the counts recorded from
 the parent commit of csrc/coarse_scan.hpp (tests/golden/coarse_survivors_parent.json, never written from here; its bf16
 entries were recorded again, under `commit_bf16`, when the bf16 margin coefficient was corrected - a change of the counts by
-design), and - the 64-query `unit` cases - against the band of the numpy restatement of the scan's test
+design -, and two int8 entries under `commit_norms`, when the norms of the bound became f64 sums rounded up: one pair more,
+which tests/coarse_tight.py::i8_survivors reproduces on the CPU - 395 574 with topk_magnitude.legacy, 395 575 with `current`,
+154 929 for the first 200 queries with both), and - the 64-query `unit` cases - against the band of the numpy restatement of the scan's test
 (tests/coarse_tight.py::count_band), so that a recorded count is not merely the code's own word.
 
 The bit-exact suites cannot see a scan that keeps too many or too few pairs outside the top K: the lists are supersets. The
@@ -103,6 +105,8 @@ def test_the_recorded_cases_are_these():
     assert len(g["commit"]) == 40 and int(g["commit"], 16) >= 0
     assert len(g["commit_bf16"]) == 40 and int(g["commit_bf16"], 16) >= 0 and g["commit_bf16"] != g["commit"] and g["reason_bf16"]
     assert [e["id"] for e in g["cases"] if e.get("recorded") == "commit_bf16"] == [case_id(c) for c in CASES if c[3] == "bf16"]
+    assert len(g["commit_norms"]) == 40 and int(g["commit_norms"], 16) >= 0 and g["commit_norms"] not in (g["commit"], g["commit_bf16"]) and g["reason_norms"]
+    assert [e["id"] for e in g["cases"] if e.get("recorded") == "commit_norms"] == ["wide2<4,2>-unit-E512-int8-Q513", "wide2<4,2>-unit-E512-int8-Q1024"]
     assert [e["id"] for e in g["cases"]] == [case_id(c) for c in CASES]
 
 
