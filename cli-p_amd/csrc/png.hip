@@ -1,16 +1,18 @@
-// png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8), and
-// the file's own-mode pixels for alpha, palette and low-depth files (clipmi_png_decode_px8: the same inflate and Adler-32
-// kernels, png_unfilter_px_kernel with a filter unit of 1, 2 or 4 bytes and an "alpha" or "index" store; for files of depth 16 -
-// RGB, RGBA, grey + alpha - a filter unit of 6, 8 or 4 bytes and PngDeepStore, which keeps each sample's high byte as Pillow does).
-// The host (cli-p_amd/png_parse.py) lets through 8-bit grey and RGB files and hands over the DEFLATE stream behind the zlib
-// header. A record may say that its file is Adam7-interlaced (bit 16 of reserved[0], see png_interlaced): the stream then holds
-// up to seven reduced images one after the other, each filtered on its own, and the unfilter kernels reconstruct them in file
-// order and scatter their pixels (PngPass, png_pixel); inflate and Adler-32 only see a byte string of another length
-// (png_scanline_bytes). Three kernels:
-//   png_inflate_kernel   one wave per image: RFC 1951 inflate into the workspace's scanline buffer, with zlib's own table checks
-//   png_unfilter_kernel  one wave per image: PNG reconstruction (None, Sub, Up, Average, Paeth) as a 64-row diagonal wavefront,
-//                        RGB8 rows out
-//   png_adler_kernel     one block per image: Adler-32 of the scanlines against the stream's trailer
+// png.hip — `Image.open(f).convert("RGB")` for PNG files on the device (include/clipmi.h clipmi_png_decode_rgb8:
+// 8-bit grey and RGB files), and the file's own-mode pixels for alpha, palette and low-depth files and for files of depth 16 - RGB,
+// RGBA, grey + alpha, of which every sample's high byte is kept as Pillow does (clipmi_png_decode_px8). The host
+// (cli-p_amd/png_parse.py) walks the chunks and hands over the DEFLATE stream behind the zlib header. Both entries run the same
+// three kernels:
+//   png_inflate_kernel          one wave per image: RFC 1951 inflate into the workspace's scanline buffer, with zlib's own table checks
+//   png_unfilter_kernel<modes>  one wave per image: PNG reconstruction (None, Sub, Up, Average, Paeth) as a 64-row diagonal
+//                               wavefront, decoded pixels out; <0> for clipmi_png_decode_rgb8, <1> for clipmi_png_decode_px8
+//   png_adler_kernel            one block per image: Adler-32 of the scanlines against the stream's trailer
+// What a record's file is - filter unit, bits per pixel, layout of the decoded pixels, Adam7 or not - is read in one place
+// (png_format -> PngFormat), and every kernel starts from it. An Adam7 file's stream holds up to seven reduced images one after the
+// other, each filtered on its own: inflate and Adler-32 only see a byte string of another length (png_scanline_bytes), and the
+// unfilter kernel reconstructs the passes in file order (png_unfilter_passes, the one walk over a record's passes) and scatters
+// their pixels (PngPass, png_pixel). What becomes of the reconstructed bytes is one of two stores': PngSampleStore for pixels of
+// whole-byte samples, PngPackedStore for palette indices and samples below a byte.
 // PNG is lossless, so a file either comes back with exactly Pillow's bytes (status 0) or goes back to Pillow. Status 0 is given
 // only where zlib certainly accepts: valid data that ends with the final block's end-of-block code after exactly
 // height x (1 + width x channels) bytes (Adam7: the sum of that over the non-empty passes), filter bytes <= 4, and a present,
@@ -38,37 +40,66 @@ constexpr int PNG_PAD = 16;                 // zero bytes behind every stream
 constexpr int PNG_MAX_WIDTH = 16384;        // the unfilter kernel holds one row in LDS (48 KiB); png_parse.MAX_WIDTH
 constexpr int PNG_MAX_ROW = 49152;          // ... that many bytes: what bounds the rows of clipmi_png_decode_px8; png_parse.MAX_ROW_BYTES
 
-// The bytes of one scanline without its filter byte, the bits of one pixel, and whether the record is one its entry takes.
-// modes == 0 (clipmi_png_decode_rgb8): 8-bit grey or RGB, `reserved` not looked at except for the Adam7 mark (png_interlaced).
-// modes == 1 (clipmi_png_decode_px8): reserved[0] = Adam7 << 16 | colour type << 8 | bit depth, reserved[1] = palette entries;
-// RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4; and at 16 bits RGB, RGBA and grey + alpha (png_deep), whose
-// rows of 6, 8 and 4 bytes a pixel are bounded by PNG_MAX_ROW like the others: 8192, 6144 and 12288 pixels.
-__device__ __forceinline__ bool png_row_bytes(const PngImage& im, int modes, int64_t& row, int& bpp) {
-    if (im.width < 1 || im.width > PNG_MAX_WIDTH) return false;
-    if (!modes) {
-        row = (int64_t)im.width * im.channels;
-        bpp = 8 * im.channels;
-        return im.channels == 1 || im.channels == 3;
-    }
-    if (im.reserved[0] >> 17) return false;
-    const int ctype = (im.reserved[0] >> 8) & 255, depth = im.reserved[0] & 255;
-    const bool low = depth == 1 || depth == 2 || depth == 4;
-    int samples;
-    if (ctype == 6 && depth == 8) samples = 4;
-    else if (ctype == 4 && depth == 8) samples = 2;
-    else if (ctype == 3 && (low || depth == 8) && im.reserved[1] >= 1 && im.reserved[1] <= (1 << depth)) samples = 1;
-    else if (ctype == 0 && low) samples = 1;
-    else if (depth == 16 && (ctype == 2 || ctype == 6 || ctype == 4)) samples = ctype == 2 ? 3 : ctype == 6 ? 4 : 2;   // png_deep
-    else return false;
-    bpp = samples * depth;
-    row = ((int64_t)im.width * bpp + 7) >> 3;
-    return im.channels == samples && row <= PNG_MAX_ROW;
-}
+// What a record's file is. A pixel has `samples` samples of `sample_bytes` bytes each, or is packed: a palette index of any depth
+// or a grey sample below a byte, several to a byte, which PNG filters byte by byte (unit 1). layout: what the entry leaves of a
+// pixel - RGB3: 3 bytes R G B (grey as L L L); ALPHA4: 4 bytes R G B A (grey + alpha as L L L A, packed grey as L L L 255);
+// INDEX1: 1 byte, the palette index (1-bit grey: 0 or 1, black and white).
+enum { PNG_RGB3 = 0, PNG_ALPHA4 = 1, PNG_INDEX1 = 2 };
+struct PngFormat {
+    int unit;                   // the filter's unit in bytes: 1, 2, 3, 4, 6 or 8
+    int bpp;                    // bits per pixel
+    int samples, sample_bytes;
+    bool packed;
+    int layout;
+    int depth, entries;         // bit depth; a packed sample has to stay below `entries` (status 5)
+    bool interlaced;            // Adam7
+};
 
-// Whether the record's file is Adam7-interlaced. clipmi_png_decode_px8: bit 16 of reserved[0]. clipmi_png_decode_rgb8 never
-// looked at `reserved`, so only the one value 1 << 16 means Adam7 there and every other value means what it meant before.
-__device__ __forceinline__ bool png_interlaced(const PngImage& im, int modes) {
-    return modes ? ((im.reserved[0] >> 16) & 1) != 0 : im.reserved[0] == (1 << 16);
+// The only reader of a record's `channels` and `reserved`. -> whether the record is one its entry takes.
+// modes == 0 (clipmi_png_decode_rgb8): 8-bit grey or RGB by `channels`. The entry never looked at `reserved`, so only the one value
+// 1 << 16 of reserved[0] means Adam7 there and every other value means what it meant before: nothing.
+// modes == 1 (clipmi_png_decode_px8): reserved[0] = Adam7 << 16 | colour type << 8 | bit depth, reserved[1] = palette entries;
+// RGBA and grey + alpha at 8 bits, palette at 1/2/4/8, grey at 1/2/4; and at 16 bits RGB, RGBA and grey + alpha, whose rows of 6, 8
+// and 4 bytes a pixel are bounded by PNG_MAX_ROW like the others: 8192, 6144 and 12288 pixels.
+__device__ __forceinline__ bool png_format(const PngImage& im, int modes, PngFormat& f) {
+    if (im.width < 1 || im.width > PNG_MAX_WIDTH) return false;
+    const int word = im.reserved[0];
+    int ctype;
+    f.sample_bytes = 1;
+    f.packed = false;
+    f.entries = 2;
+    if (!modes) {
+        if (im.channels != 1 && im.channels != 3) return false;
+        ctype = im.channels == 3 ? 2 : 0;
+        f.depth = 8;
+        f.samples = im.channels;
+        f.interlaced = word == (1 << 16);
+    } else {
+        if (word >> 17) return false;
+        ctype = (word >> 8) & 255;
+        f.depth = word & 255;
+        f.interlaced = ((word >> 16) & 1) != 0;
+        const bool low = f.depth == 1 || f.depth == 2 || f.depth == 4;
+        if (ctype == 6 && f.depth == 8) f.samples = 4;
+        else if (ctype == 4 && f.depth == 8) f.samples = 2;
+        else if (ctype == 3 && (low || f.depth == 8) && im.reserved[1] >= 1 && im.reserved[1] <= (1 << f.depth)) {
+            f.samples = 1;
+            f.packed = true;
+            f.entries = im.reserved[1];
+        } else if (ctype == 0 && low) {
+            f.samples = 1;
+            f.packed = true;
+        } else if (f.depth == 16 && (ctype == 2 || ctype == 6 || ctype == 4)) {
+            f.samples = ctype == 2 ? 3 : ctype == 6 ? 4 : 2;
+            f.sample_bytes = 2;
+        } else return false;
+        if (im.channels != f.samples) return false;
+    }
+    f.bpp = f.samples * f.depth;
+    f.unit = f.samples * f.sample_bytes;
+    if (f.packed) f.layout = ctype == 3 || f.depth == 1 ? PNG_INDEX1 : PNG_ALPHA4;
+    else f.layout = f.samples == 1 || f.samples == 3 ? PNG_RGB3 : PNG_ALPHA4;
+    return !modes || (((int64_t)im.width * f.bpp + 7) >> 3) <= PNG_MAX_ROW;
 }
 
 // Adam7: pass p holds the pixels (x0 + i dx, y0 + j dy) of the image, i < w, j < h, as an image of w x h pixels of its own. The
@@ -95,15 +126,14 @@ __device__ __forceinline__ PngPass png_pass(int width, int height, int p) {
 __device__ __forceinline__ PngPass png_whole(int width, int height) { return PngPass{0, 0, 1, 1, width, height}; }
 
 // Bytes of filtered scanlines of the record, interlace included: what the stream has to inflate to, what the Adler-32 covers and
-// what the unfilter kernels walk. row, bpp: png_row_bytes'. A pass row of w pixels has 1 + ceil(w x bpp / 8) bytes, never more
-// than a full row.
-__device__ __forceinline__ int64_t png_scanline_bytes(const PngImage& im, int modes, int64_t row, int bpp) {
+// what the unfilter kernel walks. A row of w pixels - the image's, or a pass's - has 1 + ceil(w x bpp / 8) bytes.
+__device__ __forceinline__ int64_t png_scanline_bytes(const PngImage& im, const PngFormat& f) {
     if (im.height < 1) return 0;
-    if (!png_interlaced(im, modes)) return (int64_t)im.height * (1 + row);
+    if (!f.interlaced) return (int64_t)im.height * (1 + (((int64_t)im.width * f.bpp + 7) >> 3));
     int64_t n = 0;
     for (int p = 0; p < 7; p++) {
         const PngPass ps = png_pass(im.width, im.height, p);
-        if (ps.w && ps.h) n += (int64_t)ps.h * (1 + (((int64_t)ps.w * bpp + 7) >> 3));
+        if (ps.w && ps.h) n += (int64_t)ps.h * (1 + (((int64_t)ps.w * f.bpp + 7) >> 3));
     }
     return n;
 }
@@ -226,10 +256,9 @@ __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char*
     __shared__ unsigned char lens[320], cl_lens[19];
     const int lane = threadIdx.x;
     const PngImage im = images[blockIdx.x];
-    int64_t row_bytes = 0;
-    int bpp = 0;
-    const bool known = png_row_bytes(im, modes, row_bytes, bpp);
-    const int64_t raw_bytes64 = known ? png_scanline_bytes(im, modes, row_bytes, bpp) : 0;
+    PngFormat fmt;
+    const bool known = png_format(im, modes, fmt);
+    const int64_t raw_bytes64 = known ? png_scanline_bytes(im, fmt) : 0;
     if (!known || im.height < 1 || im.stream_bytes < 0 || im.stream_off < 0 ||
         raw_bytes64 > 0x7fffffffLL || raw_bytes64 > max_raw || im.raw_off < 0 || (im.raw_off & 15) ||
         im.raw_off + raw_bytes64 > total_raw) {
@@ -422,13 +451,14 @@ __global__ void __launch_bounds__(PNG_T) png_inflate_kernel(const unsigned char*
 // ---- reconstruction. Lane j owns row r0 + j of a 64-row band and runs one step of 4 pixels behind lane j - 1: the pixels above
 // (b) are the ones lane j - 1 finished in the step before and arrive by a cross-lane move; left (a) and upper left (c) stay in
 // registers. The first row of a band needs the last row of the band before: lane 63 leaves its finished words in an LDS row
-// (`prev`, PNG_MAX_WIDTH pixels: the host parser refuses wider files) and lane 0 of the next band takes them from there, so
+// (`prev`, PNG_MAX_ROW bytes: png_format refuses longer rows) and lane 0 of the next band takes them from there, so
 // the kernel never reads back what it stored to HBM. Within a band lane 63 writes word index t - 63 while lane 0 reads index
 // t: every word is read before it is overwritten, and the barrier between two bands orders the rest.
-// The filter works on units of CH bytes: CH = 3 or 1 for the 8-bit RGB and grey rows of clipmi_png_decode_rgb8; for
-// clipmi_png_decode_px8 4 (RGBA), 2 (grey + alpha) or 1 (8-bit palette rows and every depth below 8, which PNG filters byte by
-// byte). `w` counts units. What becomes of a step's finished bytes is the store's business: store.put(row, x0, words) gets the
-// units x0 .. x0 + 3 of the row (those below w are valid), packed as they lie in the file.
+// The filter works on units of CH bytes (PngFormat.unit): a pixel's bytes, or 1 for packed rows. At depth 16 that reconstructs
+// both bytes of every sample - Sub, Average and Paeth of the high bytes' neighbours do not depend on the low bytes, but a row is
+// only complete with them and the Adler-32 covers them. `w` counts units. What becomes of a step's finished bytes is the store's
+// business: store.put(row, x0, words) gets the units x0 .. x0 + 3 of the row (those below w are valid), packed as they lie in
+// the file.
 template <int CH, class Store>
 __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, Store& store, unsigned* prev, int w, int h, int lane, bool& bad) {
     constexpr int PX = 4, NW = CH;                      // 4 units a step: CH words of 4 bytes
@@ -490,93 +520,57 @@ __device__ void png_unfilter_image(const unsigned char* __restrict__ raw, Store&
     }
 }
 
-// rows of width * 3 RGB bytes, grey replicated: what clipmi_png_decode_rgb8 leaves. The stores below get the rows of one pass
-// (`ps`: the image itself where the file is not interlaced, LACE false) and put each pixel where png_pixel says it belongs in
-// the image of `width` columns: x < ps.w and row < ps.h keep every store inside the image's width x height pixels.
-template <int CH, bool LACE>
-struct PngRgbStore {
+// The stores get the rows of one pass (`ps`: the image itself where the file is not interlaced, LACE false) and put each pixel
+// where png_pixel says it belongs in the image of `width` columns: x < ps.w and row < ps.h keep every store inside the image's
+// width x height pixels. UNIT: the filter unit png_unfilter_image runs the store with.
+//
+// Pixels of S samples of B bytes (B == 2: depth 16, a sample's high byte comes first and is the one Pillow keeps; the low bytes
+// were only needed to reconstruct the row and for the Adler-32). S == 3 and S == 1 leave rows of width * 3 bytes, R G B and L L L
+// (PNG_RGB3); S == 4 and S == 2 rows of width words, R G B A and L L L A (PNG_ALPHA4; out_off is a multiple of 16).
+template <int S, int B, bool LACE>
+struct PngSampleStore {
+    static constexpr int UNIT = S * B;
+    static constexpr bool over = false;                 // no palette, so never status 5
     unsigned char* out;
     int width;
     PngPass ps;
+    static __device__ __forceinline__ unsigned first(const unsigned* res, int p, int s) {    // the first byte of sample s of unit p
+        const int i = p * UNIT + s * B;
+        return (res[i >> 2] >> (8 * (i & 3))) & 255u;
+    }
     __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
 #pragma unroll
-        for (int q = 0; q < 4 * CH; q++) {
-            const int x = x0 + q / CH, k = q % CH;
-            const unsigned char v = (unsigned char)(res[q >> 2] >> (8 * (q & 3)));
-            if (x < ps.w) {
-                unsigned char* d = out + png_pixel<LACE>(ps, width, row, x) * 3;
-                if (CH == 3) d[k] = v;
-                else d[0] = d[1] = d[2] = v;
+        for (int p = 0; p < 4; p++) {
+            if (x0 + p >= ps.w) break;
+            const int64_t at = png_pixel<LACE>(ps, width, row, x0 + p);
+            if (S == 3 || S == 1) {
+                unsigned char* d = out + at * 3;
+#pragma unroll
+                for (int k = 0; k < 3; k++) d[k] = (unsigned char)first(res, p, S == 3 ? k : 0);
+            } else if (S == 4) {
+                reinterpret_cast<unsigned*>(out)[at] = first(res, p, 0) | first(res, p, 1) << 8 | first(res, p, 2) << 16 | first(res, p, 3) << 24;
+            } else {
+                reinterpret_cast<unsigned*>(out)[at] = first(res, p, 0) * 0x010101u | first(res, p, 1) << 24;
             }
         }
     }
 };
 
-// The record's passes in file order (one, the image, where LACE is false): each non-empty pass is an image of its own - its
-// first row has a zero row above it (png_unfilter_image reads `prev` from the second band on only), its filter bytes are
-// checked, and its bytes start where the previous pass's end. png_unfilter_image ends every band with a barrier, so the LDS row
-// is free when the next pass begins. The early passes are short of rows for the 64-row wavefront (pass 1 has height / 8).
-template <int CH, bool LACE>
-__device__ void png_unfilter_rgb(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
-                                 bool& bad) {
-    for (int p = 0; p < (LACE ? 7 : 1); p++) {
-        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
-        if (ps.w == 0 || ps.h == 0) continue;
-        PngRgbStore<CH, LACE> store{out, im.width, ps};
-        png_unfilter_image<CH>(raw, store, prev, ps.w, ps.h, lane, bad);
-        raw += (int64_t)ps.h * (1 + (int64_t)ps.w * CH);
-    }
-}
-
-__global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
-                                                             unsigned char* __restrict__ out, int32_t* status) {
-    __shared__ unsigned prev[(PNG_MAX_WIDTH + 3) / 4 * 3];      // a band's last row: 4 pixels = 3 words (RGB) or 1 word (grey)
-    if (status[blockIdx.x] != 0) return;               // nothing was inflated: the record or the stream was refused
-    const PngImage im = images[blockIdx.x];            // (width <= PNG_MAX_WIDTH: png_inflate_kernel gave status 1 otherwise)
-    const int lane = threadIdx.x;
-    const unsigned char* raw = rawbuf + im.raw_off;
-    bool bad = false;
-    if (png_interlaced(im, 0)) {
-        if (im.channels == 3) png_unfilter_rgb<3, true>(im, raw, out + im.out_off, prev, lane, bad);
-        else png_unfilter_rgb<1, true>(im, raw, out + im.out_off, prev, lane, bad);
-    } else {
-        if (im.channels == 3) png_unfilter_rgb<3, false>(im, raw, out + im.out_off, prev, lane, bad);
-        else png_unfilter_rgb<1, false>(im, raw, out + im.out_off, prev, lane, bad);
-    }
-    if (__syncthreads_or(bad ? 1 : 0) && lane == 0) status[blockIdx.x] = 3;
-}
-
-// What clipmi_png_decode_px8 leaves, by colour type and depth. "alpha": rows of width * 4 bytes R G B A - RGBA as it is, grey +
-// alpha as L L L A, grey at depth 2 / 4 as v*85 / v*17 three times and 255 (Pillow opens those files as L with these values).
-// "index": rows of width bytes, one unpacked sample each, for palette files and 1-bit grey; the most significant bits of a
-// byte come first, the padding bits at a row's end are dropped, and a sample >= `entries` sets over (status 5).
-// Like PngRgbStore the store gets the rows of one pass `ps` and scatters them: below depth 8 a pass row is packed on its own,
-// ceil(ps.w x depth / 8) bytes, and its padding bits are dropped at ps.w.
+// Palette indices at depth 1/2/4/8 and grey samples at depth 1/2/4: a step's 4 bytes hold 8 / depth samples each, the most
+// significant bits of a byte first; a pass row is packed on its own, ceil(ps.w x depth / 8) bytes, and the padding bits at its
+// end are dropped at ps.w. PNG_INDEX1: rows of width bytes, one unpacked sample each, and a sample >= `entries` sets over (status
+// 5). PNG_ALPHA4: grey at depth 2 / 4 as v*85 / v*17 three times and 255 (Pillow opens those files as L with these values).
 template <bool LACE>
-struct PngPxStore {
+struct PngPackedStore {
+    static constexpr int UNIT = 1;
     unsigned char* out;
-    int width, ctype, depth, entries;
+    int width, layout, depth, entries;
     PngPass ps;
     bool over;
     __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
-        if (ctype == 6 || ctype == 4) {
-            unsigned* dst = reinterpret_cast<unsigned*>(out);                             // (out_off is a multiple of 16)
-#pragma unroll
-            for (int p = 0; p < 4; p++) {
-                if (x0 + p >= ps.w) break;
-                unsigned v;
-                if (ctype == 6) v = res[p];
-                else {
-                    const unsigned la = res[p >> 1] >> (16 * (p & 1));
-                    v = (la & 255u) * 0x010101u | (la & 0xff00u) << 16;
-                }
-                dst[png_pixel<LACE>(ps, width, row, x0 + p)] = v;
-            }
-            return;
-        }
         const int per = 8 / depth;                                  // samples in a byte: 1, 2, 4 or 8
         const unsigned mask = (1u << depth) - 1u;
-        for (int q = 0; q < 4; q++) {                               // the step's 4 bytes (ctype 0 and 3 filter with unit 1)
+        for (int q = 0; q < 4; q++) {
             const unsigned byte = (res[0] >> (8 * q)) & 255u;
             const int64_t px0 = ((int64_t)x0 + q) * per;
             for (int s = 0; s < per; s++) {
@@ -584,7 +578,7 @@ struct PngPxStore {
                 if (px >= ps.w) return;
                 const unsigned v = (byte >> (8 - depth * (s + 1))) & mask;
                 const int64_t at = png_pixel<LACE>(ps, width, row, (int)px);
-                if (ctype == 0 && depth != 1) {
+                if (layout == PNG_ALPHA4) {
                     reinterpret_cast<unsigned*>(out)[at] = v * (depth == 2 ? 85u : 17u) * 0x010101u | 0xff000000u;
                 } else {
                     if ((int)v >= entries) over = true;
@@ -595,102 +589,71 @@ struct PngPxStore {
     }
 };
 
-// png_unfilter_rgb for the records of clipmi_png_decode_px8. -> a sample beyond the palette was seen (status 5)
-template <bool LACE>
-__device__ bool png_unfilter_px(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
-                                bool& bad) {
-    const int ctype = (im.reserved[0] >> 8) & 255, depth = im.reserved[0] & 255;
-    bool over = false;
+// The record's passes in file order (one, the image, where LACE is false): each non-empty pass is an image of its own - its
+// first row has a zero row above it (png_unfilter_image reads `prev` from the second band on only), its filter bytes are
+// checked, and its bytes start where the previous pass's end. png_unfilter_image ends every band with a barrier, so the LDS row
+// is free when the next pass begins. The early passes are short of rows for the 64-row wavefront (pass 1 has height / 8).
+// A row of unit-1 pixels is ceil(ps.w x bpp / 8) units long (several packed pixels to a byte, or one), every other row ps.w
+// units: at most PNG_MAX_ROW bytes (png_format), so ceil(units / 4) * UNIT words of `prev` fit, PNG_MAX_ROW / UNIT being a
+// multiple of 4. -> bit 0: a filter byte above 4 (status 3), bit 1: store.over (status 5)
+template <bool LACE, class Store>
+__device__ __forceinline__ int png_unfilter_passes(int width, int height, int bpp, const unsigned char* __restrict__ raw, Store store,
+                                                   unsigned* prev, int lane) {
+    constexpr int UNIT = Store::UNIT;
+    bool bad = false;
     for (int p = 0; p < (LACE ? 7 : 1); p++) {
-        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
-        if (ps.w == 0 || ps.h == 0) continue;
-        PngPxStore<LACE> store{out, im.width, ctype, depth, ctype == 3 ? im.reserved[1] : 2, ps, false};
-        const int row_bytes = (int)(((int64_t)ps.w * im.channels * depth + 7) >> 3);      // <= PNG_MAX_ROW: png_row_bytes
-        if (ctype == 6) png_unfilter_image<4>(raw, store, prev, ps.w, ps.h, lane, bad);
-        else if (ctype == 4) png_unfilter_image<2>(raw, store, prev, ps.w, ps.h, lane, bad);
-        else png_unfilter_image<1>(raw, store, prev, row_bytes, ps.h, lane, bad);
-        over |= store.over;
-        raw += (int64_t)ps.h * (1 + row_bytes);
+        store.ps = LACE ? png_pass(width, height, p) : png_whole(width, height);
+        if (store.ps.w == 0 || store.ps.h == 0) continue;
+        const int units = UNIT == 1 ? (int)(((int64_t)store.ps.w * bpp + 7) >> 3) : store.ps.w;
+        png_unfilter_image<UNIT>(raw, store, prev, units, store.ps.h, lane, bad);
+        raw += (int64_t)store.ps.h * (1 + (int64_t)units * UNIT);
     }
-    return over;
+    return (bad ? 1 : 0) | (store.over ? 2 : 0);
 }
 
-// Depth 16 (colour types 2, 6, 4): a sample is two bytes, the high one first, and PNG filters such rows byte by byte at the
-// distance of one pixel, so png_unfilter_image runs with units of CH = 6, 8 or 4 bytes and reconstructs both bytes of every
-// sample - Sub, Average and Paeth of the high bytes' neighbours do not depend on the low bytes, but the reconstruction of a row
-// is only complete with them and the Adler-32 covers them. What Pillow keeps of such a file is every sample's high byte (modes
-// RGB, RGBA, and RGBA as L L L A), and that is what this store keeps of a finished step: colour type 2 as rows of width * 3 bytes
-// (PngRgbStore's layout), 6 as R G B A and 4 as L L L A, four bytes a pixel (PngPxStore's "alpha" layout).
-template <int CH, bool LACE>
-struct PngDeepStore {
-    unsigned char* out;
-    int width;
-    PngPass ps;
-    static __device__ __forceinline__ unsigned high(const unsigned* res, int p, int s) {     // the high byte of sample s of unit p
-        const int i = p * CH + 2 * s;
-        return (res[i >> 2] >> (8 * (i & 3))) & 255u;
-    }
-    __device__ __forceinline__ void put(int row, int x0, const unsigned* res) {
-#pragma unroll
-        for (int p = 0; p < 4; p++) {
-            if (x0 + p < ps.w) {
-                const int64_t at = png_pixel<LACE>(ps, width, row, x0 + p);
-                if (CH == 6) {
-                    unsigned char* d = out + at * 3;
-                    d[0] = (unsigned char)high(res, p, 0);
-                    d[1] = (unsigned char)high(res, p, 1);
-                    d[2] = (unsigned char)high(res, p, 2);
-                } else if (CH == 8) {
-                    reinterpret_cast<unsigned*>(out)[at] = high(res, p, 0) | high(res, p, 1) << 8 | high(res, p, 2) << 16 | high(res, p, 3) << 24;
-                } else {
-                    reinterpret_cast<unsigned*>(out)[at] = high(res, p, 0) * 0x010101u | high(res, p, 1) << 24;
-                }
-            }
-        }
-    }
-};
-
-// png_unfilter_px for the depth-16 records; CH: bytes per pixel
-template <int CH, bool LACE>
-__device__ void png_unfilter_deep(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
-                                  bool& bad) {
-    for (int p = 0; p < (LACE ? 7 : 1); p++) {
-        const PngPass ps = LACE ? png_pass(im.width, im.height, p) : png_whole(im.width, im.height);
-        if (ps.w == 0 || ps.h == 0) continue;
-        PngDeepStore<CH, LACE> store{out, im.width, ps};
-        png_unfilter_image<CH>(raw, store, prev, ps.w, ps.h, lane, bad);      // ceil(ps.w / 4) * CH words of `prev`: <= PNG_MAX_ROW / 4,
-        raw += (int64_t)ps.h * (1 + (int64_t)ps.w * CH);                      // since PNG_MAX_ROW / CH is a multiple of 4
-    }
+// The walk behind a call, for png_unfilter_kernel<1>: with the walks of its six stores inlined into one body its packed rows
+// ran 3 % slower than before (435 4-bit palette files of 224 x 224: 694 us against 674 us), each behind a call of its own 2 %
+// faster (660 us; profiles/png_unfilter_refactor.txt). png_unfilter_kernel<0> inlines its two walks: a call saves registers to
+// scratch memory, and that kernel has none.
+template <bool LACE, class Store>
+__device__ __noinline__ int png_unfilter_passes_call(int width, int height, int bpp, const unsigned char* __restrict__ raw, Store store,
+                                                     unsigned* prev, int lane) {
+    return png_unfilter_passes<LACE>(width, height, bpp, raw, store, prev, lane);
 }
 
-template <bool LACE>
-__device__ void png_unfilter_deep(const PngImage& im, const unsigned char* __restrict__ raw, unsigned char* out, unsigned* prev, int lane,
-                                  bool& bad) {
-    const int ctype = (im.reserved[0] >> 8) & 255;
-    if (ctype == 2) png_unfilter_deep<6, LACE>(im, raw, out, prev, lane, bad);
-    else if (ctype == 6) png_unfilter_deep<8, LACE>(im, raw, out, prev, lane, bad);
-    else png_unfilter_deep<4, LACE>(im, raw, out, prev, lane, bad);
+// The walk with the store of the record's format; MODES as in png_unfilter_kernel: <0> never sees another format than 8-bit RGB
+// and grey
+template <int MODES, bool LACE>
+__device__ __forceinline__ int png_unfilter_record(const PngImage& im, const PngFormat& f, const unsigned char* __restrict__ raw, unsigned char* out,
+                                                   unsigned* prev, int lane) {
+    const auto run = [&](auto store) {
+        return MODES ? png_unfilter_passes_call<LACE>(im.width, im.height, f.bpp, raw, store, prev, lane)
+                     : png_unfilter_passes<LACE>(im.width, im.height, f.bpp, raw, store, prev, lane);
+    };
+    const PngPass ps{};                                 // (png_unfilter_passes sets it)
+    if (!MODES) return f.samples == 3 ? run(PngSampleStore<3, 1, LACE>{out, im.width, ps}) : run(PngSampleStore<1, 1, LACE>{out, im.width, ps});
+    if (f.packed) return run(PngPackedStore<LACE>{out, im.width, f.layout, f.depth, f.entries, ps, false});
+    if (f.sample_bytes == 1) return f.samples == 4 ? run(PngSampleStore<4, 1, LACE>{out, im.width, ps}) : run(PngSampleStore<2, 1, LACE>{out, im.width, ps});
+    return f.samples == 3   ? run(PngSampleStore<3, 2, LACE>{out, im.width, ps})
+           : f.samples == 4 ? run(PngSampleStore<4, 2, LACE>{out, im.width, ps})
+                            : run(PngSampleStore<2, 2, LACE>{out, im.width, ps});
 }
 
-__global__ void __launch_bounds__(PNG_T) png_unfilter_px_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
-                                                                unsigned char* __restrict__ out, int32_t* status) {
-    __shared__ unsigned prev[PNG_MAX_ROW / 4];         // a band's last row: PNG_MAX_ROW bytes (png_inflate_kernel refused longer rows)
-    if (status[blockIdx.x] != 0) return;
+// MODES 0: the records of clipmi_png_decode_rgb8 (units 3 and 1 only, the kernel of the measured workload: it must not carry the
+// registers of the wide units), 1: those of clipmi_png_decode_px8. Status 3: a filter byte above 4; 5: an index beyond the palette.
+template <int MODES>
+__global__ void __launch_bounds__(PNG_T) png_unfilter_kernel(const PngImage* __restrict__ images, const unsigned char* __restrict__ rawbuf,
+                                                             unsigned char* __restrict__ out, int32_t* status) {
+    __shared__ unsigned prev[PNG_MAX_ROW / 4];         // a band's last row: PNG_MAX_ROW bytes (png_format refused longer rows)
+    if (status[blockIdx.x] != 0) return;               // nothing was inflated: the record or the stream was refused
     const PngImage im = images[blockIdx.x];
     const int lane = threadIdx.x;
-    int64_t row_bytes = 0;
-    int bpp = 0;
-    if (!png_row_bytes(im, 1, row_bytes, bpp)) return; // (not reached: png_inflate_kernel gave status 1)
+    PngFormat f;
+    if (!png_format(im, MODES, f)) return;             // (not reached: png_inflate_kernel gave status 1)
     const unsigned char* raw = rawbuf + im.raw_off;
-    bool bad = false, over = false;
-    if ((im.reserved[0] & 255) == 16) {                // depth 16: no palette, so never status 5
-        if (png_interlaced(im, 1)) png_unfilter_deep<true>(im, raw, out + im.out_off, prev, lane, bad);
-        else png_unfilter_deep<false>(im, raw, out + im.out_off, prev, lane, bad);
-    } else {
-        over = png_interlaced(im, 1) ? png_unfilter_px<true>(im, raw, out + im.out_off, prev, lane, bad)
-                                     : png_unfilter_px<false>(im, raw, out + im.out_off, prev, lane, bad);
-    }
-    const int is_bad = __syncthreads_or(bad ? 1 : 0), is_over = __syncthreads_or(over ? 1 : 0);
+    const int flags = f.interlaced ? png_unfilter_record<MODES, true>(im, f, raw, out + im.out_off, prev, lane)
+                                   : png_unfilter_record<MODES, false>(im, f, raw, out + im.out_off, prev, lane);
+    const int is_bad = __syncthreads_or(flags & 1), is_over = MODES ? __syncthreads_or(flags & 2) : 0;
     if (lane == 0 && (is_bad || is_over)) status[blockIdx.x] = is_bad ? 3 : 5;
 }
 
@@ -705,10 +668,9 @@ __global__ void __launch_bounds__(PNG_ADLER_T) png_adler_kernel(const PngImage* 
     __shared__ unsigned long long red1[PNG_ADLER_T], red2[PNG_ADLER_T];
     if (status[blockIdx.x] != 0) return;
     const PngImage im = images[blockIdx.x];
-    int64_t row_bytes = 0;
-    int bpp = 0;
-    png_row_bytes(im, modes, row_bytes, bpp);
-    const unsigned n = (unsigned)png_scanline_bytes(im, modes, row_bytes, bpp);
+    PngFormat fmt;
+    if (!png_format(im, modes, fmt)) return;                       // (not reached: png_inflate_kernel gave status 1)
+    const unsigned n = (unsigned)png_scanline_bytes(im, fmt);
     const unsigned char* raw = rawbuf + im.raw_off;
     const int tid = threadIdx.x;
     unsigned long long s1 = 0, s2 = 0;
@@ -778,15 +740,9 @@ static int png_decode(const char* who, int modes, const void* streams_dev, const
     hipLaunchKernelGGL(png_inflate_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, static_cast<const unsigned char*>(streams_dev), images,
                        total_raw_bytes, max_raw_bytes, raw, want, status_dev, modes);
     CLIPMI_CHECK_LAUNCH("png_inflate_kernel");
-    if (modes) {
-        hipLaunchKernelGGL(png_unfilter_px_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw, static_cast<unsigned char*>(out_dev),
-                           status_dev);
-        CLIPMI_CHECK_LAUNCH("png_unfilter_px_kernel");
-    } else {
-        hipLaunchKernelGGL(png_unfilter_kernel, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw, static_cast<unsigned char*>(out_dev),
-                           status_dev);
-        CLIPMI_CHECK_LAUNCH("png_unfilter_kernel");
-    }
+    hipLaunchKernelGGL(modes ? png_unfilter_kernel<1> : png_unfilter_kernel<0>, dim3((unsigned)n), dim3(PNG_T), 0, st, images, raw,
+                       static_cast<unsigned char*>(out_dev), status_dev);
+    CLIPMI_CHECK_LAUNCH("png_unfilter_kernel");
     hipLaunchKernelGGL(png_adler_kernel, dim3((unsigned)n), dim3(PNG_ADLER_T), 0, st, images, raw, want, status_dev, modes);
     CLIPMI_CHECK_LAUNCH("png_adler_kernel");
     return 0;

@@ -170,11 +170,8 @@ def png_records(bigview, n, cap, slots, comp, n_px, px=3):
     raw_sz = (_png_scanlines(hd, px) + 15) // 16 * 16
     recs["stream_off"], recs["raw_off"], recs["out_off"] = slots * cap + hd[:, HDR.DATA_OFF], np.cumsum(raw_sz) - raw_sz, out_off
     recs["stream_bytes"], recs["width"], recs["height"], recs["channels"] = hd[:, HDR.COUNT], hd[:, HDR.W], hd[:, HDR.H], hd[:, HDR.NCOMP]
-    if px == 3:
-        recs["reserved"][:, 0] = np.where(_png_deep(hd), hd[:, HDR.CTYPE] << 8 | 16, 0)
-    else:
-        recs["reserved"] = np.stack([hd[:, HDR.CTYPE] << 8 | hd[:, HDR.DEPTH], hd[:, HDR.ENTRIES]], axis=1)
-    recs["reserved"][:, 0] |= np.where(hd[:, HDR.INTERLACE] != 0, P.INTERLACE_BIT, 0).astype(np.int32)
+    px8 = _png_deep(hd) if px == 3 else np.ones(len(slots), bool)       # (Parsed.px8: every file but 8-bit grey and RGB)
+    recs["reserved"] = P.reserved_words(px8, hd[:, HDR.CTYPE], hd[:, HDR.DEPTH], hd[:, HDR.ENTRIES], hd[:, HDR.INTERLACE])
     return recs, jobs, out_sz, raw_sz
 
 

@@ -6,7 +6,7 @@ bytes in HBM: rows of width*3 RGB bytes per image, the layout `clipmi_resize_cro
 palette and low-depth files decode too, to the pixels of their own mode (clipmi_png_decode_px8; status 5: a palette index beyond
 the palette), and `transform_files` runs the transform of each kind on the device. With `interlaced=True` Adam7
 files of the same colour types and depths decode as well, to the layout of the same picture stored without interlace (the record
-carries INTERLACE_BIT; the unfilter kernels reconstruct the seven passes one after the other). With `deep=True` RGB files of
+carries INTERLACE_BIT; the unfilter kernel reconstructs the seven passes one after the other). With `deep=True` RGB files of
 depth 16 decode too, and with `modes=True` beside it RGBA and grey + alpha files of depth 16: clipmi_png_decode_px8 reconstructs
 the 16-bit scanlines and keeps every sample's high byte, which is what Pillow opens such a file as; the transform is that of
 the 8-bit file (16-bit RGB is of kind "rgb": Parsed.px8 says which entry decodes a file). `chunks=True` is the host's business
@@ -31,10 +31,17 @@ PX_BYTES = {"rgb": 3, "alpha": 4, "index": 1}          # bytes per decoded pixel
 INTERLACE_BIT = 1 << 16                                # in reserved[0] of a record: the file is Adam7-interlaced (include/clipmi.h)
 
 
+def reserved_words(px8, ctype, depth, entries, interlace):
+    """The two `reserved` words of a record (include/clipmi.h; csrc/png.hip png_format reads them): a file of clipmi_png_decode_px8
+    (Parsed.px8) carries colour type << 8 | depth and its palette entries, a file of clipmi_png_decode_rgb8 zeros, and an Adam7
+    file of either INTERLACE_BIT in the first word. Scalars, or numpy arrays of one value per file -> int32 [..., 2]."""
+    first = np.where(px8, np.asarray(ctype) << 8 | depth, 0) | np.where(np.asarray(interlace) != 0, INTERLACE_BIT, 0)
+    return np.stack([first, np.where(px8, entries, 0)], axis=-1).astype(np.int32)
+
+
 def pack(items):
-    """Parsed records -> (IMAGE array, streams uint8, out_bytes, total_raw_bytes, max_raw_bytes). Records of the kinds "alpha" and
-    "index" (clipmi_png_decode_px8) carry colour type, depth and palette entries in `reserved`; the record of an Adam7 file
-    (Parsed.interlace) carries INTERLACE_BIT there, and its scanline sizes are those of its passes (Parsed.raw_bytes)."""
+    """Parsed records -> (IMAGE array, streams uint8, out_bytes, total_raw_bytes, max_raw_bytes). `reserved` says what the file is
+    (reserved_words); the scanline sizes of an Adam7 file are those of its passes (Parsed.raw_bytes)."""
     recs = np.zeros(len(items), dtype=IMAGE)
     soff = roff = ooff = 0
     max_raw = 1
@@ -43,10 +50,7 @@ def pack(items):
         r = recs[k]
         r["stream_off"], r["raw_off"], r["out_off"], r["stream_bytes"] = soff, roff, ooff, len(it.stream)
         r["width"], r["height"], r["channels"] = it.width, it.height, it.channels
-        if it.px8:
-            r["reserved"] = (it.ctype << 8 | it.depth, it.n_entries)
-        if it.interlace:
-            r["reserved"][0] |= INTERLACE_BIT
+        r["reserved"] = reserved_words(it.px8, it.ctype, it.depth, it.n_entries, it.interlace)
         pad = (-len(it.stream)) % 16 + 16
         pieces.append(it.stream)
         pieces.append(b"\0" * pad)

@@ -80,8 +80,8 @@ csrc/jpeg.hip, clipmi_jpeg_decode_progressive_rgb8 / _transform_rgb8 (jpeg_progr
   outputs  status_dev[i] on every path out of jpeg_progressive_kernel (1, 1, bad / ran out / 0); the rest as above.
 
 csrc/png.hip, clipmi_png_decode_rgb8 / clipmi_png_decode_px8 (png_decode)
-  raw    u8 [total_raw]     png_inflate_kernel writes an image's scanlines [raw_off, + raw bytes); the unfilter and Adler kernels return
-                            at once when status != 0, else read exactly those bytes.
+  raw    u8 [total_raw]     png_inflate_kernel writes an image's scanlines [raw_off, + raw bytes); png_unfilter_kernel<0> / <1> (one
+                            per entry) and png_adler_kernel return at once when status != 0, else read exactly those bytes.
   want   u32 [n]            png_inflate_kernel stores the stream's Adler-32; png_adler_kernel reads it for status-0 images only.
   outputs  status_dev[i]: png_inflate_kernel stores on every path out; the later kernels only replace a 0. out_dev: W H px bytes.
 
