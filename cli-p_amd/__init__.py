@@ -13,10 +13,10 @@ from . import build
 from . import _lib
 from ._lib import ClipmiError
 from .index import (IndexFlatIP, IndexIVFFlat, ShardedFlatIP, METRIC_INNER_PRODUCT, read_index, write_index,
-                    shard_bounds, merge_lists_host)
+                    shard_bounds, merge_lists_host, IndexSubset, shard_rows)
 
 __all__ = ["_lib", "ClipmiError", "IndexFlatIP", "ShardedFlatIP", "METRIC_INNER_PRODUCT",
-           "read_index", "write_index", "shard_bounds", "merge_lists_host"]
+           "read_index", "write_index", "shard_bounds", "merge_lists_host", "IndexSubset", "shard_rows"]
 from . import weights  # noqa: E402
 from . import model  # noqa: E402
 from .model import CLIP, load, make_transform, available_models  # noqa: E402

@@ -20,6 +20,7 @@ SYMBOLS = [
     "clipmi_encode_image_workspace_bytes", "clipmi_encode_image",
     "clipmi_encode_text_workspace_bytes", "clipmi_encode_text",
     "clipmi_topk_ip_workspace_bytes", "clipmi_topk_ip",
+    "clipmi_topk_ip_rows_workspace_bytes", "clipmi_topk_ip_rows", "clipmi_dbg_topk_rows_scan_ms",
     "clipmi_topk_ip_coarse_workspace_bytes", "clipmi_topk_ip_coarse", "clipmi_dbg_topk_coarse_scan_ms",
     "clipmi_rows_stats", "clipmi_rows_absmax", "clipmi_rows_order_workspace_bytes", "clipmi_rows_order_by_absmax", "clipmi_rows_to_bf16", "clipmi_i8_copy_bytes", "clipmi_i8_meta_bytes", "clipmi_quantize_rows_i8", "clipmi_topk_ip_coarse_i8", "clipmi_dbg_topk_coarse_i8_scan_ms",
     "clipmi_topk_ip_wide_workspace_bytes", "clipmi_topk_ip_wide_i8", "clipmi_dbg_topk_wide_i8_scan_ms",
@@ -89,6 +90,12 @@ def lib():
     L.clipmi_topk_ip_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.clipmi_topk_ip.restype = i32
     L.clipmi_topk_ip.argtypes = [vp, i32, i64, i32, vp, i32, i32, i64, vp, vp, vp, sz, vp]
+    L.clipmi_topk_ip_rows_workspace_bytes.restype = sz
+    L.clipmi_topk_ip_rows_workspace_bytes.argtypes = [i64, i32, i32, i32]
+    L.clipmi_topk_ip_rows.restype = i32
+    L.clipmi_topk_ip_rows.argtypes = [vp, i32, i64, i32, vp, i64, vp, i32, i32, i64, vp, vp, vp, sz, vp]
+    L.clipmi_dbg_topk_rows_scan_ms.restype = i32
+    L.clipmi_dbg_topk_rows_scan_ms.argtypes = [vp, i64, i32, vp, i64, vp, i32, i32, vp, vp, vp, sz, vp, i32, C.POINTER(C.c_float)]
     L.clipmi_topk_ip_coarse_workspace_bytes.restype = sz
     L.clipmi_topk_ip_coarse_workspace_bytes.argtypes = [i64, i32, i32, i32]
     L.clipmi_topk_ip_coarse.restype = i32

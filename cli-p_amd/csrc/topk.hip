@@ -97,6 +97,8 @@ struct ScanArgs {
     const unsigned* run_if; // optional device flag: the kernel exits at once when *run_if == 0
     int q_total;            // gridDim.y > 1 only: queries over all groups; group y takes queries [y*QA, y*QA + QA) and
                             // the matching slices of q, thr_in, cand, gcnt
+    const unsigned* rows = nullptr;   // the row-list form (LIST) only: u32 [nrows] row numbers of db, ascending
+    long long n_db = 0;               // the row-list form only: the rows db holds; a list entry >= n_db is skipped
 };
 
 // PREPASS only changes the kernel's NAME (profilers average per name; the threshold pre-pass over
@@ -105,7 +107,20 @@ struct ScanArgs {
 // accumulator chains. The pass stays HBM-bound up to QG = 2 (f32 MFMA: 2 x 128 instructions of 32
 // cycles per 32 KiB tile per SIMD = 16 B/clk/CU against ~10 B/clk/CU of HBM), and two chains hide
 // the 40-cycle dependent-accumulator latency of a single one.
-template <int E, bool PREPASS, int QG>
+//
+// LIST (the row-list form, clipmi_topk_ip_rows): the launch scans the rows a list names instead of rows [0, nrows). "Row" in the
+// loop below then means LIST POSITION - a.nrows is the list's length M, tile t is entries 16 t .. 16 t + 15, the bound at
+// publication is against M - and only two things differ: a lane's row address comes from its list entry rows[16 t + col], and a
+// published candidate carries the entry of its accumulator row as its id. An entry >= a.n_db (the matrix's rows) becomes LIST_SKIP
+// when it is loaded: it addresses row 0 and is never published. The entry of a tile has to be in a register one iteration before
+// the rows it addresses are requested, so the list is read TWO tiles ahead (e_cur: this tile's MFMAs and ids, e_nxt: the refill's
+// addresses, e_nn: in flight); one ahead, every tile would wait out a dependent HBM round trip.
+// LIST is a template parameter of this kernel and not a sibling kernel around a shared body: with the body in an inlined device
+// function the compiler allocates the plain form's registers differently (156 instead of 160 VGPRs at E = 512, QG = 2; 14
+// instead of 10 AGPRs at 768), and the plain form's code is to stay what it was. The `if constexpr` branches leave it so; in
+// profiles the list form is scan_topk_f32_kernel<E, PREPASS, QG, true>.
+constexpr unsigned LIST_SKIP = 0xffffffffu;       // no row id: topk_ip's N < 2^32 - 1
+template <int E, bool PREPASS, int QG, bool LIST = false>
 __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int NT = E / 16;      // float4 per lane per 16-row tile
@@ -165,9 +180,22 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
     long long tile = wg;
     if (tile < ntiles) {
         f32x4 T[NT];
+        // LIST: this lane's entry of list tile t (positions past the end clamp to the last entry, as rows do to last_row)
+        [[maybe_unused]] auto entry = [&](long long t) -> unsigned {
+            long long e = t * 16 + col;
+            e = e > last_row ? last_row : e;
+            const unsigned v = a.rows[e];
+            return (long long)v < a.n_db ? v : LIST_SKIP;
+        };
+        unsigned e_cur = 0, e_nxt = 0;
+        if constexpr (LIST) {
+            e_cur = entry(tile);
+            e_nxt = entry(tile + tw);
+        }
         {
             long long r = tile * 16 + col;
             r = r > last_row ? last_row : r;
+            if constexpr (LIST) r = e_cur == LIST_SKIP ? 0 : (long long)e_cur;
             const float* p = a.db + r * E + 4 * g;
 #pragma unroll
             for (int t = 0; t < NT; ++t) T[t] = ld16_f<3>(p + 16 * t);
@@ -177,6 +205,11 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
             const bool has_next = nxt < ntiles;
             long long rn = (has_next ? nxt : tile) * 16 + col;
             rn = rn > last_row ? last_row : rn;
+            [[maybe_unused]] unsigned e_nn = 0;
+            if constexpr (LIST) {
+                e_nn = entry(nxt + tw);                                   // two tiles ahead: consumed by the NEXT refill
+                rn = e_nxt == LIST_SKIP ? 0 : (long long)e_nxt;          // (no next tile: the list's last row, all lanes)
+            }
             const float* pn = a.db + rn * E + 4 * g;
 
             f32x4 acc[QG];
@@ -229,6 +262,16 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
                     any |= pp[qg][r];
                 }
             if (__ballot(any)) {
+                // LIST: the id of accumulator row 4g + r is the entry the lane with col = 4g + r loaded (lanes 0..15)
+                [[maybe_unused]] unsigned id[4];
+                if constexpr (LIST) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) id[r] = (unsigned)__shfl((int)e_cur, 4 * g + r);
+#pragma unroll
+                    for (int qg = 0; qg < QG; ++qg)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) pp[qg][r] = pp[qg][r] && id[r] != LIST_SKIP;
+                }
 #pragma unroll
                 for (int qg = 0; qg < QG; ++qg) {
                     const int qi = qg * 16 + col;
@@ -237,7 +280,8 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
                     for (int r = 0; r < 4; ++r)
                         if (pp[qg][r]) {
                             const int pos = atomicAdd(&cnt[qi], 1);
-                            qb[pos] = make_uint2(__float_as_uint(acc[qg][r]), (unsigned)(row0 + r));
+                            if constexpr (LIST) qb[pos] = make_uint2(__float_as_uint(acc[qg][r]), id[r]);
+                            else qb[pos] = make_uint2(__float_as_uint(acc[qg][r]), (unsigned)(row0 + r));
                         }
                 }
                 wave_lds_sync();
@@ -257,6 +301,10 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
             }
             if (!has_next) break;
             tile = nxt;
+            if constexpr (LIST) {
+                e_cur = e_nxt;
+                e_nxt = e_nn;
+            }
         }
     }
 
@@ -909,6 +957,16 @@ int launch_scan(int E, int QG, const ScanArgs& a, int grid, int waves, size_t ld
     return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2>) : go(scan_topk_f32_kernel<768, PREPASS, 1>);
 }
 
+// The row-list form's launch (a.rows, a.n_db set; a.nrows = list entries of the launch), under a name of its own in error texts.
+template <bool PREPASS>
+int launch_scan_rows(int E, int QG, const ScanArgs& a, int grid, int waves, size_t lds, hipStream_t st, hipEvent_t* ev = nullptr) {
+    auto go = [&](void (*kern)(ScanArgs)) {
+        return launch_kernel(kern, "scan_topk_f32_kernel(rows)", dim3(grid), dim3(waves * 64), lds, st, ev, a);
+    };
+    if (E == 512) return QG == 2 ? go(scan_topk_f32_kernel<512, PREPASS, 2, true>) : go(scan_topk_f32_kernel<512, PREPASS, 1, true>);
+    return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2, true>) : go(scan_topk_f32_kernel<768, PREPASS, 1, true>);
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -999,6 +1057,93 @@ extern "C" int clipmi_topk_ip(const void* db_dev, int db_dtype, int64_t N, int E
                               size_t ws_bytes, void* stream) {
     return topk_ip_impl(db_dev, db_dtype, N, E, q_dev, Q, K, id_base, out_score_dev, out_id_dev, ws_dev, ws_bytes,
                         stream, nullptr);
+}
+
+// ---- The row-list form: clipmi_topk_ip's result restricted to the rows a u32 list names. Planned by
+// make_plan(M, ...): the list's length takes the place of the row count everywhere - grid, list capacity (a scan publishes every
+// (query, list position) pair at most once), whether the pre-pass runs - and the workspace has clipmi_topk_ip's layout for M rows.
+extern "C" size_t clipmi_topk_ip_rows_workspace_bytes(int64_t M, int E, int Q, int K) {
+    return clipmi_topk_ip_workspace_bytes(M, E, Q, K);
+}
+
+static int topk_ip_rows_impl(const void* db_dev, int db_dtype, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                             const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev,
+                             void* ws_dev, size_t ws_bytes, void* stream, hipEvent_t* scan_ev) {
+    if (db_dtype != CLIPMI_F32) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_rows: db_dtype %d (only CLIPMI_F32)", db_dtype);
+    if (!q_dev || !out_score_dev || !out_id_dev) return set_err(CLIPMI_EINVAL, "topk_ip_rows: NULL pointer");
+    if (N < 0 || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_rows: N=%lld outside 0 .. 2^32-2 rows per shard", (long long)N);
+    if (M < 0 || M > N) return set_err(CLIPMI_EINVAL, "topk_ip_rows: M=%lld list entries for N=%lld rows", (long long)M, (long long)N);
+    if (M > 0 && !rows_dev) return set_err(CLIPMI_EINVAL, "topk_ip_rows: NULL row list with M=%lld", (long long)M);
+    Plan p;
+    if (!make_plan(M, E, Q, K, p))
+        return set_err(CLIPMI_EINVAL, "topk_ip_rows: unsupported M=%lld E=%d Q=%d K=%d (E in {512,768}; 1 <= K <= %d at E = 512, <= %d at E = 768)",
+                       (long long)M, E, Q, K, max_k(512), max_k(768));
+    hipStream_t st = as_stream(stream);
+    if (M == 0) {
+        const long long n = (long long)Q * K;
+        hipLaunchKernelGGL(fill_empty_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, out_score_dev,
+                           (long long*)out_id_dev, n);
+        CLIPMI_CHECK_LAUNCH("fill_empty_kernel");
+        return 0;
+    }
+    if (!db_dev || !ws_dev) return set_err(CLIPMI_EINVAL, "topk_ip_rows: NULL db or workspace");
+    const size_t need_ws = clipmi_topk_ip_rows_workspace_bytes(M, E, Q, K);
+    if (ws_bytes < need_ws) return set_err(CLIPMI_EWORKSPACE, "topk_ip_rows: workspace %zu < %zu", ws_bytes, need_ws);
+    Arena ar(ws_dev, ws_bytes);
+    uint2* cand = ar.take<uint2>((size_t)p.QA * p.cap);
+    unsigned* gcnt = ar.take<unsigned>(32);
+    float* thr0 = ar.take<float>(32);
+
+    if (int rc = opt_in_lds((const void*)select_topk_kernel, p.lds_sel)) return rc;
+    if (zero_async(gcnt, 128, st) != hipSuccess) return set_err(CLIPMI_EHIP, "topk_ip_rows: zero_async");
+    for (int q0 = 0; q0 < Q; q0 += p.QA) {
+        const int qa = (Q - q0) < p.QA ? (Q - q0) : p.QA;
+        ScanArgs a;
+        a.db = static_cast<const float*>(db_dev);
+        a.q = q_dev + (size_t)q0 * E;
+        a.QA = qa;
+        a.K = K;
+        a.C = p.C;
+        a.wave_bytes = p.wave_bytes;
+        a.cand = cand;
+        a.gcnt = gcnt;
+        a.cap = p.cap;
+        a.thr_in = nullptr;
+        a.run_if = nullptr;
+        a.q_total = 0;
+        a.rows = rows_dev;
+        a.n_db = N;
+        if (p.sample) {
+            // pre-pass over the FIRST S LIST ENTRIES (M >= SAMPLE_MIN_N >= S), never over the first S rows of the matrix: only
+            // the K-th best score of rows that ARE in the list is a lower bound for the K-th best of the list - a threshold
+            // from rows outside it can lie above every listed score and would silently drop results
+            a.nrows = p.sample_rows;
+            int rc = launch_scan_rows<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
+            if (rc) return rc;
+            SelectArgs s;
+            s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
+            s.thr_out = thr0;
+            hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
+            CLIPMI_CHECK_LAUNCH("select_topk_kernel(rows sample)");
+            a.thr_in = thr0;
+        }
+        a.nrows = M;
+        int rc = launch_scan_rows<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
+        if (rc) return rc;
+        SelectArgs s;
+        s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
+        s.id_base = id_base; s.out_s = out_score_dev + (size_t)q0 * K; s.out_i = (long long*)out_id_dev + (size_t)q0 * K;
+        hipLaunchKernelGGL(select_topk_kernel, dim3(qa), dim3(SEL_THREADS), p.lds_sel, st, s);
+        CLIPMI_CHECK_LAUNCH("select_topk_kernel(rows)");
+    }
+    return 0;
+}
+
+extern "C" int clipmi_topk_ip_rows(const void* db_dev, int db_dtype, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                                   const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev,
+                                   void* ws_dev, size_t ws_bytes, void* stream) {
+    return topk_ip_rows_impl(db_dev, db_dtype, N, E, rows_dev, M, q_dev, Q, K, id_base, out_score_dev, out_id_dev, ws_dev,
+                             ws_bytes, stream, nullptr);
 }
 
 namespace clipmi {
@@ -1635,6 +1780,31 @@ extern "C" int clipmi_dbg_topk_scan_ms(const void* db_dev, int64_t N, int E, con
     int rc = 0;
     for (int i = 0; i < reps && rc == 0; ++i) {
         rc = topk_ip_impl(db_dev, CLIPMI_F32, N, E, q_dev, Q, K, 0, out_score_dev, out_id_dev, ws_dev, ws_bytes, stream, ev);
+        if (rc) break;
+        if (hipEventSynchronize(ev[1]) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipEventSynchronize"); break; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        total += ms;
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc == 0) *scan_ms = (float)(total / reps);
+    return rc;
+}
+
+// The same for clipmi_topk_ip_rows (tools/subset_timing.py): events around the main list scan only. Q <= 32 (one pass).
+extern "C" int clipmi_dbg_topk_rows_scan_ms(const void* db_dev, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                                            const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
+                                            void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms) {
+    if (!scan_ms || reps < 1 || Q > 32 || M < 1) return set_err(CLIPMI_EINVAL, "dbg_topk_rows_scan_ms: bad arguments");
+    hipEvent_t ev[2];
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)
+        return set_err(CLIPMI_EHIP, "hipEventCreate");
+    double total = 0.0;
+    int rc = 0;
+    for (int i = 0; i < reps && rc == 0; ++i) {
+        rc = topk_ip_rows_impl(db_dev, CLIPMI_F32, N, E, rows_dev, M, q_dev, Q, K, 0, out_score_dev, out_id_dev, ws_dev, ws_bytes,
+                               stream, ev);
         if (rc) break;
         if (hipEventSynchronize(ev[1]) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipEventSynchronize"); break; }
         float ms = 0.f;

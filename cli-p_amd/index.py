@@ -321,6 +321,102 @@ class IndexFlatIP:
         s, i = self.search_device(q, int(K))
         return s.cpu().numpy(), i.cpu().numpy()
 
+    def subset(self, rows):
+        """The exact search restricted to `rows` (faiss: an IDSelector) -> IndexSubset. rows: an integer array or tensor of
+        local row numbers (add order; sorted and de-duplicated here), or a bool mask of length ntotal. Negative or >= ntotal
+        entries, a mask of another length and a float dtype raise ValueError - here, once, never in a search."""
+        return IndexSubset(self, rows)
+
+
+def shard_rows(rows, lo, hi):
+    """Global row numbers -> the local ones of the shard [lo, hi) (`shard_bounds`): those inside it, minus lo, sorted, int64.
+    Pure; `index_of_shard.subset(shard_rows(rows, lo, hi))` with id_base = lo answers in global ids again."""
+    r = np.unique(np.asarray(rows, dtype=np.int64).reshape(-1))
+    return r[(r >= lo) & (r < hi)] - int(lo)
+
+
+def _subset_list(rows, ntotal):
+    """subset()'s argument -> sorted, de-duplicated int64 tensor of row numbers (on the argument's device for a tensor)."""
+    if isinstance(rows, (list, tuple)) and len(rows) == 0:
+        rows = np.empty(0, dtype=np.int64)     # (numpy would make an empty list float64)
+    t = rows if isinstance(rows, torch.Tensor) else torch.as_tensor(np.asarray(rows))
+    if t.dtype == torch.bool:
+        if t.dim() != 1 or t.shape[0] != ntotal:
+            raise ValueError(f"subset: a bool mask must have length ntotal = {ntotal}, got shape {tuple(t.shape)}")
+        return torch.nonzero(t).reshape(-1).to(torch.int64)
+    if t.dtype.is_floating_point or t.dtype.is_complex:
+        raise ValueError(f"subset: rows must be integers or a bool mask, got {t.dtype}")
+    t = t.reshape(-1).to(torch.int64)
+    if t.numel() and (int(t.min()) < 0 or int(t.max()) >= ntotal):
+        raise ValueError(f"subset: row numbers must lie in [0, {ntotal}), got {int(t.min())} .. {int(t.max())}")
+    return torch.unique(t)                     # sorted ascending
+
+
+class IndexSubset:
+    """IndexFlatIP.subset(rows): the exact top-K among the chosen rows only, reading only those rows.
+
+    Same contracts as IndexFlatIP - search(x, K) numpy in / numpy out, search_device(q, K, out=None) device tensors, async -
+    and the same results as searching everything and discarding the other rows: bit-exact scores, descending score then
+    ascending row id, ids = parent row + id_base, pads (-FLT_MAX, -1) beyond min(K, M). Every search goes through
+    clipmi_topk_ip_rows - the exact f32 list scan - WHATEVER `coarse=` the parent has: the coarse copies have no list form,
+    and the list scan reads M (d + 1) 4 bytes, fewer than the int8 copy's pass for any subset under a quarter of the rows.
+    `id_base` is the subset's own (initialised from the parent's; ShardedFlatIP sets it), `nprobe` is accepted and ignored.
+    The u32 list lives on the parent's device and is built once, here. A parent that has grown since (`add`) makes every
+    later search raise ClipmiError: the list was checked against the rows of then."""
+
+    def __init__(self, parent, rows):
+        self.parent = parent
+        self.d, self.device = parent.d, parent.device
+        self.nprobe = 1
+        self.id_base = parent.id_base
+        self._n_parent = parent.ntotal
+        lst = _subset_list(rows, self._n_parent)
+        self._rows = lst.to(self.device)                # int64, for rows()
+        # the u32 list the library reads: the low four bytes of each little-endian int64 (row numbers < 2^32 - 1)
+        self._list = self._rows.view(torch.int32)[0::2].contiguous() if lst.numel() else torch.empty(0, dtype=torch.int32, device=self.device)
+        self._ws = {}
+
+    @property
+    def ntotal(self):
+        return int(self._list.shape[0])
+
+    def rows(self):
+        """The sorted row numbers (int64 tensor on the index's device)."""
+        return self._rows
+
+    def search_device(self, q, K, out=None):
+        """q: f32 [Q,d] -> (scores f32 [Q,K], ids i64 [Q,K]) device tensors. Async."""
+        if self.parent.ntotal != self._n_parent:
+            raise _lib.ClipmiError(f"IndexSubset: the parent index has grown from {self._n_parent} to {self.parent.ntotal} rows "
+                                   "since subset(); take a new subset")
+        if self.device.type != "cuda":
+            raise _lib.ClipmiError("IndexSubset.search needs the HIP path (device is not a GPU); no CPU fallback")
+        L = _lib.lib()
+        db = self.parent.matrix()
+        q = q.to(device=self.device, dtype=torch.float32).contiguous()
+        Q, M = q.shape[0], self.ntotal
+        need = L.clipmi_topk_ip_rows_workspace_bytes(M, self.d, Q, K)
+        if need == 0:
+            raise _lib.ClipmiError("topk_ip_rows: " + _lib.last_error())
+        skey = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(skey)
+        if ws is None or ws.numel() < need:
+            ws = self._ws[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
+        out_s, out_i = _alloc_out(out, Q, K, self.device)
+        rc = L.clipmi_topk_ip_rows(db.data_ptr(), _lib.F32, db.shape[0], self.d, self._list.data_ptr() if M else None, M,
+                                   q.data_ptr(), Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
+                                   ws.numel(), _lib.stream_ptr(self.device))
+        _lib.check(rc, "clipmi_topk_ip_rows")
+        return out_s, out_i
+
+    def search(self, x, K):
+        """D, I = subset.search(features, K): numpy in, numpy out."""
+        q = torch.from_numpy(np.array(x, dtype=np.float32, order="C")) if not isinstance(x, torch.Tensor) else x
+        if q.dim() != 2 or q.shape[1] != self.d:
+            raise ValueError(f"search: expected [Q,{self.d}], got {tuple(q.shape)}")
+        s, i = self.search_device(q, int(K))
+        return s.cpu().numpy(), i.cpu().numpy()
+
 
 def IndexIVFFlat(quantizer, d, nlist=100, metric=METRIC_INNER_PRODUCT):
     """faiss.IndexIVFFlat(quantizer, 512, 100, faiss.METRIC_INNER_PRODUCT) (build-index.py:81) — returns

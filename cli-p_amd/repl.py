@@ -78,6 +78,20 @@ class Viewer:
             self.cv2.destroyAllWindows()
 
 
+def within_rows(db, spec):
+    """$CLIPMI_WITHIN -> sorted int64 row numbers. spec: key prefixes separated by os.pathsep (directories, as
+    `build-index.py DIR1/ DIR2/` stored their paths); a leading "!" on the whole spec means everything EXCEPT them. Each
+    prefix is one contiguous run of rows (VectorStore.prefix_rows); the result is their union, or its complement."""
+    invert = spec.startswith("!")
+    n = db.b.count("idx_db")
+    mask = np.zeros(n, dtype=bool)
+    for p in (spec[1:] if invert else spec).split(os.pathsep):
+        if p:
+            lo, hi = db.prefix_rows(os.fsencode(p))
+            mask[lo:hi] = True
+    return np.flatnonzero(~mask if invert else mask).astype(np.int64)
+
+
 def repl(model, index, db, inp=input, out=print):
     k, offset, last_j = 50, 0, 0
     features, have_text = None, False
@@ -202,6 +216,13 @@ def main():
     device = str(ranks.device)
     # large libraries: scan a coarse copy first (identical results; CLIPMI_COARSE = int8 | bf16 | none)
     coarse = os.environ.get("CLIPMI_COARSE", "int8")
+    # CLIPMI_WITHIN: search only the rows whose path starts with one of these prefixes ("!" in front: all but those)
+    within = os.environ.get("CLIPMI_WITHIN", "")
+    if within and ranks.world > 1:
+        if ranks.leader:
+            print("CLIPMI_WITHIN filters on a single GPU for now: run query-index.py as one process.")
+        ranks.close()
+        sys.exit(1)
     if ranks.world > 1:
         sharded = open_sharded("images.index", ranks, coarse=coarse)
         if not ranks.leader:
@@ -216,6 +237,10 @@ def main():
     model, _ = load(os.environ.get("CLIPMI_WEIGHTS", "ViT-B/32"), device=device, jit=False)
     model.eval()
     db = vstore.VectorStore("vectors.lmdb", dim=model.embed_dim)
+    if within:
+        rows = within_rows(db, within)
+        print(f"Searching {len(rows)} of {index.ntotal} images.")
+        index = index.subset(rows)
     index.nprobe = 32
     try:
         repl(model, index, db)

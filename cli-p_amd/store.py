@@ -232,6 +232,30 @@ class VectorStore:
     def idx_get(self, i):
         return self.b.get("idx_db", str(int(i)).encode())                    # query-index.py:92,117-118
 
+    def prefix_rows(self, prefix):
+        """(lo, hi): the rows whose key starts with `prefix` (bytes or str). Rows are in bytewise key order (assemble), so
+        they are one contiguous run; its ends are found by two binary searches over idx_get, O(log n) gets. No match gives
+        an empty range (lo == hi), b"" gives (0, n)."""
+        p = prefix if isinstance(prefix, bytes) else prefix.encode()
+        n = self.b.count("idx_db")
+
+        def first(pred):
+            """the first row of [0, n) for which pred(key) holds (pred is monotone: False ... False True ... True), else n"""
+            lo, hi = 0, n
+            while lo < hi:
+                mid = (lo + hi) // 2
+                if pred(self.idx_get(mid)):
+                    hi = mid
+                else:
+                    lo = mid + 1
+            return lo
+        # keys before the run are < p; the run's keys are >= p and start with it; behind it they are > p and do not
+        lo = first(lambda k: k >= p)
+        if not p:
+            return lo, n
+        hi = first(lambda k: k >= p and not k.startswith(p))
+        return lo, hi
+
     def export_lmdb(self, path):
         """Write this store out as an LMDB environment (data.mdb) with the reference's three tables, for the
         reference's own tools (lmdbfile.write_environment: one bulk transaction)."""

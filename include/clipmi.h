@@ -160,6 +160,30 @@ int clipmi_topk_ip(const void* db_dev, int db_dtype, int64_t N, int E,
                    float* out_score_dev, int64_t* out_id_dev,
                    void* ws_dev, size_t ws_bytes, void* stream);
 
+/* ---- a12 over a chosen subset of the rows (an addition to ABI 8 in the sense of the PNG note below: two new entry points,
+ * nothing existing changes, CLIPMI_ABI_VERSION stays 8). clipmi_topk_ip_rows is clipmi_topk_ip's result restricted to the
+ * rows `rows_dev` names, reading only those rows (M * E * 4 + M * 4 bytes per pass of <= 32 queries instead of N * E * 4).
+ *   rows_dev : u32 [M] row numbers of db_dev, strictly ascending. 0 <= M <= N; NULL with M > 0, M < 0 and M > N are
+ *              CLIPMI_EINVAL, db_dtype != CLIPMI_F32 is CLIPMI_EUNSUPPORTED - all decided on the host, nothing is launched.
+ *              M = 0 fills the outputs with pads and reads nothing.
+ *   result   : scores bit-exact (the same MFMA sequence per (row, query): DESIGN.md "score order"), ordered by descending
+ *              score, then ascending ROW ID; out_id = id_base + row; slots beyond min(K, M) hold (-FLT_MAX, -1). Non-finite
+ *              rows and queries as in clipmi_topk_ip (a NaN score is never selected). E, the K range, asynchrony, "no
+ *              allocation, no synchronisation" and workspace independence as there; the workspace is clipmi_topk_ip's for M rows.
+ *   safety   : the list is not validated on the device, but whatever it holds the kernels form no address outside
+ *              db_dev[0 .. N): an entry >= N is skipped - never addressed, never published, as if it were absent. A
+ *              DUPLICATE entry is not checked either: it is a second candidate with the same (score, id), which the
+ *              selects' rank counting (distinct keys assumed) may return once, twice or - at a list boundary - in place of
+ *              a neighbour; memory-safe, but outside the contract. So is a list that is not ascending: the result is still the
+ *              exact top-K of the listed rows (ordering is by row id, not by list position), only the pre-pass then samples
+ *              the first list entries rather than the lowest rows. */
+size_t clipmi_topk_ip_rows_workspace_bytes(int64_t M, int E, int Q, int K);
+int clipmi_topk_ip_rows(const void* db_dev, int db_dtype, int64_t N, int E,
+                        const uint32_t* rows_dev, int64_t M,
+                        const float* q_dev, int Q, int K, int64_t id_base,
+                        float* out_score_dev, int64_t* out_id_dev,
+                        void* ws_dev, size_t ws_bytes, void* stream);
+
 /* ---- a12, coarse-then-exact variant: the same exact result (bit-exact scores, same ordering rule) from a
  * bf16 coarse scan of `db_bf16_dev` (the matrix rounded to bf16, [N][E]) that keeps a provable superset,
  * followed by exact f32 re-scoring of the survivors from `db_dev` (DESIGN.md "coarse path"). Half the HBM
@@ -547,6 +571,12 @@ int clipmi_dbg_attention_fp8mx(const void* qkv_dev, void* out_bf16_dev, void* ou
 int clipmi_dbg_topk_scan_ms(const void* db_dev, int64_t N, int E, const float* q_dev, int Q, int K,
                             float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
                             void* stream, int reps, float* scan_ms);
+
+/* The same for clipmi_topk_ip_rows: events around the main list scan (tools/subset_timing.py). Q <= 32, M >= 1. (An addition
+ * to ABI 8 in the sense of the note above: nothing existing changes, CLIPMI_ABI_VERSION stays 8.) */
+int clipmi_dbg_topk_rows_scan_ms(const void* db_dev, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                                 const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
+                                 void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms);
 
 /* clipmi_topk_ip_coarse `reps` times with HIP events around the bf16 scan kernel (Q <= 64) */
 int clipmi_dbg_topk_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
