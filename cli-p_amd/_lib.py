@@ -13,7 +13,7 @@ DEV_LIB = os.environ.get("CLIPMI_DEV_LIB", "") not in ("", "0")
 LIB_PATH = os.path.join(HERE, "libclipmi_dev.so" if DEV_LIB else "libclipmi.so")
 
 ABI_VERSION = 8
-F32, BF16, U8 = 0, 1, 2
+F32, BF16, U8, F16 = 0, 1, 2, 3
 
 # every symbol include/clipmi.h declares (tests check the .so exports all of them)
 SYMBOLS = [
@@ -21,6 +21,7 @@ SYMBOLS = [
     "clipmi_encode_text_workspace_bytes", "clipmi_encode_text",
     "clipmi_topk_ip_workspace_bytes", "clipmi_topk_ip",
     "clipmi_topk_ip_rows_workspace_bytes", "clipmi_topk_ip_rows", "clipmi_dbg_topk_rows_scan_ms",
+    "clipmi_rows_to_f16", "clipmi_dbg_topk_scan_f16_ms",
     "clipmi_topk_ip_coarse_workspace_bytes", "clipmi_topk_ip_coarse", "clipmi_dbg_topk_coarse_scan_ms",
     "clipmi_rows_stats", "clipmi_rows_absmax", "clipmi_rows_order_workspace_bytes", "clipmi_rows_order_by_absmax", "clipmi_rows_to_bf16", "clipmi_i8_copy_bytes", "clipmi_i8_meta_bytes", "clipmi_quantize_rows_i8", "clipmi_topk_ip_coarse_i8", "clipmi_dbg_topk_coarse_i8_scan_ms",
     "clipmi_topk_ip_wide_workspace_bytes", "clipmi_topk_ip_wide_i8", "clipmi_dbg_topk_wide_i8_scan_ms",
@@ -106,6 +107,10 @@ def lib():
     L.clipmi_dbg_gemm_fp8.argtypes = [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]
     L.clipmi_rows_stats.restype = i32
     L.clipmi_rows_stats.argtypes = [vp, i64, i32, vp, vp, vp]
+    L.clipmi_rows_to_f16.restype = i32
+    L.clipmi_rows_to_f16.argtypes = [vp, i64, i32, vp, vp, vp]
+    L.clipmi_dbg_topk_scan_f16_ms.restype = i32
+    L.clipmi_dbg_topk_scan_f16_ms.argtypes = [vp, i64, i32, vp, i64, vp, i32, i32, vp, vp, vp, sz, vp, i32, C.POINTER(C.c_float)]
     L.clipmi_rows_to_bf16.restype = i32
     L.clipmi_rows_to_bf16.argtypes = [vp, i64, i32, vp, vp]
     L.clipmi_i8_copy_bytes.restype = sz

@@ -131,6 +131,44 @@ __global__ void __launch_bounds__(256) rows_to_bf16_kernel(const float* __restri
     }
 }
 
+// The CLIPMI_F16 matrix of an index kept in fp16: each element rounded to the nearest binary16, ties to even
+// (v_cvt_f16_f32 under the default rounding mode; the f16 denormal mode is IEEE, so subnormal results are produced and kept).
+// counts2[0] += elements whose value changed (f32(f16(x)) != x; a NaN that stays NaN is not a change), counts2[1] += finite
+// elements that became infinite (|x| >= 65520): a wave reduction, the four wave sums through LDS, one atomic pair per workgroup.
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+__global__ void __launch_bounds__(256) rows_to_f16_kernel(const float* __restrict__ db, long long n4, f16x4* __restrict__ out,
+                                                          unsigned long long* __restrict__ counts2) {
+    __shared__ unsigned red[2][4];
+    unsigned changed = 0, over = 0;
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += (long long)gridDim.x * 256) {
+        const f32x4 v = reinterpret_cast<const f32x4*>(db)[i];
+        const f16x4 h = __builtin_convertvector(v, f16x4);
+        const f32x4 b = __builtin_convertvector(h, f32x4);
+        out[i] = h;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            changed += (v[j] == v[j] && b[j] != v[j]) ? 1u : 0u;
+            over += (fabsf(v[j]) < INFINITY && fabsf(b[j]) == INFINITY) ? 1u : 0u;
+        }
+    }
+    if (!counts2) return;                                   // uniform
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+        changed += __shfl_xor(changed, o);
+        over += __shfl_xor(over, o);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        red[0][wave] = changed;
+        red[1][wave] = over;
+    }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        const unsigned long long t = (unsigned long long)red[threadIdx.x][0] + red[threadIdx.x][1] + red[threadIdx.x][2] + red[threadIdx.x][3];
+        if (t) atomicAdd(counts2 + threadIdx.x, t);
+    }
+}
+
 // ---- clipmi_rows_order_by_absmax: the row order of the int8 copy (slot t holds row perm[t]), built by the
 // library itself so that a C-ABI caller needs no framework sort: perm = the rows ordered by their largest |component|
 // ascending, equal maxima in row order (a stable sort). Keys are the f32 bits of the maxima (non-negative floats order as
@@ -325,5 +363,16 @@ extern "C" int clipmi_rows_to_bf16(const float* db_dev, int64_t N, int E, void* 
     const unsigned grid = (unsigned)(want < 16 * NUM_CU ? want : 16 * NUM_CU);
     hipLaunchKernelGGL(rows_to_bf16_kernel, dim3(grid), dim3(256), 0, as_stream(stream), db_dev, n4, static_cast<uint2*>(out_bf16_dev));
     CLIPMI_CHECK_LAUNCH("rows_to_bf16_kernel");
+    return 0;
+}
+
+extern "C" int clipmi_rows_to_f16(const float* db_dev, int64_t N, int E, void* out_f16_dev, uint64_t* counts2_dev, void* stream) {
+    if (!db_dev || !out_f16_dev || N < 1 || E < 4 || E % 4 != 0)
+        return set_err(CLIPMI_EINVAL, "rows_to_f16: bad arguments (N=%lld E=%d; E must be a multiple of 4)", (long long)N, E);
+    const long long n4 = (long long)N * E / 4, want = (n4 + 255) / 256;
+    const unsigned grid = (unsigned)(want < 16 * NUM_CU ? want : 16 * NUM_CU);
+    hipLaunchKernelGGL(rows_to_f16_kernel, dim3(grid), dim3(256), 0, as_stream(stream), db_dev, n4, static_cast<f16x4*>(out_f16_dev),
+                       reinterpret_cast<unsigned long long*>(counts2_dev));
+    CLIPMI_CHECK_LAUNCH("rows_to_f16_kernel");
     return 0;
 }

@@ -119,11 +119,25 @@ struct ScanArgs {
 // function the compiler allocates the plain form's registers differently (156 instead of 160 VGPRs at E = 512, QG = 2; 14
 // instead of 10 AGPRs at 768), and the plain form's code is to stay what it was. The `if constexpr` branches leave it so; in
 // profiles the list form is scan_topk_f32_kernel<E, PREPASS, QG, true>.
+//
+// RT (the row type; CLIPMI_F16 storage): float, or _Float16 for a matrix of IEEE binary16 rows of pitch 2 E bytes
+// behind a.db. A lane then holds elements 16t + 4g .. + 3 of its row as four halves (8 bytes per t, half the tile's registers)
+// and converts them to f32 - exactly, subnormals included: the f16 denormal mode is IEEE - in front of the four MFMAs of step t,
+// which are the f32 form's own: the same operand values in the same chain, so the score order holds on the converted rows. The
+// ring is the f32 form's (a chunk = 8 loads, refilled where its registers fall free). Like LIST it is a template parameter with
+// its branches in `if constexpr`, and for the same reason: the float instantiations' code stays what it was.
 constexpr unsigned LIST_SKIP = 0xffffffffu;       // no row id: topk_ip's N < 2^32 - 1
-template <int E, bool PREPASS, int QG, bool LIST = false>
+typedef _Float16 f16x4 __attribute__((ext_vector_type(4)));
+template <typename RT>
+__device__ __forceinline__ auto ld_row(const RT* p) {
+    if constexpr (std::is_same<RT, float>::value) return ld16_f<3>(p);
+    else return *reinterpret_cast<const f16x4*>(p);
+}
+template <int E, bool PREPASS, int QG, bool LIST = false, typename RT = float>
 __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int NT = E / 16;      // float4 per lane per 16-row tile
+    constexpr bool F16 = !std::is_same<RT, float>::value;
+    constexpr int NT = E / 16;      // float4 (F16: four halves) per lane per 16-row tile
     constexpr int NCH = NT / 8;     // chunks of 8 float4
     if (a.run_if && *a.run_if == 0) return;       // fallback launch that is not needed (uniform)
     if (gridDim.y > 1) {                          // the coarse path's fallback: all query groups in one launch
@@ -179,7 +193,8 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
 
     long long tile = wg;
     if (tile < ntiles) {
-        f32x4 T[NT];
+        typename std::conditional<F16, f16x4, f32x4>::type T[NT];
+        const RT* const rdb = reinterpret_cast<const RT*>(a.db);
         // LIST: this lane's entry of list tile t (positions past the end clamp to the last entry, as rows do to last_row)
         [[maybe_unused]] auto entry = [&](long long t) -> unsigned {
             long long e = t * 16 + col;
@@ -196,9 +211,9 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
             long long r = tile * 16 + col;
             r = r > last_row ? last_row : r;
             if constexpr (LIST) r = e_cur == LIST_SKIP ? 0 : (long long)e_cur;
-            const float* p = a.db + r * E + 4 * g;
+            const RT* p = rdb + r * E + 4 * g;
 #pragma unroll
-            for (int t = 0; t < NT; ++t) T[t] = ld16_f<3>(p + 16 * t);
+            for (int t = 0; t < NT; ++t) T[t] = ld_row<RT>(p + 16 * t);
         }
         while (true) {
             const long long nxt = tile + tw;
@@ -210,7 +225,7 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
                 e_nn = entry(nxt + tw);                                   // two tiles ahead: consumed by the NEXT refill
                 rn = e_nxt == LIST_SKIP ? 0 : (long long)e_nxt;          // (no next tile: the list's last row, all lanes)
             }
-            const float* pn = a.db + rn * E + 4 * g;
+            const RT* pn = rdb + rn * E + 4 * g;
 
             f32x4 acc[QG];
 #pragma unroll
@@ -223,14 +238,17 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
                     f32x4 bq[QG];
 #pragma unroll
                     for (int qg = 0; qg < QG; ++qg) bq[qg] = qimg[(qg * NT + t) * 64 + lane];
+                    f32x4 tv;
+                    if constexpr (F16) tv = __builtin_convertvector(T[t], f32x4);      // exact
+                    else tv = T[t];
 #pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(T[t].x, bq[qg].x, acc[qg], 0, 0, 0);
+                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv.x, bq[qg].x, acc[qg], 0, 0, 0);
 #pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(T[t].y, bq[qg].y, acc[qg], 0, 0, 0);
+                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv.y, bq[qg].y, acc[qg], 0, 0, 0);
 #pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(T[t].z, bq[qg].z, acc[qg], 0, 0, 0);
+                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv.z, bq[qg].z, acc[qg], 0, 0, 0);
 #pragma unroll
-                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(T[t].w, bq[qg].w, acc[qg], 0, 0, 0);
+                    for (int qg = 0; qg < QG; ++qg) acc[qg] = __builtin_amdgcn_mfma_f32_16x16x4f32(tv.w, bq[qg].w, acc[qg], 0, 0, 0);
                 }
                 // this chunk's registers are free: refill them with the next tile (stays in
                 // flight across the candidate step below and the first chunks of the next pass).
@@ -245,7 +263,7 @@ __global__ void __launch_bounds__(256) scan_topk_f32_kernel(ScanArgs a) {
 #pragma unroll
                 for (int j = 0; j < 8; ++j) {
                     const int t = 8 * c + j;
-                    T[t] = ld16_f<3>(pn + 16 * t);
+                    T[t] = ld_row<RT>(pn + 16 * t);
                 }
                 __builtin_amdgcn_sched_barrier(0);
             }
@@ -967,6 +985,27 @@ int launch_scan_rows(int E, int QG, const ScanArgs& a, int grid, int waves, size
     return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2, true>) : go(scan_topk_f32_kernel<768, PREPASS, 1, true>);
 }
 
+// The launches over a CLIPMI_F16 matrix (a.db points at halves): the same plan, grid and LDS as the f32 forms'.
+template <bool PREPASS>
+int launch_scan_f16(int E, int QG, const ScanArgs& a, int grid, int waves, size_t lds, hipStream_t st, hipEvent_t* ev = nullptr) {
+    auto go = [&](void (*kern)(ScanArgs)) {
+        return launch_kernel(kern, "scan_topk_f32_kernel(f16)", dim3(grid), dim3(waves * 64), lds, st, ev, a);
+    };
+    if (E == 512)
+        return QG == 2 ? go(scan_topk_f32_kernel<512, PREPASS, 2, false, _Float16>) : go(scan_topk_f32_kernel<512, PREPASS, 1, false, _Float16>);
+    return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2, false, _Float16>) : go(scan_topk_f32_kernel<768, PREPASS, 1, false, _Float16>);
+}
+
+template <bool PREPASS>
+int launch_scan_rows_f16(int E, int QG, const ScanArgs& a, int grid, int waves, size_t lds, hipStream_t st, hipEvent_t* ev = nullptr) {
+    auto go = [&](void (*kern)(ScanArgs)) {
+        return launch_kernel(kern, "scan_topk_f32_kernel(f16 rows)", dim3(grid), dim3(waves * 64), lds, st, ev, a);
+    };
+    if (E == 512)
+        return QG == 2 ? go(scan_topk_f32_kernel<512, PREPASS, 2, true, _Float16>) : go(scan_topk_f32_kernel<512, PREPASS, 1, true, _Float16>);
+    return QG == 2 ? go(scan_topk_f32_kernel<768, PREPASS, 2, true, _Float16>) : go(scan_topk_f32_kernel<768, PREPASS, 1, true, _Float16>);
+}
+
 }  // namespace
 }  // namespace clipmi
 
@@ -985,7 +1024,9 @@ extern "C" size_t clipmi_topk_ip_workspace_bytes(int64_t N, int E, int Q, int K)
 static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, const float* q_dev, int Q, int K,
                         int64_t id_base, float* out_score_dev, int64_t* out_id_dev, void* ws_dev, size_t ws_bytes,
                         void* stream, hipEvent_t* scan_ev) {
-    if (db_dtype != CLIPMI_F32) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip: db_dtype %d (only CLIPMI_F32)", db_dtype);
+    if (db_dtype != CLIPMI_F32 && db_dtype != CLIPMI_F16)
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip: db_dtype %d (only CLIPMI_F32 and CLIPMI_F16)", db_dtype);
+    const bool f16 = db_dtype == CLIPMI_F16;
     if (!q_dev || !out_score_dev || !out_id_dev) return set_err(CLIPMI_EINVAL, "topk_ip: NULL pointer");
     if (N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip: N=%lld exceeds 2^32-2 rows per shard", (long long)N);
     Plan p;
@@ -1015,7 +1056,7 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
     for (int q0 = 0; q0 < Q; q0 += p.QA) {
         const int qa = (Q - q0) < p.QA ? (Q - q0) : p.QA;
         ScanArgs a;
-        a.db = static_cast<const float*>(db_dev);
+        a.db = static_cast<const float*>(db_dev);        // CLIPMI_F16: halves, read as such by the f16 instantiations
         a.q = q_dev + (size_t)q0 * E;
         a.QA = qa;
         a.K = K;
@@ -1031,7 +1072,8 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
             // pre-pass: exact K-th best score of the first S rows = a valid lower bound for the
             // K-th best of all rows; the main pass then only buffers scores >= that bound
             a.nrows = p.sample_rows;
-            int rc = launch_scan<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
+            int rc = f16 ? launch_scan_f16<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st)
+                         : launch_scan<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
             if (rc) return rc;
             SelectArgs s;
             s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
@@ -1041,7 +1083,8 @@ static int topk_ip_impl(const void* db_dev, int db_dtype, int64_t N, int E, cons
             a.thr_in = thr0;
         }
         a.nrows = N;
-        int rc = launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
+        int rc = f16 ? launch_scan_f16<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev)
+                     : launch_scan<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
         if (rc) return rc;
         SelectArgs s;
         s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
@@ -1069,7 +1112,9 @@ extern "C" size_t clipmi_topk_ip_rows_workspace_bytes(int64_t M, int E, int Q, i
 static int topk_ip_rows_impl(const void* db_dev, int db_dtype, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
                              const float* q_dev, int Q, int K, int64_t id_base, float* out_score_dev, int64_t* out_id_dev,
                              void* ws_dev, size_t ws_bytes, void* stream, hipEvent_t* scan_ev) {
-    if (db_dtype != CLIPMI_F32) return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_rows: db_dtype %d (only CLIPMI_F32)", db_dtype);
+    if (db_dtype != CLIPMI_F32 && db_dtype != CLIPMI_F16)
+        return set_err(CLIPMI_EUNSUPPORTED, "topk_ip_rows: db_dtype %d (only CLIPMI_F32 and CLIPMI_F16)", db_dtype);
+    const bool f16 = db_dtype == CLIPMI_F16;
     if (!q_dev || !out_score_dev || !out_id_dev) return set_err(CLIPMI_EINVAL, "topk_ip_rows: NULL pointer");
     if (N < 0 || N >= (1ll << 32) - 1) return set_err(CLIPMI_EINVAL, "topk_ip_rows: N=%lld outside 0 .. 2^32-2 rows per shard", (long long)N);
     if (M < 0 || M > N) return set_err(CLIPMI_EINVAL, "topk_ip_rows: M=%lld list entries for N=%lld rows", (long long)M, (long long)N);
@@ -1099,7 +1144,7 @@ static int topk_ip_rows_impl(const void* db_dev, int db_dtype, int64_t N, int E,
     for (int q0 = 0; q0 < Q; q0 += p.QA) {
         const int qa = (Q - q0) < p.QA ? (Q - q0) : p.QA;
         ScanArgs a;
-        a.db = static_cast<const float*>(db_dev);
+        a.db = static_cast<const float*>(db_dev);        // CLIPMI_F16: halves, read as such by the f16 instantiations
         a.q = q_dev + (size_t)q0 * E;
         a.QA = qa;
         a.K = K;
@@ -1118,7 +1163,8 @@ static int topk_ip_rows_impl(const void* db_dev, int db_dtype, int64_t N, int E,
             // the K-th best score of rows that ARE in the list is a lower bound for the K-th best of the list - a threshold
             // from rows outside it can lie above every listed score and would silently drop results
             a.nrows = p.sample_rows;
-            int rc = launch_scan_rows<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
+            int rc = f16 ? launch_scan_rows_f16<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st)
+                         : launch_scan_rows<true>(E, p.QG, a, p.grid_sample, p.waves, p.lds_scan, st);
             if (rc) return rc;
             SelectArgs s;
             s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
@@ -1128,7 +1174,8 @@ static int topk_ip_rows_impl(const void* db_dev, int db_dtype, int64_t N, int E,
             a.thr_in = thr0;
         }
         a.nrows = M;
-        int rc = launch_scan_rows<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
+        int rc = f16 ? launch_scan_rows_f16<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev)
+                     : launch_scan_rows<false>(E, p.QG, a, p.grid, p.waves, p.lds_scan, st, scan_ev);
         if (rc) return rc;
         SelectArgs s;
         s.cand = cand; s.gcnt = gcnt; s.cap = p.cap; s.K = K;
@@ -1805,6 +1852,34 @@ extern "C" int clipmi_dbg_topk_rows_scan_ms(const void* db_dev, int64_t N, int E
     for (int i = 0; i < reps && rc == 0; ++i) {
         rc = topk_ip_rows_impl(db_dev, CLIPMI_F32, N, E, rows_dev, M, q_dev, Q, K, 0, out_score_dev, out_id_dev, ws_dev, ws_bytes,
                                stream, ev);
+        if (rc) break;
+        if (hipEventSynchronize(ev[1]) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipEventSynchronize"); break; }
+        float ms = 0.f;
+        (void)hipEventElapsedTime(&ms, ev[0], ev[1]);
+        total += ms;
+    }
+    (void)hipEventDestroy(ev[0]);
+    (void)hipEventDestroy(ev[1]);
+    if (rc == 0) *scan_ms = (float)(total / reps);
+    return rc;
+}
+
+// Both hooks above in one, for a CLIPMI_F16 matrix (tools/f16_timing.py): rows_dev == NULL times the plain scan, otherwise the
+// list form over M entries. Events around the main scan only. Q <= 32 (one pass).
+extern "C" int clipmi_dbg_topk_scan_f16_ms(const void* db_f16_dev, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                                           const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
+                                           void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms) {
+    if (!scan_ms || reps < 1 || Q > 32 || (rows_dev && M < 1)) return set_err(CLIPMI_EINVAL, "dbg_topk_scan_f16_ms: bad arguments");
+    hipEvent_t ev[2];
+    if (hipEventCreate(&ev[0]) != hipSuccess || hipEventCreate(&ev[1]) != hipSuccess)
+        return set_err(CLIPMI_EHIP, "hipEventCreate");
+    double total = 0.0;
+    int rc = 0;
+    for (int i = 0; i < reps && rc == 0; ++i) {
+        rc = rows_dev ? topk_ip_rows_impl(db_f16_dev, CLIPMI_F16, N, E, rows_dev, M, q_dev, Q, K, 0, out_score_dev, out_id_dev,
+                                          ws_dev, ws_bytes, stream, ev)
+                      : topk_ip_impl(db_f16_dev, CLIPMI_F16, N, E, q_dev, Q, K, 0, out_score_dev, out_id_dev, ws_dev, ws_bytes,
+                                     stream, ev);
         if (rc) break;
         if (hipEventSynchronize(ev[1]) != hipSuccess) { rc = set_err(CLIPMI_EHIP, "hipEventSynchronize"); break; }
         float ms = 0.f;

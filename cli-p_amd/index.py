@@ -96,9 +96,9 @@ def _alloc_out(out, Q, K, device):
 
 
 class IndexFlatIP:
-    """Exact inner-product index over f32 vectors resident in HBM."""
+    """Exact inner-product index over f32 vectors resident in HBM (storage="f16": over fp16 vectors, half the bytes)."""
 
-    def __init__(self, d, device="cuda:0", coarse=None, wide_768=None):
+    def __init__(self, d, device="cuda:0", coarse=None, wide_768=None, storage="f32"):
         """coarse="bf16": keep a bf16 copy of the matrix beside the f32 one (+50 % HBM) and search through
         clipmi_topk_ip_coarse — a bf16-MFMA scan that keeps a provable superset, then exact f32
         re-scoring: same bit-exact results, half the bytes per pass, 64 queries per pass.
@@ -107,9 +107,22 @@ class IndexFlatIP:
         one dominant component loosen it (more survivors, or the exact fallback) but never change results.
         wide_768 (opt-in; d = 768 with coarse="int8" only, ignored otherwise): searches of more than 64 queries go through
         clipmi_topk_ip_wide_i8 - one pass of the int8 copy per <= 1024 queries instead of one per 64. Same bit-exact
-        results. None takes $CLIPMI_WIDE_768 ("" or "0": off, anything else: on); the default is off."""
+        results. None takes $CLIPMI_WIDE_768 ("" or "0": off, anything else: on); the default is off.
+        storage="f16" (opt-in): the rows are kept as IEEE binary16 - `add` rounds each chunk to nearest even as
+        it arrives and drops the f32 chunk - and searched EXACTLY as the f32 values of those halves (clipmi_topk_ip with
+        CLIPMI_F16: the same fmaf chain on the up-converted rows), at half the HBM and file bytes. `f16_changed` counts the
+        elements the rounding changed (0: the index lost nothing, e.g. rows a GPU build of the reference produced in fp16),
+        `f16_overflowed` stays 0: an element beyond the fp16 range makes `add` raise. No coarse copy: coarse= must be None."""
         if coarse not in (None, "bf16", "int8"):
             raise ValueError("IndexFlatIP: coarse must be None, 'bf16' or 'int8'")
+        if storage not in ("f32", "f16"):
+            raise ValueError(f"IndexFlatIP: storage must be 'f32' or 'f16', got {storage!r}")
+        if storage == "f16" and coarse is not None:
+            raise ValueError("IndexFlatIP: storage='f16' has no coarse path (the coarse passes re-score from the f32 matrix); "
+                             "coarse must be None")
+        self.storage = storage
+        self.f16_changed = 0
+        self.f16_overflowed = 0
         self.coarse = coarse
         if wide_768 is None:
             wide_768 = os.environ.get("CLIPMI_WIDE_768", "") not in ("", "0")
@@ -146,18 +159,72 @@ class IndexFlatIP:
         if t.dim() != 2 or t.shape[1] != self.d:
             raise ValueError(f"add: expected [n,{self.d}], got {tuple(t.shape)}")
         t = t.to(device=self.device, dtype=torch.float32).contiguous()
+        if self.storage == "f16":
+            t = self._to_f16(t)             # raises, with the index untouched, if an element leaves the fp16 range
         self._chunks.append(t)
         self._db = None
         self._dbh = None
         self._db8 = None
         self._rmax = None
 
+    def _to_f16(self, t):
+        """One f32 chunk -> its fp16 rows (nearest even), with the counts added to f16_changed: clipmi_rows_to_f16 on a GPU,
+        torch's own conversion on a CPU device (host-logic tests). ValueError if a finite element became infinite."""
+        if t.shape[0] == 0:
+            return torch.empty(t.shape, dtype=torch.float16, device=t.device)
+        if self.device.type == "cuda":
+            h = torch.empty(t.shape, dtype=torch.float16, device=t.device)
+            counts = torch.zeros(2, dtype=torch.int64, device=t.device)
+            _lib.check(_lib.lib().clipmi_rows_to_f16(t.data_ptr(), t.shape[0], self.d, h.data_ptr(), counts.data_ptr(),
+                                                     _lib.stream_ptr(self.device)), "clipmi_rows_to_f16")
+            changed, over = (int(v) for v in counts.cpu())
+        else:
+            h = t.to(torch.float16)
+            back = h.to(torch.float32)
+            changed = int(((back != t) & ~torch.isnan(t)).sum())
+            over = int((torch.isfinite(t) & torch.isinf(back)).sum())
+        if over:
+            raise ValueError(f"add: {over} element(s) beyond the fp16 range (largest finite fp16 value: 65504) would become "
+                             "infinite; storage='f16' cannot hold these rows")
+        self.f16_changed += changed
+        return h
+
+    def _add_f16(self, h):
+        """Append rows that ARE fp16 already (a version-2 file): nothing is rounded, nothing counted."""
+        self._chunks.append(torch.as_tensor(h).to(device=self.device, dtype=torch.float16).contiguous())
+        self._db = None
+
     @property
     def ntotal(self):
         return sum(c.shape[0] for c in self._chunks)
 
+    def _packed(self, dtype):
+        if self._db is None:
+            if not self._chunks:
+                self._db = torch.empty((0, self.d), dtype=dtype, device=self.device)
+            elif len(self._chunks) == 1:
+                self._db = self._chunks[0]
+            else:
+                self._db = torch.cat(self._chunks, dim=0)
+                self._chunks = [self._db]
+        return self._db
+
+    def matrix_f16(self):
+        """The stored [N][d] torch.float16 device matrix of an fp16 index (concatenated once, like matrix())."""
+        if self.storage != "f16":
+            raise ValueError("matrix_f16: the index stores f32 rows (storage='f32')")
+        return self._packed(torch.float16)
+
+    def _stored(self):
+        """(the stored matrix, its CLIPMI dtype code): what the exact searches read."""
+        return (self.matrix_f16(), _lib.F16) if self.storage == "f16" else (self.matrix(), _lib.F32)
+
     def matrix(self):
-        """The packed [N][d] f32 device matrix (rows in add order = LMDB key order, build-index.py:75-89)."""
+        """The packed [N][d] f32 device matrix (rows in add order = LMDB key order, build-index.py:75-89).
+        On an fp16 index (storage="f16"): a FRESH f32 up-conversion of the stored halves on every call (exact; 4 N d bytes,
+        never cached - the index itself keeps only the fp16 rows)."""
+        if self.storage == "f16":
+            return self.matrix_f16().to(torch.float32)
         if self._db is None:
             if not self._chunks:
                 self._db = torch.empty((0, self.d), dtype=torch.float32, device=self.device)
@@ -170,6 +237,8 @@ class IndexFlatIP:
 
     def matrix_bf16(self):
         """(bf16 copy [N][d], upper bound of the largest row norm) for the coarse path; built once (clipmi_rows_to_bf16)."""
+        if self.storage == "f16":
+            raise ValueError("matrix_bf16: an fp16 index has no coarse copy")
         if self._dbh is None:
             db = self.matrix()
             dbh = torch.empty(db.shape, dtype=torch.bfloat16, device=db.device)
@@ -201,6 +270,8 @@ class IndexFlatIP:
         """(int8 copy in 32-row blocks of [d / 32][64][16 B] - include/clipmi.h clipmi_quantize_rows_i8 -, f32 meta:
         (block scale, error norm) per row padded to 32 rows (+32) then (scale, largest error norm) per block, largest
         error norm, largest row norm) for the int8 coarse path; built once by clipmi_quantize_rows_i8 + clipmi_rows_stats."""
+        if self.storage == "f16":
+            raise ValueError("matrix_i8: an fp16 index has no coarse copy")
         if self._db8 is None:
             L = _lib.lib()
             db = self.matrix()
@@ -229,15 +300,16 @@ class IndexFlatIP:
         return self._db8 + (self._row_norm_max(),)
 
     def uses_coarse(self):
-        """True when searches go through a coarse-then-exact path (coarse copy requested, d = 512 or 768, N >= 65536)."""
-        return coarse_eligible(self.coarse, self.d, self.ntotal)
+        """True when searches go through a coarse-then-exact path (coarse copy requested, d = 512 or 768, N >= 65536).
+        Never on an fp16 index, whatever `.coarse` was set to after construction: its searches are the exact fp16 scan."""
+        return self.storage != "f16" and coarse_eligible(self.coarse, self.d, self.ntotal)
 
     # -- query side ---------------------------------------------------------------------------
     def search_device(self, q, K, out=None, _one_pass=False):
         """q: f32 [Q,d] device tensor -> (scores f32 [Q,K], ids i64 [Q,K]) device tensors. Async.
         `out` = (scores, ids) views to write into (the packed all-gather record of ShardedFlatIP)."""
         L = _lib.lib()
-        db = self.matrix()
+        db, db_dtype = self._stored()
         if self.device.type != "cuda":
             raise _lib.ClipmiError("IndexFlatIP.search needs the HIP path (device is not a GPU); no CPU fallback")
         q = q.to(device=self.device, dtype=torch.float32).contiguous()
@@ -272,7 +344,7 @@ class IndexFlatIP:
         elif coarse:
             lead = (db.data_ptr(), dbh.data_ptr(), N, self.d, rmax)
         else:
-            lead = (db.data_ptr(), _lib.F32, N, self.d)
+            lead = (db.data_ptr(), db_dtype, N, self.d)
         rc = getattr(L, route.entry)(*lead, q.data_ptr(), Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
                                      ws.numel(), _lib.stream_ptr(self.device))
         _lib.check(rc, route.entry)
@@ -355,6 +427,7 @@ def _subset_list(rows, ntotal):
 class IndexSubset:
     """IndexFlatIP.subset(rows): the exact top-K among the chosen rows only, reading only those rows.
 
+    Over an fp16 parent (storage="f16") the list scan reads the stored halves (CLIPMI_F16), M (2 d + 4) bytes.
     Same contracts as IndexFlatIP - search(x, K) numpy in / numpy out, search_device(q, K, out=None) device tensors, async -
     and the same results as searching everything and discarding the other rows: bit-exact scores, descending score then
     ascending row id, ids = parent row + id_base, pads (-FLT_MAX, -1) beyond min(K, M). Every search goes through
@@ -392,7 +465,7 @@ class IndexSubset:
         if self.device.type != "cuda":
             raise _lib.ClipmiError("IndexSubset.search needs the HIP path (device is not a GPU); no CPU fallback")
         L = _lib.lib()
-        db = self.parent.matrix()
+        db, db_dtype = self.parent._stored()
         q = q.to(device=self.device, dtype=torch.float32).contiguous()
         Q, M = q.shape[0], self.ntotal
         need = L.clipmi_topk_ip_rows_workspace_bytes(M, self.d, Q, K)
@@ -403,7 +476,7 @@ class IndexSubset:
         if ws is None or ws.numel() < need:
             ws = self._ws[skey] = torch.empty(need, dtype=torch.uint8, device=self.device)
         out_s, out_i = _alloc_out(out, Q, K, self.device)
-        rc = L.clipmi_topk_ip_rows(db.data_ptr(), _lib.F32, db.shape[0], self.d, self._list.data_ptr() if M else None, M,
+        rc = L.clipmi_topk_ip_rows(db.data_ptr(), db_dtype, db.shape[0], self.d, self._list.data_ptr() if M else None, M,
                                    q.data_ptr(), Q, K, self.id_base, out_s.data_ptr(), out_i.data_ptr(), ws.data_ptr(),
                                    ws.numel(), _lib.stream_ptr(self.device))
         _lib.check(rc, "clipmi_topk_ip_rows")
@@ -515,13 +588,21 @@ FAISS_FOURCC_FLAT_IP = b"IxFI"
 def write_index(index, path, format="clipmi"):
     """faiss.write_index stand-in (build-index.py:109).
     format="clipmi": own packed format, little-endian: 8-byte magic, u32 version, u32 d, u64 ntotal, then
-        ntotal*d f32 rows.
+        ntotal*d f32 rows (version 1: an f32 index, the bytes as ever). An fp16 index (storage="f16") writes VERSION 2:
+        magic, <IIQ (2, d, ntotal), <II (dtype code 3 = CLIPMI_F16, 0), then ntotal*d little-endian halves.
     format="faiss": the serialisation of a faiss IndexFlatIP as published in faiss/impl/index_write.cpp
         (fourcc "IxFI"; header d:i32, ntotal:i64, two i64 placeholders = 1<<20, is_trained:u8,
         metric_type:i32 = 0; then u64 count of floats + the f32 rows), so that the ORIGINAL
         query-index.py:29 (`faiss.read_index("images.index")`) can open an index built here
         (SURVEY.md §8f next-3). faiss is not available offline: this layout is restated from the
-        upstream source, PARITY UNPINNED until checked against a real faiss build."""
+        upstream source, PARITY UNPINNED until checked against a real faiss build.
+        An fp16 index writes its rows up-converted to f32 here (exact), so the reference can still open the file."""
+    if format == "clipmi" and getattr(index, "storage", "f32") == "f16":
+        dbh = np.ascontiguousarray(index.matrix_f16().cpu().numpy(), dtype="<f2")
+        with open(path, "wb") as f:
+            f.write(MAGIC + struct.pack("<IIQ", 2, index.d, dbh.shape[0]) + struct.pack("<II", _lib.F16, 0))
+            f.write(dbh.tobytes())
+        return
     db = np.ascontiguousarray(index.matrix().cpu().numpy(), dtype="<f4")
     with open(path, "wb") as f:
         if format == "faiss":
@@ -608,19 +689,46 @@ def _read_faiss_ivfflat(f, path):
     return d, mat
 
 
-def read_index(path, device="cuda:0", rows=None, coarse=None, wide_768=None):
+def storage_from_env(environ=os.environ):
+    """$CLIPMI_STORAGE -> the `storage=` of read_index / IndexFlatIP on the command-line paths: None (unset, "" or "f32":
+    the file's own kind, an f32 index when building) or "f16". Anything else raises ValueError with the line to print."""
+    v = environ.get("CLIPMI_STORAGE", "")
+    if v in ("", "f32"):
+        return None
+    if v == "f16":
+        return "f16"
+    raise ValueError(f"CLIPMI_STORAGE must be f32 or f16, got {v!r}.")
+
+
+F16_ADD_ROWS = 1 << 20      # rows per `add` when read_index converts an f32 file into an fp16 index
+
+
+def read_index(path, device="cuda:0", rows=None, coarse=None, wide_768=None, storage=None):
     """faiss.read_index stand-in (query-index.py:29): reads both formats write_index produces and the
     IndexIVFFlat file the reference's build-index.py writes (rows come back in id order and are searched
     exactly; `nprobe` is accepted and ignored).
     rows=(lo, hi): load only that contiguous row range (one rank's shard) — the flat formats
-    seek straight to it; the returned index has `id_base = lo` and `n_file` = the file's row count."""
+    seek straight to it (by the file's element size); the returned index has `id_base = lo` and `n_file` = the file's row count.
+    storage: None keeps the file's own kind (a version-2 clipmi file gives an fp16 index, everything else an f32 one); "f16" on
+    an f32 file converts while loading, in `add` calls of at most 2^20 rows; "f32" on a version-2 file up-converts (exact)."""
+    if storage not in (None, "f32", "f16"):
+        raise ValueError(f"read_index: storage must be None, 'f32' or 'f16', got {storage!r}")
+    esize, ftype = 4, "<f4"
     with open(path, "rb") as f:
         head = f.read(8)
         if head[:4] == FAISS_FOURCC_FLAT_IP or head == MAGIC:
             if head == MAGIC:
                 ver, d, n = struct.unpack("<IIQ", f.read(16))
-                if ver != 1:
+                if ver not in (1, 2):
                     raise ValueError(f"{path}: unsupported version {ver}")
+                if ver == 2:
+                    ext = f.read(8)
+                    if len(ext) != 8:
+                        raise ValueError(f"{path}: truncated version-2 header")
+                    code, _reserved = struct.unpack("<II", ext)
+                    if code != _lib.F16:
+                        raise ValueError(f"{path}: version-2 file with dtype code {code}; only 3 (fp16) is defined")
+                    esize, ftype = 2, "<f2"
             else:
                 f.seek(4)
                 d, n, metric = _read_faiss_header(f)
@@ -632,8 +740,8 @@ def read_index(path, device="cuda:0", rows=None, coarse=None, wide_768=None):
             lo, hi = (0, n) if rows is None else (int(rows[0]), int(rows[1]))
             if not (0 <= lo <= hi <= n):
                 raise ValueError(f"{path}: rows {rows} outside 0..{n}")
-            f.seek((lo * d) * 4, 1)
-            data = np.fromfile(f, dtype="<f4", count=(hi - lo) * d)
+            f.seek((lo * d) * esize, 1)
+            data = np.fromfile(f, dtype=ftype, count=(hi - lo) * d)
         elif head[:4] == b"IwFl":
             f.seek(4)
             d, mat = _read_faiss_ivfflat(f, path)
@@ -646,9 +754,19 @@ def read_index(path, device="cuda:0", rows=None, coarse=None, wide_768=None):
             raise ValueError(f"{path}: not a clipmi, faiss IndexFlatIP or faiss IndexIVFFlat file")
     if data.size != (hi - lo) * d:
         raise ValueError(f"{path}: truncated ({data.size} of {(hi - lo) * d} floats)")
-    idx = IndexFlatIP(d, device=device, coarse=coarse, wide_768=wide_768)
+    file_f16 = esize == 2
+    if storage is None:
+        storage = "f16" if file_f16 else "f32"
+    idx = IndexFlatIP(d, device=device, coarse=coarse, wide_768=wide_768, storage=storage)
+    data = data.reshape(hi - lo, d)
     if hi > lo:
-        idx.add(data.reshape(hi - lo, d))
+        if storage == "f16" and file_f16:
+            idx._add_f16(data)                                # the halves themselves
+        elif storage == "f16":
+            for r0 in range(0, hi - lo, F16_ADD_ROWS):        # the f32 matrix is never resident as a whole
+                idx.add(data[r0:r0 + F16_ADD_ROWS])
+        else:
+            idx.add(data.astype(np.float32) if file_f16 else data)
     idx.id_base = lo
     idx.n_file = n
     return idx
@@ -659,7 +777,7 @@ def index_rows(path):
     with open(path, "rb") as f:
         head = f.read(8)
         if head == MAGIC:
-            _, d, n = struct.unpack("<IIQ", f.read(16))
+            _, d, n = struct.unpack("<IIQ", f.read(16))      # versions 1 and 2 share these 16 bytes
             return n, d
         if head[:4] in (FAISS_FOURCC_FLAT_IP, b"IwFl"):
             f.seek(4)

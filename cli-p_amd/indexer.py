@@ -47,7 +47,7 @@ binds; `threads`: the old form).
 import os
 
 from . import pipeline, store as vstore
-from .index import IndexFlatIP, shard_bounds, write_index
+from .index import IndexFlatIP, shard_bounds, storage_from_env, write_index
 from .model import load
 from .ranks import Ranks
 
@@ -263,9 +263,15 @@ def finalise(db, device, out="images.index"):
     print(f"Preparing index for {n} entries...")
     print(f"Generating {(n, db.dim)} matrix...")
     matrix, _ = db.assemble()
-    index = IndexFlatIP(db.dim, device=device)
+    # CLIPMI_STORAGE=f16: an fp16 index and a version-2 file (half the bytes); its rows are converted 2^20 at a time
+    storage = storage_from_env() or "f32"
+    index = IndexFlatIP(db.dim, device=device, storage=storage)
     print("Adding to index...")
-    index.add(matrix)
+    if storage == "f16":
+        for r0 in range(0, len(matrix), 1 << 20):
+            index.add(matrix[r0:r0 + (1 << 20)])
+    else:
+        index.add(matrix)
     print("Saving index...")
     write_index(index, out)
 

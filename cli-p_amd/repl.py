@@ -21,7 +21,7 @@ import time
 import numpy as np
 
 from . import store as vstore, tokenizer
-from .index import ShardedFlatIP, coarse_eligible, index_rows, read_index, shard_bounds
+from .index import ShardedFlatIP, coarse_eligible, index_rows, read_index, shard_bounds, storage_from_env
 from .model import load
 from .ranks import Ranks
 
@@ -198,20 +198,27 @@ def follow(sharded, ranks):
         sharded.search(f, K)
 
 
-def open_sharded(path, ranks, coarse=None, local_search=None):
+def open_sharded(path, ranks, coarse=None, local_search=None, storage=None):
     """This rank's shard of the index file + the all-gather merge around it. `local_search(q, K, lo)` replaces the
-    GPU search on the CPU/gloo path (tests of the host logic; the product path has no CPU search)."""
+    GPU search on the CPU/gloo path (tests of the host logic; the product path has no CPU search).
+    storage: read_index's (None: the file's own kind; "f16": the shard is kept in fp16 and no coarse copy is built)."""
     n, d = index_rows(path)
     lo, hi = shard_bounds(n, ranks.world, ranks.rank)
     if local_search is not None:
         return ShardedFlatIP(None, n, group=ranks.data, local_search=local_search)
-    local = read_index(path, device=str(ranks.device), rows=(lo, hi))
-    if coarse_eligible(coarse, local.d, local.ntotal):
+    local = read_index(path, device=str(ranks.device), rows=(lo, hi), storage=storage)
+    if local.storage != "f16" and coarse_eligible(coarse, local.d, local.ntotal):
         local.coarse = coarse
     return ShardedFlatIP(local, n, group=ranks.data)
 
 
 def main():
+    # CLIPMI_STORAGE=f16: keep the index in fp16 (half the HBM; exact search of the rounded rows, no coarse copy)
+    try:
+        storage = storage_from_env()
+    except ValueError as e:
+        print(e)
+        sys.exit(1)
     ranks = Ranks("cuda").init()
     device = str(ranks.device)
     # large libraries: scan a coarse copy first (identical results; CLIPMI_COARSE = int8 | bf16 | none)
@@ -224,15 +231,15 @@ def main():
         ranks.close()
         sys.exit(1)
     if ranks.world > 1:
-        sharded = open_sharded("images.index", ranks, coarse=coarse)
+        sharded = open_sharded("images.index", ranks, coarse=coarse, storage=storage)
         if not ranks.leader:
             follow(sharded, ranks)
             ranks.close()
             sys.exit(0)
         index = LeaderIndex(sharded, ranks)
     else:
-        index = read_index("images.index", device=device)
-        if coarse_eligible(coarse, index.d, index.ntotal):
+        index = read_index("images.index", device=device, storage=storage)
+        if index.storage != "f16" and coarse_eligible(coarse, index.d, index.ntotal):
             index.coarse = coarse
     model, _ = load(os.environ.get("CLIPMI_WEIGHTS", "ViT-B/32"), device=device, jit=False)
     model.eval()

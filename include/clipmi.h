@@ -44,7 +44,10 @@ enum {
 enum {
     CLIPMI_F32 = 0,
     CLIPMI_BF16 = 1,
-    CLIPMI_U8 = 2
+    CLIPMI_U8 = 2,
+    CLIPMI_F16 = 3   /* IEEE binary16, little-endian; as clipmi_topk_ip's / clipmi_topk_ip_rows' db_dtype: [N][E] row-major,
+                        row pitch 2 E bytes (an addition to ABI 8 in the sense of the PNG note below: one newly accepted
+                        argument value and two new entry points, nothing existing changes, CLIPMI_ABI_VERSION stays 8) */
 };
 
 /*
@@ -143,7 +146,11 @@ int clipmi_encode_text(const clipmi_tower* t, const void* blob_dev,
 /* ---- a12: index.search(features, k + offset + 1) ----------------------------------------
  * Replaces query-index.py:111 (`D, I = index.search(features, K)`), as EXACT flat inner-product
  * search over this rank's shard of the packed matrix that build-index.py:68-107 assembles.
- *   db_dev     : [N][E] row-major, CLIPMI_F32 (E in {512, 768})
+ *   db_dev     : [N][E] row-major (E in {512, 768}), CLIPMI_F32, or CLIPMI_F16: binary16 rows of pitch 2 E bytes, as
+ *                clipmi_rows_to_f16 writes them (half the bytes per pass). Every other db_dtype is
+ *                CLIPMI_EUNSUPPORTED. With CLIPMI_F16 everything below holds word for word ON THE ROWS' VALUES CONVERTED TO
+ *                F32, which is exact (subnormals included; +-inf and NaN components as in f32 rows): the same fmaf chain, the
+ *                same plan and workspace (clipmi_topk_ip_workspace_bytes has no dtype argument), the same ordering and pads.
  *   q_dev      : f32 [Q][E]
  *   out_score  : f32 [Q][K] descending; out_id: int64 [Q][K] = id_base + row; ties broken by
  *                ascending id; slots beyond min(K, N) hold score -FLT_MAX and id -1
@@ -164,7 +171,8 @@ int clipmi_topk_ip(const void* db_dev, int db_dtype, int64_t N, int E,
  * nothing existing changes, CLIPMI_ABI_VERSION stays 8). clipmi_topk_ip_rows is clipmi_topk_ip's result restricted to the
  * rows `rows_dev` names, reading only those rows (M * E * 4 + M * 4 bytes per pass of <= 32 queries instead of N * E * 4).
  *   rows_dev : u32 [M] row numbers of db_dev, strictly ascending. 0 <= M <= N; NULL with M > 0, M < 0 and M > N are
- *              CLIPMI_EINVAL, db_dtype != CLIPMI_F32 is CLIPMI_EUNSUPPORTED - all decided on the host, nothing is launched.
+ *              CLIPMI_EINVAL, a db_dtype other than CLIPMI_F32 and CLIPMI_F16 (as in clipmi_topk_ip: M * E * 2 bytes of rows
+ *              per pass) is CLIPMI_EUNSUPPORTED - all decided on the host, nothing is launched.
  *              M = 0 fills the outputs with pads and reads nothing.
  *   result   : scores bit-exact (the same MFMA sequence per (row, query): DESIGN.md "score order"), ordered by descending
  *              score, then ascending ROW ID; out_id = id_base + row; slots beyond min(K, M) hold (-FLT_MAX, -1). Non-finite
@@ -217,6 +225,12 @@ int clipmi_topk_ip_coarse(const void* db_dev, const void* db_bf16_dev, int64_t N
  * writes the bf16 copy (round to nearest even) clipmi_topk_ip_coarse scans. E a multiple of 4. Asynchronous on `stream`. */
 int clipmi_rows_stats(const float* db_dev, int64_t N, int E, const float* meta_dev, float* stats2_dev, void* stream);
 int clipmi_rows_to_bf16(const float* db_dev, int64_t N, int E, void* out_bf16_dev, void* stream);
+/* The CLIPMI_F16 matrix of an index kept in fp16 (an addition to ABI 8, see CLIPMI_F16): out_f16_dev[N][E] = db_dev rounded to
+ * the nearest binary16, ties to even; finite values of magnitude >= 65520 become +-inf, the sign of zero is kept, NaN stays NaN.
+ * counts2_dev is NULL or two u64 the call ADDS to (the caller zeroes them): [0] += elements whose value changed
+ * (f32(f16(x)) != x; a NaN that stays NaN is not counted), [1] += finite elements that became infinite. E a multiple of 4.
+ * Asynchronous on `stream`. */
+int clipmi_rows_to_f16(const float* db_dev, int64_t N, int E, void* out_f16_dev, uint64_t* counts2_dev, void* stream);
 size_t clipmi_i8_copy_bytes(int64_t N, int E);
 size_t clipmi_i8_meta_bytes(int64_t N);
 /* (ABI 4: the two buffer sizes are arguments - a copy or meta buffer smaller than clipmi_i8_copy_bytes / clipmi_i8_meta_bytes
@@ -577,6 +591,12 @@ int clipmi_dbg_topk_scan_ms(const void* db_dev, int64_t N, int E, const float* q
 int clipmi_dbg_topk_rows_scan_ms(const void* db_dev, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
                                  const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
                                  void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms);
+
+/* Both hooks above in one for a CLIPMI_F16 matrix (tools/f16_timing.py): rows_dev == NULL is the plain scan, otherwise the
+ * list form over M >= 1 entries. Q <= 32. (An addition to ABI 8, see CLIPMI_F16.) */
+int clipmi_dbg_topk_scan_f16_ms(const void* db_f16_dev, int64_t N, int E, const uint32_t* rows_dev, int64_t M,
+                                const float* q_dev, int Q, int K, float* out_score_dev, int64_t* out_id_dev,
+                                void* ws_dev, size_t ws_bytes, void* stream, int reps, float* scan_ms);
 
 /* clipmi_topk_ip_coarse `reps` times with HIP events around the bf16 scan kernel (Q <= 64) */
 int clipmi_dbg_topk_coarse_scan_ms(const void* db_dev, const void* db_bf16_dev, int64_t N, int E, float rmax,
